@@ -7,7 +7,7 @@ YoloLoss (batch sum) + backward + Adam, fp32.  Inputs and targets are resident i
 the timed region.  Weak scaling: every rank trains on its own 256-image shard, gradients are
 SUM-all-reduced over RCCL.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 `python bench.py --gpus N` without a launcher environment starts the N rank processes itself
@@ -617,6 +617,27 @@ def pmc_traffic_for(kernel_group: str, B: int, F_: int):
         return None
 
 
+DUMP_BYTES = 64 << 20                   # --dump-outputs: cap on everything written
+
+
+def dump_outputs(path, arrays):
+    """Write each tensor as <path>/<name>.npy (float32, or float64 where it already is).  A tensor above its share of
+    DUMP_BYTES is replaced by a fixed sample of its flattened elements (seed 0, ascending indices): the same arguments give
+    the same sample, so two builds compare element for element."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_BYTES // len(arrays)
+    for name, t in arrays.items():
+        t = t.detach()
+        t = t.double() if t.dtype == torch.float64 else t.float()
+        if t.numel() * t.element_size() > share:
+            n = share // t.element_size()
+            idx = torch.randperm(t.numel(), generator=torch.Generator().manual_seed(0))[:n].sort().values
+            t = t.reshape(-1)[idx.to(t.device)]
+            _log(f"dump-outputs: {name} sampled to {n} elements")
+        np.save(os.path.join(path, name + ".npy"), t.cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -631,7 +652,12 @@ def main():
     ap.add_argument("--no-p16", action="store_true", help="skip the precision16 leg (second key)")
     ap.add_argument("--concat-ranks", type=int, default=0,
                     help="(tests) one process whose batch is the concatenation of the shards R ranks would draw")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed (loss sum, y_hat, the updated parameters) "
+                         "as DIR/<name>.npy (rank 0)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(self_launch(args))                        # N fresh rank processes; this one never touches the GPU
@@ -695,7 +721,7 @@ def main():
     for s_ in range(args.steps):
         if s_ == n_timed:
             model.engine.timer = None
-        lsum, _, _ = mm.fused_train_step(x, y)
+        lsum, y_hat, _ = mm.fused_train_step(x, y)
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -710,7 +736,13 @@ def main():
         dist.all_reduce(lt)
         loss_val = float(lt)
     else:
+        lt = lsum
         loss_val = float(lsum)
+
+    if rank == 0 and args.dump_outputs:                     # before any other leg reuses the engine's buffers
+        dump_outputs(args.dump_outputs, {
+            "loss_sum": lt, "y_hat": y_hat,
+            "params": torch.cat([p.detach().reshape(-1) for p in model.state_dict().values()])})
 
     if rank == 0:
         ms = dt / args.steps * 1e3
@@ -724,7 +756,8 @@ def main():
         # fp32 path one f32 MFMA pass (157.3 TFLOP/s); `bound` names the larger term.
         per = timer.summary()                                # name -> (launches, total ms, flops/launch, bytes/launch)
         if not per:                                          # FDET_BENCH_NO_TIMER=1 (development: the cost of the live timing itself)
-            print(json.dumps({"ms_per_step_without_kernel_timer": round(ms, 3), "value": round(value, 1)}))
+            print(json.dumps({"ms_per_step_without_kernel_timer": round(ms, 3), "ms_per_step": round(ms, 3),
+                              "value": round(value, 1)}))
             return
         x3 = bool(model.engine.x3)
         mf_mult, mf_peak = (3.0, PEAK_BF16_MFMA_TFLOPS) if x3 else (1.0, PEAK_FP32_MFMA_TFLOPS)
