@@ -498,6 +498,35 @@ int fdet_block_chain_bwd_ps_p16(const float* dout, const void* const* h_wpk1b, c
                                 void* const* h_dz1_ps, void* const* h_dz2_ps, float* dx, int nblocks, int N, int F,
                                 int H, int W, float slope, void* stream);
 
+/* precision16 on the fp32-I/O conv kernels (every channel count that is a multiple of 16; the pooled pair needs multiples
+ * of 32 as its bf16x3 twin does): same arguments, panels (fdet_pack_conv3x3_weights_bf16x3), workspace sizes
+ * (fdet_conv3x3_wgrad_bf16x3[_batched]_ws_bytes) and support predicates (fdet_conv3x3_pool_fusion_ok) as the _bf16x3 twins.
+ * Contract:
+ *   - every fp32 operand the kernel loads is rounded to bf16 (RNE, the hi part only); the panels' lo half is not read;
+ *   - ONE v_mfma_f32_32x32x16_bf16 per (m, n) tile instead of three, fp32 accumulation;
+ *   - epilogue arithmetic in fp32 (bias, LeakyReLU, dropout scale, skip add, max-pool, routing bytes, lrelu' mask, `add`);
+ *   - every activation / activation gradient the kernel stores is rounded ONCE to bf16 (RNE) and stored in its fp32 word
+ *     (y == bf16(y)); pooled maxima are taken on the fp32 values, so the routing bytes are those of the bf16x3 kernel
+ *     on the same accumulators;
+ *   - weight and bias gradients are fp32 sums of products of the bf16-rounded operands (bias: sum of bf16(dz)).
+ * The F=64 pre-split precision16 path above has the same contract. */
+int fdet_conv3x3_fwd_bf16(const float* x, const void* wpk, const float* bias, float* y_full,
+                          const float* skip, const float* drop_scale, float* y_out, int N, int Cin,
+                          int Cout, int H, int W, int pool, float slope, void* stream);
+int fdet_conv3x3_dgrad_bf16(const float* dz, const void* wpk, const float* act, const float* add,
+                            float* dx, int N, int Cin, int Cout, int H, int W, float slope, void* stream);
+int fdet_conv3x3_fwd_pool_bf16(const float* x, const void* wpk, const float* bias, const float* skip,
+                               const float* drop_scale, float* out_pooled, unsigned char* route, int N,
+                               int Cin, int Cout, int H, int W, float slope, void* stream);
+int fdet_conv3x3_dgrad_unpool_bf16(const float* dz, const void* wpk, const float* dout_pooled,
+                                   const unsigned char* route, float* dx, int N, int Cin, int Cout,
+                                   int H, int W, float slope, void* stream);
+int fdet_conv3x3_wgrad_bf16(const float* x, const float* dz, float* dW, float* db, void* ws,
+                            size_t ws_bytes, int N, int Cin, int Cout, int H, int W, void* stream);
+int fdet_conv3x3_wgrad_bf16_batched(const float* const* h_x, const float* const* h_dz, float* const* h_dW,
+                                    float* const* h_db, int L, void* ws, size_t ws_bytes, int N, int Cin,
+                                    int Cout, int H, int W, void* stream);
+
 /* MobileNetV3-small backbone, training pieces (round 4; models/MobilenetV3Backbone.py:49-60 trained through
  * models/ModelMeta.py:115-227): fp32 NCHW tensors [N][C][P = H*W].  The 1x1 convs use fdet_pointwise_*_bf16x3, the head
  * fdet_head_fwd / fdet_head_bwd.  PARITY UNPINNED (timm absent): checked against torch autograd on the CPU oracle.

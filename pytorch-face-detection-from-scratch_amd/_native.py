@@ -133,6 +133,12 @@ SIGNATURES = {
     "fdet_conv3x3_wgrad_ps_batched_p16": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _SZ, _P]),
     "fdet_block_chain_fwd_ps_p16": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _P]),
     "fdet_block_chain_bwd_ps_p16": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _P]),
+    "fdet_conv3x3_fwd_bf16": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _P]),
+    "fdet_conv3x3_dgrad_bf16": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _P]),
+    "fdet_conv3x3_fwd_pool_bf16": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _P]),
+    "fdet_conv3x3_dgrad_unpool_bf16": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _P]),
+    "fdet_conv3x3_wgrad_bf16": (_I, [_P, _P, _P, _P, _P, _SZ, _I, _I, _I, _I, _I, _P]),
+    "fdet_conv3x3_wgrad_bf16_batched": (_I, [_P, _P, _P, _P, _I, _P, _SZ, _I, _I, _I, _I, _I, _P]),
     "fdet_mbt_stem_fwd": (_I, [_P, _P, _P, _I, _I, _I, _P]),
     "fdet_mbt_taps_ws_bytes": (_SZ, [_I, _I]),
     "fdet_mbt_stem_wgrad": (_I, [_P, _P, _P, _P, _SZ, _I, _I, _I, _P]),

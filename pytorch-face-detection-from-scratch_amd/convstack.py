@@ -161,11 +161,13 @@ class ConvStack:
         self.ps = self.pool_fusion and geo.filters == 64 and os.environ.get("FDET_PS", "1") != "0"
         self._ps_pool: Dict[tuple, list] = {}
         self.ps_strips = self.ps and os.environ.get("FDET_PS_STRIPS", "1") != "0"
-        # precision16 (FDET_PRECISION=bf16 or set_precision("bf16")): the PS kernels run ONE bf16 MFMA pass on the hi planes
-        # (bf16 activations and weights, fp32 accumulation / epilogues / master weights) -- the arithmetic of the reference's
-        # Trainer(precision=16), train_model.py:50, with bf16 as the 16-bit type.  Only where the PS path runs (64 channels);
-        # the stem, the head and the pooled-gradient routing keep their fp32-grade kernels.
-        self.p16 = self.ps and want == "bf16"
+        # precision16 (FDET_PRECISION=bf16 or set_precision("bf16")): the conv kernels run ONE bf16 MFMA pass (bf16
+        # activations and weights, fp32 accumulation / epilogues / master weights, every stored activation and activation
+        # gradient rounded to bf16) -- the arithmetic of the reference's Trainer(precision=16), train_model.py:50, with bf16
+        # as the 16-bit type.  Wherever the bf16x3 kernels run: the PS kernels (64 channels) and the fp32-I/O kernels (any
+        # multiple of 16 channels, e.g. PoolResnet-large F=128).  The stem forward, the head, the pooled-gradient routing and
+        # the fp32-I/O block chain (64 channels with FDET_PS=0) keep their fp32-grade kernels.
+        self.p16 = self.x3 and want == "bf16"
         self._cur_N = 1                                    # batch size of the pass being planned (forward() sets it)
         # training head fused with the loss (fdet_head_loss_fused: forward + yolo_loss + their gradients in one kernel on
         # the matrix cores); FDET_HEAD_FUSED=0 keeps the separate head_fwd / yolo_loss / head_bwd launches
@@ -173,11 +175,13 @@ class ConvStack:
         self._zero_ws: Dict[str, torch.Tensor] = {}
 
     def set_precision(self, name: str) -> None:
-        """"bf16x3" (fp32-grade, default) or "bf16" (precision16: one MFMA pass; needs the PS path)."""
+        """"bf16x3" (fp32-grade, default) or "bf16" (precision16: one MFMA pass; needs the bf16 matrix-core kernels).  A
+        pass saved by forward(save=True) keeps the precision it ran in: backward() follows it, not this setting."""
         if name not in ("bf16x3", "bf16"):
             raise ValueError("precision must be 'bf16x3' or 'bf16'")
-        if name == "bf16" and not self.ps:
-            raise ValueError("precision16 needs the pre-split path (64 channels, bf16x3-capable geometry)")
+        if name == "bf16" and not self.x3:
+            raise ValueError("precision16 needs the bf16 matrix-core conv kernels: this engine runs the exact-fp32 path "
+                             f"(FDET_PRECISION=f32, or {self.geo.filters} channels is not a multiple of 16)")
         self.p16 = name == "bf16"
         self._ps_pool.clear()                              # a bf16x3 pass may have left lo planes in pooled buffers
 
@@ -343,7 +347,8 @@ class ConvStack:
                 psm.stem_fwd_ps(x, P["conv1.weight"], P["conv1.bias"], h_ps, g.stem_k, g.stem_s, g.stem_p, p16=self.p16)
             else:
                 hp.stem_fwd(x, P["conv1.weight"], P["conv1.bias"], h, ws, g.stem_k, g.stem_s, g.stem_p, x3=stem_x3)
-        saved = {"x": x, "blocks": [], "masks": masks, "ps_scope": scope} if save else None
+        # (the precision is stamped into the saved state: backward() runs the pass in the precision of its forward)
+        saved = {"x": x, "blocks": [], "masks": masks, "ps_scope": scope, "p16": self.p16} if save else None
         k = -1
         while k + 1 < len(self.lv):
             k += 1
@@ -414,25 +419,28 @@ class ConvStack:
             sc = masks[name] if masks is not None else None
             a = torch.empty(N, F_, hk, hk, dtype=F32, device=dev)
             with self._t("conv3x3_fwd", N, hk, self._conv_flops(N, hk), self._act_bytes(N, hk, 2)):
-                hp.conv3x3_fwd(h, self._wpk[name + ".conv1.f"], P[name + ".conv1.bias"], F_, y_full=a, slope=self.slope, x3=self.x3)
+                hp.conv3x3_fwd(h, self._wpk[name + ".conv1.f"], P[name + ".conv1.bias"], F_, y_full=a, slope=self.slope, x3=self.x3,
+                               p16=self.p16)
             out = torch.empty(N, F_, hk // pool, hk // pool, dtype=F32, device=dev)
             if pool == 2 and self._fused_pool(hk, N):
                 # conv2 + lrelu + dropout*skip + maxpool in one kernel; c is never written, backward gets one
                 # routing byte per pooling window instead
                 c = torch.empty(N, F_, hk // 2, hk // 2, dtype=torch.uint8, device=dev) if save else None
                 with self._t("conv3x3_fwd_pool", N, hk, self._conv_flops(N, hk), self._act_bytes(N, hk, 2 + 0.25 + (1 / 16 if save else 0))):
-                    hp.conv3x3_fwd_pool(a, self._wpk[name + ".conv2.f"], P[name + ".conv2.bias"], h, sc, out, c, self.slope)
+                    hp.conv3x3_fwd_pool(a, self._wpk[name + ".conv2.f"], P[name + ".conv2.bias"], h, sc, out, c, self.slope,
+                                        p16=self.p16)
             elif pool == 2:
                 c = torch.empty_like(a)
                 with self._t("conv3x3_fwd", N, hk, self._conv_flops(N, hk), self._act_bytes(N, hk, 2)):
-                    hp.conv3x3_fwd(a, self._wpk[name + ".conv2.f"], P[name + ".conv2.bias"], F_, y_full=c, slope=self.slope, x3=self.x3)
+                    hp.conv3x3_fwd(a, self._wpk[name + ".conv2.f"], P[name + ".conv2.bias"], F_, y_full=c, slope=self.slope, x3=self.x3,
+                                   p16=self.p16)
                 with self._t("tail_fwd", N, hk, 0.0, self._act_bytes(N, hk, 2.25)):
                     hp.block_tail_fwd(c, h, sc, out, 2)
             else:
                 c = torch.empty_like(a) if save else None
                 with self._t("conv3x3_fwd", N, hk, self._conv_flops(N, hk), self._act_bytes(N, hk, 4 if save else 3)):
                     hp.conv3x3_fwd(a, self._wpk[name + ".conv2.f"], P[name + ".conv2.bias"], F_, y_full=c, skip=h,
-                                   drop_scale=sc, y_out=out, slope=self.slope, x3=self.x3)
+                                   drop_scale=sc, y_out=out, slope=self.slope, x3=self.x3, p16=self.p16)
             if save:
                 saved["blocks"].append((h, a, c))
             h = out
@@ -470,7 +478,19 @@ class ConvStack:
                  after_block=None) -> None:
         """dy = d loss / d y (N,5,S,S).  Writes every parameter gradient into G[name]
         (overwrites; same names/shapes as P).  `after_block(k)` is called once block k's
-        gradients have been enqueued (data-parallel bucket launch)."""
+        gradients have been enqueued (data-parallel bucket launch).  Runs in the precision the forward pass ran in
+        (saved["p16"]), whatever set_precision() said since."""
+        p16 = bool(saved.get("p16", self.p16))
+        if p16 and not self.x3:
+            raise ValueError("backward: the saved pass ran in precision16, which this engine cannot run")
+        keep = self.p16
+        self.p16 = p16
+        try:
+            self._backward(saved, dy, P, G, after_block)
+        finally:
+            self.p16 = keep
+
+    def _backward(self, saved, dy, P, G, after_block) -> None:
         g = self.geo
         F_ = g.filters
         x, masks = saved["x"], saved["masks"]
@@ -517,7 +537,8 @@ class ConvStack:
                     wsb_ = self._workspace("wgrad_batched", hp.conv3x3_wgrad_batched_ws_bytes(len(grp), N, F_, F_, hk_, hk_), dev)
                     with self._t("conv3x3_wgrad", N, hk_, fl_ * len(grp), self._act_bytes(N, hk_, 2) * len(grp)):
                         hp.conv3x3_wgrad_batched([p_[0] for p_ in grp], [p_[1] for p_ in grp],
-                                                 [G[p_[2] + ".weight"] for p_ in grp], [G[p_[2] + ".bias"] for p_ in grp], wsb_)
+                                                 [G[p_[2] + ".weight"] for p_ in grp], [G[p_[2] + ".bias"] for p_ in grp], wsb_,
+                                                 p16=self.p16)
             if side is not None:
                 side_keep.extend(pending)
             pending.clear()
@@ -684,17 +705,17 @@ class ConvStack:
                     hp.conv3x3_wgrad(a, dz2, G[name + ".conv2.weight"], G[name + ".conv2.bias"], wws)
             dz1 = torch.empty_like(a)
             with self._t("conv3x3_dgrad", N, hk, fl, self._act_bytes(N, hk, 3)):
-                hp.conv3x3_dgrad(dz2, self._wpk[name + ".conv2.b"], F_, dz1, act=a, slope=self.slope, x3=self.x3)
+                hp.conv3x3_dgrad(dz2, self._wpk[name + ".conv2.b"], F_, dz1, act=a, slope=self.slope, x3=self.x3, p16=self.p16)
             if not batched:
                 with self._t("conv3x3_wgrad", N, hk, fl, self._act_bytes(N, hk, 2)):
                     hp.conv3x3_wgrad(xin, dz1, G[name + ".conv1.weight"], G[name + ".conv1.bias"], wws)
             dx = torch.empty_like(a) if batched else dz2      # batched: dz2 stays alive until the flush
             if fused_pool:
                 with self._t("conv3x3_dgrad_unpool", N, hk, fl, self._act_bytes(N, hk, 2 + 0.25 + 1 / 16)):
-                    hp.conv3x3_dgrad_unpool(dz1, self._wpk[name + ".conv1.b"], F_, dout, c, dx, self.slope)
+                    hp.conv3x3_dgrad_unpool(dz1, self._wpk[name + ".conv1.b"], F_, dout, c, dx, self.slope, p16=self.p16)
             else:
                 with self._t("conv3x3_dgrad", N, hk, fl, self._act_bytes(N, hk, 3)):
-                    hp.conv3x3_dgrad(dz1, self._wpk[name + ".conv1.b"], F_, dx, add=de, slope=self.slope, x3=self.x3)
+                    hp.conv3x3_dgrad(dz1, self._wpk[name + ".conv1.b"], F_, dx, add=de, slope=self.slope, x3=self.x3, p16=self.p16)
             dout = dx
             if batched:
                 pending.append((a, dz2, name + ".conv2"))

@@ -67,4 +67,6 @@ int fdet_x3_sb_pool_run(fdet::ConvArgs a, fdet::PoolArgs q, hipStream_t st);
 // instantiation for (MT, NW, NT, VW, seg) and launches it
 #define X3_DECL_LAUNCH(M_) int fdet_x3_launch_m##M_(const X3Args& p, int MT, int NW, int NT, int VW, bool seg, size_t lds, int grid, hipStream_t st);
 X3_DECL_LAUNCH(0) X3_DECL_LAUNCH(1) X3_DECL_LAUNCH(2) X3_DECL_LAUNCH(3) X3_DECL_LAUNCH(4) X3_DECL_LAUNCH(5)
+// ... and their precision16 (one bf16 pass) forms, fdet_conv3x3_x3_m<MODE>_bf16.hip
+X3_DECL_LAUNCH(0_bf16) X3_DECL_LAUNCH(1_bf16) X3_DECL_LAUNCH(2_bf16) X3_DECL_LAUNCH(3_bf16) X3_DECL_LAUNCH(4_bf16) X3_DECL_LAUNCH(5_bf16)
 #undef X3_DECL_LAUNCH

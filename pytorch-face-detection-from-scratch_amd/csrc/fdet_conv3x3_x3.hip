@@ -71,7 +71,7 @@ int run_x3(ConvArgs a, hipStream_t st) {
     if (a.W <= 64 && kernel_choice != 'g') {
       // ping-pong kernel first (one 8-wave workgroup per CU, barrier-enforced MFMA / memory alternation), then the
       // round-1 small-tile kernel (FDET_CONV_KERNEL=s), then the general persistent kernel (=g)
-      if (kernel_choice != 's') {
+      if (kernel_choice != 's' && !a.p16) {           // (the ping-pong kernel has no precision16 form)
         const int rc = fdet_x3_pp_run(a, PoolArgs{nullptr, nullptr, nullptr, nullptr}, st);
         if (rc != 1) return rc;
       }
@@ -187,6 +187,16 @@ int run_x3(ConvArgs a, hipStream_t st) {
   if (const char* e = getenv("FDET_CONV_STAGGER")) p.c.stagger = atoi(e);
   const bool seg = bestNSEG > 1;
   p.stamps = g_probe_stamps;
+  if (a.p16) {
+    switch (a.mode) {
+      case EPI_FWD_FULL: return fdet_x3_launch_m1_bf16(p, MT, NW, NT, VW, seg, lds, grid, st);
+      case EPI_FWD_BOTH: return fdet_x3_launch_m2_bf16(p, MT, NW, NT, VW, seg, lds, grid, st);
+      case EPI_FWD_OUT: return fdet_x3_launch_m3_bf16(p, MT, NW, NT, VW, seg, lds, grid, st);
+      case EPI_DGRAD_ACT: return fdet_x3_launch_m4_bf16(p, MT, NW, NT, VW, seg, lds, grid, st);
+      case EPI_DGRAD_ADD: return fdet_x3_launch_m5_bf16(p, MT, NW, NT, VW, seg, lds, grid, st);
+      default: return fdet_x3_launch_m0_bf16(p, MT, NW, NT, VW, seg, lds, grid, st);
+    }
+  }
   switch (a.mode) {
     case EPI_FWD_FULL: return fdet_x3_launch_m1(p, MT, NW, NT, VW, seg, lds, grid, st);
     case EPI_FWD_BOTH: return fdet_x3_launch_m2(p, MT, NW, NT, VW, seg, lds, grid, st);
@@ -266,9 +276,9 @@ extern "C" int fdet_pack_conv3x3_weights_bf16x3_batched(const float* const* h_w,
   return FDET_OK;
 }
 
-extern "C" int fdet_conv3x3_fwd_bf16x3(const float* x, const void* wpk, const float* bias, float* y_full,
-                                       const float* skip, const float* drop_scale, float* y_out, int N, int Cin,
-                                       int Cout, int H, int W, int pool, float slope, void* stream) {
+static int conv3x3_fwd_x3(const float* x, const void* wpk, const float* bias, float* y_full, const float* skip,
+                          const float* drop_scale, float* y_out, int N, int Cin, int Cout, int H, int W, int pool, float slope,
+                          int p16, void* stream) {
   FDET_REQUIRE(x && wpk && (y_full || y_out), "conv3x3_fwd_bf16x3: null pointer");
   FDET_REQUIRE(N > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0 && Cin % 16 == 0 && Cout % 16 == 0,
                "conv3x3_fwd_bf16x3: unsupported shape N=%d Cin=%d Cout=%d H=%d W=%d (channels must be multiples of 16)",
@@ -277,15 +287,29 @@ extern "C" int fdet_conv3x3_fwd_bf16x3(const float* x, const void* wpk, const fl
   ConvArgs a{};
   a.x = x; a.wpk = (const float*)wpk; a.bias = bias; a.y_full = y_full; a.skip = skip; a.scale = drop_scale;
   a.y_out = y_out; a.act = nullptr; a.N = N; a.Cin = Cin; a.Cout = Cout; a.H = H; a.W = W; a.dgrad = 0; a.slope = slope;
+  a.p16 = p16;
   return run_x3(a, (hipStream_t)stream);
 }
 
+extern "C" int fdet_conv3x3_fwd_bf16x3(const float* x, const void* wpk, const float* bias, float* y_full,
+                                       const float* skip, const float* drop_scale, float* y_out, int N, int Cin,
+                                       int Cout, int H, int W, int pool, float slope, void* stream) {
+  return conv3x3_fwd_x3(x, wpk, bias, y_full, skip, drop_scale, y_out, N, Cin, Cout, H, W, pool, slope, 0, stream);
+}
+
+extern "C" int fdet_conv3x3_fwd_bf16(const float* x, const void* wpk, const float* bias, float* y_full,
+                                     const float* skip, const float* drop_scale, float* y_out, int N, int Cin,
+                                     int Cout, int H, int W, int pool, float slope, void* stream) {
+  return conv3x3_fwd_x3(x, wpk, bias, y_full, skip, drop_scale, y_out, N, Cin, Cout, H, W, pool, slope, 1, stream);
+}
+
 // pooled-block modes: aligned-band small-tile kernel (two workgroups per CU), or the ping-pong kernel (FDET_POOL_KERNEL=pp)
+// (precision16 always takes the aligned-band kernel: the ping-pong kernel has no one-pass form)
 static int run_x3_pooled(const ConvArgs& a, const PoolArgs& q, hipStream_t st) {
   static const bool use_pp = [] { const char* e = getenv("FDET_POOL_KERNEL"); return e && e[0] == 'p'; }();
-  if (!use_pp) {
+  if (!use_pp || a.p16) {
     const int rc = fdet_x3_sb_pool_run(a, q, st);
-    if (rc != 1) return rc;
+    if (rc != 1 || a.p16) return rc;
   }
   return fdet_x3_pp_run(a, q, st);
 }
@@ -302,9 +326,9 @@ extern "C" int fdet_conv3x3_pool_fusion_ok(int N, int Cin, int Cout, int H, int 
   return bands < (1 << 20) ? 1 : 0;
 }
 
-extern "C" int fdet_conv3x3_fwd_pool_bf16x3(const float* x, const void* wpk, const float* bias, const float* skip,
-                                            const float* drop_scale, float* out_pooled, unsigned char* route, int N,
-                                            int Cin, int Cout, int H, int W, float slope, void* stream) {
+static int conv3x3_fwd_pool_x3(const float* x, const void* wpk, const float* bias, const float* skip, const float* drop_scale,
+                               float* out_pooled, unsigned char* route, int N, int Cin, int Cout, int H, int W, float slope,
+                               int p16, void* stream) {
   FDET_REQUIRE(x && wpk && bias && skip && out_pooled, "conv3x3_fwd_pool_bf16x3: null pointer");
   FDET_REQUIRE(N > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0 && Cin % 16 == 0 && Cout % 32 == 0 && !(H & 1) && !(W & 1),
                "conv3x3_fwd_pool_bf16x3: unsupported shape N=%d Cin=%d Cout=%d H=%d W=%d (even maps, Cin %% 16 == 0, Cout %% 32 == 0)",
@@ -312,30 +336,66 @@ extern "C" int fdet_conv3x3_fwd_pool_bf16x3(const float* x, const void* wpk, con
   ConvArgs a{};
   a.x = x; a.wpk = (const float*)wpk; a.bias = bias; a.y_full = nullptr; a.skip = skip; a.scale = drop_scale;
   a.y_out = nullptr; a.act = nullptr; a.N = N; a.Cin = Cin; a.Cout = Cout; a.H = H; a.W = W; a.dgrad = 0; a.slope = slope;
+  a.p16 = p16;
   const int rc = run_x3_pooled(a, PoolArgs{out_pooled, route, nullptr, nullptr}, (hipStream_t)stream);
-  return rc == 1 ? fail(FDET_EINVAL, "conv3x3_fwd_pool_bf16x3: no tiling for H=%d W=%d", H, W) : rc;
+  return rc == 1 ? fail(FDET_EINVAL, "conv3x3_fwd_pool_bf16%s: no tiling for H=%d W=%d", p16 ? "" : "x3", H, W) : rc;
 }
 
-extern "C" int fdet_conv3x3_dgrad_unpool_bf16x3(const float* dz, const void* wpk, const float* dout_pooled,
-                                                const unsigned char* route, float* dx, int N, int Cin, int Cout,
-                                                int H, int W, float slope, void* stream) {
+extern "C" int fdet_conv3x3_fwd_pool_bf16x3(const float* x, const void* wpk, const float* bias, const float* skip,
+                                            const float* drop_scale, float* out_pooled, unsigned char* route, int N,
+                                            int Cin, int Cout, int H, int W, float slope, void* stream) {
+  return conv3x3_fwd_pool_x3(x, wpk, bias, skip, drop_scale, out_pooled, route, N, Cin, Cout, H, W, slope, 0, stream);
+}
+
+extern "C" int fdet_conv3x3_fwd_pool_bf16(const float* x, const void* wpk, const float* bias, const float* skip,
+                                          const float* drop_scale, float* out_pooled, unsigned char* route, int N,
+                                          int Cin, int Cout, int H, int W, float slope, void* stream) {
+  return conv3x3_fwd_pool_x3(x, wpk, bias, skip, drop_scale, out_pooled, route, N, Cin, Cout, H, W, slope, 1, stream);
+}
+
+static int conv3x3_dgrad_unpool_x3(const float* dz, const void* wpk, const float* dout_pooled, const unsigned char* route,
+                                   float* dx, int N, int Cin, int Cout, int H, int W, float slope, int p16, void* stream) {
   FDET_REQUIRE(dz && wpk && dout_pooled && route && dx, "conv3x3_dgrad_unpool_bf16x3: null pointer");
   FDET_REQUIRE(N > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0 && Cin % 32 == 0 && Cout % 16 == 0 && !(H & 1) && !(W & 1),
                "conv3x3_dgrad_unpool_bf16x3: unsupported shape N=%d Cin=%d Cout=%d H=%d W=%d", N, Cin, Cout, H, W);
   ConvArgs a{};
   a.x = dz; a.wpk = (const float*)wpk; a.bias = nullptr; a.y_full = dx; a.skip = nullptr; a.scale = nullptr; a.y_out = nullptr;
   a.act = nullptr; a.N = N; a.Cin = Cout; a.Cout = Cin; a.H = H; a.W = W; a.dgrad = 1; a.slope = slope;
+  a.p16 = p16;
   const int rc = run_x3_pooled(a, PoolArgs{nullptr, nullptr, dout_pooled, route}, (hipStream_t)stream);
-  return rc == 1 ? fail(FDET_EINVAL, "conv3x3_dgrad_unpool_bf16x3: no tiling for H=%d W=%d", H, W) : rc;
+  return rc == 1 ? fail(FDET_EINVAL, "conv3x3_dgrad_unpool_bf16%s: no tiling for H=%d W=%d", p16 ? "" : "x3", H, W) : rc;
 }
 
-extern "C" int fdet_conv3x3_dgrad_bf16x3(const float* dz, const void* wpk, const float* act, const float* add,
-                                         float* dx, int N, int Cin, int Cout, int H, int W, float slope, void* stream) {
+extern "C" int fdet_conv3x3_dgrad_unpool_bf16x3(const float* dz, const void* wpk, const float* dout_pooled,
+                                                const unsigned char* route, float* dx, int N, int Cin, int Cout,
+                                                int H, int W, float slope, void* stream) {
+  return conv3x3_dgrad_unpool_x3(dz, wpk, dout_pooled, route, dx, N, Cin, Cout, H, W, slope, 0, stream);
+}
+
+extern "C" int fdet_conv3x3_dgrad_unpool_bf16(const float* dz, const void* wpk, const float* dout_pooled,
+                                              const unsigned char* route, float* dx, int N, int Cin, int Cout,
+                                              int H, int W, float slope, void* stream) {
+  return conv3x3_dgrad_unpool_x3(dz, wpk, dout_pooled, route, dx, N, Cin, Cout, H, W, slope, 1, stream);
+}
+
+static int conv3x3_dgrad_x3(const float* dz, const void* wpk, const float* act, const float* add, float* dx, int N, int Cin,
+                            int Cout, int H, int W, float slope, int p16, void* stream) {
   FDET_REQUIRE(dz && wpk && dx, "conv3x3_dgrad_bf16x3: null pointer");
   FDET_REQUIRE(N > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0 && Cin % 16 == 0 && Cout % 16 == 0,
                "conv3x3_dgrad_bf16x3: unsupported shape N=%d Cin=%d Cout=%d H=%d W=%d", N, Cin, Cout, H, W);
   ConvArgs a{};
   a.x = dz; a.wpk = (const float*)wpk; a.bias = nullptr; a.y_full = dx; a.skip = add; a.scale = nullptr; a.y_out = nullptr;
   a.act = act; a.N = N; a.Cin = Cout; a.Cout = Cin; a.H = H; a.W = W; a.dgrad = 1; a.slope = slope;
+  a.p16 = p16;
   return run_x3(a, (hipStream_t)stream);
+}
+
+extern "C" int fdet_conv3x3_dgrad_bf16x3(const float* dz, const void* wpk, const float* act, const float* add,
+                                         float* dx, int N, int Cin, int Cout, int H, int W, float slope, void* stream) {
+  return conv3x3_dgrad_x3(dz, wpk, act, add, dx, N, Cin, Cout, H, W, slope, 0, stream);
+}
+
+extern "C" int fdet_conv3x3_dgrad_bf16(const float* dz, const void* wpk, const float* act, const float* add,
+                                       float* dx, int N, int Cin, int Cout, int H, int W, float slope, void* stream) {
+  return conv3x3_dgrad_x3(dz, wpk, act, add, dx, N, Cin, Cout, H, W, slope, 1, stream);
 }

@@ -157,8 +157,9 @@ __device__ __forceinline__ void epi_loads(const ARGS& p, const EpiGeo& e, f32x4 
   }
 }
 
-// part 2: transposes, arithmetic, stores
-template <int MT, int MODE, class ARGS>
+// part 2: transposes, arithmetic, stores (P16: stored values rounded to bf16 -- after the max and the routing bytes, which
+// therefore match the fp32-grade kernel's on the same accumulators)
+template <int MT, int MODE, class ARGS, bool P16 = false>
 __device__ __forceinline__ void epi_finish(const ARGS& p, const EpiGeo& e, f32x16 (&acc)[MT][2], f32x4 (&u)[MT][2][4],
                                            float (&dg)[MT][4][2], unsigned (&mk)[MT][4], const float (&bzm)[MT][4],
                                            const float (&scm)[MT][4], int img, int cob0, int l31, int half) {
@@ -238,6 +239,8 @@ __device__ __forceinline__ void epi_finish(const ARGS& p, const EpiGeo& e, f32x1
                                    (t[1][g][2 * pc] > 0.f ? 4 : 0) | (t[1][g][2 * pc + 1] > 0.f ? 8 : 0) | (arg << 4));
         }
         const int pi = e.pidx0 + (32 * m + 8 * g) * HWp;
+        po[0] = st16<P16>(po[0]);
+        po[1] = st16<P16>(po[1]);
         if (e.npair == 2) {
           __builtin_memcpy(g_pool + pi, po, 8);
           if (g_mk) { g_mk[pi] = pm[0]; g_mk[pi + 1] = pm[1]; }
@@ -249,6 +252,10 @@ __device__ __forceinline__ void epi_finish(const ARGS& p, const EpiGeo& e, f32x1
     } else {
 #pragma unroll
       for (int n = 0; n < 2; ++n) {
+        if (P16) {
+#pragma unroll
+          for (int g = 0; g < 4; ++g) { t[n][g] = st16<P16>(t[n][g]); u[m][n][g] = st16<P16>(u[m][n][g]); }
+        }
 #define PP_ST(BYTES)                                                                               \
   _Pragma("unroll") for (int g = 0; g < 4; ++g) {                                                  \
     const int idx_ = e.idx0[n] + (32 * m + 8 * g) * HW;                                            \

@@ -26,7 +26,11 @@
 // the MFMAs of the later taps.  One barrier per chunk.
 // This file is included by fdet_conv3x3_x3_m<MODE>.hip with X3_MODE defined (one translation unit
 // per epilogue mode keeps each kernel's register allocation independent and the build parallel).
+// X3_P16 = 1 (fdet_conv3x3_x3_m<MODE>_bf16.hip) instantiates the precision16 form instead: one bf16 pass (P16 below).
 #include "fdet_conv3x3_x3.h"
+#ifndef X3_P16
+#define X3_P16 0
+#endif
 
 namespace {
 
@@ -85,7 +89,7 @@ __device__ __forceinline__ void quad_transpose(f32x16& a, bool b0, bool b1) {
 // {quad} x {half} of one instruction cover 32 consecutive positions (128 B) of ONE channel.
 // Memory phases are batched explicitly (all loads of rows [N0,N1), then all stores): a load -> use ->
 // store chain per 16 bytes would expose one HBM round trip each.
-template <int MT, int NT, int VW, int MODE, int N0, int N1>
+template <int MT, int NT, int VW, int MODE, int N0, int N1, bool P16>
 __device__ __forceinline__ void epilogue_rows(const X3Args& p, f32x16 (&acc)[NT][MT], int v0, int x0, int cw, int cob,
                                               int qwave, int l31, int half) {
   const ConvArgs& a = p.c;
@@ -189,8 +193,8 @@ __device__ __forceinline__ void epilogue_rows(const X3Args& p, f32x16 (&acc)[NT]
     if (co[m][k] < 0) continue;                                                                    \
     const int idx_ = idx0[n] + co[m][k] * HW;                                                      \
     const f32x4 z_ = {acc[n][m][4 * k], acc[n][m][4 * k + 1], acc[n][m][4 * k + 2], acc[n][m][4 * k + 3]}; \
-    if (st_full) stv<NV_, AL>(g_full + idx_, z_);                                                  \
-    if (st_out) stv<NV_, AL>(g_out + idx_, ta[n - N0][m][k]);                                      \
+    if (st_full) stv<NV_, AL>(g_full + idx_, st16<P16>(z_));                                       \
+    if (st_out) stv<NV_, AL>(g_out + idx_, st16<P16>(ta[n - N0][m][k]));                           \
   }
 #pragma unroll
   for (int n = N0; n < N1; ++n) {
@@ -202,32 +206,35 @@ __device__ __forceinline__ void epilogue_rows(const X3Args& p, f32x16 (&acc)[NT]
 #undef X3_ST_ROWS
 }
 
-template <int MT, int NT, int VW, int MODE>
+template <int MT, int NT, int VW, int MODE, bool P16>
 __device__ __forceinline__ void epilogue_x3(const X3Args& p, f32x16 (&acc)[NT][MT], int v0, int x0, int cw, int cob,
                                             int qwave, int l31, int half) {
   if (MODE != EPI_GENERIC) {                              // two 32-position row blocks per memory batch
-    epilogue_rows<MT, NT, VW, MODE, 0, (NT > 2 ? 2 : NT)>(p, acc, v0, x0, cw, cob, qwave, l31, half);
-    if (NT > 2) epilogue_rows<MT, NT, VW, MODE, (NT > 2 ? 2 : 0), (NT > 2 ? 4 : 1)>(p, acc, v0, x0, cw, cob, qwave, l31, half);
+    epilogue_rows<MT, NT, VW, MODE, 0, (NT > 2 ? 2 : NT), P16>(p, acc, v0, x0, cw, cob, qwave, l31, half);
+    if (NT > 2) epilogue_rows<MT, NT, VW, MODE, (NT > 2 ? 2 : 0), (NT > 2 ? 4 : 1), P16>(p, acc, v0, x0, cw, cob, qwave, l31, half);
   } else {                                                // slow path: one 32-position row block at a time
-    epilogue_rows<MT, NT, VW, MODE, 0, 1>(p, acc, v0, x0, cw, cob, qwave, l31, half);
-    if (NT > 1) epilogue_rows<MT, NT, VW, MODE, (NT > 1 ? 1 : 0), (NT > 1 ? 2 : 1)>(p, acc, v0, x0, cw, cob, qwave, l31, half);
+    epilogue_rows<MT, NT, VW, MODE, 0, 1, P16>(p, acc, v0, x0, cw, cob, qwave, l31, half);
+    if (NT > 1) epilogue_rows<MT, NT, VW, MODE, (NT > 1 ? 1 : 0), (NT > 1 ? 2 : 1), P16>(p, acc, v0, x0, cw, cob, qwave, l31, half);
     if (NT > 2) {
-      epilogue_rows<MT, NT, VW, MODE, (NT > 2 ? 2 : 0), (NT > 2 ? 3 : 1)>(p, acc, v0, x0, cw, cob, qwave, l31, half);
-      epilogue_rows<MT, NT, VW, MODE, (NT > 2 ? 3 : 0), (NT > 2 ? 4 : 1)>(p, acc, v0, x0, cw, cob, qwave, l31, half);
+      epilogue_rows<MT, NT, VW, MODE, (NT > 2 ? 2 : 0), (NT > 2 ? 3 : 1), P16>(p, acc, v0, x0, cw, cob, qwave, l31, half);
+      epilogue_rows<MT, NT, VW, MODE, (NT > 2 ? 3 : 0), (NT > 2 ? 4 : 1), P16>(p, acc, v0, x0, cw, cob, qwave, l31, half);
     }
   }
 }
 
 // NW waves per workgroup (4: one per SIMD, 512 registers; 8: two per SIMD, 256 registers each -- the
 // partner wave's VALU / LDS / memory instructions fill the gaps of this wave's MFMA stream)
-template <int MT, int NT, int VW, bool SEG, int NW, int MODE>
+// P16 (precision16): one bf16 pass -- operands rounded to bf16 (hi only: no lo staging, the panels' lo half is not read),
+// one MFMA per (n, m) tile, fp32 accumulation and epilogue, stored values rounded to bf16.
+template <int MT, int NT, int VW, bool SEG, int NW, int MODE, bool P16 = false>
 __global__ void __launch_bounds__(NW * 64, 1)
 k_conv3x3_x3(const X3Args p) {
   constexpr int NTHR = NW * 64;
   constexpr int NBS = nbs_of(NW, NT, VW);
   constexpr int MB = MT * 32;
   constexpr int A_UNITS = 9 * 2 * MB;                 // 16-byte units per weight array per chunk
-  constexpr int NA = (2 * A_UNITS + NTHR - 1) / NTHR; // hi and lo
+  constexpr int NAU = P16 ? A_UNITS : 2 * A_UNITS;    // weight units staged per chunk: hi and lo (P16: hi only)
+  constexpr int NA = (NAU + NTHR - 1) / NTHR;
   constexpr int NJOBS = NA + NBS * VW + (SEG ? 1 : 0);
   using VT = typename Vec<VW>::T;
   const ConvArgs& a = p.c;
@@ -330,7 +337,7 @@ k_conv3x3_x3(const X3Args p) {
 #define X3_ISSUE_LOADS(C16, COB)                                                                   \
   {                                                                                                \
     _Pragma("unroll") for (int s_ = 0; s_ < NA; ++s_) {                                            \
-      const int u_ = min(tid + s_ * NTHR, 2 * A_UNITS - 1);                                        \
+      const int u_ = min(tid + s_ * NTHR, NAU - 1);                                                \
       const int lo_ = u_ >= A_UNITS ? 1 : 0;                                                       \
       const int r_ = u_ - lo_ * A_UNITS;                                                           \
       const int th_ = r_ / MB, co_ = r_ - th_ * MB;                                                \
@@ -353,26 +360,28 @@ k_conv3x3_x3(const X3Args p) {
   {                                                                                                \
     if ((J) < NA) {                                                                                \
       const int u_ = tid + (J) * NTHR;                                                             \
-      lds[((LIVE) && u_ < 2 * A_UNITS) ? (NB) + u_ : junk] = pa[(J) < NA ? (J) : 0];               \
+      lds[((LIVE) && u_ < NAU) ? (NB) + u_ : junk] = pa[(J) < NA ? (J) : 0];                       \
     } else if ((J) < NA + NBS * VW) {                                                              \
       const int s_ = ((J) - NA) / VW < NBS ? ((J) - NA) / VW : 0, i_ = ((J) - NA) % VW;            \
       const bool w_ = (LIVE) && b_tr[s_] >= 0 && b_col[s_] + i_ < n_cw;                            \
       float f_[8];                                                                                 \
       _Pragma("unroll") for (int j_ = 0; j_ < 8; ++j_) f_[j_] = b_ok[s_] ? vget<VW>(pb[s_][j_], i_) : 0.f; \
       bf16x8 hi_, lo_;                                                                             \
-      split8(f_, hi_, lo_);                                                                        \
+      if (P16) { _Pragma("unroll") for (int j_ = 0; j_ < 8; ++j_) hi_[j_] = (__bf16)f_[j_]; }      \
+      else split8(f_, hi_, lo_);                                                                   \
       const int d_ = (NB) + 2 * A_UNITS + b_dst[s_] + i_;                                          \
       lds[w_ ? d_ : junk] = hi_;                                                                   \
-      lds[w_ ? d_ + 2 * PT : junk] = lo_;                                                          \
+      if (!P16) lds[w_ ? d_ + 2 * PT : junk] = lo_;                                                \
     } else if (SEG) {                                                                              \
       const bool w_ = (LIVE) && h_tr >= 0;                                                         \
       float f_[8];                                                                                 \
       _Pragma("unroll") for (int j_ = 0; j_ < 8; ++j_) f_[j_] = h_ok ? ph[j_] : 0.f;               \
       bf16x8 hi_, lo_;                                                                             \
-      split8(f_, hi_, lo_);                                                                        \
+      if (P16) { _Pragma("unroll") for (int j_ = 0; j_ < 8; ++j_) hi_[j_] = (__bf16)f_[j_]; }      \
+      else split8(f_, hi_, lo_);                                                                   \
       const int d_ = (NB) + 2 * A_UNITS + h_dst + (h_side ? n_cw + 1 : 0);                         \
       lds[w_ ? d_ : junk] = hi_;                                                                   \
-      lds[w_ ? d_ + 2 * PT : junk] = lo_;                                                          \
+      if (!P16) lds[w_ ? d_ + 2 * PT : junk] = lo_;                                                \
     }                                                                                              \
   }
 
@@ -431,9 +440,9 @@ k_conv3x3_x3(const X3Args p) {
       // fragments of tap t+1 are fetched before the MFMAs of tap t
       bf16x8 wh[2][MT], wl[2][MT], xh[2][NT], xl[2][NT];
 #pragma unroll
-      for (int m = 0; m < MT; ++m) { wh[0][m] = Ww[m * 32]; wl[0][m] = Ww[A_UNITS + m * 32]; }
+      for (int m = 0; m < MT; ++m) { wh[0][m] = Ww[m * 32]; if (!P16) wl[0][m] = Ww[A_UNITS + m * 32]; }
 #pragma unroll
-      for (int n = 0; n < NT; ++n) { xh[0][n] = Xw[tapoff[0] + n * 32]; xl[0][n] = Xw[2 * PT + tapoff[0] + n * 32]; }
+      for (int n = 0; n < NT; ++n) { xh[0][n] = Xw[tapoff[0] + n * 32]; if (!P16) xl[0][n] = Xw[2 * PT + tapoff[0] + n * 32]; }
 #pragma unroll
       for (int t = 0; t < 9; ++t) {
         const int cur = t & 1, nxt = cur ^ 1;
@@ -441,12 +450,12 @@ k_conv3x3_x3(const X3Args p) {
 #pragma unroll
           for (int m = 0; m < MT; ++m) {
             wh[nxt][m] = Ww[(t + 1) * 2 * MB + m * 32];
-            wl[nxt][m] = Ww[A_UNITS + (t + 1) * 2 * MB + m * 32];
+            if (!P16) wl[nxt][m] = Ww[A_UNITS + (t + 1) * 2 * MB + m * 32];
           }
 #pragma unroll
           for (int n = 0; n < NT; ++n) {
             xh[nxt][n] = Xw[tapoff[t + 1] + n * 32];
-            xl[nxt][n] = Xw[2 * PT + tapoff[t + 1] + n * 32];
+            if (!P16) xl[nxt][n] = Xw[2 * PT + tapoff[t + 1] + n * 32];
           }
         }
         __builtin_amdgcn_sched_barrier(0);
@@ -460,14 +469,16 @@ k_conv3x3_x3(const X3Args p) {
         for (int n = 0; n < NT; ++n)
 #pragma unroll
           for (int m = 0; m < MT; ++m) {
-            acc[n][m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xh[cur][n], wl[cur][m], acc[n][m], 0, 0, 0);
-            acc[n][m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xl[cur][n], wh[cur][m], acc[n][m], 0, 0, 0);
+            if (!P16) {
+              acc[n][m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xh[cur][n], wl[cur][m], acc[n][m], 0, 0, 0);
+              acc[n][m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xl[cur][n], wh[cur][m], acc[n][m], 0, 0, 0);
+            }
             acc[n][m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xh[cur][n], wh[cur][m], acc[n][m], 0, 0, 0);
           }
         if (t >= TW0) {
           // weave: per MFMA a few VALU (split) and now and then one LDS write
 #pragma unroll
-          for (int i = 0; i < 3 * MT * NT; ++i) {
+          for (int i = 0; i < (P16 ? 1 : 3) * MT * NT; ++i) {
             __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
             __builtin_amdgcn_sched_group_barrier(0x002, 4, 0);
             if ((i & 1) == 0) __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);
@@ -483,7 +494,7 @@ k_conv3x3_x3(const X3Args p) {
     if (tcount == 1) X3_STAMP(7)
 
     // ---- epilogue of this tile
-    epilogue_x3<MT, NT, VW, MODE>(p, acc, v0, x0, cw, cob, qwave, l31, half);
+    epilogue_x3<MT, NT, VW, MODE, P16>(p, acc, v0, x0, cw, cob, qwave, l31, half);
 #pragma unroll
     for (int n = 0; n < NT; ++n)
 #pragma unroll
@@ -507,16 +518,21 @@ k_conv3x3_x3(const X3Args p) {
 
 template <int MT, int NT, int VW, bool SEG, int NW>
 int launch_x3(const X3Args& p, size_t lds, int grid, hipStream_t st) {
-  (void)hipFuncSetAttribute((const void*)k_conv3x3_x3<MT, NT, VW, SEG, NW, X3_MODE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  hipLaunchKernelGGL((k_conv3x3_x3<MT, NT, VW, SEG, NW, X3_MODE>), dim3(grid), dim3(NW * 64), lds, st, p);
-  return check_launch("fdet_conv3x3_bf16x3");
+  (void)hipFuncSetAttribute((const void*)k_conv3x3_x3<MT, NT, VW, SEG, NW, X3_MODE, X3_P16 != 0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  hipLaunchKernelGGL((k_conv3x3_x3<MT, NT, VW, SEG, NW, X3_MODE, X3_P16 != 0>), dim3(grid), dim3(NW * 64), lds, st, p);
+  return check_launch(X3_P16 ? "fdet_conv3x3_bf16" : "fdet_conv3x3_bf16x3");
 }
 
 }  // namespace
 
 #define X3_CAT2(a, b) a##b
 #define X3_CAT(a, b) X3_CAT2(a, b)
-int X3_CAT(fdet_x3_launch_m, X3_MODE_ID)(const X3Args& p, int MT, int NW, int NT, int VW, bool seg, size_t lds, int grid, hipStream_t st) {
+#if X3_P16
+#define X3_LAUNCH_NAME X3_CAT(X3_CAT(fdet_x3_launch_m, X3_MODE_ID), _bf16)
+#else
+#define X3_LAUNCH_NAME X3_CAT(fdet_x3_launch_m, X3_MODE_ID)
+#endif
+int X3_LAUNCH_NAME(const X3Args& p, int MT, int NW, int NT, int VW, bool seg, size_t lds, int grid, hipStream_t st) {
 #define X3_CASE(M_, W_, N_, V_) \
   if (MT == M_ && NW == W_ && NT == N_ && VW == V_) return seg ? launch_x3<M_, N_, V_, true, W_>(p, lds, grid, st) : launch_x3<M_, N_, V_, false, W_>(p, lds, grid, st);
 #define X3_CASE_NOSEG(M_, W_, N_, V_) \

@@ -66,7 +66,7 @@ __device__ __forceinline__ void quad_transpose4(float (&v)[4], bool b0, bool b1)
 // 4 registers = 4 consecutive positions of one row (WP % 4 == 0, so a quad never straddles rows):
 // 16 memory instructions per tensor instead of 64, each covering 128-byte runs.  Loads of all
 // tiles first, then arithmetic, then stores; the branch on the valid count sits outside the loops.
-template <int MT, int NT, int MODE>
+template <int MT, int NT, int MODE, bool P16 = false>
 __device__ __forceinline__ void epilogue_sb(const ConvArgs& a, f32x16 (&acc)[MT][NT], int v0, int qwave, int cob0,
                                             int l31, int half) {
   const float* __restrict__ g_bias = a.bias;
@@ -140,6 +140,12 @@ __device__ __forceinline__ void epilogue_sb(const ConvArgs& a, f32x16 (&acc)[MT]
           }
           t[m][g][i] = z;
         }
+    if (P16) {
+#pragma unroll
+      for (int m = 0; m < MT; ++m)
+#pragma unroll
+        for (int g = 0; g < 4; ++g) { t[m][g] = st16<P16>(t[m][g]); u[m][g] = st16<P16>(u[m][g]); }
+    }
 #define SB_ST(BYTES)                                                                               \
   _Pragma("unroll") for (int m = 0; m < MT; ++m) _Pragma("unroll") for (int g = 0; g < 4; ++g) {   \
     const int idx_ = idx0[n] + (32 * m + 8 * g) * HW;                                              \
@@ -154,7 +160,9 @@ __device__ __forceinline__ void epilogue_sb(const ConvArgs& a, f32x16 (&acc)[MT]
 // AL (aligned bands): tiles are bands of R rows of ONE image (halo rows outside the image are zeros, no separator rows),
 // a wave owns two adjacent rows x 32 columns (NT == 2), and the epilogue is the shared one of fdet_conv3x3_x3_epi.h,
 // which holds whole 2x2 pooling windows per lane: the pooled-block modes EPI_FWD_POOL / EPI_DGRAD_ADDPOOL.
-template <int MT, int NT, int VW, int MODE, bool AL = false>
+// P16 (precision16): one bf16 pass -- operands rounded to bf16 (the hi part only: no lo staging, the panels' lo half is not
+// read), one MFMA per (m, n) tile, fp32 accumulation and epilogue, stored values rounded to bf16.
+template <int MT, int NT, int VW, int MODE, bool AL = false, bool P16 = false>
 __global__ void __launch_bounds__(NTHR, 2)
 k_conv3x3_x3_sb(const X3SbArgs p) {
   constexpr int NBS = nbs_sb(NT, VW);
@@ -163,7 +171,8 @@ k_conv3x3_x3_sb(const X3SbArgs p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int MB = MT * 32;
   constexpr int A_UNITS = 9 * 2 * MB;                 // 16-byte units per A array per chunk
-  constexpr int NA = (2 * A_UNITS + NTHR - 1) / NTHR; // hi and lo
+  constexpr int NAU = P16 ? A_UNITS : 2 * A_UNITS;    // weight units staged per chunk: hi and lo (P16: hi only)
+  constexpr int NA = (NAU + NTHR - 1) / NTHR;
   const int PT = p.PT, WP = a.WP;
   const int buf_units = 2 * A_UNITS + 4 * PT;         // 16-byte units per buffer
   bf16x8* lds = reinterpret_cast<bf16x8*>(smem);
@@ -237,7 +246,7 @@ k_conv3x3_x3_sb(const X3SbArgs p) {
 #define X3_ISSUE_LOADS(C16)                                                                        \
   {                                                                                                \
     _Pragma("unroll") for (int s_ = 0; s_ < NA; ++s_) {                                            \
-      const int u_ = min(tid + s_ * NTHR, 2 * A_UNITS - 1);                                        \
+      const int u_ = min(tid + s_ * NTHR, NAU - 1);                                                \
       const int lo_ = u_ >= A_UNITS ? 1 : 0;                                                       \
       const int r_ = u_ - lo_ * A_UNITS;                                                           \
       const int th_ = r_ / MB, co_ = r_ - th_ * MB;                                                \
@@ -255,7 +264,7 @@ k_conv3x3_x3_sb(const X3SbArgs p) {
     bf16x8* buf_ = (BUF);                                                                          \
     _Pragma("unroll") for (int s_ = 0; s_ < NA; ++s_) {                                            \
       const int u_ = tid + s_ * NTHR;                                                              \
-      if (u_ < 2 * A_UNITS) buf_[u_] = pa[s_];                                                     \
+      if (u_ < NAU) buf_[u_] = pa[s_];                                                             \
     }                                                                                              \
     bf16x8* B_ = buf_ + 2 * A_UNITS;                                                               \
     _Pragma("unroll") for (int s_ = 0; s_ < NBS; ++s_) {                                           \
@@ -264,9 +273,13 @@ k_conv3x3_x3_sb(const X3SbArgs p) {
           float f_[8];                                                                             \
           _Pragma("unroll") for (int j_ = 0; j_ < 8; ++j_) f_[j_] = b_src[s_] >= 0 ? vget<VW>(pb[s_][j_], i_) : 0.f; \
           bf16x8 hi_, lo_;                                                                         \
-          split8(f_, hi_, lo_);                                                                    \
+          if (P16) {                                                                               \
+            _Pragma("unroll") for (int j_ = 0; j_ < 8; ++j_) hi_[j_] = (__bf16)f_[j_];             \
+          } else {                                                                                 \
+            split8(f_, hi_, lo_);                                                                  \
+            B_[b_dst[s_] + i_ + 2 * PT] = lo_;                                                     \
+          }                                                                                        \
           B_[b_dst[s_] + i_] = hi_;                                                                \
-          B_[b_dst[s_] + i_ + 2 * PT] = lo_;                                                       \
         }                                                                                          \
       }                                                                                            \
     }                                                                                              \
@@ -319,6 +332,20 @@ k_conv3x3_x3_sb(const X3SbArgs p) {
 #pragma unroll
     for (int t = 0; t < 9; ++t) {
       bf16x8 ah[MT], al[MT], bh[NT], bl[NT];
+      if constexpr (P16) {
+#pragma unroll
+        for (int m = 0; m < MT; ++m) ah[m] = Aw[t * 2 * MB + m * 32];
+#pragma unroll
+        for (int n = 0; n < NT; ++n) bh[n] = Bw[tapoff[t] + n * nstride];
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int m = 0; m < MT; ++m)
+#pragma unroll
+          for (int n = 0; n < NT; ++n)
+            acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[m], bh[n], acc[m][n], 0, 0, 0);
+        __builtin_amdgcn_sched_barrier(0);
+        continue;
+      }
 #pragma unroll
       for (int m = 0; m < MT; ++m) ah[m] = Aw[t * 2 * MB + m * 32];
 #pragma unroll
@@ -353,10 +380,10 @@ k_conv3x3_x3_sb(const X3SbArgs p) {
       float dg[MT][4][2], bzm[MT][4], scm[MT][4];
       unsigned mk[MT][4];
       epi_loads<MT, MODE>(p, eg, u, dg, mk, bzm, scm, cur_img, cur_mb * MB, l31, half);
-      epi_finish<MT, MODE>(p, eg, acc, u, dg, mk, bzm, scm, cur_img, cur_mb * MB, l31, half);
+      epi_finish<MT, MODE, X3SbArgs, P16>(p, eg, acc, u, dg, mk, bzm, scm, cur_img, cur_mb * MB, l31, half);
     }
   } else if (MODE != EPI_GENERIC) {
-    epilogue_sb<MT, NT, MODE>(a, acc, cur_v0, qwave, cur_mb * MB, l31, half);
+    epilogue_sb<MT, NT, MODE, P16>(a, acc, cur_v0, qwave, cur_mb * MB, l31, half);
   } else {
     const int qlimit = a.R * WP;
     bool okn[NT];
@@ -372,7 +399,7 @@ k_conv3x3_x3_sb(const X3SbArgs p) {
       basen[n] = ((size_t)img * a.Cout * a.H + oy) * a.W + ox;
       imgn[n] = img;
     }
-    epilogue<MT, NT, EPI_GENERIC>(a, acc, okn, basen, imgn, cur_mb * MB + 4 * half, HW);
+    epilogue<MT, NT, EPI_GENERIC, P16>(a, acc, okn, basen, imgn, cur_mb * MB + 4 * half, HW);
   }
 #pragma unroll
   for (int m = 0; m < MT; ++m)
@@ -383,7 +410,7 @@ k_conv3x3_x3_sb(const X3SbArgs p) {
   }                                      // tile loop
 }
 
-template <int MT, int NT>
+template <int MT, int NT, bool P16 = false>
 int launch_sb(const X3SbArgs& p, int VW, size_t lds, dim3 grid, hipStream_t st) {
   int rc = FDET_OK;
   auto go = [&](auto kern) {
@@ -396,12 +423,12 @@ int launch_sb(const X3SbArgs& p, int VW, size_t lds, dim3 grid, hipStream_t st) 
   };
 #define SB_MODES(V_)                                                                               \
   switch (p.c.mode) {                                                                              \
-    case EPI_FWD_FULL: go(k_conv3x3_x3_sb<MT, NT, V_, EPI_FWD_FULL>); break;                       \
-    case EPI_FWD_BOTH: go(k_conv3x3_x3_sb<MT, NT, V_, EPI_FWD_BOTH>); break;                       \
-    case EPI_FWD_OUT: go(k_conv3x3_x3_sb<MT, NT, V_, EPI_FWD_OUT>); break;                         \
-    case EPI_DGRAD_ACT: go(k_conv3x3_x3_sb<MT, NT, V_, EPI_DGRAD_ACT>); break;                     \
-    case EPI_DGRAD_ADD: go(k_conv3x3_x3_sb<MT, NT, V_, EPI_DGRAD_ADD>); break;                     \
-    default: go(k_conv3x3_x3_sb<MT, NT, V_, EPI_GENERIC>); break;                                  \
+    case EPI_FWD_FULL: go(k_conv3x3_x3_sb<MT, NT, V_, EPI_FWD_FULL, false, P16>); break;                       \
+    case EPI_FWD_BOTH: go(k_conv3x3_x3_sb<MT, NT, V_, EPI_FWD_BOTH, false, P16>); break;                       \
+    case EPI_FWD_OUT: go(k_conv3x3_x3_sb<MT, NT, V_, EPI_FWD_OUT, false, P16>); break;                         \
+    case EPI_DGRAD_ACT: go(k_conv3x3_x3_sb<MT, NT, V_, EPI_DGRAD_ACT, false, P16>); break;                     \
+    case EPI_DGRAD_ADD: go(k_conv3x3_x3_sb<MT, NT, V_, EPI_DGRAD_ADD, false, P16>); break;                     \
+    default: go(k_conv3x3_x3_sb<MT, NT, V_, EPI_GENERIC, false, P16>); break;                                  \
   }
   if (VW == 4) { SB_MODES(4) } else if (VW == 2) { SB_MODES(2) } else { SB_MODES(1) }
 #undef SB_MODES
@@ -410,7 +437,7 @@ int launch_sb(const X3SbArgs& p, int VW, size_t lds, dim3 grid, hipStream_t st) 
 }
 
 // aligned-band variant: the pooled-block modes
-template <int MT>
+template <int MT, bool P16 = false>
 int launch_sb_pool(const X3SbArgs& p, int VW, size_t lds, dim3 grid, hipStream_t st) {
   int rc = FDET_OK;
   auto go = [&](auto kern) {
@@ -423,13 +450,13 @@ int launch_sb_pool(const X3SbArgs& p, int VW, size_t lds, dim3 grid, hipStream_t
   };
 #define SB_PMODES(V_)                                                                              \
   switch (p.c.mode) {                                                                              \
-    case EPI_FWD_POOL: go(k_conv3x3_x3_sb<MT, 2, V_, EPI_FWD_POOL, true>); break;                  \
-    case EPI_DGRAD_ADDPOOL: go(k_conv3x3_x3_sb<MT, 2, V_, EPI_DGRAD_ADDPOOL, true>); break;        \
-    case EPI_FWD_FULL: go(k_conv3x3_x3_sb<MT, 2, V_, EPI_FWD_FULL, true>); break;                  \
-    case EPI_FWD_BOTH: go(k_conv3x3_x3_sb<MT, 2, V_, EPI_FWD_BOTH, true>); break;                  \
-    case EPI_FWD_OUT: go(k_conv3x3_x3_sb<MT, 2, V_, EPI_FWD_OUT, true>); break;                    \
-    case EPI_DGRAD_ACT: go(k_conv3x3_x3_sb<MT, 2, V_, EPI_DGRAD_ACT, true>); break;                \
-    default: go(k_conv3x3_x3_sb<MT, 2, V_, EPI_DGRAD_ADD, true>); break;                           \
+    case EPI_FWD_POOL: go(k_conv3x3_x3_sb<MT, 2, V_, EPI_FWD_POOL, true, P16>); break;                  \
+    case EPI_DGRAD_ADDPOOL: go(k_conv3x3_x3_sb<MT, 2, V_, EPI_DGRAD_ADDPOOL, true, P16>); break;        \
+    case EPI_FWD_FULL: go(k_conv3x3_x3_sb<MT, 2, V_, EPI_FWD_FULL, true, P16>); break;                  \
+    case EPI_FWD_BOTH: go(k_conv3x3_x3_sb<MT, 2, V_, EPI_FWD_BOTH, true, P16>); break;                  \
+    case EPI_FWD_OUT: go(k_conv3x3_x3_sb<MT, 2, V_, EPI_FWD_OUT, true, P16>); break;                    \
+    case EPI_DGRAD_ACT: go(k_conv3x3_x3_sb<MT, 2, V_, EPI_DGRAD_ACT, true, P16>); break;                \
+    default: go(k_conv3x3_x3_sb<MT, 2, V_, EPI_DGRAD_ADD, true, P16>); break;                           \
   }
   if (VW == 4) { SB_PMODES(4) } else if (VW == 2) { SB_PMODES(2) } else { SB_PMODES(1) }
 #undef SB_PMODES
@@ -515,6 +542,12 @@ int fdet_x3_sb_run(ConvArgs a, hipStream_t st) {
   if (force.grid >= 0) gsz = force.grid > 0 ? force.grid : p.ntiles;
   dim3 grid(p.ntiles < gsz ? p.ntiles : gsz, 1);
   p.c.stagger = 0;
+  if (a.p16) {                            // precision16: the one-pass instantiations of the same tilings
+    if (MT == 2 && NT == 2) return launch_sb<2, 2, true>(p, VW, lds, grid, st);
+    if (MT == 2 && NT == 1) return launch_sb<2, 1, true>(p, VW, lds, grid, st);
+    if (MT == 1 && NT == 2) return launch_sb<1, 2, true>(p, VW, lds, grid, st);
+    return launch_sb<1, 1, true>(p, VW, lds, grid, st);
+  }
   if (MT == 2 && NT == 2) return launch_sb<2, 2>(p, VW, lds, grid, st);
   if (MT == 2 && NT == 1) return launch_sb<2, 1>(p, VW, lds, grid, st);
   if (MT == 1 && NT == 2) return launch_sb<1, 2>(p, VW, lds, grid, st);
@@ -572,5 +605,6 @@ int fdet_x3_sb_pool_run(ConvArgs a, PoolArgs q, hipStream_t st) {
   p.ntiles = (int)nbt * p.ncob;
   const int gsz = 2 * sb_num_cus();
   dim3 grid(p.ntiles < gsz ? p.ntiles : gsz, 1);
+  if (a.p16) return MT == 2 ? launch_sb_pool<2, true>(p, VW, lds, grid, st) : launch_sb_pool<1, true>(p, VW, lds, grid, st);
   return MT == 2 ? launch_sb_pool<2>(p, VW, lds, grid, st) : launch_sb_pool<1>(p, VW, lds, grid, st);
 }

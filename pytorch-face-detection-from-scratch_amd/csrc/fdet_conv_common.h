@@ -27,6 +27,7 @@ struct ConvArgs {
   unsigned magic_h1;     // ceil(2^32/(H+1))
   unsigned magic_rows;   // ceil(2^32/(R+2))
   float slope;
+  int p16;               // precision16: the host picks the one-pass (P16) instantiation; kernels never read it
 };
 }  // namespace fdet
 
@@ -62,7 +63,16 @@ enum { EPI_GENERIC = 0,
        EPI_FWD_POOL,    // pool_out = maxpool2x2(z*scale + skip) + routing bytes   (pooled block tail; ping-pong kernel only)
        EPI_DGRAD_ADDPOOL }; // dx = acc + unpool(dout) through the routing bytes  (ping-pong kernel only)
 
-template <int MT, int NT, int MODE>
+// precision16 (one bf16 MFMA pass, P16 template flag of the bf16x3 kernels): every activation / activation gradient the
+// epilogue stores is rounded once to bf16 (RNE) and stored in its fp32 word; the epilogue arithmetic itself stays fp32
+template <bool P16>
+__device__ __forceinline__ float st16(float v) { return P16 ? (float)(__bf16)v : v; }
+template <bool P16>
+__device__ __forceinline__ f32x4 st16(const f32x4& v) {
+  return P16 ? f32x4{st16<true>(v[0]), st16<true>(v[1]), st16<true>(v[2]), st16<true>(v[3])} : v;
+}
+
+template <int MT, int NT, int MODE, bool P16 = false>
 __device__ __forceinline__ void epilogue(const ConvArgs& a, f32x16 (&acc)[MT][NT], const bool (&okn)[NT],
                                          const size_t (&basen)[NT], const int (&imgn)[NT], int cob0, size_t HW) {
   const float* __restrict__ g_bias = a.bias;
@@ -94,7 +104,7 @@ __device__ __forceinline__ void epilogue(const ConvArgs& a, f32x16 (&acc)[MT][NT
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           float z = acc[m][n][r] + bz[r];
-          g_full[idx0 + ((r & 3) + 8 * (r >> 2)) * HW] = z > 0.f ? z : z * a.slope;
+          g_full[idx0 + ((r & 3) + 8 * (r >> 2)) * HW] = st16<P16>(z > 0.f ? z : z * a.slope);
         }
       } else if (MODE == EPI_FWD_BOTH || MODE == EPI_FWD_OUT) {
 #pragma unroll
@@ -108,8 +118,8 @@ __device__ __forceinline__ void epilogue(const ConvArgs& a, f32x16 (&acc)[MT][NT
           const int cr = (r & 3) + 8 * (r >> 2);
           float z = acc[m][n][r] + bz[r];
           z = z > 0.f ? z : z * a.slope;
-          if (MODE == EPI_FWD_BOTH) { g_full[idx0 + cr * HW] = z; g_out[idx0 + cr * HW] = z * t1[r] + t0[r]; }
-          else g_out[idx0 + cr * HW] = z + t0[r];
+          if (MODE == EPI_FWD_BOTH) { g_full[idx0 + cr * HW] = st16<P16>(z); g_out[idx0 + cr * HW] = st16<P16>(z * t1[r] + t0[r]); }
+          else g_out[idx0 + cr * HW] = st16<P16>(z + t0[r]);
         }
       } else if (MODE == EPI_DGRAD_ACT || MODE == EPI_DGRAD_ADD) {
 #pragma unroll
@@ -119,7 +129,7 @@ __device__ __forceinline__ void epilogue(const ConvArgs& a, f32x16 (&acc)[MT][NT
         for (int r = 0; r < 16; ++r) {
           float z = acc[m][n][r];
           if (MODE == EPI_DGRAD_ACT) z *= (t0[r] > 0.f) ? 1.f : a.slope; else z += t0[r];
-          g_full[idx0 + ((r & 3) + 8 * (r >> 2)) * HW] = z;
+          g_full[idx0 + ((r & 3) + 8 * (r >> 2)) * HW] = st16<P16>(z);
         }
       } else if (!a.dgrad) {                              // GENERIC forward
 #pragma unroll
@@ -135,8 +145,8 @@ __device__ __forceinline__ void epilogue(const ConvArgs& a, f32x16 (&acc)[MT][NT
           if (cobase + cr >= a.Cout) continue;
           float z = acc[m][n][r] + bz[r];
           z = z > 0.f ? z : z * a.slope;
-          if (g_full) g_full[idx0 + cr * HW] = z;
-          if (g_out) g_out[idx0 + cr * HW] = z * t1[r] + t0[r];
+          if (g_full) g_full[idx0 + cr * HW] = st16<P16>(z);
+          if (g_out) g_out[idx0 + cr * HW] = st16<P16>(z * t1[r] + t0[r]);
         }
       } else {                                            // GENERIC data gradient
 #pragma unroll
@@ -153,7 +163,7 @@ __device__ __forceinline__ void epilogue(const ConvArgs& a, f32x16 (&acc)[MT][NT
           float z = acc[m][n][r];
           if (g_act) z *= (t0[r] > 0.f) ? 1.f : a.slope;
           z += t1[r];
-          g_full[idx0 + cr * HW] = z;
+          g_full[idx0 + cr * HW] = st16<P16>(z);
         }
       }
     }

@@ -80,6 +80,31 @@ __device__ __forceinline__ void put_split(__bf16* hi, __bf16* lo, int e, const t
   }
 }
 
+// precision16 (P16): the hi part only (bf16 RNE); the lo rows of the LDS tiles are never written (they stay zero-filled
+// and are not read)
+template <int VW>
+__device__ __forceinline__ void put_hi(__bf16* hi, int e, const typename Vec<VW>::T& v) {
+  __bf16 h[VW];
+#pragma unroll
+  for (int k = 0; k < VW; ++k) h[k] = (__bf16)vget<VW>(v, k);
+  if constexpr (VW == 4) {
+    typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
+    *reinterpret_cast<bf16x4*>(hi + e) = bf16x4{h[0], h[1], h[2], h[3]};
+  } else if constexpr (VW == 2) {
+    typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+    *reinterpret_cast<bf16x2*>(hi + e) = bf16x2{h[0], h[1]};
+  } else {
+    hi[e] = h[0];
+  }
+}
+template <bool P16, int VW>
+__device__ __forceinline__ void put_sp(__bf16* hi, __bf16* lo, int e, const typename Vec<VW>::T& v) {
+  if constexpr (P16) put_hi<VW>(hi, e, v); else put_split<VW>(hi, lo, e, v);
+}
+// the bias gradient's summand: dz itself, or (P16) its bf16 value
+template <bool P16>
+__device__ __forceinline__ float bsum(float v) { return P16 ? (float)(__bf16)v : v; }
+
 // vector load; PACK rows are only 4-byte aligned (row width not a multiple of 4)
 template <int VW, bool UNALIGNED>
 __device__ __forceinline__ typename Vec<VW>::T ldvec(const float* p) {
@@ -130,7 +155,8 @@ __device__ __forceinline__ bf16x8 shift_chunks(const bf16x8& c_lo, const bf16x8&
 // sub-index, column quad) -- with 16-byte loads; the last quad of a row whose width is not a multiple
 // of 4 loads the row's last four elements and shifts them into place (branch-free, never reads past
 // the row).  One dword-per-lane staging pass per row made the 15x15 layers instruction-issue bound.
-template <int MTC, int VW, bool SEG, bool PACK = false>
+// P16 (precision16): operands rounded to bf16 (hi only), ONE MFMA per tap instead of three, fp32 accumulation.
+template <int MTC, int VW, bool SEG, bool PACK = false, bool P16 = false>
 __global__ void __launch_bounds__(NTHR, 1)
 k_wgrad3x3_x3(const WgX3Args a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -236,8 +262,8 @@ k_wgrad3x3_x3(const WgX3Args a) {
         if (rr_ < R) {                                                                            \
           _Pragma("unroll") for (int c_ = 0; c_ < ZCH; ++c_) {                                    \
             const int row_ = (c_ * 16 + chl) * a.QZ;                                              \
-            put_split<VW>(Zh + row_, Zl + row_, ZP + rr_ * P + (PACK ? 4 * xq : xv * VW), pz[c_][r_]); \
-            _Pragma("unroll") for (int k_ = 0; k_ < VW; ++k_) bpart[c_] += vget<VW>(pz[c_][r_], k_); \
+            put_sp<P16, VW>(Zh + row_, Zl + row_, ZP + rr_ * P + (PACK ? 4 * xq : xv * VW), pz[c_][r_]); \
+            _Pragma("unroll") for (int k_ = 0; k_ < VW; ++k_) bpart[c_] += bsum<P16>(vget<VW>(pz[c_][r_], k_)); \
           }                                                                                       \
         }                                                                                         \
       }                                                                                           \
@@ -246,7 +272,7 @@ k_wgrad3x3_x3(const WgX3Args a) {
         if (rr_ < R + 2) {                                                                        \
           _Pragma("unroll") for (int c_ = 0; c_ < XCH; ++c_) {                                    \
             const int row_ = (c_ * 16 + chl) * a.PX;                                              \
-            put_split<VW>(Xh + row_, Xl + row_, XP + rr_ * P + (PACK ? 4 * xq : xv * VW), px[c_][r_]); \
+            put_sp<P16, VW>(Xh + row_, Xl + row_, XP + rr_ * P + (PACK ? 4 * xq : xv * VW), px[c_][r_]); \
           }                                                                                       \
         }                                                                                         \
       }                                                                                           \
@@ -257,7 +283,7 @@ k_wgrad3x3_x3(const WgX3Args a) {
         if (r_ < R) {                                                                             \
           _Pragma("unroll") for (int c_ = 0; c_ < ZCH; ++c_) {                                    \
             const int row_ = (c_ * 16 + chl) * a.QZ;                                              \
-            put_split<1>(Zh + row_, Zl + row_, ZP + r_ * P + (xv == 14 ? -1 : s_wcur), pzh[c_][r_]); \
+            put_sp<P16, 1>(Zh + row_, Zl + row_, ZP + r_ * P + (xv == 14 ? -1 : s_wcur), pzh[c_][r_]); \
           }                                                                                       \
         }                                                                                         \
       }                                                                                           \
@@ -279,6 +305,20 @@ k_wgrad3x3_x3(const WgX3Args a) {
     for (int ks = ks0; ks < ks1; ++ks) {
       // dz chunks at elements e, e+8, e+16 (e = 16*ks + 8*half); kx=1 <- [e+8,e+16)
       const bf16x8 z0h = zrow_h[2 * ks], z1h = zrow_h[2 * ks + 1], z2h = zrow_h[2 * ks + 2];
+      if constexpr (P16) {
+        bf16x8 ah[3], bh[3];
+        ah[1] = z1h;
+        ah[0] = shift_chunks<0>(z1h, z2h);
+        ah[2] = shift_chunks<1>(z0h, z1h);
+#pragma unroll
+        for (int ky = 0; ky < 3; ++ky) bh[ky] = xrow_h[2 * ks + ky * p8];
+#pragma unroll
+        for (int ky = 0; ky < 3; ++ky)
+#pragma unroll
+          for (int kx = 0; kx < 3; ++kx)
+            acc[ky * 3 + kx] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[kx], bh[ky], acc[ky * 3 + kx], 0, 0, 0);
+        continue;
+      }
       const bf16x8 z0l = zrow_l[2 * ks], z1l = zrow_l[2 * ks + 1], z2l = zrow_l[2 * ks + 2];
       bf16x8 ah[3], al[3];
       ah[1] = z1h; al[1] = z1l;
@@ -354,9 +394,11 @@ __device__ __forceinline__ void split_pair(float f0, float f1, unsigned& hi, uns
   const bf16x2_t lb = {(__bf16)l[0], (__bf16)l[1]};
   lo = __builtin_bit_cast(unsigned, lb);
 }
-template <int VW, int DBG = 0>
+template <int VW, int DBG = 0, bool P16 = false>
 __device__ __forceinline__ void put_split_pk(__bf16* hi, __bf16* lo, const typename Vec<VW>::T& v) {
-  if constexpr (VW == 4) {
+  if constexpr (P16) {
+    put_hi<VW>(hi, 0, v);
+  } else if constexpr (VW == 4) {
     unsigned h0, l0, h1, l1;
     if (DBG & 32) { h0 = __builtin_bit_cast(unsigned, v[0]); h1 = __builtin_bit_cast(unsigned, v[1]); l0 = __builtin_bit_cast(unsigned, v[2]); l1 = __builtin_bit_cast(unsigned, v[3]); }
     else { split_pair(v[0], v[1], h0, l0); split_pair(v[2], v[3], h1, l1); }
@@ -426,7 +468,9 @@ __device__ __forceinline__ void apass(T& d) {
 // zeros behind the row's end) instead of W dword loads, 32/P register slots per thread and channel slot (rows rsub + 4 j):
 // a quarter of the load / split / LDS-write instructions of the one-float form, which was issue-bound on the 15x15 layers
 // (0.344 -> 0.283 ms for the 16 layers).
-template <int VW, int DBG = 0, int LPR = 16, int PK4 = 0>
+// P16 (a trailing parameter, so the asm-load audit prefixes of the bf16x3 instantiations still cover it): precision16, operands
+// rounded to bf16 (hi only; the lo rows stay zero and are not read), ONE MFMA per tap and step.
+template <int VW, int DBG = 0, int LPR = 16, int PK4 = 0, bool P16 = false>
 __global__ void __launch_bounds__(NTHR, 1)
 k_wgrad3x3_x3_pipe(const WgX3Args a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -530,13 +574,13 @@ k_wgrad3x3_x3_pipe(const WgX3Args a) {
       const int c_ = (J) / RZ, r_ = (J) % RZ;                                                 \
       __bf16* zh_ = tb_ + (c_ * CPP + chl) * QZ + ZP + WGP_ROW(r_) * P + ecol;                    \
       const VT t_ = pk_shift<VW, PK4 != 0>(pz##S[c_][r_], shq);                                    \
-      put_split_pk<VW, DBG>(zh_, zh_ + MB * QZ, t_);                                              \
-      _Pragma("unroll") for (int k_ = 0; k_ < VW; ++k_) bpart[c_] += vget<VW>(t_, k_);            \
+      put_split_pk<VW, DBG, P16>(zh_, zh_ + MB * QZ, t_);                                         \
+      _Pragma("unroll") for (int k_ = 0; k_ < VW; ++k_) bpart[c_] += bsum<P16>(vget<VW>(t_, k_)); \
     } else {                                                                                      \
       const int j2_ = (J) - NZJ < NXJ ? (J) - NZJ : 0;                                        \
       const int c_ = j2_ / RZ, r_ = 2 + j2_ % RZ;                                                 \
       __bf16* xh_ = tb_ + 2 * MB * QZ + (c_ * CPP + chl) * PX + XP + (2 + WGP_ROW(j2_ % RZ)) * P + ecol; \
-      put_split_pk<VW, DBG>(xh_, xh_ + 32 * PX, pk_shift<VW, PK4 != 0>(px##S[c_][r_], shq));      \
+      put_split_pk<VW, DBG, P16>(xh_, xh_ + 32 * PX, pk_shift<VW, PK4 != 0>(px##S[c_][r_], shq)); \
     }                                                                                             \
   }
   // operand fragments of one 16-position MFMA step, two sets (the reads of step s+1 are issued inside step s)
@@ -555,8 +599,8 @@ k_wgrad3x3_x3_pipe(const WgX3Args a) {
     const bf16x8* xh_ = reinterpret_cast<const bf16x8*>(tb_ + 2 * MB * QZ + l31 * PX) + half;  \
     const bf16x8* xl_ = reinterpret_cast<const bf16x8*>(tb_ + 2 * MB * QZ + 32 * PX + l31 * PX) + half; \
     _Pragma("unroll") for (int i_ = 0; i_ < 3; ++i_) {                                            \
-      fz[F][i_] = zh_[2 * (KS_) + i_]; fz[F][3 + i_] = zl_[2 * (KS_) + i_];                       \
-      fb[F][i_] = xh_[2 * (KS_) + i_ * p8]; fb[F][3 + i_] = xl_[2 * (KS_) + i_ * p8];             \
+      fz[F][i_] = zh_[2 * (KS_) + i_]; fb[F][i_] = xh_[2 * (KS_) + i_ * p8];                      \
+      if (!P16) { fz[F][3 + i_] = zl_[2 * (KS_) + i_]; fb[F][3 + i_] = xl_[2 * (KS_) + i_ * p8]; } \
     }                                                                                             \
   }
   // slot U (0 .. 31: eight per MFMA step, behind tap groups 1..8) of a band: its jobs, then its loads
@@ -576,15 +620,22 @@ k_wgrad3x3_x3_pipe(const WgX3Args a) {
 #define WGP_STEP(PAR, S, ST, F, V0N)                                                              \
   {                                                                                               \
     bf16x8 ah[3], al[3];                                                                          \
-    ah[1] = fz[F][1]; al[1] = fz[F][4];                                                           \
-    ah[0] = shift_chunks<0>(fz[F][1], fz[F][2]); al[0] = shift_chunks<0>(fz[F][4], fz[F][5]);     \
-    ah[2] = shift_chunks<1>(fz[F][0], fz[F][1]); al[2] = shift_chunks<1>(fz[F][3], fz[F][4]);     \
+    ah[1] = fz[F][1];                                                                             \
+    ah[0] = shift_chunks<0>(fz[F][1], fz[F][2]);                                                  \
+    ah[2] = shift_chunks<1>(fz[F][0], fz[F][1]);                                                  \
+    if (!P16) {                                                                                   \
+      al[1] = fz[F][4];                                                                           \
+      al[0] = shift_chunks<0>(fz[F][4], fz[F][5]);                                                \
+      al[2] = shift_chunks<1>(fz[F][3], fz[F][4]);                                                \
+    }                                                                                             \
     _Pragma("unroll") for (int ky = 0; ky < 3; ++ky)                                              \
       _Pragma("unroll") for (int kx = 0; kx < 3; ++kx) {                                          \
         const int t = ky * 3 + kx;                                                                \
         if (!(DBG & 4)) {                                                                         \
-          acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[kx], fb[F][3 + ky], acc[t], 0, 0, 0); \
-          acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[kx], fb[F][ky], acc[t], 0, 0, 0);   \
+          if (!P16) {                                                                             \
+            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[kx], fb[F][3 + ky], acc[t], 0, 0, 0); \
+            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[kx], fb[F][ky], acc[t], 0, 0, 0); \
+          }                                                                                       \
           acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[kx], fb[F][ky], acc[t], 0, 0, 0);   \
         }                                                                                         \
         if (t == 1 && (ST) < 3) WGP_FRAGS((F) ^ 1, PAR, ks0 + (ST) + 1)                           \
@@ -623,7 +674,7 @@ k_wgrad3x3_x3_pipe(const WgX3Args a) {
 #pragma unroll
     for (int r = 0; r < 2; ++r) {
       __bf16* xh_ = base + 2 * MB * QZ + (c * CPP + chl) * PX + XP + r * P + ecol;
-      if (!PK4 || rsub == r) put_split<VW>(xh_, xh_ + 32 * PX, 0, pk_shift<VW, PK4 != 0>(hx[c][r], shq));
+      if (!PK4 || rsub == r) put_sp<P16, VW>(xh_, xh_ + 32 * PX, 0, pk_shift<VW, PK4 != 0>(hx[c][r], shq));
     }
 #pragma unroll
   for (int j = 0; j < NJ; ++j) WGP_JOB(0, j, 0)
@@ -823,7 +874,7 @@ WgX3Plan plan_x3(int N, int Cin, int Cout, int H, int W, int L = 1) {
   return p;
 }
 
-template <int MTC>
+template <int MTC, bool P16 = false>
 int launch_x3(const WgX3Args& a, const WgX3Plan& p, dim3 grid, hipStream_t st) {
   int rc = FDET_OK;
   auto go = [&](auto kern) {
@@ -837,22 +888,22 @@ int launch_x3(const WgX3Args& a, const WgX3Plan& p, dim3 grid, hipStream_t st) {
 #define WG_DBG_CASE(D) if (dbg == D && !p.lpr32 && p.vw == 4) { go(k_wgrad3x3_x3_pipe<4, D>); return rc; }
     WG_DBG_CASE(1) WG_DBG_CASE(3) WG_DBG_CASE(8) WG_DBG_CASE(9) WG_DBG_CASE(24) WG_DBG_CASE(40) WG_DBG_CASE(73)
 #endif
-    if (p.lpr32 && p.pk4) go(k_wgrad3x3_x3_pipe<4, 0, 32, 1>);
-    else if (p.lpr32) go(k_wgrad3x3_x3_pipe<1, 0, 32>);
-    else if (p.pk4) go(k_wgrad3x3_x3_pipe<4, 0, 16, 1>);
-    else go(k_wgrad3x3_x3_pipe<4>);                     // p.vw == 4 (plan_x3 routes the one-float 16-lane form to the staged kernel)
-  } else if (p.NSEG > 1) go(k_wgrad3x3_x3<MTC, 4, true>);
-  else if (p.pack) go(k_wgrad3x3_x3<MTC, 4, false, true>);
-  else if (p.vw == 4) go(k_wgrad3x3_x3<MTC, 4, false>);
-  else if (p.vw == 2) go(k_wgrad3x3_x3<MTC, 2, false>);
-  else go(k_wgrad3x3_x3<MTC, 1, false>);
+    if (p.lpr32 && p.pk4) go(k_wgrad3x3_x3_pipe<4, 0, 32, 1, P16>);
+    else if (p.lpr32) go(k_wgrad3x3_x3_pipe<1, 0, 32, 0, P16>);
+    else if (p.pk4) go(k_wgrad3x3_x3_pipe<4, 0, 16, 1, P16>);
+    else go(k_wgrad3x3_x3_pipe<4, 0, 16, 0, P16>);      // p.vw == 4 (plan_x3 routes the one-float 16-lane form to the staged kernel)
+  } else if (p.NSEG > 1) go(k_wgrad3x3_x3<MTC, 4, true, false, P16>);
+  else if (p.pack) go(k_wgrad3x3_x3<MTC, 4, false, true, P16>);
+  else if (p.vw == 4) go(k_wgrad3x3_x3<MTC, 4, false, false, P16>);
+  else if (p.vw == 2) go(k_wgrad3x3_x3<MTC, 2, false, false, P16>);
+  else go(k_wgrad3x3_x3<MTC, 1, false, false, P16>);
   return rc;
 }
 
 }  // namespace
 
 static int run_wg_x3(const float* const* xs, const float* const* dzs, float* const* dWs, float* const* dbs, int L,
-                     void* ws, size_t ws_bytes, int N, int Cin, int Cout, int H, int W, hipStream_t st) {
+                     void* ws, size_t ws_bytes, int N, int Cin, int Cout, int H, int W, hipStream_t st, bool p16 = false) {
   const WgX3Plan p = plan_x3(N, Cin, Cout, H, W, L);
   FDET_REQUIRE(p.ok, "conv3x3_wgrad_bf16x3: no tiling for N=%d H=%d W=%d (rows wider than 64 need W %% 4 == 0)", N, H, W);
   if (ws_bytes < p.ws_floats * 4)
@@ -865,7 +916,8 @@ static int run_wg_x3(const float* const* xs, const float* const* dzs, float* con
   a.VR = p.VR; a.QZ = p.QZ; a.PX = p.PX; a.Kext = p.Kext; a.nbands = p.nbands; a.magic_h1 = magic_of(H + 1);
   a.L = L; a.ncob = p.CoP / (p.MTC * 32); a.NSEG = p.NSEG; a.CW = p.CW;
   dim3 grid(p.nblk, p.CiP / 32, a.ncob * L);
-  if (int rc = p.MTC == 2 ? launch_x3<2>(a, p, grid, st) : launch_x3<1>(a, p, grid, st)) return rc;
+  if (int rc = p16 ? (p.MTC == 2 ? launch_x3<2, true>(a, p, grid, st) : launch_x3<1, true>(a, p, grid, st))
+                   : (p.MTC == 2 ? launch_x3<2>(a, p, grid, st) : launch_x3<1>(a, p, grid, st))) return rc;
   if (int rc = check_launch("fdet_conv3x3_wgrad_bf16x3")) return rc;
   hipLaunchKernelGGL(k_wgx3_reduce, dim3(9, (Cout + 3) / 4, L), dim3(1024), 0, st, a.ws, a.wsb, p.nblk, Cout, Cin, p.CoP,
                      p.CiP, r);
@@ -898,4 +950,21 @@ extern "C" int fdet_conv3x3_wgrad_bf16x3_batched(const float* const* h_x, const 
   for (int l = 0; l < L; ++l) FDET_REQUIRE(h_x[l] && h_dz[l] && h_dW[l] && h_db[l], "conv3x3_wgrad_bf16x3_batched: null pointer in layer %d", l);
   FDET_REQUIRE(N > 0 && Cin > 0 && Cout > 0 && H > 0 && W > 0, "conv3x3_wgrad_bf16x3_batched: bad shape");
   return run_wg_x3(h_x, h_dz, h_dW, h_db, L, ws, ws_bytes, N, Cin, Cout, H, W, (hipStream_t)stream);
+}
+
+// precision16: the same plans, workspaces and reduction; operands rounded to bf16 and one MFMA per tap (fdet.h)
+extern "C" int fdet_conv3x3_wgrad_bf16(const float* x, const float* dz, float* dW, float* db, void* ws,
+                                       size_t ws_bytes, int N, int Cin, int Cout, int H, int W, void* stream) {
+  FDET_REQUIRE(x && dz && dW && db && ws, "conv3x3_wgrad_bf16: null pointer");
+  FDET_REQUIRE(N > 0 && Cin > 0 && Cout > 0 && H > 0 && W > 0, "conv3x3_wgrad_bf16: bad shape");
+  return run_wg_x3(&x, &dz, &dW, &db, 1, ws, ws_bytes, N, Cin, Cout, H, W, (hipStream_t)stream, true);
+}
+
+extern "C" int fdet_conv3x3_wgrad_bf16_batched(const float* const* h_x, const float* const* h_dz, float* const* h_dW,
+                                               float* const* h_db, int L, void* ws, size_t ws_bytes, int N, int Cin,
+                                               int Cout, int H, int W, void* stream) {
+  FDET_REQUIRE(h_x && h_dz && h_dW && h_db && ws && L >= 1 && L <= MAXL, "conv3x3_wgrad_bf16_batched: bad arguments (L=%d, max %d)", L, MAXL);
+  for (int l = 0; l < L; ++l) FDET_REQUIRE(h_x[l] && h_dz[l] && h_dW[l] && h_db[l], "conv3x3_wgrad_bf16_batched: null pointer in layer %d", l);
+  FDET_REQUIRE(N > 0 && Cin > 0 && Cout > 0 && H > 0 && W > 0, "conv3x3_wgrad_bf16_batched: bad shape");
+  return run_wg_x3(h_x, h_dz, h_dW, h_db, L, ws, ws_bytes, N, Cin, Cout, H, W, (hipStream_t)stream, true);
 }

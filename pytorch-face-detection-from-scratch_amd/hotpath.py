@@ -371,8 +371,18 @@ def pack_conv3x3_weights_batched(ws, wpk_fwds, wpk_bwds) -> None:
                                                          stream()), "fdet_pack_conv3x3_weights_bf16x3_batched")
 
 
+def _p16_fn(name: str, x3: bool, p16: bool):
+    """The C entry of a conv op: `<name>_bf16` (precision16: one bf16 MFMA pass, bf16-rounded stores; include/fdet.h),
+    `<name>_bf16x3`, or the exact-fp32 `<name>`.  precision16 exists only beside the bf16x3 kernels."""
+    if p16:
+        if not x3:
+            raise ValueError(f"{name}: precision16 (p16=True) runs on the bf16 matrix-core kernels only (x3=True)")
+        return getattr(lib(), name + "_bf16")
+    return getattr(lib(), name + "_bf16x3") if x3 else getattr(lib(), name)
+
+
 def conv3x3_fwd(x, wpk, bias, cout: int, y_full=None, skip=None, drop_scale=None, y_out=None, slope: float = 0.2,
-                x3: bool = False):
+                x3: bool = False, p16: bool = False):
     Nn, cin, H, W = x.shape
     if wpk.numel() != packed_sizes(cout, cin)[0]:
         raise ValueError("conv3x3_fwd: packed weight size does not match (Cout,Cin)")
@@ -383,12 +393,12 @@ def conv3x3_fwd(x, wpk, bias, cout: int, y_full=None, skip=None, drop_scale=None
         _chk4(bias, (cout,), "bias")
     if drop_scale is not None:
         _chk4(drop_scale, (Nn, cout), "drop_scale")
-    fn = lib().fdet_conv3x3_fwd_bf16x3 if x3 else lib().fdet_conv3x3_fwd
+    fn = _p16_fn("fdet_conv3x3_fwd", x3, p16)
     check(fn(ptr(x), ptr(wpk), ptr(bias), ptr(y_full), ptr(skip), ptr(drop_scale), ptr(y_out),
              Nn, cin, cout, H, W, 1, float(slope), stream()), "fdet_conv3x3_fwd")
 
 
-def conv3x3_dgrad(dz, wpk_bwd, cin: int, dx, act=None, add=None, slope: float = 0.2, x3: bool = False):
+def conv3x3_dgrad(dz, wpk_bwd, cin: int, dx, act=None, add=None, slope: float = 0.2, x3: bool = False, p16: bool = False):
     Nn, cout, H, W = dz.shape
     if wpk_bwd.numel() != packed_sizes(cout, cin)[1]:
         raise ValueError("conv3x3_dgrad: packed weight size does not match (Cout,Cin)")
@@ -396,7 +406,7 @@ def conv3x3_dgrad(dz, wpk_bwd, cin: int, dx, act=None, add=None, slope: float = 
     for t, nm in ((act, "act"), (add, "add")):
         if t is not None:
             _chk4(t, (Nn, cin, H, W), nm)
-    fn = lib().fdet_conv3x3_dgrad_bf16x3 if x3 else lib().fdet_conv3x3_dgrad
+    fn = _p16_fn("fdet_conv3x3_dgrad", x3, p16)
     check(fn(ptr(dz), ptr(wpk_bwd), ptr(act), ptr(add), ptr(dx), Nn, cin, cout, H, W, float(slope), stream()),
           "fdet_conv3x3_dgrad")
 
@@ -407,8 +417,9 @@ def pool_fusion_supported(cout: int, cin: int, H: int, W: int, N: int = 1) -> bo
     return bool(lib().fdet_conv3x3_pool_fusion_ok(int(N), int(cin), int(cout), int(H), int(W)))
 
 
-def conv3x3_fwd_pool(x, wpk, bias, skip, drop_scale, out_pooled, route, slope: float = 0.2):
-    """out_pooled = maxpool2x2(lrelu(conv(x)+bias)*drop_scale + skip); route: uint8 routing bytes or None (eval)."""
+def conv3x3_fwd_pool(x, wpk, bias, skip, drop_scale, out_pooled, route, slope: float = 0.2, p16: bool = False):
+    """out_pooled = maxpool2x2(lrelu(conv(x)+bias)*drop_scale + skip); route: uint8 routing bytes or None (eval).
+    p16: precision16 (fdet_conv3x3_fwd_pool_bf16)."""
     Nn, cin, H, W = x.shape
     cout = bias.shape[0]
     if wpk.numel() != packed_sizes(cout, cin)[0]:
@@ -419,22 +430,23 @@ def conv3x3_fwd_pool(x, wpk, bias, skip, drop_scale, out_pooled, route, slope: f
         _chk4(route, (Nn, cout, H // 2, W // 2), "route")
     if drop_scale is not None:
         _chk4(drop_scale, (Nn, cout), "drop_scale")
-    check(lib().fdet_conv3x3_fwd_pool_bf16x3(ptr(x), ptr(wpk), ptr(bias), ptr(skip), ptr(drop_scale), ptr(out_pooled),
-                                             ptr(route, torch.uint8), Nn, cin, cout, H, W, float(slope), stream()),
-          "fdet_conv3x3_fwd_pool_bf16x3")
+    fn = _p16_fn("fdet_conv3x3_fwd_pool", True, p16)
+    check(fn(ptr(x), ptr(wpk), ptr(bias), ptr(skip), ptr(drop_scale), ptr(out_pooled), ptr(route, torch.uint8), Nn, cin, cout,
+             H, W, float(slope), stream()), fn.__name__)
 
 
-def conv3x3_dgrad_unpool(dz, wpk_bwd, cin: int, dout_pooled, route, dx, slope: float = 0.2):
-    """dx = conv^T(dz) + unpool(dout_pooled) through the routing bytes of the forward pass."""
+def conv3x3_dgrad_unpool(dz, wpk_bwd, cin: int, dout_pooled, route, dx, slope: float = 0.2, p16: bool = False):
+    """dx = conv^T(dz) + unpool(dout_pooled) through the routing bytes of the forward pass.
+    p16: precision16 (fdet_conv3x3_dgrad_unpool_bf16)."""
     Nn, cout, H, W = dz.shape
     if wpk_bwd.numel() != packed_sizes(cout, cin)[1]:
         raise ValueError("conv3x3_dgrad_unpool: packed weight size does not match (Cout,Cin)")
     _chk4(dx, (Nn, cin, H, W), "dx")
     _chk4(dout_pooled, (Nn, cin, H // 2, W // 2), "dout_pooled")
     _chk4(route, (Nn, cin, H // 2, W // 2), "route")
-    check(lib().fdet_conv3x3_dgrad_unpool_bf16x3(ptr(dz), ptr(wpk_bwd), ptr(dout_pooled), ptr(route, torch.uint8), ptr(dx),
-                                                 Nn, cin, cout, H, W, float(slope), stream()),
-          "fdet_conv3x3_dgrad_unpool_bf16x3")
+    fn = _p16_fn("fdet_conv3x3_dgrad_unpool", True, p16)
+    check(fn(ptr(dz), ptr(wpk_bwd), ptr(dout_pooled), ptr(route, torch.uint8), ptr(dx), Nn, cin, cout, H, W, float(slope),
+             stream()), fn.__name__)
 
 
 def pool_route_bwd(dout_pooled, route, drop_scale, dz2, slope: float = 0.2):
@@ -511,13 +523,14 @@ def wgrad_x3_supported(Nn, cin, cout, H, W) -> bool:
     return int(lib().fdet_conv3x3_wgrad_bf16x3_ws_bytes(Nn, cin, cout, H, W)) > 0
 
 
-def conv3x3_wgrad(x, dz, dW, db, ws, x3: bool = False):
+def conv3x3_wgrad(x, dz, dW, db, ws, x3: bool = False, p16: bool = False):
+    """p16: precision16 (fdet_conv3x3_wgrad_bf16: bf16-rounded operands, fp32 sums; the bf16x3 workspace size)."""
     Nn, cin, H, W = x.shape
     cout = dz.shape[1]
     _chk4(dz, (Nn, cout, H, W), "dz")
     _chk4(dW, (cout, cin, 3, 3), "dW")
     _chk4(db, (cout,), "db")
-    fn = lib().fdet_conv3x3_wgrad_bf16x3 if x3 else lib().fdet_conv3x3_wgrad
+    fn = _p16_fn("fdet_conv3x3_wgrad", x3, p16)
     check(fn(ptr(x), ptr(dz), ptr(dW), ptr(db), ptr(ws, ws.dtype), ws.numel() * ws.element_size(),
              Nn, cin, cout, H, W, stream()), "fdet_conv3x3_wgrad")
 
@@ -526,8 +539,9 @@ def conv3x3_wgrad_batched_ws_bytes(L, Nn, cin, cout, H, W) -> int:
     return int(lib().fdet_conv3x3_wgrad_bf16x3_batched_ws_bytes(L, Nn, cin, cout, H, W))
 
 
-def conv3x3_wgrad_batched(xs, dzs, dWs, dbs, ws):
-    """bf16x3 weight gradients of L <= 16 same-shape layers in one launch (+ one reduce)."""
+def conv3x3_wgrad_batched(xs, dzs, dWs, dbs, ws, p16: bool = False):
+    """bf16x3 weight gradients of L <= 16 same-shape layers in one launch (+ one reduce); p16: precision16
+    (fdet_conv3x3_wgrad_bf16_batched, same workspace)."""
     L = len(xs)
     if not (1 <= L <= 16 and len(dzs) == len(dWs) == len(dbs) == L):
         raise ValueError("conv3x3_wgrad_batched: 1..16 layers, equal list lengths")
@@ -542,8 +556,9 @@ def conv3x3_wgrad_batched(xs, dzs, dWs, dbs, ws):
     arr = ctypes.c_void_p * L
     hx, hdz = arr(*[ptr(t) for t in xs]), arr(*[ptr(t) for t in dzs])
     hdW, hdb = arr(*[ptr(t) for t in dWs]), arr(*[ptr(t) for t in dbs])
-    check(lib().fdet_conv3x3_wgrad_bf16x3_batched(hx, hdz, hdW, hdb, L, ptr(ws, ws.dtype), ws.numel() * ws.element_size(),
-                                                  Nn, cin, cout, H, W, stream()), "fdet_conv3x3_wgrad_bf16x3_batched")
+    fn = lib().fdet_conv3x3_wgrad_bf16_batched if p16 else lib().fdet_conv3x3_wgrad_bf16x3_batched
+    check(fn(hx, hdz, hdW, hdb, L, ptr(ws, ws.dtype), ws.numel() * ws.element_size(), Nn, cin, cout, H, W, stream()),
+          fn.__name__)
 
 
 def _ptr_array(ts, dtype=F32):

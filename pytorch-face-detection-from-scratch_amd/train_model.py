@@ -6,6 +6,10 @@ is what there is on a box without network.  `--data DIR` expects `DIR/images_u8.
 (list of (n_i,5) [1,x,y,w,h]) prepared offline.
 
     python -m fdet_amd.train_model --filters 64 --epochs 2 --batch-size 8 --steps-per-epoch 20 --save model.pt
+
+`--precision 16` is the reference's Trainer(precision=16) (train_model.py:50) with bf16 as the 16-bit type: the conv kernels
+run one bf16 MFMA pass (engine.set_precision("bf16")); with the defaults (F=128, S=10, batch 8) that is the reference's
+own training recipe.  `--precision 32` (default) keeps the fp32-grade bf16x3 arithmetic.
 """
 import argparse
 from pathlib import Path
@@ -38,6 +42,7 @@ def main(argv=None):
     ap.add_argument("--steps-per-epoch", type=int, default=50)
     ap.add_argument("--val-steps", type=int, default=5)
     ap.add_argument("--save", default=None)
+    ap.add_argument("--precision", type=int, choices=(32, 16), default=32)   # train_model.py:50 Trainer(precision=...)
     args = ap.parse_args(argv)
     torch.random.manual_seed(0)                                  # train_model.py:13
     from .models import ModelMeta
@@ -49,6 +54,8 @@ def main(argv=None):
     log_path.unlink(missing_ok=True)
     model = PoolResnet(filters=args.filters, input_shape=(3, args.size, args.size), num_of_patches=args.patches,
                        num_of_residual_blocks=10).cuda()
+    if args.precision == 16:
+        model.engine.set_precision("bf16")
     model.summary()
     model_setup = ModelMeta(model=model, lr=args.lr, log_path=log_path)
     train = synthetic_loader(args.steps_per_epoch, args.batch_size, args.size, args.patches, seed=1)
