@@ -389,6 +389,16 @@ int fdet_pointwise_dgrad_bf16x3(const float* dz, const void* wpk_bwd, const floa
 size_t fdet_pointwise_wgrad_ws_bytes(int N, int Cin, int Cout, int P);
 int fdet_pointwise_wgrad_bf16x3(const float* x, const float* dz, float* dW, float* db, void* ws, size_t ws_bytes, int N,
                                 int Cin, int Cout, int P, void* stream);
+/* precision16 twins (the one-pass contract of fdet_conv3x3_*_bf16 below): same arguments, panels
+ * (fdet_pack_pointwise_weights_bf16x3, hi half read only) and workspace size (fdet_pointwise_wgrad_ws_bytes).  Operands
+ * rounded to bf16 (RNE), ONE v_mfma_f32_32x32x16_bf16 per (m, n) tile, fp32 accumulation and epilogue (bias, slope, add);
+ * every stored y / dx rounded once to bf16 in its fp32 word; dW / db fp32 sums over bf16 operands (db = sum of bf16(dz)). */
+int fdet_pointwise_fwd_bf16(const float* x, const void* wpk_fwd, const float* bias, float* y, int N, int Cin, int Cout,
+                            int P, float slope, void* stream);
+int fdet_pointwise_dgrad_bf16(const float* dz, const void* wpk_bwd, const float* add, float* dx, int N, int Cin,
+                              int Cout, int P, void* stream);
+int fdet_pointwise_wgrad_bf16(const float* x, const float* dz, float* dW, float* db, void* ws, size_t ws_bytes, int N,
+                              int Cin, int Cout, int P, void* stream);
 
 /* MobileNetV3-small backbone, inference, bf16 (BASELINE.json config 5).  Replaces the forward of
  * models/MobilenetV3Backbone.py:35-60 (timm tf_mobilenetv3_small_100 feature extractor + Conv2d(576,5,3,p1) + sigmoid).
@@ -484,6 +494,8 @@ int fdet_stem_fwd_ps_p16(const float* x, const float* w, const float* bias, void
  * W % 4 == 0; precision16 != 0: one MFMA pass, hi plane only. */
 int fdet_stem_fwd_ps_u8(const unsigned char* frames, const float* w, const float* bias, void* y_ps, int N, int Cin, int F, int H,
                         int W, int k, int stride, int pad, int precision16, void* stream);
+/* precision16 stem weight gradient (one MFMA pass on bf16(dy) x bf16(x), fp32 sums; the workspace of fdet_stem_wgrad_bf16x3):
+ * the PoolResnet stem (k10 s8 p2) and the Resnet / SSD stem (3ch k3 s2 p1, the shapes of its bf16x3 matrix-core kernel). */
 int fdet_stem_wgrad_bf16(const float* x, const float* dy, float* dW, float* db, void* ws, size_t ws_bytes,
                          int N, int Cin, int F, int H, int W, int k, int stride, int pad, void* stream);
 int fdet_conv3x3_wgrad_ps_batched_p16(const void* const* h_x, const void* const* h_dz, float* const* h_dW,

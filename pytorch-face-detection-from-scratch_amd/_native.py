@@ -94,6 +94,9 @@ SIGNATURES = {
     "fdet_pointwise_dgrad_bf16x3": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P]),
     "fdet_pointwise_wgrad_ws_bytes": (_SZ, [_I, _I, _I, _I]),
     "fdet_pointwise_wgrad_bf16x3": (_I, [_P, _P, _P, _P, _P, _SZ, _I, _I, _I, _I, _P]),
+    "fdet_pointwise_fwd_bf16": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _F, _P]),
+    "fdet_pointwise_dgrad_bf16": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P]),
+    "fdet_pointwise_wgrad_bf16": (_I, [_P, _P, _P, _P, _P, _SZ, _I, _I, _I, _I, _P]),
     "fdet_mb_stem": (_I, [_P, _I, _P, _P, _P, _I, _I, _I, _P]),
     "fdet_mb_depthwise": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     "fdet_mb_depthwise_pool_slots": (_I, [_I, _I, _I, _I, _I, _I]),

@@ -15,6 +15,10 @@
 //       which are CONTIGUOUS in both operands: every lane loads its 8 positions of its row straight into the fragment
 //       (no LDS at all), splits, and feeds the MFMA.  Workgroups cut the (n, p) range into slabs; a second kernel adds the
 //       slab partials in a fixed order (deterministic), and reduces the bias gradient.
+//   precision16 (template flag P16, the `_bf16` entries): the arithmetic of the conv kernels' P16 form
+//       (fdet_conv_common.h st16): operands rounded to bf16 (RNE, the hi part only -- no lo array in LDS, the panels' lo
+//       half is not read), ONE MFMA per (m, n) instead of three, fp32 accumulation and epilogue, every stored y / dx
+//       rounded once to bf16 in its fp32 word; dW and db are fp32 sums over bf16 operands (db = sum of bf16(dz)).
 #include "fdet_conv3x3_x3.h"
 #include <algorithm>
 #include <cstdint>
@@ -70,12 +74,20 @@ k_pack_pw_x3(const float* __restrict__ w, int Cout, int Cin, int CoP, int CiP, i
   }
 }
 
-template <int MT, int VW>
+// the bf16 (RNE) values of 8 floats: the hi part of split8
+__device__ __forceinline__ bf16x8 round8(const float (&f)[8]) {
+  bf16x8 h;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) h[j] = (__bf16)f[j];
+  return h;
+}
+
+template <int MT, int VW, bool P16 = false>
 __global__ void __launch_bounds__(PW_THR)
 k_pw_x3(const PwArgs a) {
   constexpr int NT = 2, MB = MT * 32;
   constexpr int PT = PW_POS + 4;                       // units per LDS array (pad: the two k-halves on different banks)
-  __shared__ __attribute__((aligned(16))) bf16x8 lds[4 * PT];   // hi {h0,h1}, lo {h0,h1}
+  __shared__ __attribute__((aligned(16))) bf16x8 lds[(P16 ? 2 : 4) * PT];   // hi {h0,h1}, lo {h0,h1} (P16: hi only)
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int l31 = lane & 31, half = lane >> 5;
   const int img = blockIdx.x / a.tiles_per_img;
@@ -128,16 +140,31 @@ k_pw_x3(const PwArgs a) {
           float f[8];
 #pragma unroll
           for (int j = 0; j < 8; ++j) f[j] = vget<VW>(pb[s][j], i);
-          bf16x8 hi, lo;
-          split8(f, hi, lo);
-          lds[h * PT + pp + i] = hi;
-          lds[(2 + h) * PT + pp + i] = lo;
+          if constexpr (P16) {
+            lds[h * PT + pp + i] = round8(f);
+          } else {
+            bf16x8 hi, lo;
+            split8(f, hi, lo);
+            lds[h * PT + pp + i] = hi;
+            lds[(2 + h) * PT + pp + i] = lo;
+          }
         }
       }
     }
     __syncthreads();
     const size_t wbase = (size_t)(c * 2 + half) * a.CoP + cob0 + l31;
     bf16x8 ah[MT], al[MT], bh[NT], bl[NT];
+    if constexpr (P16) {
+#pragma unroll
+      for (int m = 0; m < MT; ++m) ah[m] = a.a_hi[wbase + m * 32];
+#pragma unroll
+      for (int n = 0; n < NT; ++n) bh[n] = lds[b_off + n * 32];
+#pragma unroll
+      for (int m = 0; m < MT; ++m)
+#pragma unroll
+        for (int n = 0; n < NT; ++n) acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[m], bh[n], acc[m][n], 0, 0, 0);
+      continue;
+    }
 #pragma unroll
     for (int m = 0; m < MT; ++m) { ah[m] = a.a_hi[wbase + m * 32]; al[m] = a.a_lo[wbase + m * 32]; }
 #pragma unroll
@@ -167,7 +194,7 @@ k_pw_x3(const PwArgs a) {
         float z = acc[m][n][r] + (a.bias ? a.bias[ch] : 0.f);
         z = z > 0.f ? z : z * a.slope;
         if (a.add) z += a.add[idx];
-        a.y[idx] = z;
+        a.y[idx] = st16<P16>(z);
       }
   }
 }
@@ -198,7 +225,7 @@ __device__ __forceinline__ void pw_load8(const float* __restrict__ row, int p, i
 // one wave = one 32x32 block of dW over a slab of positions; workgroup = 4 waves = 4 consecutive (co-tile, ci-tile) blocks
 // (round 4: the bias gradient rides along -- the waves of input-channel tile 0 sum their dz fragments before splitting them,
 //  one partial per (slab, output channel); the separate pass over dz, k_pw_bias_part, is gone)
-template <bool VEC>
+template <bool VEC, bool P16 = false>
 __global__ void __launch_bounds__(256)
 k_pw_wgrad_x3(const PwWgArgs a, float* __restrict__ bias_part /*[nslab][CoT*32] or null*/) {
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
@@ -221,7 +248,11 @@ k_pw_wgrad_x3(const PwWgArgs a, float* __restrict__ bias_part /*[nslab][CoT*32] 
     pw_load8<VEC>(ci < a.Cin ? a.x + ((size_t)n * a.Cin + ci) * a.P : nullptr, p, a.P, fb);
     if (want_b) {
 #pragma unroll
-      for (int j = 0; j < 8; ++j) bsum += fa[j];
+      for (int j = 0; j < 8; ++j) bsum += st16<P16>(fa[j]);
+    }
+    if constexpr (P16) {
+      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(round8(fa), round8(fb), acc, 0, 0, 0);
+      continue;
     }
     bf16x8 ah, al, bh, bl;
     split8(fa, ah, al);
@@ -298,6 +329,7 @@ int pw_num_cus() {
   return ncu;
 }
 
+template <bool P16>
 int run_pw(const float* x, const void* wpk, const float* bias, const float* add, float* y, int N, int Cin, int Cout, int P,
            float slope, hipStream_t st, const char* what) {
   PwArgs a;
@@ -311,8 +343,8 @@ int run_pw(const float* x, const void* wpk, const float* bias, const float* add,
   const int MT = (a.CoP % 64 == 0) ? 2 : 1;
   dim3 grid((unsigned)((size_t)N * a.tiles_per_img), a.CoP / (32 * MT));
   const bool v4 = (P % 4 == 0) && ((uintptr_t)x % 16 == 0);
-  if (MT == 2) { if (v4) hipLaunchKernelGGL((k_pw_x3<2, 4>), grid, dim3(PW_THR), 0, st, a); else hipLaunchKernelGGL((k_pw_x3<2, 1>), grid, dim3(PW_THR), 0, st, a); }
-  else { if (v4) hipLaunchKernelGGL((k_pw_x3<1, 4>), grid, dim3(PW_THR), 0, st, a); else hipLaunchKernelGGL((k_pw_x3<1, 1>), grid, dim3(PW_THR), 0, st, a); }
+  if (MT == 2) { if (v4) hipLaunchKernelGGL((k_pw_x3<2, 4, P16>), grid, dim3(PW_THR), 0, st, a); else hipLaunchKernelGGL((k_pw_x3<2, 1, P16>), grid, dim3(PW_THR), 0, st, a); }
+  else { if (v4) hipLaunchKernelGGL((k_pw_x3<1, 4, P16>), grid, dim3(PW_THR), 0, st, a); else hipLaunchKernelGGL((k_pw_x3<1, 1, P16>), grid, dim3(PW_THR), 0, st, a); }
   return check_launch(what);
 }
 
@@ -337,14 +369,14 @@ extern "C" int fdet_pointwise_fwd_bf16x3(const float* x, const void* wpk_fwd, co
                                          int Cout, int P, float slope, void* stream) {
   FDET_REQUIRE(x && wpk_fwd && y && N > 0 && Cin > 0 && Cout > 0 && P > 0, "pointwise_fwd_bf16x3: bad arguments");
   FDET_REQUIRE((size_t)N * std::max(Cin, Cout) * P < ((size_t)1 << 40), "pointwise_fwd_bf16x3: tensor too large");
-  return run_pw(x, wpk_fwd, bias, nullptr, y, N, Cin, Cout, P, slope, (hipStream_t)stream, "fdet_pointwise_fwd_bf16x3");
+  return run_pw<false>(x, wpk_fwd, bias, nullptr, y, N, Cin, Cout, P, slope, (hipStream_t)stream, "fdet_pointwise_fwd_bf16x3");
 }
 
 extern "C" int fdet_pointwise_dgrad_bf16x3(const float* dz, const void* wpk_bwd, const float* add, float* dx, int N, int Cin,
                                            int Cout, int P, void* stream) {
   FDET_REQUIRE(dz && wpk_bwd && dx && N > 0 && Cin > 0 && Cout > 0 && P > 0, "pointwise_dgrad_bf16x3: bad arguments");
   // dX = W^T dZ: the same GEMM with the roles of the channel counts exchanged
-  return run_pw(dz, wpk_bwd, nullptr, add, dx, N, Cout, Cin, P, 1.0f, (hipStream_t)stream, "fdet_pointwise_dgrad_bf16x3");
+  return run_pw<false>(dz, wpk_bwd, nullptr, add, dx, N, Cout, Cin, P, 1.0f, (hipStream_t)stream, "fdet_pointwise_dgrad_bf16x3");
 }
 
 extern "C" size_t fdet_pointwise_wgrad_ws_bytes(int N, int Cin, int Cout, int P) {
@@ -356,10 +388,10 @@ extern "C" size_t fdet_pointwise_wgrad_ws_bytes(int N, int Cin, int Cout, int P)
   return ((size_t)nslab * CoT * 32 * CiT * 32 + (size_t)nslab * CoT * 32) * sizeof(float);
 }
 
-extern "C" int fdet_pointwise_wgrad_bf16x3(const float* x, const float* dz, float* dW, float* db, void* ws, size_t ws_bytes,
-                                           int N, int Cin, int Cout, int P, void* stream) {
-  FDET_REQUIRE(x && dz && dW && ws && N > 0 && Cin > 0 && Cout > 0 && P > 0, "pointwise_wgrad_bf16x3: bad arguments");
-  FDET_REQUIRE(ws_bytes >= fdet_pointwise_wgrad_ws_bytes(N, Cin, Cout, P), "pointwise_wgrad_bf16x3: workspace too small (%zu bytes)", ws_bytes);
+namespace {
+template <bool P16>
+int run_pw_wgrad(const float* x, const float* dz, float* dW, float* db, void* ws, int N, int Cin, int Cout, int P,
+                 hipStream_t st, const char* what) {
   PwWgArgs a;
   a.x = x; a.dz = dz; a.ws = (float*)ws; a.N = N; a.Cin = Cin; a.Cout = Cout; a.P = P;
   a.CoT = (Cout + 31) / 32; a.CiT = (Cin + 31) / 32;
@@ -373,10 +405,39 @@ extern "C" int fdet_pointwise_wgrad_bf16x3(const float* x, const float* dz, floa
   a.vec_ok = vec;
   dim3 grid((unsigned)blocks, (unsigned)a.nslab);
   float* bpart = db ? (float*)ws + (size_t)a.nslab * a.CoT * 32 * a.CiT * 32 : nullptr;     // [nslab][CoT*32]
-  if (vec) hipLaunchKernelGGL(k_pw_wgrad_x3<true>, grid, dim3(256), 0, (hipStream_t)stream, a, bpart);
-  else hipLaunchKernelGGL(k_pw_wgrad_x3<false>, grid, dim3(256), 0, (hipStream_t)stream, a, bpart);
-  hipLaunchKernelGGL(k_pw_wgrad_reduce, dim3((Cout * Cin + 15) / 16), dim3(256), 0, (hipStream_t)stream, (const float*)ws,
+  if (vec) hipLaunchKernelGGL((k_pw_wgrad_x3<true, P16>), grid, dim3(256), 0, st, a, bpart);
+  else hipLaunchKernelGGL((k_pw_wgrad_x3<false, P16>), grid, dim3(256), 0, st, a, bpart);
+  hipLaunchKernelGGL(k_pw_wgrad_reduce, dim3((Cout * Cin + 15) / 16), dim3(256), 0, st, (const float*)ws,
                      a.nslab, a.CoT * 32, a.CiT * 32, Cout, Cin, dW);
-  if (db) hipLaunchKernelGGL(k_pw_bias_slabs, dim3(Cout), dim3(256), 0, (hipStream_t)stream, (const float*)bpart, a.nslab, a.CoT * 32, Cout, db);
-  return check_launch("fdet_pointwise_wgrad_bf16x3");
+  if (db) hipLaunchKernelGGL(k_pw_bias_slabs, dim3(Cout), dim3(256), 0, st, (const float*)bpart, a.nslab, a.CoT * 32, Cout, db);
+  return check_launch(what);
+}
+}  // namespace
+
+extern "C" int fdet_pointwise_wgrad_bf16x3(const float* x, const float* dz, float* dW, float* db, void* ws, size_t ws_bytes,
+                                           int N, int Cin, int Cout, int P, void* stream) {
+  FDET_REQUIRE(x && dz && dW && ws && N > 0 && Cin > 0 && Cout > 0 && P > 0, "pointwise_wgrad_bf16x3: bad arguments");
+  FDET_REQUIRE(ws_bytes >= fdet_pointwise_wgrad_ws_bytes(N, Cin, Cout, P), "pointwise_wgrad_bf16x3: workspace too small (%zu bytes)", ws_bytes);
+  return run_pw_wgrad<false>(x, dz, dW, db, ws, N, Cin, Cout, P, (hipStream_t)stream, "fdet_pointwise_wgrad_bf16x3");
+}
+
+// ---- precision16 twins (include/fdet.h): same arguments, panels and workspace as the _bf16x3 entries
+extern "C" int fdet_pointwise_fwd_bf16(const float* x, const void* wpk_fwd, const float* bias, float* y, int N, int Cin,
+                                       int Cout, int P, float slope, void* stream) {
+  FDET_REQUIRE(x && wpk_fwd && y && N > 0 && Cin > 0 && Cout > 0 && P > 0, "pointwise_fwd_bf16: bad arguments");
+  FDET_REQUIRE((size_t)N * std::max(Cin, Cout) * P < ((size_t)1 << 40), "pointwise_fwd_bf16: tensor too large");
+  return run_pw<true>(x, wpk_fwd, bias, nullptr, y, N, Cin, Cout, P, slope, (hipStream_t)stream, "fdet_pointwise_fwd_bf16");
+}
+
+extern "C" int fdet_pointwise_dgrad_bf16(const float* dz, const void* wpk_bwd, const float* add, float* dx, int N, int Cin,
+                                         int Cout, int P, void* stream) {
+  FDET_REQUIRE(dz && wpk_bwd && dx && N > 0 && Cin > 0 && Cout > 0 && P > 0, "pointwise_dgrad_bf16: bad arguments");
+  return run_pw<true>(dz, wpk_bwd, nullptr, add, dx, N, Cout, Cin, P, 1.0f, (hipStream_t)stream, "fdet_pointwise_dgrad_bf16");
+}
+
+extern "C" int fdet_pointwise_wgrad_bf16(const float* x, const float* dz, float* dW, float* db, void* ws, size_t ws_bytes,
+                                         int N, int Cin, int Cout, int P, void* stream) {
+  FDET_REQUIRE(x && dz && dW && ws && N > 0 && Cin > 0 && Cout > 0 && P > 0, "pointwise_wgrad_bf16: bad arguments");
+  FDET_REQUIRE(ws_bytes >= fdet_pointwise_wgrad_ws_bytes(N, Cin, Cout, P), "pointwise_wgrad_bf16: workspace too small (%zu bytes)", ws_bytes);
+  return run_pw_wgrad<true>(x, dz, dW, db, ws, N, Cin, Cout, P, (hipStream_t)stream, "fdet_pointwise_wgrad_bf16");
 }

@@ -25,7 +25,8 @@ int stem_x3_wgrad(const float* x, const float* dy, float* dW, float* db, float* 
 // fdet_stem_k3.hip: the Resnet stem (k3 s2 p1) on the matrix cores / with a PS (column-strip) output
 bool stem3_wgrad_ok(int Cin, int F, int H, int W, int k, int stride, int pad);
 size_t stem3_wgrad_ws_floats(int N, int F, int H, int W);
-int stem3_wgrad(const float* x, const float* dz, float* dW, float* db, float* ws, size_t ws_floats, int N, int F, int H, int W, hipStream_t st);
+int stem3_wgrad(const float* x, const float* dz, float* dW, float* db, float* ws, size_t ws_floats, int N, int F, int H, int W, hipStream_t st,
+                bool p16);
 bool stem3_fwd_ps_ok(int Cin, int F, int H, int W, int k, int stride, int pad);
 int stem3_fwd_ps(const float* x, const float* w, const float* bias, void* y_ps, int N, int F, int H, int W, hipStream_t st, bool p16);
 }
@@ -415,7 +416,7 @@ extern "C" int fdet_stem_wgrad_bf16x3(const float* x, const float* dy, float* dW
                                       int N, int Cin, int F, int H, int W, int k, int stride, int pad, void* stream) {
   FDET_REQUIRE(x && dy && dW && db && ws && N > 0 && F > 0, "stem_wgrad_bf16x3: bad arguments");
   if (stem3_wgrad_ok(Cin, F, H, W, k, stride, pad))       // the Resnet stem (k3 s2 p1), fdet_stem_k3.hip
-    return stem3_wgrad(x, dy, dW, db, (float*)ws, ws_bytes / 4, N, F, H, W, (hipStream_t)stream);
+    return stem3_wgrad(x, dy, dW, db, (float*)ws, ws_bytes / 4, N, F, H, W, (hipStream_t)stream, false);
   FDET_REQUIRE(stem_mfma_ok(Cin, F, H, W, k, stride, pad) && W % 16 == 0,
                "stem_wgrad_bf16x3: only the PoolResnet stem (3ch k10 s8 p2, W%%16==0, W<=512) is built; got Cin=%d k=%d s=%d p=%d W=%d",
                Cin, k, stride, pad, W);
@@ -427,6 +428,8 @@ extern "C" int fdet_stem_wgrad_bf16x3(const float* x, const float* dy, float* dW
 extern "C" int fdet_stem_wgrad_bf16(const float* x, const float* dy, float* dW, float* db, void* ws, size_t ws_bytes,
                                     int N, int Cin, int F, int H, int W, int k, int stride, int pad, void* stream) {
   FDET_REQUIRE(x && dy && dW && db && ws && N > 0 && F > 0, "stem_wgrad_bf16: bad arguments");
+  if (stem3_wgrad_ok(Cin, F, H, W, k, stride, pad))       // the Resnet / SSD stem (k3 s2 p1), fdet_stem_k3.hip
+    return stem3_wgrad(x, dy, dW, db, (float*)ws, ws_bytes / 4, N, F, H, W, (hipStream_t)stream, true);
   FDET_REQUIRE(stem_mfma_ok(Cin, F, H, W, k, stride, pad) && W % 16 == 0,
                "stem_wgrad_bf16: only the PoolResnet stem (3ch k10 s8 p2, W%%16==0, W<=512) is built; got Cin=%d k=%d s=%d p=%d W=%d",
                Cin, k, stride, pad, W);

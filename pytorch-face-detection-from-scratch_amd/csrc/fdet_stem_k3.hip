@@ -9,6 +9,9 @@
 //   k_stem3_fwd_ps     the forward with a pre-split (PS, fdet_ps.h) output written directly in the column-strip layout of the
 //                      first block (halo slots included): fp32 VALU, lane = output column, weights wave-uniform.
 //
+// precision16 (template flag P16, fdet_stem_wgrad_bf16 on this shape): both operands rounded to bf16 (RNE, the hi part),
+// ONE MFMA per fragment pair, fp32 accumulation; db = sum of bf16(dz) (the ones column is exact in bf16).
+//
 // The scalar-fed VALU weight gradient this replaces (k_stem_wgrad_k3, fdet_stem.hip) took 0.79 ms at 640^2 bs 32; it remains
 // for shapes this kernel does not cover (Wo % 16 != 0, Wo > 320) and for the exact-fp32 path.
 #include "fdet_conv3x3_x3.h"
@@ -40,6 +43,7 @@ __device__ __forceinline__ void s3_split8(const float (&f)[8], bf16x8& hi, bf16x
 // One workgroup (4 waves) walks output rows; per row the nine input rows (3 channels x 3 ky) sit in LDS as
 // [row][4 zero floats | W floats], pitch == 4 (mod 64) floats so that the taps of a fragment read fall on distinct banks.
 // blockIdx.y = 64-channel block of F.
+template <bool P16 = false>
 __global__ void __launch_bounds__(256)
 k_stem3_wgrad_x3(const Stem3WgArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -106,6 +110,10 @@ k_stem3_wgrad_x3(const Stem3WgArgs a) {
           const float af[8] = {av[s][m][0].x, av[s][m][0].y, av[s][m][0].z, av[s][m][0].w,
                                av[s][m][1].x, av[s][m][1].y, av[s][m][1].z, av[s][m][1].w};
           s3_split8(af, ah, al);
+          if constexpr (P16) {
+            acc[m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, acc[m], 0, 0, 0);
+            continue;
+          }
           acc[m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl, acc[m], 0, 0, 0);
           acc[m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh, acc[m], 0, 0, 0);
           acc[m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, acc[m], 0, 0, 0);
@@ -234,7 +242,7 @@ size_t stem3_wgrad_ws_floats(int N, int F, int H, int W) {
 }
 
 int stem3_wgrad(const float* x, const float* dz, float* dW, float* db, float* ws, size_t ws_floats, int N, int F, int H, int W,
-                hipStream_t st) {
+                hipStream_t st, bool p16) {
   Stem3WgArgs a;
   a.x = x; a.dz = dz; a.ws = ws; a.N = N; a.F = F; a.H = H; a.W = W;
   a.Ho = H / 2; a.Wo = W / 2;
@@ -246,16 +254,18 @@ int stem3_wgrad(const float* x, const float* dz, float* dW, float* db, float* ws
   grid = (int)std::min<size_t>((size_t)grid, ws_floats / ((size_t)fblk * 2048));
   if (grid < 1) return fail(FDET_EWORKSPACE, "stem_wgrad_bf16x3 (k3): workspace too small");
   const size_t lds = std::max<size_t>((size_t)9 * a.pitch * 4, (size_t)4 * 2048 * 4);
-  static bool attr = false;
-  if (!attr) {
-    if (hipFuncSetAttribute((const void*)k_stem3_wgrad_x3, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024) != hipSuccess) {
+  static bool attr[2] = {false, false};
+  if (!attr[p16]) {
+    const void* k = p16 ? (const void*)k_stem3_wgrad_x3<true> : (const void*)k_stem3_wgrad_x3<false>;
+    if (hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024) != hipSuccess) {
       (void)hipGetLastError();
       return fail(FDET_ELAUNCH, "stem_wgrad_bf16x3 (k3): cannot reserve LDS");
     }
-    attr = true;
+    attr[p16] = true;
   }
   if (lds > 64 * 1024) return fail(FDET_EINVAL, "stem_wgrad_bf16x3 (k3): rows of %d columns do not fit the LDS plan", W);
-  hipLaunchKernelGGL(k_stem3_wgrad_x3, dim3(grid, fblk), dim3(256), lds, st, a);
+  if (p16) hipLaunchKernelGGL(k_stem3_wgrad_x3<true>, dim3(grid, fblk), dim3(256), lds, st, a);
+  else hipLaunchKernelGGL(k_stem3_wgrad_x3<false>, dim3(grid, fblk), dim3(256), lds, st, a);
   if (int rc = check_launch("fdet_stem_wgrad_bf16x3(k3)")) return rc;
   hipLaunchKernelGGL(k_stem3_reduce, dim3(F), dim3(256), 0, st, ws, grid, F, dW, db);
   return check_launch("fdet_stem_wgrad_bf16x3(k3 reduce)");

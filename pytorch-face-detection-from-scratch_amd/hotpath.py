@@ -472,8 +472,8 @@ def pointwise_pack(w: torch.Tensor):
     return f_, b_
 
 
-def pointwise_fwd(x, wpk_fwd, bias, y, slope: float = 1.0):
-    """y (N,Cout,H,W) = lrelu_slope(W x + bias) for x (N,Cin,H,W)."""
+def pointwise_fwd(x, wpk_fwd, bias, y, slope: float = 1.0, p16: bool = False):
+    """y (N,Cout,H,W) = lrelu_slope(W x + bias) for x (N,Cin,H,W).  p16: precision16 (fdet_pointwise_fwd_bf16)."""
     Nn, cin = x.shape[0], x.shape[1]
     cout = y.shape[1]
     P = x.numel() // (Nn * cin)
@@ -483,12 +483,12 @@ def pointwise_fwd(x, wpk_fwd, bias, y, slope: float = 1.0):
         _chk4(bias, (cout,), "bias")
     if wpk_fwd.numel() * 4 < int(lib().fdet_pointwise_packed_bytes(cout, cin)):
         raise ValueError("pointwise_fwd: packed weight buffer too small for (Cout,Cin)")
-    check(lib().fdet_pointwise_fwd_bf16x3(ptr(x), ptr(wpk_fwd), ptr(bias), ptr(y), Nn, cin, cout, P, float(slope), stream()),
-          "fdet_pointwise_fwd_bf16x3")
+    fn = lib().fdet_pointwise_fwd_bf16 if p16 else lib().fdet_pointwise_fwd_bf16x3
+    check(fn(ptr(x), ptr(wpk_fwd), ptr(bias), ptr(y), Nn, cin, cout, P, float(slope), stream()), fn.__name__)
 
 
-def pointwise_dgrad(dz, wpk_bwd, dx, add=None):
-    """dx (N,Cin,H,W) = W^T dz (+ add)."""
+def pointwise_dgrad(dz, wpk_bwd, dx, add=None, p16: bool = False):
+    """dx (N,Cin,H,W) = W^T dz (+ add).  p16: precision16 (fdet_pointwise_dgrad_bf16)."""
     Nn, cout = dz.shape[0], dz.shape[1]
     cin = dx.shape[1]
     P = dz.numel() // (Nn * cout)
@@ -496,12 +496,13 @@ def pointwise_dgrad(dz, wpk_bwd, dx, add=None):
         raise ValueError("pointwise_dgrad: shapes disagree")
     if wpk_bwd.numel() * 4 < int(lib().fdet_pointwise_packed_bytes(cout, cin)):
         raise ValueError("pointwise_dgrad: packed weight buffer too small for (Cout,Cin)")
-    check(lib().fdet_pointwise_dgrad_bf16x3(ptr(dz), ptr(wpk_bwd), ptr(add), ptr(dx), Nn, cin, cout, P, stream()),
-          "fdet_pointwise_dgrad_bf16x3")
+    fn = lib().fdet_pointwise_dgrad_bf16 if p16 else lib().fdet_pointwise_dgrad_bf16x3
+    check(fn(ptr(dz), ptr(wpk_bwd), ptr(add), ptr(dx), Nn, cin, cout, P, stream()), fn.__name__)
 
 
-def pointwise_wgrad(x, dz, dW, db=None):
-    """dW (Cout,Cin[,1,1]) = sum dz x^T, db (Cout,) = sum dz."""
+def pointwise_wgrad(x, dz, dW, db=None, p16: bool = False):
+    """dW (Cout,Cin[,1,1]) = sum dz x^T, db (Cout,) = sum dz.  p16: precision16 (fdet_pointwise_wgrad_bf16: bf16-rounded
+    operands, fp32 sums; the same workspace)."""
     Nn, cin = x.shape[0], x.shape[1]
     cout = dz.shape[1]
     P = x.numel() // (Nn * cin)
@@ -509,8 +510,8 @@ def pointwise_wgrad(x, dz, dW, db=None):
         raise ValueError("pointwise_wgrad: shapes disagree")
     nb = int(lib().fdet_pointwise_wgrad_ws_bytes(Nn, cin, cout, P))
     ws = torch.empty(nb // 4 + 4, dtype=F32, device=x.device)
-    check(lib().fdet_pointwise_wgrad_bf16x3(ptr(x), ptr(dz), ptr(dW), ptr(db), ptr(ws), ws.numel() * 4, Nn, cin, cout, P, stream()),
-          "fdet_pointwise_wgrad_bf16x3")
+    fn = lib().fdet_pointwise_wgrad_bf16 if p16 else lib().fdet_pointwise_wgrad_bf16x3
+    check(fn(ptr(x), ptr(dz), ptr(dW), ptr(db), ptr(ws), ws.numel() * 4, Nn, cin, cout, P, stream()), fn.__name__)
 
 
 def conv3x3_wgrad_ws_bytes(Nn, cin, cout, H, W) -> int:

@@ -88,8 +88,9 @@ class ModelMetaSSD(_Base):
     validation_epoch_end = _YoloMeta.validation_epoch_end
     test_epoch_end = _YoloMeta.test_epoch_end
 
-    def fused_train_step(self, x, y):
-        """One optimisation step on (x (N,3,480,480) in [0,1], y (N,4774,5)); returns (loss (1,), y_hat)."""
+    def fused_train_step(self, x, y, with_metrics=False):
+        """One optimisation step on (x (N,3,480,480) in [0,1], y (N,4774,5)); returns (loss (1,), y_hat), or with
+        `with_metrics` (trainer.fit) (loss, y_hat, tot) with tot = (total_iou, total_recall, total_precision) of step()."""
         if self.opt is None:
             self.configure_optimizers()
         model, eng = self.model, self.model.engine
@@ -128,4 +129,6 @@ class ModelMetaSSD(_Base):
             self._reducer.launch_tail()
             self._reducer.wait()
         self.opt.step(grads_in_flat=True)
+        if with_metrics:
+            return loss, y_hat, self._metrics(y_hat, y)
         return loss, y_hat

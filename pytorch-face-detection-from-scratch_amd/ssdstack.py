@@ -6,11 +6,20 @@ sequence of HIP kernel launches, assembled from the same bf16x3 primitives as th
     after each of the last four blocks: Linear(C,5) on the NHWC map -> rows of the (N,4774,5) output,
     sigmoid on the score, apply_priors.
 
-The 1x1 skip convs and the Linear heads run through the 3x3 kernels with centre-tap weights
-(identity activation: slope 1) -- correctness first; they are a few percent of the model's MACs.
-A dedicated pointwise kernel is the next step for this row."""
+The 1x1 skip convs and the Linear heads run on the pointwise GEMM kernels (fdet_pointwise_*, identity activation:
+slope 1).
+
+Precision: bf16x3 (fp32-grade, default) or precision16 (FDET_PRECISION=bf16 at construction, or set_precision("bf16")):
+the arithmetic of the reference's Trainer(precision=16) (train_model_ssd.py:46-50) with bf16 as the 16-bit type.  In
+precision16 the 3x3 convs (forward, data and weight gradients, batched weight gradients included), the 1x1 skip convs and
+the Linear heads (forward, data and weight gradients) and the stem weight gradient run ONE bf16 MFMA pass with fp32
+accumulation and epilogues, and round every stored activation / activation gradient to bf16.  What stays fp32-grade: the
+stem forward (VALU), block_tail_fwd / block_tail_bwd (dropout, skip add, max-pool and their gradients),
+ssd_head_pack_fwd / _bwd (sigmoid and priors) and ssd_loss.  A pass saved by forward(save=True) carries its precision:
+backward() runs in it, whatever set_precision() said since."""
 from __future__ import annotations
 
+import os
 from typing import Dict, List, Optional
 
 import torch
@@ -64,6 +73,16 @@ class SSDStack:
         self.slope = 0.2
         self._pending: list = []                           # same-shape weight gradients awaiting one batched launch
         self.timer = None                                  # convstack.KernelTimer: per-launch HIP events (bench.py's config-4 table)
+        # precision16 (FDET_PRECISION=bf16 or set_precision("bf16")): one bf16 MFMA pass on every matrix-core layer, as
+        # ConvStack's; any other value (unset included) keeps the fp32-grade bf16x3 arithmetic
+        self.p16 = os.environ.get("FDET_PRECISION", "bf16x3") == "bf16"
+
+    def set_precision(self, name: str) -> None:
+        """"bf16x3" (fp32-grade, default) or "bf16" (precision16: one MFMA pass).  A pass saved by forward(save=True) keeps
+        the precision it ran in: backward() follows it, not this setting."""
+        if name not in ("bf16x3", "bf16"):
+            raise ValueError("precision must be 'bf16x3' or 'bf16'")
+        self.p16 = name == "bf16"
 
     def _t(self, kind: str, hk: int, ci: int, co: int):
         if self.timer is None:
@@ -122,7 +141,9 @@ class SSDStack:
         with self._t("stem_fwd", h0, 3, f):
             hp.stem_fwd(x, P["input_normalizer.weight"], P["input_normalizer.bias"], h, ws, 3, 2, 1)
         y = torch.empty(N, self.P, 5, dtype=F32, device=dev)
-        saved = {"x": x, "blocks": [], "masks": masks, "heads": {}} if save else None
+        p16 = self.p16
+        # (the precision is stamped into the saved state: backward() runs the pass in the precision of its forward)
+        saved = {"x": x, "blocks": [], "masks": masks, "heads": {}, "p16": p16} if save else None
         for name, ci, co, pool, head in self.specs:
             hk = h.shape[2]
             sc = masks[name] if masks is not None else None
@@ -131,22 +152,24 @@ class SSDStack:
             else:
                 skip = torch.empty(N, co, hk, hk, dtype=F32, device=dev)
                 with self._t("skip1x1_fwd", hk, ci, co):
-                    hp.pointwise_fwd(h, self._wpk[name + ".skip.f"], P[name + ".pointwise_conv_skip.bias"], skip)
+                    hp.pointwise_fwd(h, self._wpk[name + ".skip.f"], P[name + ".pointwise_conv_skip.bias"], skip, p16=p16)
             a = torch.empty(N, co, hk, hk, dtype=F32, device=dev)
             with self._t("conv3x3_fwd", hk, ci, co):
-                hp.conv3x3_fwd(h, self._wpk[name + ".conv1.f"], P[name + ".conv1.bias"], co, y_full=a, slope=self.slope, x3=True)
+                hp.conv3x3_fwd(h, self._wpk[name + ".conv1.f"], P[name + ".conv1.bias"], co, y_full=a, slope=self.slope, x3=True,
+                               p16=p16)
             ho = hk // 2 if pool else hk
             out = torch.empty(N, co, ho, ho, dtype=F32, device=dev)
             c = torch.empty_like(a) if (pool or save) else None
             if pool:
                 with self._t("conv3x3_fwd", hk, co, co):
-                    hp.conv3x3_fwd(a, self._wpk[name + ".conv2.f"], P[name + ".conv2.bias"], co, y_full=c, slope=self.slope, x3=True)
+                    hp.conv3x3_fwd(a, self._wpk[name + ".conv2.f"], P[name + ".conv2.bias"], co, y_full=c, slope=self.slope, x3=True,
+                                   p16=p16)
                 with self._t("tail_fwd", hk, co, co):
                     hp.block_tail_fwd(c, skip, sc, out, 2)
             else:
                 with self._t("conv3x3_fwd", hk, co, co):
                     hp.conv3x3_fwd(a, self._wpk[name + ".conv2.f"], P[name + ".conv2.bias"], co, y_full=c, skip=skip,
-                                   drop_scale=sc, y_out=out, slope=self.slope, x3=True)
+                                   drop_scale=sc, y_out=out, slope=self.slope, x3=True, p16=p16)
             if save:
                 saved["blocks"].append((h, skip, a, c))
             h = out
@@ -154,7 +177,7 @@ class SSDStack:
                 hn = f"extracting_layers.{head}.0"
                 z = torch.empty(N, 5, ho, ho, dtype=F32, device=dev)       # Linear(C,5) at every position
                 with self._t("head", ho, co, 5):
-                    hp.pointwise_fwd(h, self._wpk[hn + ".f"], P[hn + ".bias"], z)
+                    hp.pointwise_fwd(h, self._wpk[hn + ".f"], P[hn + ".bias"], z, p16=p16)
                     hp.ssd_head_pack_fwd(z, PATCH_SIZES[head], self.starts[head], y)
                 if save:
                     saved["heads"][head] = h
@@ -163,25 +186,25 @@ class SSDStack:
         return y, saved
 
     # ------------------------------------------------------------------ backward
-    def _wgrad(self, xin, dz, dW, db, dev):
+    def _wgrad(self, xin, dz, dW, db, dev, p16: bool):
         """dW / db (the caller's gradient tensors, written in place) of one 3x3 conv.  Same-shape layers (the six 2F -> 2F
         blocks at 60x60: twelve weight gradients of ~45 us each) are collected and go out in ONE batched launch."""
         N, ci, H, W = xin.shape
         co = dz.shape[1]
         key = (N, ci, co, H, W)
         if self._pending and self._pending[0][0] != key:
-            self._flush_wgrads(dev)
+            self._flush_wgrads(dev, p16)
         if hp.conv3x3_wgrad_batched_ws_bytes(2, N, ci, co, H, W) > 0:
             self._pending.append((key, xin, dz, dW, db))
             if len(self._pending) == 16:
-                self._flush_wgrads(dev)
+                self._flush_wgrads(dev, p16)
             return
         x3 = hp.wgrad_x3_supported(N, ci, co, H, W)
         ws = self._workspace("wgrad", hp.conv3x3_wgrad_ws_bytes(N, ci, co, H, W), dev)
         with self._t("conv3x3_wgrad", H, ci, co):
-            hp.conv3x3_wgrad(xin, dz, dW, db, ws, x3=x3)
+            hp.conv3x3_wgrad(xin, dz, dW, db, ws, x3=x3, p16=p16 and x3)
 
-    def _flush_wgrads(self, dev):
+    def _flush_wgrads(self, dev, p16: bool):
         grp, self._pending = self._pending, []
         if not grp:
             return
@@ -191,14 +214,18 @@ class SSDStack:
             ws = self._workspace("wgrad", hp.conv3x3_wgrad_ws_bytes(N, ci, co, H, W), dev)
             for _, xin, dz, dW, db in grp:
                 with self._t("conv3x3_wgrad", H, ci, co):
-                    hp.conv3x3_wgrad(xin, dz, dW, db, ws, x3=hp.wgrad_x3_supported(N, ci, co, H, W))
+                    x3 = hp.wgrad_x3_supported(N, ci, co, H, W)
+                    hp.conv3x3_wgrad(xin, dz, dW, db, ws, x3=x3, p16=p16 and x3)
             return
         ws = self._workspace("wgrad_batched", nb, dev)
         with self._t(f"conv3x3_wgrad(x{len(grp)})", H, ci, co):
-            hp.conv3x3_wgrad_batched([g_[1] for g_ in grp], [g_[2] for g_ in grp], [g_[3] for g_ in grp], [g_[4] for g_ in grp], ws)
+            hp.conv3x3_wgrad_batched([g_[1] for g_ in grp], [g_[2] for g_ in grp], [g_[3] for g_ in grp], [g_[4] for g_ in grp], ws,
+                                     p16=p16)
 
     def backward(self, saved, dy, P, G) -> None:
-        """dy = d loss / d y (N,4774,5); writes the gradient of every parameter into G[name]."""
+        """dy = d loss / d y (N,4774,5); writes the gradient of every parameter into G[name].  Runs in the precision the
+        forward pass ran in (saved["p16"]), whatever set_precision() said since."""
+        p16 = bool(saved.get("p16", self.p16))
         x, masks, y = saved["x"], saved["masks"], saved["y"]
         N, dev = x.shape[0], x.device
         dy = dy.to(F32).contiguous()
@@ -215,9 +242,9 @@ class SSDStack:
                 dz = torch.empty(N, 5, ho, ho, dtype=F32, device=dev)
                 with self._t("head_bwd", ho, co, 5):
                     hp.ssd_head_pack_bwd(dy, y, PATCH_SIZES[head], self.starts[head], dz)
-                    hp.pointwise_wgrad(hout, dz, G[hn + ".weight"], G[hn + ".bias"])
+                    hp.pointwise_wgrad(hout, dz, G[hn + ".weight"], G[hn + ".bias"], p16=p16)
                     dout = torch.empty_like(hout)
-                    hp.pointwise_dgrad(dz, self._wpk[hn + ".b"], dout, add=dtrunk)
+                    hp.pointwise_dgrad(dz, self._wpk[hn + ".b"], dout, add=dtrunk, p16=p16)
             else:
                 dout = dtrunk
             sc = masks[name] if masks is not None else None
@@ -229,27 +256,29 @@ class SSDStack:
                 else:
                     de = dout
                     hp.block_tail_bwd(dout, c, None, sc, dz2, None, 1, self.slope)
-            self._wgrad(a, dz2, G[name + ".conv2.weight"], G[name + ".conv2.bias"], dev)
+            self._wgrad(a, dz2, G[name + ".conv2.weight"], G[name + ".conv2.bias"], dev, p16)
             dz1 = torch.empty_like(a)
             with self._t("conv3x3_dgrad", hk, co, co):
-                hp.conv3x3_dgrad(dz2, self._wpk[name + ".conv2.b"], co, dz1, act=a, slope=self.slope, x3=True)
-            self._wgrad(hin, dz1, G[name + ".conv1.weight"], G[name + ".conv1.bias"], dev)
+                hp.conv3x3_dgrad(dz2, self._wpk[name + ".conv2.b"], co, dz1, act=a, slope=self.slope, x3=True, p16=p16)
+            self._wgrad(hin, dz1, G[name + ".conv1.weight"], G[name + ".conv1.bias"], dev, p16)
             if ci == co:
                 addt = de
             else:
                 with self._t("skip1x1_bwd", hk, ci, co):
-                    hp.pointwise_wgrad(hin, de, G[name + ".pointwise_conv_skip.weight"], G[name + ".pointwise_conv_skip.bias"])
+                    hp.pointwise_wgrad(hin, de, G[name + ".pointwise_conv_skip.weight"], G[name + ".pointwise_conv_skip.bias"],
+                                       p16=p16)
                     addt = torch.empty_like(hin)
-                    hp.pointwise_dgrad(de, self._wpk[name + ".skip.b"], addt)
+                    hp.pointwise_dgrad(de, self._wpk[name + ".skip.b"], addt, p16=p16)
             dx = torch.empty_like(hin)
             with self._t("conv3x3_dgrad", hk, co, ci):
-                hp.conv3x3_dgrad(dz1, self._wpk[name + ".conv1.b"], ci, dx, add=addt, slope=self.slope, x3=True)
+                hp.conv3x3_dgrad(dz1, self._wpk[name + ".conv1.b"], ci, dx, add=addt, slope=self.slope, x3=True, p16=p16)
             dtrunk = dx
-        self._flush_wgrads(dev)
+        self._flush_wgrads(dev, p16)
         ws = self._workspace("stem", hp.stem_ws_bytes(N, 3, self.filters, self.size, self.size, 3, 2, 1), dev)
+        stem_x3 = hp.stem_k3_wgrad_x3_supported(3, self.filters, self.size, self.size, 3, 2, 1)   # bf16x3 like every other layer
         with self._t("stem_wgrad", self.size // 2, 3, self.filters):
             hp.stem_wgrad(x, dtrunk, G["input_normalizer.weight"], G["input_normalizer.bias"], ws, 3, 2, 1,
-                          x3=hp.stem_k3_wgrad_x3_supported(3, self.filters, self.size, self.size, 3, 2, 1))   # bf16x3 like every other layer of the stack
+                          x3=stem_x3, p16=p16 and stem_x3)
 
 
 class SSDStackFn(torch.autograd.Function):

@@ -96,6 +96,7 @@ def _op_ssd_forward(x: torch.Tensor, params: List[torch.Tensor], filters: int, s
     eng = _ssd_engines.get((filters, size))
     if eng is None:
         eng = _ssd_engines[(filters, size)] = SSDStack(filters, size)
+        eng.set_precision("bf16x3")                          # the scripted module is default precision (FDET_PRECISION aside)
     names = ssd_param_names(filters)
     if len(params) != len(names):
         raise ValueError(f"fdet::ssd_forward: expected {len(names)} parameter tensors, got {len(params)}")
