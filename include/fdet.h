@@ -259,6 +259,9 @@ int fdet_conv3x3_wgrad_bf16x3_batched(const float* const* h_x, const float* cons
  *             dout <- conv1_k^T(dz1_k) + dout, for k = nblocks-1 .. 0; dx = final dout.
  *     h_wpk1b/h_wpk2b: backward panels; h_dz1/h_dz2 [N,64,H,W] are written (operands of the weight gradients). */
 int fdet_block_chain_supported(int F, int H, int W);
+/* Plan query (launches nothing): the chain kernels run N images of this map (batch-size limits included); ps = 1: the PS
+ * flavour (fdet_block_chain_fwd_ps / _bwd_ps).  The entry points refuse exactly what this refuses. */
+int fdet_block_chain_ok(int N, int F, int H, int W, int ps);
 int fdet_block_chain_fwd_bf16x3(const float* x, const void* const* h_wpk1, const float* const* h_b1,
                                 const void* const* h_wpk2, const float* const* h_b2,
                                 const float* const* h_scale, float* const* h_a, float* const* h_c,
@@ -301,6 +304,10 @@ int fdet_block_tail_fwd(const float* c, const float* x, const float* drop_scale,
  *             fdet_conv3x3_dgrad_unpool  dx = conv^T(dz) + unpool(dout_pooled)      (conv1's data gradient + skip path)
  * wpk: forward / backward panels of fdet_pack_conv3x3_weights_bf16x3. */
 int fdet_conv3x3_pool_fusion_ok(int N, int Cin, int Cout, int H, int W);   /* 1: the two kernels below have a tiling for the shape */
+/* Plan query of the PS conv kernels (fdet_conv3x3_ps_*; launches nothing): 1 when they accept N images of this shape.
+ * pooled: 0 = conv / data gradient, 1 = pooled block with an fp32 pooled output (and its backward), 2 = pooled block
+ * with a PS pooled output.  The entry points refuse exactly what this refuses. */
+int fdet_conv3x3_ps_ok(int N, int Cin, int Cout, int H, int W, int pooled);
 int fdet_conv3x3_fwd_pool_bf16x3(const float* x, const void* wpk, const float* bias, const float* skip,
                                  const float* drop_scale, float* out_pooled, unsigned char* route, int N, int Cin,
                                  int Cout, int H, int W, float slope, void* stream);
@@ -498,6 +505,13 @@ int fdet_stem_fwd_ps_u8(const unsigned char* frames, const float* w, const float
  * the PoolResnet stem (k10 s8 p2) and the Resnet / SSD stem (3ch k3 s2 p1, the shapes of its bf16x3 matrix-core kernel). */
 int fdet_stem_wgrad_bf16(const float* x, const float* dy, float* dW, float* db, void* ws, size_t ws_bytes,
                          int N, int Cin, int F, int H, int W, int k, int stride, int pad, void* stream);
+/* Plan queries of the stem (launch nothing; the entry points refuse exactly what these refuse, batch sizes included):
+ *   fdet_stem_fwd_ps_ok    fdet_stem_fwd_ps / _p16 (u8 = 0) or fdet_stem_fwd_ps_u8 (u8 = 1) accept N images of this shape
+ *   fdet_stem_wgrad_x3_ok  fdet_stem_wgrad_bf16x3 (precision16 = 0) or fdet_stem_wgrad_bf16 (precision16 = 1) do
+ * The PoolResnet stem runs batches beyond the 32-bit offsets of its pipelined kernels as consecutive launches over image
+ * chunks; its weight gradient sums the per-workgroup partials of every chunk in one reduction (fdet_stem_ws_bytes). */
+int fdet_stem_fwd_ps_ok(int N, int Cin, int F, int H, int W, int k, int stride, int pad, int precision16, int u8);
+int fdet_stem_wgrad_x3_ok(int N, int Cin, int F, int H, int W, int k, int stride, int pad, int precision16);
 int fdet_conv3x3_wgrad_ps_batched_p16(const void* const* h_x, const void* const* h_dz, float* const* h_dW,
                                       float* const* h_db, int L, int N, int C, int H, int W, void* ws,
                                       size_t ws_bytes, void* stream);

@@ -264,6 +264,22 @@ class ConvStack:
             return self.ps_strips and psm.strips_of(hk)[0] > 1 and psm.conv3x3_wgrad_ps_ws_bytes(1, self._cur_N, self.geo.filters, hk, hk) > 0
         return self._fused_pool(hk, self._cur_N)
 
+    def _stem_ps(self) -> bool:
+        """The stem writes the first block's PS input itself (for the batch size of the pass, _cur_N): the PoolResnet stem
+        (k10 s8 p2, plain layout) or the Resnet stem (k3 s2 p1, column strips included)."""
+        g = self.geo
+        return self._ps_block(0) and self.x3 and \
+            ((not self._strips(self.h0) and hp.stem_x3_supported(g.in_ch, g.W, g.stem_k, g.stem_s, g.stem_p)) or
+             hp.stem_k3_fwd_ps_supported(g.in_ch, g.filters, g.H, g.W, g.stem_k, g.stem_s, g.stem_p))
+
+    def _stem_wgrad_kind(self):
+        """(x3, p16) of the stem weight gradient: the matrix-core kernel where one exists for the stem's shape, in precision16
+        where the engine runs it and the PoolResnet stem's kernel has its one-pass form (48 < Wo <= 60)."""
+        g = self.geo
+        x3 = self.x3 and ((g.W % 16 == 0 and hp.stem_x3_supported(g.in_ch, g.W, g.stem_k, g.stem_s, g.stem_p)) or
+                          hp.stem_k3_wgrad_x3_supported(g.in_ch, g.filters, g.H, g.W, g.stem_k, g.stem_s, g.stem_p))
+        return x3, self.p16 and x3 and 48 < self.h0 <= 60
+
     def _strips(self, hk: int) -> bool:
         return hk > 62
 
@@ -330,9 +346,7 @@ class ConvStack:
         ws = self._workspace("stem", hp.stem_ws_bytes(N, g.in_ch, F_, g.H, g.W, g.stem_k, g.stem_s, g.stem_p), dev)
         # the stem writes the first block's PS input itself: the PoolResnet stem (k10 s8 p2, plain layout) or the Resnet stem
         # (k3 s2 p1, column strips included)
-        stem_ps = self._ps_block(0) and self.x3 and \
-            ((not self._strips(self.h0) and hp.stem_x3_supported(g.in_ch, g.W, g.stem_k, g.stem_s, g.stem_p)) or
-             hp.stem_k3_fwd_ps_supported(g.in_ch, F_, g.H, g.W, g.stem_k, g.stem_s, g.stem_p))
+        stem_ps = self._stem_ps()
         if u8_frames and not stem_ps:                      # (a batch too large for the pre-split path: the separate x / 255)
             x = hp.u8_to_f32_norm(x)
         h = torch.empty(N, F_, self.h0, self.h0, dtype=F32, device=dev) if not stem_ps else None
@@ -733,10 +747,8 @@ class ConvStack:
         ws = self._workspace("stem", hp.stem_ws_bytes(N, g.in_ch, F_, g.H, g.W, g.stem_k, g.stem_s, g.stem_p), dev)
         stem_flops = 2.0 * N * F_ * g.in_ch * g.stem_k * g.stem_k * self.h0 * self.h0
         with self._t("stem_wgrad", N, self.h0, stem_flops, 4.0 * N * (g.in_ch * g.H * g.W + F_ * self.h0 * self.h0)):
-            stem_x3 = self.x3 and ((g.W % 16 == 0 and hp.stem_x3_supported(g.in_ch, g.W, g.stem_k, g.stem_s, g.stem_p)) or
-                                   hp.stem_k3_wgrad_x3_supported(g.in_ch, F_, g.H, g.W, g.stem_k, g.stem_s, g.stem_p))
-            hp.stem_wgrad(x, dout, G["conv1.weight"], G["conv1.bias"], ws, g.stem_k, g.stem_s, g.stem_p, x3=stem_x3,
-                          p16=self.p16 and stem_x3 and 48 < self.h0 <= 60)
+            stem_x3, stem_p16 = self._stem_wgrad_kind()
+            hp.stem_wgrad(x, dout, G["conv1.weight"], G["conv1.bias"], ws, g.stem_k, g.stem_s, g.stem_p, x3=stem_x3, p16=stem_p16)
         join()
         if saved.get("ps_scope") is not None:
             saved["ps_scope"].release()                    # the saved PS activations / gradients are dead: back to the pool

@@ -781,11 +781,16 @@ int chain_geometry(int F, int H, int W, int& WP, int& PT, size_t& lds) {
   return lds <= 160 * 1024;
 }
 
+// the batch-size limit of launch_chain (fdet_block_chain_ok answers with it): 32-bit offsets of the fp32 tensors
+bool chain_batch_ok(int N, int H, int W) {
+  return N > 0 && (size_t)N * FCH * H * W < ((size_t)1 << 31);
+}
+
 int launch_chain(ChainArgs& a, hipStream_t st) {
   size_t lds = 0;
   if (!chain_geometry(FCH, a.H, a.W, a.WP, a.PT, lds))
     return fail(FDET_EINVAL, "block_chain_bf16x3: unsupported map %dx%d (needs 64 channels and H*roundup4(W+1) <= 256)", a.H, a.W);
-  if ((size_t)a.N * FCH * a.H * a.W >= ((size_t)1 << 31)) return fail(FDET_EINVAL, "block_chain_bf16x3: tensor too large");
+  if (!chain_batch_ok(a.N, a.H, a.W)) return fail(FDET_EINVAL, "block_chain_bf16x3: tensor too large");
   { const char* e_ = FDET_ENV_ONCE("FDET_CHAIN_STAGGER"); a.stagger = e_ ? atoi(e_) : 0; }
   if ((a.psio & 1) && (a.psio & 4) && a.bwd) {             // psio bit 2: precision16
     { if (int rc_ = set_lds_attr((const void*)k_block_chain_ps<true, true>, (size_t)(lds), __func__)) return rc_; }
@@ -880,6 +885,13 @@ int chain_ps_geo(ChainArgs& a, int N, int H, int W) {
   return 1;
 }
 }  // namespace
+
+// plan query (no launch): the chain kernels (ps = 1: the PS flavour) run N images of this map
+extern "C" int fdet_block_chain_ok(int N, int F, int H, int W, int ps) {
+  int WP, PT; size_t lds;
+  ChainArgs a{};
+  return chain_geometry(F, H, W, WP, PT, lds) && chain_batch_ok(N, H, W) && (!ps || chain_ps_geo(a, N, H, W));
+}
 
 namespace {
 int chain_fwd_ps_run(const void* x, int x_is_ps, const void* const* h_wpk1, const float* const* h_b1,

@@ -698,18 +698,37 @@ struct PsPoolIO {
   const float* dout = nullptr; const unsigned char* route_in = nullptr; float* dx_f32 = nullptr;
 };
 
-int run_ps(int mode, const void* x, const void* wpk, const float* bias, const void* aux, void* y, const PsPoolIO& io, int N,
-           int Cin, int Cout, int H, int W, float slope, hipStream_t st, bool p16 = false) {
+// The shape and batch-size checks of run_ps (fdet_conv3x3_ps_ok answers with the same function): nullptr = the plan
+// exists, else why not.  pooled: 0 = plain conv, 1 = pooled block with an fp32 pooled output, 2 = with a PS pooled output.
+const char* ps_conv_refusal(int pooled, int N, int Cin, int Cout, int H, int W) {
   PsGeo gi, go, gp;
   PsStrips sp, spo;
+  if (!(Cout == 64 && Cin % 16 == 0 && Cin >= 32)) return "Cout must be 64 and Cin a multiple of 16, at least 32";
+  // maps wider than 62 columns run as column strips (fdet_ps.h)
+  if (!(ps_geo_strips(N, Cin, H, W, gi, sp) && ps_geo_strips(N, Cout, H, W, go, spo) && gi.WP >= 32 && sp.Ws + 2 <= gi.WP))
+    return "unsupported map (W + 2 <= 32 or 64 slots, or an even width in strips)";
+  if (!((size_t)(gi.N + 2) * gi.img * 16 < ((size_t)1 << 32) && (size_t)(go.N + 2) * go.img * 16 < ((size_t)1 << 32)))
+    return "tensor too large for the 32-bit byte offsets of the DMA descriptors";
+  if (pooled) {
+    if ((H & 1) || (W & 1) || Cin != 64) return "pooled block: even map and 64 channels required";
+    if ((size_t)N * 64 * H * W * 4 >= ((size_t)1 << 31)) return "pooled block: tensor too large for 32-bit offsets";
+    if (pooled == 2 && sp.S != 1) return "a strip map writes its pooled output as fp32 NCHW (pool_f32)";
+    if (pooled == 2 && !ps_geo(gi.N, 64, H / 2, W / 2, gp)) return "the pooled map has no PS layout";
+  }
+  if ((long)gi.N * gi.HP + gi.HP >= (1 << 20)) return "too many rows";
+  return nullptr;
+}
+
+int run_ps(int mode, const void* x, const void* wpk, const float* bias, const void* aux, void* y, const PsPoolIO& io, int N,
+           int Cin, int Cout, int H, int W, float slope, hipStream_t st, bool p16 = false) {
+  PsGeo gi, gp;
+  PsStrips sp;
   const bool pooled = mode == PSE_FWD_POOL || mode == PSE_DGRAD_ADDPOOL;
   FDET_REQUIRE(x && wpk && (y || pooled), "conv3x3_ps: null pointer");
-  FDET_REQUIRE(Cout == 64 && Cin % 16 == 0 && Cin >= 32, "conv3x3_ps: Cout must be 64 and Cin a multiple of 16 (Cin=%d Cout=%d)", Cin, Cout);
-  // maps wider than 62 columns run as column strips (fdet_ps.h): N, W below are those of the strip-images
-  FDET_REQUIRE(ps_geo_strips(N, Cin, H, W, gi, sp) && ps_geo_strips(N, Cout, H, W, go, spo) && gi.WP >= 32 && sp.Ws + 2 <= gi.WP,
-               "conv3x3_ps: unsupported map %dx%d (W + 2 <= 32 or 64 slots, or an even width in strips)", H, W);
-  FDET_REQUIRE((size_t)(gi.N + 2) * gi.img * 16 < ((size_t)1 << 32) && (size_t)(go.N + 2) * go.img * 16 < ((size_t)1 << 32),
-               "conv3x3_ps: tensor too large for the 32-bit byte offsets of the DMA descriptors (N=%d H=%d W=%d)", N, H, W);
+  const int pool_mode = !pooled ? 0 : (mode == PSE_FWD_POOL && io.pool_ps ? 2 : 1);
+  if (const char* why = ps_conv_refusal(pool_mode, N, Cin, Cout, H, W))
+    return fail(FDET_EINVAL, "conv3x3_ps: %s (N=%d Cin=%d Cout=%d H=%d W=%d)", why, N, Cin, Cout, H, W);
+  ps_geo_strips(N, Cin, H, W, gi, sp);
   const int Nimg = N, Wfull = W;
   N = gi.N; W = sp.Ws;
   FDET_REQUIRE(slope >= 0.f && slope <= 1.f, "conv3x3_ps: slope must be in [0, 1]");
@@ -726,20 +745,17 @@ int run_ps(int mode, const void* x, const void* wpk, const float* bias, const vo
   p.Hp = H / 2; p.Wp = W / 2; p.HPp = p.WPp = p.plane_p = p.img_p = 0;
   p.Nimg = Nimg; p.last0 = sp.S > 1 ? (sp.S - 1) * Nimg : 0; p.Wlast = sp.Wlast; p.Wf = Wfull; p.Wpf = Wfull / 2; p.xo = sp.Ws;
   p.magic_nimg = Nimg > 1 ? magic_of(Nimg) : 0u;
-  if (pooled) {
-    FDET_REQUIRE(!(H & 1) && !(W & 1) && Cin == 64, "conv3x3_ps (pooled block): even map and 64 channels required (H=%d W=%d Cin=%d)", H, W, Cin);
-    FDET_REQUIRE((size_t)Nimg * 64 * H * Wfull * 4 < ((size_t)1 << 31), "conv3x3_ps (pooled block): tensor too large for 32-bit offsets");
-    FDET_REQUIRE(sp.S == 1 || !io.pool_ps, "conv3x3_ps_fwd_pool: a strip map writes its pooled output as fp32 NCHW (pool_f32)");
-    if (mode == PSE_FWD_POOL && io.pool_ps) {
-      FDET_REQUIRE(ps_geo(N, 64, H / 2, W / 2, gp), "conv3x3_ps_fwd_pool: the pooled map %dx%d has no PS layout", H / 2, W / 2);
-      p.HPp = gp.HP; p.WPp = gp.WP; p.plane_p = gp.plane; p.img_p = gp.img;
-    }
+  PsGeo go;
+  PsStrips spo;
+  ps_geo_strips(Nimg, Cout, H, Wfull, go, spo);
+  if (pool_mode == 2) {
+    ps_geo(N, 64, H / 2, W / 2, gp);
+    p.HPp = gp.HP; p.WPp = gp.WP; p.plane_p = gp.plane; p.img_p = gp.img;
   }
   p.N = N; p.H = H; p.W = W; p.HP = gi.HP;
   p.nch = Cin / 16;
   const int R = 512 / gi.WP, PT = (R + 2) * gi.WP + 8;
   const long vr = (long)N * gi.HP;
-  FDET_REQUIRE(vr + gi.HP < (1 << 20), "conv3x3_ps: too many rows");
   p.ntiles = (int)((vr + R - 1) / R);
   p.plane_i = gi.plane; p.img_i = gi.img; p.plane_o = go.plane; p.img_o = go.img;
   p.magic_hp = magic_of(gi.HP);
@@ -768,6 +784,12 @@ int run_ps(int mode, const void* x, const void* wpk, const float* bias, const vo
 }  // namespace
 
 #if PS_TU == -1
+// plan query (no launch): run_ps accepts this shape and batch; pooled: 0 = conv, 1 = pooled block (fp32 pooled output),
+// 2 = pooled block with a PS pooled output
+extern "C" int fdet_conv3x3_ps_ok(int N, int Cin, int Cout, int H, int W, int pooled) {
+  return ps_conv_refusal(pooled, N, Cin, Cout, H, W) == nullptr;
+}
+
 // y_ps = LeakyReLU(conv3x3(x_ps, W) + bias); x_ps / y_ps: PS tensors (image 0), wpk: forward panels of
 // fdet_pack_conv3x3_weights_bf16x3
 extern "C" int fdet_conv3x3_ps_fwd(const void* x_ps, const void* wpk, const float* bias, void* y_ps, int N, int Cin,

@@ -7,6 +7,7 @@
 // (ix+pad = stride*bx + phase) so that the 64 lanes of a wave (consecutive ox) read
 // consecutive dwords for every tap.
 #include "fdet_common.h"
+#include "fdet_ps.h"
 #include <algorithm>
 #include <cstdlib>
 #include <cstdint>
@@ -22,6 +23,9 @@ int stem_x3_fwd(const float* x, const float* w, const float* bias, float* y, int
 int stem_x3_fwd_ps(const void* x, const float* w, const float* bias, void* y_ps, int N, int F, int H, int W, hipStream_t st, bool p16, bool u8 = false);
 int stem_dma_fwd_ps(const float* x, const float* w, const float* bias, void* y_ps, int N, int F, int H, int W, hipStream_t st, bool p16);
 int stem_x3_wgrad(const float* x, const float* dy, float* dW, float* db, float* ws, int N, int F, int H, int W, hipStream_t st, bool p16);
+bool stem_x3_fwd_ps_ok(int N, int F, int H, int W);
+bool stem_x3_wgrad_pipe_ok(int N, int F, int H, int W);
+size_t stem_x3_wgrad_ws_floats(int N, int F, int H, int W);
 // fdet_stem_k3.hip: the Resnet stem (k3 s2 p1) on the matrix cores / with a PS (column-strip) output
 bool stem3_wgrad_ok(int Cin, int F, int H, int W, int k, int stride, int pad);
 size_t stem3_wgrad_ws_floats(int N, int F, int H, int W);
@@ -334,7 +338,8 @@ extern "C" size_t fdet_stem_ws_bytes(int N, int Cin, int F, int H, int W, int k,
   StemPlan p;
   if (!stem_plan(N, Cin, F, H, W, k, stride, pad, p)) return 0;
   size_t fl = p.ws_floats;
-  if (stem_mfma_ok(Cin, F, H, W, k, stride, pad)) fl = std::max(fl, stem_mfma_ws_floats(N, F, H, W));
+  if (stem_mfma_ok(Cin, F, H, W, k, stride, pad))
+    fl = std::max(fl, std::max(stem_mfma_ws_floats(N, F, H, W), stem_x3_wgrad_ws_floats(N, F, H, W)));
   if (stem3_wgrad_ok(Cin, F, H, W, k, stride, pad)) fl = std::max(fl, stem3_wgrad_ws_floats(N, F, H, W));
   return fl * 4;
 }
@@ -372,10 +377,39 @@ extern "C" int fdet_stem_fwd_bf16x3(const float* x, const float* w, const float*
   return stem_x3_fwd(x, w, bias, y, N, F, H, W, (hipStream_t)stream);
 }
 
+// Plan queries (no launch): the batch-size and shape checks the PS stem forward and the bf16x3 / precision16 stem weight
+// gradient apply before they launch anything -- the entry points below call the same functions.
+namespace {
+bool stem_fwd_ps_plan_ok(int N, int Cin, int F, int H, int W, int k, int stride, int pad, bool u8) {
+  if (N <= 0) return false;
+  if (!u8 && stem3_fwd_ps_ok(Cin, F, H, W, k, stride, pad)) {
+    PsGeo g; PsStrips sp;
+    return ps_geo_strips(N, F, H / 2, W / 2, g, sp);
+  }
+  return F == 64 && stem_mfma_ok(Cin, F, H, W, k, stride, pad) && stem_x3_fwd_ps_ok(N, F, H, W);
+}
+bool stem_wgrad_x3_plan_ok(int N, int Cin, int F, int H, int W, int k, int stride, int pad, bool p16) {
+  if (N <= 0 || F <= 0) return false;
+  if (stem3_wgrad_ok(Cin, F, H, W, k, stride, pad)) return true;
+  return stem_mfma_ok(Cin, F, H, W, k, stride, pad) && W % 16 == 0 && (!p16 || stem_x3_wgrad_pipe_ok(N, F, H, W));
+}
+}  // namespace
+
+extern "C" int fdet_stem_fwd_ps_ok(int N, int Cin, int F, int H, int W, int k, int stride, int pad, int precision16, int u8) {
+  (void)precision16;                                       // the precision16 forms run the same plan
+  return stem_fwd_ps_plan_ok(N, Cin, F, H, W, k, stride, pad, u8 != 0);
+}
+
+extern "C" int fdet_stem_wgrad_x3_ok(int N, int Cin, int F, int H, int W, int k, int stride, int pad, int precision16) {
+  return stem_wgrad_x3_plan_ok(N, Cin, F, H, W, k, stride, pad, precision16 != 0);
+}
+
 // the PoolResnet stem with a pre-split (PS) output: y_ps = image-0 pointer of a PS tensor (N, 64, Ho, Wo)
 extern "C" int fdet_stem_fwd_ps(const float* x, const float* w, const float* bias, void* y_ps, int N, int Cin, int F, int H,
                                 int W, int k, int stride, int pad, void* stream) {
   FDET_REQUIRE(x && w && bias && y_ps && N > 0, "stem_fwd_ps: bad arguments");
+  FDET_REQUIRE(stem_fwd_ps_plan_ok(N, Cin, F, H, W, k, stride, pad, false),
+               "stem_fwd_ps: no PS stem plan for N=%d Cin=%d F=%d %dx%d k=%d s=%d p=%d", N, Cin, F, H, W, k, stride, pad);
   if (stem3_fwd_ps_ok(Cin, F, H, W, k, stride, pad)) return stem3_fwd_ps(x, w, bias, y_ps, N, F, H, W, (hipStream_t)stream, false);
   FDET_REQUIRE(F == 64, "stem_fwd_ps: F must be 64");
   FDET_REQUIRE(stem_mfma_ok(Cin, F, H, W, k, stride, pad),
@@ -390,6 +424,8 @@ extern "C" int fdet_stem_fwd_ps(const float* x, const float* w, const float* bia
 extern "C" int fdet_stem_fwd_ps_p16(const float* x, const float* w, const float* bias, void* y_ps, int N, int Cin, int F, int H,
                                     int W, int k, int stride, int pad, void* stream) {
   FDET_REQUIRE(x && w && bias && y_ps && N > 0, "stem_fwd_ps_p16: bad arguments");
+  FDET_REQUIRE(stem_fwd_ps_plan_ok(N, Cin, F, H, W, k, stride, pad, false),
+               "stem_fwd_ps_p16: no PS stem plan for N=%d Cin=%d F=%d %dx%d k=%d s=%d p=%d", N, Cin, F, H, W, k, stride, pad);
   if (stem3_fwd_ps_ok(Cin, F, H, W, k, stride, pad)) return stem3_fwd_ps(x, w, bias, y_ps, N, F, H, W, (hipStream_t)stream, true);
   FDET_REQUIRE(F == 64, "stem_fwd_ps_p16: F must be 64");
   FDET_REQUIRE(stem_mfma_ok(Cin, F, H, W, k, stride, pad),
@@ -409,6 +445,7 @@ extern "C" int fdet_stem_fwd_ps_u8(const unsigned char* frames, const float* w, 
   FDET_REQUIRE(stem_mfma_ok(Cin, F, H, W, k, stride, pad) && ((uintptr_t)frames % 4) == 0,
                "stem_fwd_ps_u8: only the PoolResnet stem (3ch k10 s8 p2, W%%4==0, W<=512) on 4-byte aligned frames; got Cin=%d k=%d s=%d p=%d W=%d",
                Cin, k, stride, pad, W);
+  FDET_REQUIRE(stem_fwd_ps_plan_ok(N, Cin, F, H, W, k, stride, pad, true), "stem_fwd_ps_u8: no PS stem plan for N=%d %dx%d", N, H, W);
   return stem_x3_fwd_ps(frames, w, bias, y_ps, N, F, H, W, (hipStream_t)stream, precision16 != 0, true);
 }
 
@@ -420,7 +457,8 @@ extern "C" int fdet_stem_wgrad_bf16x3(const float* x, const float* dy, float* dW
   FDET_REQUIRE(stem_mfma_ok(Cin, F, H, W, k, stride, pad) && W % 16 == 0,
                "stem_wgrad_bf16x3: only the PoolResnet stem (3ch k10 s8 p2, W%%16==0, W<=512) is built; got Cin=%d k=%d s=%d p=%d W=%d",
                Cin, k, stride, pad, W);
-  if (ws_bytes < stem_mfma_ws_floats(N, F, H, W) * 4) return fail(FDET_EWORKSPACE, "stem_wgrad_bf16x3: workspace too small");
+  FDET_REQUIRE(stem_wgrad_x3_plan_ok(N, Cin, F, H, W, k, stride, pad, false), "stem_wgrad_bf16x3: no plan for N=%d %dx%d", N, H, W);
+  if (ws_bytes < stem_x3_wgrad_ws_floats(N, F, H, W) * 4) return fail(FDET_EWORKSPACE, "stem_wgrad_bf16x3: workspace too small");
   return stem_x3_wgrad(x, dy, dW, db, (float*)ws, N, F, H, W, (hipStream_t)stream, false);
 }
 
@@ -433,7 +471,8 @@ extern "C" int fdet_stem_wgrad_bf16(const float* x, const float* dy, float* dW, 
   FDET_REQUIRE(stem_mfma_ok(Cin, F, H, W, k, stride, pad) && W % 16 == 0,
                "stem_wgrad_bf16: only the PoolResnet stem (3ch k10 s8 p2, W%%16==0, W<=512) is built; got Cin=%d k=%d s=%d p=%d W=%d",
                Cin, k, stride, pad, W);
-  if (ws_bytes < stem_mfma_ws_floats(N, F, H, W) * 4) return fail(FDET_EWORKSPACE, "stem_wgrad_bf16: workspace too small");
+  FDET_REQUIRE(stem_wgrad_x3_plan_ok(N, Cin, F, H, W, k, stride, pad, true), "stem_wgrad_bf16: no plan for N=%d %dx%d", N, H, W);
+  if (ws_bytes < stem_x3_wgrad_ws_floats(N, F, H, W) * 4) return fail(FDET_EWORKSPACE, "stem_wgrad_bf16: workspace too small");
   return stem_x3_wgrad(x, dy, dW, db, (float*)ws, N, F, H, W, (hipStream_t)stream, true);
 }
 

@@ -10,6 +10,7 @@
 // Weights live in registers for the whole kernel (30 rows x (hi,lo) x 4 VGPRs = 240 per lane).
 #include "fdet_common.h"
 #include "fdet_ps.h"
+#include <algorithm>
 #include <cstdlib>
 #include <utility>
 
@@ -851,18 +852,32 @@ int stem_x3_fwd(const float* x, const float* w, const float* bias, float* y, int
   return check_launch("fdet_stem_fwd(bf16x3)");
 }
 
-// the same forward with a pre-split (PS) output: y_ps = image-0 pointer of a PS tensor (N, 64, Ho, Wo)
+// Images per launch of the pipelined kernels: their buffer descriptors take 32-bit byte offsets (x, dy < 2^29 floats;
+// the PS output < 2^31 bytes), so a larger batch runs as consecutive launches over image chunks.  0: not one image fits.
+int stem_x3_chunk(int F, int H, int W, int ps_img) {
+  const int Ho = (H + 4 - 10) / 8 + 1, Wo = (W + 4 - 10) / 8 + 1;
+  const size_t lim = ((size_t)1 << 29) - 1;
+  size_t c = lim / ((size_t)CIN * H * W);
+  c = std::min(c, lim / ((size_t)F * Ho * Wo));
+  if (ps_img > 0) c = std::min(c, (((size_t)1 << 31) - 1) / ((size_t)ps_img * 16));
+  return (int)std::min<size_t>(c, (size_t)1 << 30);
+}
+
+bool stem_x3_fwd_ps_ok(int N, int F, int H, int W) {
+  PsGeo g;
+  const int Ho = (H + 4 - 10) / 8 + 1, Wo = (W + 4 - 10) / 8 + 1;
+  return F == 64 && N > 0 && H >= 10 && ps_geo(N, F, Ho, Wo, g) && stem_x3_chunk(F, H, W, g.img) >= 1;
+}
+
+// the same forward with a pre-split (PS) output: y_ps = image-0 pointer of a PS tensor (N, 64, Ho, Wo); chunks of
+// stem_x3_chunk images, each launch on its slice of x and of the PS images (rows never cross images: same arithmetic)
 int stem_x3_fwd_ps(const void* xin, const float* w, const float* bias, void* y_ps, int N, int F, int H, int W, hipStream_t st, bool p16,
                    bool u8) {
-  StemX3Args a{};
-  a.x = reinterpret_cast<const float*>(xin);               // u8: uint8 frames [N][3][H][W], 4-byte aligned rows (W % 4 == 0)
-  a.w = w; a.bias = bias; a.y = reinterpret_cast<float*>(y_ps); a.N = N; a.F = F; a.H = H; a.W = W;
-  a.Ho = (H + 4 - 10) / 8 + 1; a.Wo = (W + 4 - 10) / 8 + 1; a.nrows = N * a.Ho;
+  const int Ho = (H + 4 - 10) / 8 + 1, Wo = (W + 4 - 10) / 8 + 1;
   PsGeo g;
-  if (F != 64 || !ps_geo(N, F, a.Ho, a.Wo, g) || (size_t)N * CIN * H * W >= ((size_t)1 << 29))
-    return fail(FDET_EINVAL, "stem_fwd_ps: unsupported shape (F=%d, output %dx%d)", F, a.Ho, a.Wo);
-  a.ps_hp = g.HP; a.ps_wp = g.WP; a.ps_plane = g.plane; a.ps_img = g.img;
-  const int nblk = a.nrows < 256 ? a.nrows : 256;
+  if (!stem_x3_fwd_ps_ok(N, F, H, W) || !ps_geo(N, F, Ho, Wo, g))
+    return fail(FDET_EINVAL, "stem_fwd_ps: unsupported shape (F=%d, output %dx%d, N=%d)", F, Ho, Wo, N);
+  const int chunk = stem_x3_chunk(F, H, W, g.img);
   const size_t lds = (size_t)NROW * RL * 2 * 2;
   const size_t ldsb = 2 * lds + 256 + 1024;                // tiles, bias, the uint8 table
   const void* kern = u8 ? (p16 ? (const void*)k_stem_fwd_x3_pipe<true, true, true> : (const void*)k_stem_fwd_x3_pipe<true, false, true>)
@@ -871,41 +886,78 @@ int stem_x3_fwd_ps(const void* xin, const float* w, const float* bias, void* y_p
     (void)hipGetLastError();
     return fail(FDET_ELAUNCH, "stem_fwd_ps: cannot reserve %zu bytes of LDS", ldsb);
   }
-  if (u8 && p16) hipLaunchKernelGGL((k_stem_fwd_x3_pipe<true, true, true>), dim3(nblk, 1), dim3(256), ldsb, st, a);
-  else if (u8) hipLaunchKernelGGL((k_stem_fwd_x3_pipe<true, false, true>), dim3(nblk, 1), dim3(256), ldsb, st, a);
-  else if (p16) hipLaunchKernelGGL((k_stem_fwd_x3_pipe<true, true>), dim3(nblk, 1), dim3(256), ldsb, st, a);
-  else hipLaunchKernelGGL((k_stem_fwd_x3_pipe<true, false>), dim3(nblk, 1), dim3(256), ldsb, st, a);
-  return check_launch("fdet_stem_fwd_ps");
+  const size_t in_img = (size_t)CIN * H * W * (u8 ? 1 : 4);          // bytes per input image
+  for (int n0 = 0; n0 < N; n0 += chunk) {
+    StemX3Args a{};
+    a.x = reinterpret_cast<const float*>(reinterpret_cast<const char*>(xin) + (size_t)n0 * in_img);   // u8: uint8 frames [N][3][H][W], 4-byte aligned rows (W % 4 == 0)
+    a.w = w; a.bias = bias; a.y = reinterpret_cast<float*>(reinterpret_cast<char*>(y_ps) + (size_t)n0 * g.img * 16);
+    a.N = std::min(chunk, N - n0); a.F = F; a.H = H; a.W = W;
+    a.Ho = Ho; a.Wo = Wo; a.nrows = a.N * Ho;
+    a.ps_hp = g.HP; a.ps_wp = g.WP; a.ps_plane = g.plane; a.ps_img = g.img;
+    const int nblk = a.nrows < 256 ? a.nrows : 256;
+    if (u8 && p16) hipLaunchKernelGGL((k_stem_fwd_x3_pipe<true, true, true>), dim3(nblk, 1), dim3(256), ldsb, st, a);
+    else if (u8) hipLaunchKernelGGL((k_stem_fwd_x3_pipe<true, false, true>), dim3(nblk, 1), dim3(256), ldsb, st, a);
+    else if (p16) hipLaunchKernelGGL((k_stem_fwd_x3_pipe<true, true>), dim3(nblk, 1), dim3(256), ldsb, st, a);
+    else hipLaunchKernelGGL((k_stem_fwd_x3_pipe<true, false>), dim3(nblk, 1), dim3(256), ldsb, st, a);
+    if (int rc = check_launch("fdet_stem_fwd_ps")) return rc;
+  }
+  return 0;
+}
+
+// the pipelined weight gradient covers this shape (any N: chunks of stem_x3_chunk images); precision16 has no other kernel
+bool stem_x3_wgrad_pipe_ok(int N, int F, int H, int W) {
+  const char* e = FDET_ENV_ONCE("FDET_STEM_PIPE");
+  const int Wo = (W + 4 - 10) / 8 + 1;
+  return !(e && e[0] == '0') && N > 0 && F > 0 && H >= 10 && Wo <= 60 && Wo > 48 && stem_x3_chunk(F, H, W, 0) >= 1;
+}
+
+// workspace of stem_x3_wgrad: per-workgroup partials [slabs][FP][320] then [slabs][FP]; one slab per workgroup of every chunk
+size_t stem_x3_wgrad_ws_floats(int N, int F, int H, int W) {
+  const int Ho = (H + 4 - 10) / 8 + 1;
+  const int FP = (F + 63) / 64 * 64;
+  const int chunk = std::max(1, stem_x3_chunk(F, H, W, 0));
+  size_t slabs = 0;
+  for (int n0 = 0; n0 < N; n0 += chunk) slabs += (size_t)std::min(std::min(chunk, N - n0) * Ho, 256);
+  return slabs * FP * 320 + slabs * FP;
 }
 
 int stem_x3_wgrad(const float* x, const float* dy, float* dW, float* db, float* ws, int N, int F, int H, int W,
                   hipStream_t st, bool p16) {
-  StemWgX3Args a{};
-  a.x = x; a.dy = dy; a.N = N; a.F = F; a.H = H; a.W = W;
-  a.Ho = (H + 4 - 10) / 8 + 1; a.Wo = (W + 4 - 10) / 8 + 1; a.nrows = N * a.Ho;
+  const int Ho = (H + 4 - 10) / 8 + 1, Wo = (W + 4 - 10) / 8 + 1;
   const int FP = (F + 63) / 64 * 64;
-  const int nblk = a.nrows < 256 ? a.nrows : 256;
-  a.ws = ws; a.wsb = ws + (size_t)nblk * FP * 320;
   const size_t lds = ((size_t)NPLANE * PE * 2 + 64 * DL * 2) * 2;
-  const char* e = FDET_ENV_ONCE("FDET_STEM_PIPE");
-  const bool pipe = !(e && e[0] == '0') && a.Wo <= 60 && a.Wo > 48 && (size_t)N * CIN * H * W < ((size_t)1 << 29) &&
-                    (size_t)N * F * a.Ho * a.Wo < ((size_t)1 << 29);
-  if (pipe) {     // pipelined: two plane tiles of 9-chunk planes, exactly four 16-column k-steps (48 < Wo <= 60), 32-bit byte offsets
+  StemWgX3Args a{};
+  a.F = F; a.H = H; a.W = W; a.Ho = Ho; a.Wo = Wo;
+  int slabs = 0;
+  if (stem_x3_wgrad_pipe_ok(N, F, H, W)) {
+    // pipelined: two plane tiles of 9-chunk planes, exactly four 16-column k-steps (48 < Wo <= 60), 32-bit byte offsets:
+    // a chunk's workgroups write consecutive slabs of one workspace, and one reduction sums the slabs of all chunks
     const size_t lds2 = ((size_t)2 * TILEP + 2 * 64 * DL + 8 * PEP) * 2;
-    if (p16) {
-      { if (int rc_ = set_lds_attr((const void*)k_stem_wgrad_x3_pipe<true>, (size_t)(lds2), __func__)) return rc_; }
-      hipLaunchKernelGGL(k_stem_wgrad_x3_pipe<true>, dim3(nblk, FP / 64), dim3(256), lds2, st, a);
-    } else {
-      { if (int rc_ = set_lds_attr((const void*)k_stem_wgrad_x3_pipe<false>, (size_t)(lds2), __func__)) return rc_; }
-      hipLaunchKernelGGL(k_stem_wgrad_x3_pipe<false>, dim3(nblk, FP / 64), dim3(256), lds2, st, a);
+    const void* kern = p16 ? (const void*)k_stem_wgrad_x3_pipe<true> : (const void*)k_stem_wgrad_x3_pipe<false>;
+    { if (int rc_ = set_lds_attr(kern, (size_t)(lds2), __func__)) return rc_; }
+    const int chunk = stem_x3_chunk(F, H, W, 0);
+    const size_t tot = stem_x3_wgrad_ws_floats(N, F, H, W) / ((size_t)FP * 321);
+    for (int n0 = 0; n0 < N; n0 += chunk) {
+      a.N = std::min(chunk, N - n0); a.nrows = a.N * Ho;
+      a.x = x + (size_t)n0 * CIN * H * W; a.dy = dy + (size_t)n0 * F * Ho * Wo;
+      const int nblk = a.nrows < 256 ? a.nrows : 256;
+      a.ws = ws + (size_t)slabs * FP * 320; a.wsb = ws + tot * FP * 320 + (size_t)slabs * FP;
+      if (p16) hipLaunchKernelGGL(k_stem_wgrad_x3_pipe<true>, dim3(nblk, FP / 64), dim3(256), lds2, st, a);
+      else hipLaunchKernelGGL(k_stem_wgrad_x3_pipe<false>, dim3(nblk, FP / 64), dim3(256), lds2, st, a);
+      if (int rc = check_launch("fdet_stem_wgrad(bf16x3)")) return rc;
+      slabs += nblk;
     }
+    a.ws = ws; a.wsb = ws + tot * FP * 320;
   } else {
     if (p16) return fail(FDET_EINVAL, "stem_wgrad (precision16): only the pipelined kernel's shapes (48 < Wo <= 60) are built");
+    a.x = x; a.dy = dy; a.N = N; a.nrows = N * Ho;
+    slabs = a.nrows < 256 ? a.nrows : 256;
+    a.ws = ws; a.wsb = ws + (size_t)slabs * FP * 320;
     { if (int rc_ = set_lds_attr((const void*)k_stem_wgrad_x3, (size_t)(lds), __func__)) return rc_; }
-    hipLaunchKernelGGL(k_stem_wgrad_x3, dim3(nblk, FP / 64), dim3(256), lds, st, a);
+    hipLaunchKernelGGL(k_stem_wgrad_x3, dim3(slabs, FP / 64), dim3(256), lds, st, a);
+    if (int rc = check_launch("fdet_stem_wgrad(bf16x3)")) return rc;
   }
-  if (int rc = check_launch("fdet_stem_wgrad(bf16x3)")) return rc;
-  hipLaunchKernelGGL(k_stem_x3_reduce, dim3(5, F), dim3(1024), 0, st, a.ws, a.wsb, nblk, F, FP, dW, db);
+  hipLaunchKernelGGL(k_stem_x3_reduce, dim3(5, F), dim3(1024), 0, st, a.ws, a.wsb, slabs, F, FP, dW, db);
   return check_launch("fdet_stem_wgrad(bf16x3 reduce)");
 }
 

@@ -574,6 +574,12 @@ def block_chain_supported(F_: int, H: int, W: int) -> bool:
     return bool(lib().fdet_block_chain_supported(int(F_), int(H), int(W)))
 
 
+def block_chain_ok(N: int, F_: int, H: int, W: int, ps: bool = False) -> bool:
+    """The chain kernels run N images of this map (fdet_block_chain_ok: the entry points' own check, batch size included);
+    ps: the PS flavour."""
+    return bool(lib().fdet_block_chain_ok(int(N), int(F_), int(H), int(W), int(ps)))
+
+
 def block_chain_fwd(x, wpk1, b1, wpk2, b2, scales, a_out, c_out, outs, slope: float = 0.2):
     """Run len(wpk1) un-pooled residual blocks in one launch (fdet_block_chain_fwd_bf16x3).
     Lists of per-block tensors; `scales`, `a_out`, `c_out` may be None; `outs` entries may be None
@@ -671,6 +677,17 @@ def stem_k3_wgrad_x3_supported(cin, F_, H, W, k, stride, pad) -> bool:
 
 def stem_k3_fwd_ps_supported(cin, F_, H, W, k, stride, pad) -> bool:
     return cin == 3 and (k, stride, pad) == (3, 2, 1) and F_ % 8 == 0 and H % 2 == 0 and W % 2 == 0
+
+
+def stem_fwd_ps_ok(N, cin, F_, H, W, k, stride, pad, p16: bool = False, u8: bool = False) -> bool:
+    """fdet_stem_fwd_ps (p16: _p16; u8: the uint8-frame form) accepts N images of this shape (fdet_stem_fwd_ps_ok)."""
+    return bool(lib().fdet_stem_fwd_ps_ok(int(N), int(cin), int(F_), int(H), int(W), int(k), int(stride), int(pad), int(p16), int(u8)))
+
+
+def stem_wgrad_x3_ok(N, cin, F_, H, W, k, stride, pad, p16: bool = False) -> bool:
+    """The matrix-core stem weight gradient (bf16x3, or precision16 with p16) accepts N images of this shape
+    (fdet_stem_wgrad_x3_ok)."""
+    return bool(lib().fdet_stem_wgrad_x3_ok(int(N), int(cin), int(F_), int(H), int(W), int(k), int(stride), int(pad), int(p16)))
 
 
 def stem_wgrad(x, dy, dW, db, ws, k, stride, pad, x3: bool = False, p16: bool = False):

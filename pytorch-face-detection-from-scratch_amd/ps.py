@@ -120,6 +120,12 @@ def conv3x3_ps_dgrad_act(dz: PsTensor, wpk_bwd: torch.Tensor, act: PsTensor, dx:
                                                 stream()), "fdet_conv3x3_ps_dgrad_act")
 
 
+def conv3x3_ps_ok(N: int, Cin: int, Cout: int, H: int, W: int, pooled: int = 0) -> bool:
+    """The PS conv kernels accept N images of this shape (fdet_conv3x3_ps_ok, the entry points' own check).  pooled: 0 = conv /
+    data gradient, 1 = pooled block with an fp32 pooled output (and its backward), 2 = with a PS pooled output."""
+    return bool(lib().fdet_conv3x3_ps_ok(int(N), int(Cin), int(Cout), int(H), int(W), int(pooled)))
+
+
 def conv3x3_wgrad_ps_ws_bytes(L: int, N: int, C: int, H: int, W: int) -> int:
     return int(lib().fdet_conv3x3_wgrad_ps_ws_bytes(L, N, C, H, W))
 
