@@ -242,6 +242,10 @@ int fdet_conv3x3_wgrad_bf16x3(const float* x, const float* dz, float* dW, float*
  * h_db are HOST arrays of L device pointers.  Small layers (15x15) are launch/reduction-overhead
  * bound one at a time; batched, every workgroup owns bands of a single layer and writes one slab. */
 size_t fdet_conv3x3_wgrad_bf16x3_batched_ws_bytes(int L, int N, int Cin, int Cout, int H, int W);
+/* Plan query of the bf16x3 / precision16 weight gradient of L layers (launches nothing): fills out[0..min(n,8)-1] with
+ * ok, pipelined kernel, 32-lane rows (lpr32), float4 quads (pk4), packed narrow rows (pack), vector width, output-channel
+ * tiles (MTC) and column segments (NSEG).  ok == 0 exactly when the entry points refuse the shape. */
+int fdet_conv3x3_wgrad_bf16x3_plan(int N, int Cin, int Cout, int H, int W, int L, int* out, int n);
 int fdet_conv3x3_wgrad_bf16x3_batched(const float* const* h_x, const float* const* h_dz, float* const* h_dW,
                                       float* const* h_db, int L, void* ws, size_t ws_bytes,
                                       int N, int Cin, int Cout, int H, int W, void* stream);
@@ -304,6 +308,11 @@ int fdet_block_tail_fwd(const float* c, const float* x, const float* drop_scale,
  *             fdet_conv3x3_dgrad_unpool  dx = conv^T(dz) + unpool(dout_pooled)      (conv1's data gradient + skip path)
  * wpk: forward / backward panels of fdet_pack_conv3x3_weights_bf16x3. */
 int fdet_conv3x3_pool_fusion_ok(int N, int Cin, int Cout, int H, int W);   /* 1: the two kernels below have a tiling for the shape */
+/* Diagnostic: the route of the last fdet_conv3x3_{fwd,dgrad}[_pool|_unpool]_bf16{x3,} call on the calling thread, as
+ * recorded where the launch was issued: out[0..min(n,6)-1] = kernel family (1 ping-pong, 2 aligned-band small-tile,
+ * 3 small-tile, 4 general persistent), vector width, output-channel tiles (MT), epilogue mode (EPI_* of
+ * csrc/fdet_conv_common.h), column-segmented rows (0/1), precision16 (0/1).  All zero after a refused call. */
+int fdet_conv3x3_x3_last_route(int* out, int n);
 /* Plan query of the PS conv kernels (fdet_conv3x3_ps_*; launches nothing): 1 when they accept N images of this shape.
  * pooled: 0 = conv / data gradient, 1 = pooled block with an fp32 pooled output (and its backward), 2 = pooled block
  * with a PS pooled output.  The entry points refuse exactly what this refuses. */

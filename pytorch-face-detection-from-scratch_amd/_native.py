@@ -74,6 +74,7 @@ SIGNATURES = {
     "fdet_conv3x3_dgrad_unpool_bf16x3": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _P]),
     "fdet_pool_route_bwd": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _F, _P]),
     "fdet_conv3x3_pool_fusion_ok": (_I, [_I, _I, _I, _I, _I]),
+    "fdet_conv3x3_x3_last_route": (_I, [_P, _I]),
     "fdet_conv3x3_ps_ok": (_I, [_I, _I, _I, _I, _I, _I]),
     "fdet_stem_fwd_ps_ok": (_I, [_I, _I, _I, _I, _I, _I, _I, _I, _I, _I]),
     "fdet_stem_wgrad_x3_ok": (_I, [_I, _I, _I, _I, _I, _I, _I, _I, _I]),
@@ -112,6 +113,7 @@ SIGNATURES = {
     "fdet_conv3x3_wgrad_bf16x3_ws_bytes": (_SZ, [_I, _I, _I, _I, _I]),
     "fdet_conv3x3_wgrad_bf16x3": (_I, [_P, _P, _P, _P, _P, _SZ, _I, _I, _I, _I, _I, _P]),
     "fdet_conv3x3_wgrad_bf16x3_batched_ws_bytes": (_SZ, [_I, _I, _I, _I, _I, _I]),
+    "fdet_conv3x3_wgrad_bf16x3_plan": (_I, [_I, _I, _I, _I, _I, _I, _P, _I]),
     "fdet_conv3x3_wgrad_bf16x3_batched": (_I, [_P, _P, _P, _P, _I, _P, _SZ, _I, _I, _I, _I, _I, _P]),
     "fdet_block_chain_supported": (_I, [_I, _I, _I]),
     "fdet_block_chain_ok": (_I, [_I, _I, _I, _I, _I]),

@@ -58,6 +58,12 @@ struct PoolArgs {
 // ping-pong variant for rows of <= 63 columns (fdet_conv3x3_x3_pp.hip); returns 1 when it has no tiling
 int fdet_x3_pp_run(fdet::ConvArgs a, fdet::PoolArgs q, hipStream_t st);
 
+// diagnostic record of the kernel the last fwd / dgrad / pooled launch on this thread went to (fdet_conv3x3_x3_last_route):
+// each runner notes its route where it launches; the C entry points clear it first, so a refused call leaves zeros
+enum { X3_ROUTE_PP = 1, X3_ROUTE_AL = 2, X3_ROUTE_SB = 3, X3_ROUTE_GENERAL = 4 };
+void x3_note_route(int family, int vw, int mt, int mode, bool seg, bool p16);
+void x3_clear_route();
+
 // small-tile single-buffer variant (fdet_conv3x3_x3_sb.hip); returns 1 when it has no tiling
 int fdet_x3_sb_run(fdet::ConvArgs a, hipStream_t st);
 // ... its aligned-band variant with the pooled-block epilogues

@@ -187,6 +187,7 @@ int run_x3(ConvArgs a, hipStream_t st) {
   if (const char* e = getenv("FDET_CONV_STAGGER")) p.c.stagger = atoi(e);
   const bool seg = bestNSEG > 1;
   p.stamps = g_probe_stamps;
+  x3_note_route(X3_ROUTE_GENERAL, VW, MT, a.mode, seg, a.p16);
   if (a.p16) {
     switch (a.mode) {
       case EPI_FWD_FULL: return fdet_x3_launch_m1_bf16(p, MT, NW, NT, VW, seg, lds, grid, st);
@@ -208,6 +209,20 @@ int run_x3(ConvArgs a, hipStream_t st) {
 }
 
 }  // namespace
+
+namespace {
+thread_local int g_route[6];     // family, VW, MT, epilogue mode, NSEG > 1, precision16
+}
+void x3_note_route(int family, int vw, int mt, int mode, bool seg, bool p16) {
+  g_route[0] = family; g_route[1] = vw; g_route[2] = mt; g_route[3] = mode; g_route[4] = seg ? 1 : 0; g_route[5] = p16 ? 1 : 0;
+}
+void x3_clear_route() { for (int& v : g_route) v = 0; }
+
+extern "C" int fdet_conv3x3_x3_last_route(int* out, int n) {
+  FDET_REQUIRE(out && n >= 0, "conv3x3_x3_last_route: bad arguments");
+  for (int i = 0; i < n && i < 6; ++i) out[i] = g_route[i];
+  return FDET_OK;
+}
 
 #ifdef FDET_X3_STAMPS
 extern "C" int fdet_x3_probe_set(long long* buf) { g_probe_stamps = buf; return 0; }
@@ -279,6 +294,7 @@ extern "C" int fdet_pack_conv3x3_weights_bf16x3_batched(const float* const* h_w,
 static int conv3x3_fwd_x3(const float* x, const void* wpk, const float* bias, float* y_full, const float* skip,
                           const float* drop_scale, float* y_out, int N, int Cin, int Cout, int H, int W, int pool, float slope,
                           int p16, void* stream) {
+  x3_clear_route();
   FDET_REQUIRE(x && wpk && (y_full || y_out), "conv3x3_fwd_bf16x3: null pointer");
   FDET_REQUIRE(N > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0 && Cin % 16 == 0 && Cout % 16 == 0,
                "conv3x3_fwd_bf16x3: unsupported shape N=%d Cin=%d Cout=%d H=%d W=%d (channels must be multiples of 16)",
@@ -329,6 +345,7 @@ extern "C" int fdet_conv3x3_pool_fusion_ok(int N, int Cin, int Cout, int H, int 
 static int conv3x3_fwd_pool_x3(const float* x, const void* wpk, const float* bias, const float* skip, const float* drop_scale,
                                float* out_pooled, unsigned char* route, int N, int Cin, int Cout, int H, int W, float slope,
                                int p16, void* stream) {
+  x3_clear_route();
   FDET_REQUIRE(x && wpk && bias && skip && out_pooled, "conv3x3_fwd_pool_bf16x3: null pointer");
   FDET_REQUIRE(N > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0 && Cin % 16 == 0 && Cout % 32 == 0 && !(H & 1) && !(W & 1),
                "conv3x3_fwd_pool_bf16x3: unsupported shape N=%d Cin=%d Cout=%d H=%d W=%d (even maps, Cin %% 16 == 0, Cout %% 32 == 0)",
@@ -355,6 +372,7 @@ extern "C" int fdet_conv3x3_fwd_pool_bf16(const float* x, const void* wpk, const
 
 static int conv3x3_dgrad_unpool_x3(const float* dz, const void* wpk, const float* dout_pooled, const unsigned char* route,
                                    float* dx, int N, int Cin, int Cout, int H, int W, float slope, int p16, void* stream) {
+  x3_clear_route();
   FDET_REQUIRE(dz && wpk && dout_pooled && route && dx, "conv3x3_dgrad_unpool_bf16x3: null pointer");
   FDET_REQUIRE(N > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0 && Cin % 32 == 0 && Cout % 16 == 0 && !(H & 1) && !(W & 1),
                "conv3x3_dgrad_unpool_bf16x3: unsupported shape N=%d Cin=%d Cout=%d H=%d W=%d", N, Cin, Cout, H, W);
@@ -380,6 +398,7 @@ extern "C" int fdet_conv3x3_dgrad_unpool_bf16(const float* dz, const void* wpk, 
 
 static int conv3x3_dgrad_x3(const float* dz, const void* wpk, const float* act, const float* add, float* dx, int N, int Cin,
                             int Cout, int H, int W, float slope, int p16, void* stream) {
+  x3_clear_route();
   FDET_REQUIRE(dz && wpk && dx, "conv3x3_dgrad_bf16x3: null pointer");
   FDET_REQUIRE(N > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0 && Cin % 16 == 0 && Cout % 16 == 0,
                "conv3x3_dgrad_bf16x3: unsupported shape N=%d Cin=%d Cout=%d H=%d W=%d", N, Cin, Cout, H, W);

@@ -466,6 +466,7 @@ int fdet_x3_pp_run(ConvArgs a, PoolArgs q, hipStream_t st) {
   if (g % p.ncob) g = g / p.ncob * p.ncob;
   if (g < p.ncob) g = p.ncob;
   dim3 grid(g, 1);
+  x3_note_route(X3_ROUTE_PP, VW, MT, a.mode, false, a.p16);
   return MT == 2 ? launch_pp<2>(p, VW, lds, grid, st) : launch_pp<1>(p, VW, lds, grid, st);
 }
 

@@ -542,6 +542,7 @@ int fdet_x3_sb_run(ConvArgs a, hipStream_t st) {
   if (force.grid >= 0) gsz = force.grid > 0 ? force.grid : p.ntiles;
   dim3 grid(p.ntiles < gsz ? p.ntiles : gsz, 1);
   p.c.stagger = 0;
+  x3_note_route(X3_ROUTE_SB, VW, MT, a.mode, false, a.p16);
   if (a.p16) {                            // precision16: the one-pass instantiations of the same tilings
     if (MT == 2 && NT == 2) return launch_sb<2, 2, true>(p, VW, lds, grid, st);
     if (MT == 2 && NT == 1) return launch_sb<2, 1, true>(p, VW, lds, grid, st);
@@ -562,7 +563,7 @@ int fdet_x3_sb_pool_run(ConvArgs a, PoolArgs q, hipStream_t st) {
   if (!pooled_ && a.W < 17) return 1;     // narrow plain maps: the 64-positions-per-wave mapping wastes fewer lanes
   a.WP = a.W <= 31 ? 32 : 64;             // a wave owns two rows x 32 columns: row pitch 32 or 64
   auto aligned = [](const void* ptr, size_t b) { return ((uintptr_t)ptr % b) == 0; };
-  const int VW = (a.W % 4 == 0 && aligned(a.x, 16)) ? 4 : (aligned(a.x, 8) ? 2 : 1);
+  const int VW = (a.W % 4 == 0 && aligned(a.x, 16)) ? 4 : ((a.W % 2 == 0 && aligned(a.x, 8)) ? 2 : 1);
   if ((size_t)a.N * std::max(a.Cin, a.Cout) * a.H * a.W >= (size_t)1 << 31) return 1;
   a.CoP = a.Cout;
   const bool pooled = q.pool_out || q.pool_din;
@@ -605,6 +606,7 @@ int fdet_x3_sb_pool_run(ConvArgs a, PoolArgs q, hipStream_t st) {
   p.ntiles = (int)nbt * p.ncob;
   const int gsz = 2 * sb_num_cus();
   dim3 grid(p.ntiles < gsz ? p.ntiles : gsz, 1);
+  x3_note_route(X3_ROUTE_AL, VW, MT, a.mode, false, a.p16);
   if (a.p16) return MT == 2 ? launch_sb_pool<2, true>(p, VW, lds, grid, st) : launch_sb_pool<1, true>(p, VW, lds, grid, st);
   return MT == 2 ? launch_sb_pool<2>(p, VW, lds, grid, st) : launch_sb_pool<1>(p, VW, lds, grid, st);
 }

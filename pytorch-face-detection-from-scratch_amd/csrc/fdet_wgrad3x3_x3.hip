@@ -936,6 +936,15 @@ extern "C" size_t fdet_conv3x3_wgrad_bf16x3_batched_ws_bytes(int L, int N, int C
   return p.ok ? p.ws_floats * 4 : 0;
 }
 
+extern "C" int fdet_conv3x3_wgrad_bf16x3_plan(int N, int Cin, int Cout, int H, int W, int L, int* out, int n) {
+  FDET_REQUIRE(out && n >= 0 && N > 0 && Cin > 0 && Cout > 0 && H > 0 && W > 0 && L >= 1 && L <= MAXL,
+               "conv3x3_wgrad_bf16x3_plan: bad arguments");
+  const WgX3Plan p = plan_x3(N, Cin, Cout, H, W, L);
+  const int v[8] = {p.ok ? 1 : 0, p.pipe, p.lpr32, p.pk4, p.pack, p.vw, p.MTC, p.NSEG};
+  for (int i = 0; i < n && i < 8; ++i) out[i] = v[i];
+  return FDET_OK;
+}
+
 extern "C" int fdet_conv3x3_wgrad_bf16x3(const float* x, const float* dz, float* dW, float* db, void* ws,
                                          size_t ws_bytes, int N, int Cin, int Cout, int H, int W, void* stream) {
   FDET_REQUIRE(x && dz && dW && db && ws, "conv3x3_wgrad_bf16x3: null pointer");

@@ -411,6 +411,35 @@ def conv3x3_dgrad(dz, wpk_bwd, cin: int, dx, act=None, add=None, slope: float = 
           "fdet_conv3x3_dgrad")
 
 
+X3_ROUTE_FIELDS = ("family", "vw", "mt", "mode", "seg", "p16")
+X3_FAMILIES = {1: "pp", 2: "al", 3: "sb", 4: "general"}
+
+
+def conv3x3_x3_last_route() -> dict:
+    """Kernel route of the last bf16x3 / precision16 conv3x3 forward, data-gradient or pooled launch on this thread
+    (fdet_conv3x3_x3_last_route): family ("pp", "al", "sb", "general"; None after a refused call), vector width VW, MT,
+    epilogue mode (EPI_*), column-segmented rows and precision16."""
+    import ctypes
+    out = (ctypes.c_int * len(X3_ROUTE_FIELDS))()
+    check(lib().fdet_conv3x3_x3_last_route(out, len(out)), "fdet_conv3x3_x3_last_route")
+    r = dict(zip(X3_ROUTE_FIELDS, list(out)))
+    r["family"] = X3_FAMILIES.get(r["family"])
+    return r
+
+
+WGRAD_PLAN_FIELDS = ("ok", "pipe", "lpr32", "pk4", "pack", "vw", "mtc", "nseg")
+
+
+def conv3x3_wgrad_x3_plan(Nn, cin, cout, H, W, L: int = 1) -> dict:
+    """The bf16x3 / precision16 weight-gradient plan of L same-shape layers (fdet_conv3x3_wgrad_bf16x3_plan; launches
+    nothing): ok, pipe, lpr32, pk4, pack, vw, mtc, nseg."""
+    import ctypes
+    out = (ctypes.c_int * len(WGRAD_PLAN_FIELDS))()
+    check(lib().fdet_conv3x3_wgrad_bf16x3_plan(int(Nn), int(cin), int(cout), int(H), int(W), int(L), out, len(out)),
+          "fdet_conv3x3_wgrad_bf16x3_plan")
+    return dict(zip(WGRAD_PLAN_FIELDS, list(out)))
+
+
 def pool_fusion_supported(cout: int, cin: int, H: int, W: int, N: int = 1) -> bool:
     """Pooled residual blocks whose tail runs inside the conv epilogues (fdet_conv3x3_fwd_pool_bf16x3): the library's own
     plan check (fdet_conv3x3_pool_fusion_ok), batch-size limits included when N is given."""
