@@ -622,6 +622,62 @@ int fdet_dropout_scales(float* out, size_t n, float p, uint64_t seed, uint64_t o
 int fdet_dropout_scales_layers(float* out, int n, int nlayers, const int* channels, const float* p,
                                uint64_t seed, uint64_t base, uint64_t first_image, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * On-device training augmentation (csrc/fdet_augment.hip).  Replaces the albumentations
+ * pipelines of datasets/WIDERFace/datamodule.py:105-134 (training_transform /
+ * default_transform) and the box rounding of dataset.py:81-91 on a ragged batch:
+ *   bank    one device byte buffer of HWC uint8 RGB images
+ *   table   [n_images] {offset (bytes, 64-bit), h, w}; h_table: the same rows in host memory
+ *   params  [B] per-image records sampled on the host (fdet_amd/datasets/augment.py);
+ *           h_params: the same records in host memory (validated before any launch)
+ * Per-pixel draws (noise, glass offsets) come from a hash of (seed, params.key, tag, y, x).
+ * ------------------------------------------------------------------------------------- */
+typedef struct fdet_aug_image {
+  int64_t offset;            /* byte offset of pixel (0,0) in the bank */
+  int32_t h, w;
+} fdet_aug_image;
+
+#define FDET_AUG_FLIP 1            /* HorizontalFlip */
+#define FDET_AUG_ROTATE 2          /* Rotate by angle (cos_a, sin_a), reflect-101 border */
+#define FDET_AUG_BRIGHTNESS 4      /* v*alpha + beta */
+#define FDET_AUG_NOISE 8           /* v + sigma*N(0,1) per pixel and channel */
+#define FDET_AUG_GLASS 16          /* GlassBlur(sigma 0.1, max_delta 1, 1 iteration, fast mode) */
+#define FDET_AUG_MOTION 32         /* MotionBlur with the motion_k x motion_k kernel motion_w */
+#define FDET_AUG_CROP 64           /* informational: RandomResizedCrop drew the crop window */
+#define FDET_AUG_CROP_FALLBACK 128 /* informational: ... by its centre-crop fallback */
+
+typedef struct fdet_aug_params {
+  int32_t image;                   /* row of the image table */
+  int32_t flags;                   /* FDET_AUG_* */
+  int32_t crop_x0, crop_y0, crop_w, crop_h;   /* crop window in source pixels (whole image when no crop) */
+  float angle, cos_a, sin_a;       /* degrees, positive = counter-clockwise on screen */
+  float alpha, beta;               /* contrast factor, brightness offset (0..255 units) */
+  float sigma;                     /* noise standard deviation */
+  uint32_t key;                    /* per-image key of the pixel hash */
+  int32_t motion_k;                /* 1, 3, 5 or 7 */
+  float motion_w[49];              /* row-major motion_k x motion_k weights (sum 1) */
+  int32_t reserved;
+} fdet_aug_params;                 /* 256 bytes */
+
+/* Geometric chain + photometric ops -> uint8 intermediate mid [B,3,Ho,Wo] (one bilinear sample
+ * of the source per pixel, one rounding). */
+int fdet_aug_warp(const uint8_t* bank, const fdet_aug_image* table, const fdet_aug_image* h_table, int n_images,
+                  const fdet_aug_params* params, const fdet_aug_params* h_params, int B, int Ho, int Wo,
+                  uint32_t seed, uint8_t* mid, void* stream);
+/* GlassBlur + MotionBlur on mid -> out_u8 [B,3,Ho,Wo] and out_f32 = out_u8 / 255 (bit-identical to
+ * fdet_u8_to_f32_norm).  Wo % 4 == 0 takes the vector stores (4-byte / 16-byte aligned outputs). */
+int fdet_aug_finish(const uint8_t* mid, const fdet_aug_params* params, const fdet_aug_params* h_params, int B, int Ho,
+                    int Wo, uint32_t seed, uint8_t* out_u8, float* out_f32, void* stream);
+/* Box transform of the same chain.  boxes [total,5] rows [conf,x,y,w,h] in source pixels of the
+ * bank's images, box_offset [n_images+1] (image i owns rows box_offset[i]..box_offset[i+1]-1).
+ * Writes the surviving rows [1,x,y,w,h] (clipped area >= 10, rounded half-to-even) of the batch
+ * compacted into rows [max_rows,5] and out_offset [B+1] (the layout of fdet_encode_targets);
+ * rows past max_rows are counted in out_offset but not written. */
+int fdet_aug_boxes(const float* boxes, const int32_t* box_offset, const fdet_aug_image* table,
+                   const fdet_aug_image* h_table, int n_images, const fdet_aug_params* params,
+                   const fdet_aug_params* h_params, int B, int Ho, int Wo, int max_rows, float* rows,
+                   int32_t* out_offset, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

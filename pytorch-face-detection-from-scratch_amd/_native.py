@@ -37,7 +37,7 @@ def build(verbose: bool = False) -> str:
 
 
 _c = ctypes
-_P, _I, _F, _D, _SZ, _U64 = _c.c_void_p, _c.c_int, _c.c_float, _c.c_double, _c.c_size_t, _c.c_uint64
+_P, _I, _F, _D, _SZ, _U64, _U32 = _c.c_void_p, _c.c_int, _c.c_float, _c.c_double, _c.c_size_t, _c.c_uint64, _c.c_uint32
 
 # name -> (restype, argtypes); mirrors include/fdet.h declaration by declaration
 SIGNATURES = {
@@ -163,6 +163,9 @@ SIGNATURES = {
     "fdet_head_loss_fused": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _SZ, _I, _I, _I, _I, _I, _I, _P]),
     "fdet_dropout_scales": (_I, [_P, _SZ, _F, _U64, _U64, _P]),
     "fdet_dropout_scales_layers": (_I, [_P, _I, _I, _P, _P, _U64, _U64, _U64, _P]),
+    "fdet_aug_warp": (_I, [_P, _P, _P, _I, _P, _P, _I, _I, _I, _U32, _P, _P]),
+    "fdet_aug_finish": (_I, [_P, _P, _P, _I, _I, _I, _U32, _P, _P, _P]),
+    "fdet_aug_boxes": (_I, [_P, _P, _P, _P, _I, _P, _P, _I, _I, _I, _I, _P, _P, _P]),
 }
 
 

@@ -45,6 +45,28 @@ def encode_targets(boxes: Sequence[torch.Tensor], img_size: Tuple[int, int], num
     return out
 
 
+def _device_rows(rows: torch.Tensor, box_offset: torch.Tensor):
+    if not (rows.is_cuda and box_offset.is_cuda):
+        raise N.FdetError("device-input target encode: rows and box_offset must be GPU tensors")
+    if rows.dtype != F32 or rows.dim() != 2 or rows.shape[1] != 5 or rows.shape[0] < 1:
+        raise ValueError(f"rows must be a (cap>=1,5) float32 tensor, got {tuple(rows.shape)} {rows.dtype}")
+    if box_offset.dtype != I32 or box_offset.dim() != 1 or box_offset.numel() < 2:
+        raise ValueError("box_offset must be a (B+1,) int32 tensor")
+    return rows.contiguous(), box_offset.contiguous(), box_offset.numel() - 1
+
+
+def encode_targets_device(rows: torch.Tensor, box_offset: torch.Tensor, img_size: Tuple[int, int],
+                          num_of_patches: int) -> torch.Tensor:
+    """encode_targets on rows already on the device: rows (cap,5) [conf,x,y,w,h], box_offset (B+1,) int32 (image n owns
+    rows box_offset[n]..box_offset[n+1]-1, box_offset[B] <= cap) -> (B,5,S,S).  No host round trip, no synchronisation."""
+    rows, box_offset, B = _device_rows(rows, box_offset)
+    S = int(num_of_patches)
+    out = torch.empty(B, 5, S, S, dtype=F32, device=rows.device)
+    check(lib().fdet_encode_targets(ptr(rows), ptr(box_offset, I32), B, S, float(img_size[0]), float(img_size[1]),
+                                    ptr(out), stream()), "fdet_encode_targets")
+    return out
+
+
 def yolo_loss_fwd_bwd(pred: torch.Tensor, gt: torch.Tensor, want_grad: bool = True, grad_scale: float = 1.0):
     """(B,5,S,S) x2 -> (loss_per_image (B,), loss_sum (1,), grad (B,5,S,S) or None)."""
     pred, gt = _f32(pred), _f32(gt)
@@ -160,6 +182,17 @@ def ssd_encode_targets(boxes: Sequence[torch.Tensor], img_size: Tuple[int, int],
     if B:
         check(lib().fdet_ssd_encode_targets(ptr(flat), ptr(offs.to(device), I32), B, arr, ns, float(img_size[0]),
                                             float(img_size[1]), ptr(out), stream()), "fdet_ssd_encode_targets")
+    return out
+
+
+def ssd_encode_targets_device(rows: torch.Tensor, box_offset: torch.Tensor, img_size: Tuple[int, int],
+                              patch_sizes=SSD_PATCH_SIZES) -> torch.Tensor:
+    """ssd_encode_targets on rows already on the device (layout of encode_targets_device) -> (B,P,5)."""
+    rows, box_offset, B = _device_rows(rows, box_offset)
+    arr, ns = _ps_array(patch_sizes)
+    out = torch.empty(B, ssd_num_priors(patch_sizes), 5, dtype=F32, device=rows.device)
+    check(lib().fdet_ssd_encode_targets(ptr(rows), ptr(box_offset, I32), B, arr, ns, float(img_size[0]),
+                                        float(img_size[1]), ptr(out), stream()), "fdet_ssd_encode_targets")
     return out
 
 

@@ -10,6 +10,10 @@ is what there is on a box without network.  `--data DIR` expects `DIR/images_u8.
 `--precision 16` is the reference's Trainer(precision=16) (train_model.py:50) with bf16 as the 16-bit type: the conv kernels
 run one bf16 MFMA pass (engine.set_precision("bf16")); with the defaults (F=128, S=10, batch 8) that is the reference's
 own training recipe.  `--precision 32` (default) keeps the fp32-grade bf16x3 arithmetic.
+
+`--augment` trains instead on a device-resident bank of seeded synthetic images of WIDER-like ragged sizes through the
+reference's training_transform (datamodule.py:105-124) run on the GPU (datasets/augment.py); validation uses
+default_transform (Resize alone).
 """
 import argparse
 from pathlib import Path
@@ -43,6 +47,8 @@ def main(argv=None):
     ap.add_argument("--val-steps", type=int, default=5)
     ap.add_argument("--save", default=None)
     ap.add_argument("--precision", type=int, choices=(32, 16), default=32)   # train_model.py:50 Trainer(precision=...)
+    ap.add_argument("--augment", action="store_true", help="on-device training_transform over a synthetic image bank")
+    ap.add_argument("--bank-size", type=int, default=None, help="--augment: images in the bank (default: one epoch's worth)")
     args = ap.parse_args(argv)
     torch.random.manual_seed(0)                                  # train_model.py:13
     from .models import ModelMeta
@@ -58,8 +64,17 @@ def main(argv=None):
         model.engine.set_precision("bf16")
     model.summary()
     model_setup = ModelMeta(model=model, lr=args.lr, log_path=log_path)
-    train = synthetic_loader(args.steps_per_epoch, args.batch_size, args.size, args.patches, seed=1)
-    val = synthetic_loader(args.val_steps, args.batch_size, args.size, args.patches, seed=2)
+    if args.augment:
+        from .datasets.augment import DeviceBatches, default_transform, synthetic_bank, training_transform
+        shape = (args.size, args.size)
+        n_train = args.bank_size or args.steps_per_epoch * args.batch_size
+        bank, boxes = synthetic_bank(n_train, "cuda", seed=1)
+        vbank, vboxes = synthetic_bank(args.val_steps * args.batch_size, "cuda", seed=2)
+        train = DeviceBatches(bank, boxes, args.batch_size, training_transform(shape, seed=1), args.patches, seed=1)
+        val = DeviceBatches(vbank, vboxes, args.batch_size, default_transform(shape), args.patches, shuffle=False)
+    else:
+        train = synthetic_loader(args.steps_per_epoch, args.batch_size, args.size, args.patches, seed=1)
+        val = synthetic_loader(args.val_steps, args.batch_size, args.size, args.patches, seed=2)
     hist = fit(model_setup, train, val, epochs=args.epochs, torchscript_path=args.save)
     print(f"\nfinal training loss {float(hist['train'][-1]['loss']):.3f}")
     return hist

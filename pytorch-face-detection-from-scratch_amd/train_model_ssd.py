@@ -9,6 +9,9 @@ As in train_model.py, the WIDER-Face datamodule of the reference (downloads and 
 The defaults are the reference's recipe: SSD(filters=16) at 480x480, batch 24, lr 1e-4, 70 epochs.  `--precision 16` is
 its Trainer(precision=16) (train_model_ssd.py:46-50) with bf16 as the 16-bit type: every matrix-core layer runs one bf16
 MFMA pass (engine.set_precision("bf16"), ssdstack.py).  `--precision 32` (default) keeps the fp32-grade bf16x3 arithmetic.
+
+`--augment` trains instead on a device-resident bank of seeded synthetic images of WIDER-like ragged sizes through
+default_transform (Resize alone, datasets/augment.py) with the SSD encoder, as the SSD datamodule does.
 """
 import argparse
 from pathlib import Path
@@ -41,6 +44,8 @@ def parser():
     ap.add_argument("--val-steps", type=int, default=5)
     ap.add_argument("--save", default=None)
     ap.add_argument("--precision", type=int, choices=(32, 16), default=32)   # train_model_ssd.py:49 Trainer(precision=...)
+    ap.add_argument("--augment", action="store_true", help="on-device default_transform over a synthetic image bank")
+    ap.add_argument("--bank-size", type=int, default=None, help="--augment: images in the bank (default: one epoch's worth)")
     return ap
 
 
@@ -59,8 +64,18 @@ def main(argv=None):
         model.engine.set_precision("bf16")
     print(f"SSD: {sum(p.numel() for p in model.parameters()):,} parameters, input {tuple(model.input_shape)}")
     model_setup = ModelMetaSSD(model=model, lr=args.lr, log_path=log_path)
-    train = synthetic_loader(args.steps_per_epoch, args.batch_size, args.size, seed=1)
-    val = synthetic_loader(args.val_steps, args.batch_size, args.size, seed=2)
+    if args.augment:
+        from . import hotpath as hp
+        from .datasets.augment import DeviceBatches, default_transform, synthetic_bank
+        shape = (args.size, args.size)
+        bank, boxes = synthetic_bank(args.bank_size or args.steps_per_epoch * args.batch_size, "cuda", seed=1)
+        vbank, vboxes = synthetic_bank(args.val_steps * args.batch_size, "cuda", seed=2)
+        train = DeviceBatches(bank, boxes, args.batch_size, default_transform(shape), hp.SSD_PATCH_SIZES, encoder="ssd", seed=1)
+        val = DeviceBatches(vbank, vboxes, args.batch_size, default_transform(shape), hp.SSD_PATCH_SIZES, encoder="ssd",
+                            shuffle=False)
+    else:
+        train = synthetic_loader(args.steps_per_epoch, args.batch_size, args.size, seed=1)
+        val = synthetic_loader(args.val_steps, args.batch_size, args.size, seed=2)
     hist = fit(model_setup, train, val, epochs=args.epochs, torchscript_path=args.save)
     print(f"\nfinal training loss {float(hist['train'][-1]['loss']):.3f}")
     return hist
