@@ -678,6 +678,39 @@ int fdet_aug_boxes(const float* boxes, const int32_t* box_offset, const fdet_aug
                    const fdet_aug_params* h_params, int B, int Ho, int Wo, int max_rows, float* rows,
                    int32_t* out_offset, void* stream);
 
+/* ---- dataset-level evaluation (csrc/fdet_eval.hip) ------------------------------------------------
+ * PASCAL VOC / WIDER Face matching of one batch, accumulated (+=) into score-binned true/false-positive
+ * histograms: the device-side state of a precision/recall curve and its AP over a whole validation set.
+ * No counterpart in the reference (its only quality numbers are the per-batch step metrics above).
+ *   pred [B,Kmax,5] rows [score,x,y,w,h] + pred_counts [B]: the output pair of fdet_reduce_bounding_boxes /
+ *        fdet_ssd_reduce_bounding_boxes; rows need not be sorted
+ *   gt_rows [gt_cap,5] rows [conf,x,y,w,h] + gt_offset [B+1]: the layout of fdet_encode_targets / fdet_aug_boxes
+ *   iou_thresholds [T]: HOST array, 1 <= T <= FDET_EVAL_MAX_THRESHOLDS;  max_gt: largest box count of one image the
+ *        launch reserves LDS for (<= FDET_EVAL_MAX_GT);  n_bins <= FDET_EVAL_MAX_BINS (1000: the WIDER protocol)
+ *   tp, fp [T,n_bins] uint32, bin = min(n_bins-1, (int)floorf(score * n_bins)) in fp32; a negative score, -inf and
+ *        NaN go to bin 0 (NaN is ordered as -inf: visited last), a score >= 1 and +inf to the last bin
+ *   counters [FDET_EVAL_N_COUNTERS] uint64: ground-truth boxes, images, detections, rejected images
+ *   match [B,Kmax] int32 or NULL: for iou_thresholds[0], the row of gt_rows a detection matched, else -1
+ * Per image and threshold: detections in descending score (ties: ascending row); the candidate of a detection is
+ * the box of highest IoU among ALL of the image's boxes (ties: lowest row; fp32 box_iou as in fdet_step_metrics on
+ * x, y, x+w, y+h; a NaN IoU is never a candidate); true positive iff IoU >= threshold and the candidate has not been
+ * claimed by an earlier detection, else false positive.
+ * Sizes known on the host that exceed the limits return FDET_EINVAL.  Counts only the device knows (pred_counts[n] >
+ * Kmax, more than max_gt boxes, offsets outside 0..gt_cap) reject that image as a whole: it adds nothing but
+ * counters[FDET_EVAL_N_REJECTED] += 1, which the caller must read as an error; nothing is ever truncated. */
+#define FDET_EVAL_MAX_THRESHOLDS 10
+#define FDET_EVAL_MAX_DET 4864
+#define FDET_EVAL_MAX_GT 4096
+#define FDET_EVAL_MAX_BINS 4096
+#define FDET_EVAL_N_GT 0
+#define FDET_EVAL_N_IMAGES 1
+#define FDET_EVAL_N_DET 2
+#define FDET_EVAL_N_REJECTED 3
+#define FDET_EVAL_N_COUNTERS 4
+int fdet_eval_match(const float* pred, const int32_t* pred_counts, int B, int Kmax, const float* gt_rows,
+                    const int32_t* gt_offset, int gt_cap, int max_gt, const float* iou_thresholds, int T,
+                    int n_bins, uint32_t* tp, uint32_t* fp, uint64_t* counters, int32_t* match, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -166,6 +166,7 @@ SIGNATURES = {
     "fdet_aug_warp": (_I, [_P, _P, _P, _I, _P, _P, _I, _I, _I, _U32, _P, _P]),
     "fdet_aug_finish": (_I, [_P, _P, _P, _I, _I, _I, _U32, _P, _P, _P]),
     "fdet_aug_boxes": (_I, [_P, _P, _P, _P, _I, _P, _P, _I, _I, _I, _I, _P, _P, _P]),
+    "fdet_eval_match": (_I, [_P, _P, _I, _I, _P, _P, _I, _I, _P, _I, _I, _P, _P, _P, _P, _P]),
 }
 
 

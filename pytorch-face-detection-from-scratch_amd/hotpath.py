@@ -148,6 +148,73 @@ def step_metrics(gt: torch.Tensor, gt_counts: torch.Tensor, pred: torch.Tensor, 
 
 
 # ------------------------------------------------------------------------------------------
+# dataset-level evaluation (csrc/fdet_eval.hip)
+# ------------------------------------------------------------------------------------------
+EVAL_MAX_THRESHOLDS, EVAL_MAX_DET, EVAL_MAX_GT, EVAL_MAX_BINS = 10, 4864, 4096, 4096      # FDET_EVAL_* of include/fdet.h
+EVAL_N_GT, EVAL_N_IMAGES, EVAL_N_DET, EVAL_N_REJECTED = 0, 1, 2, 3
+
+
+class EvalState:
+    """The accumulators of fdet_eval_match: `hist` (2,T,n_bins) int32 holding the uint32 bit patterns of the tp (hist[0])
+    and fp (hist[1]) histograms, `counters` (4,) int64 [ground-truth boxes, images, detections, rejected images].  Lives
+    on `device`; a CPU state is good for merging / reducing what was copied off a GPU, not for eval_match."""
+
+    def __init__(self, iou_thresholds=(0.5,), n_bins: int = 1000, device="cuda"):
+        import ctypes
+        import numpy as np
+        thr = [float(t) for t in iou_thresholds]
+        if not 1 <= len(thr) <= EVAL_MAX_THRESHOLDS:
+            raise ValueError(f"eval: {len(thr)} IoU thresholds, 1..{EVAL_MAX_THRESHOLDS} are supported")
+        if not 1 <= int(n_bins) <= EVAL_MAX_BINS:
+            raise ValueError(f"eval: n_bins={n_bins}, 1..{EVAL_MAX_BINS} are supported")
+        self.iou_thresholds = np.asarray(thr, dtype=np.float32)            # the values the kernel compares with
+        self._thr_c = (ctypes.c_float * len(thr))(*self.iou_thresholds.tolist())
+        self.n_bins = int(n_bins)
+        self.device = torch.device(device)
+        self.hist = torch.zeros(2, len(thr), self.n_bins, dtype=I32, device=self.device)
+        self.counters = torch.zeros(4, dtype=torch.int64, device=self.device)
+
+    @property
+    def T(self) -> int:
+        return len(self.iou_thresholds)
+
+    def zero_(self) -> None:
+        self.hist.zero_()
+        self.counters.zero_()
+
+
+def eval_match(pred: torch.Tensor, pred_counts: torch.Tensor, gt_rows: torch.Tensor, gt_offset: torch.Tensor,
+               state: EvalState, max_gt: Optional[int] = None, want_match: bool = False):
+    """Match one batch and add it to `state` (fdet_eval_match): pred (B,Kmax,5) [score,x,y,w,h] with pred_counts (B,) as
+    `forward_batch` of either reducer returns them, gt_rows (cap,5) [conf,x,y,w,h] with gt_offset (B+1,) int32 as
+    GtBoxes holds them.  `max_gt`: the most boxes one image can have (default min(cap, 4096)).  One launch, no host
+    synchronisation.  -> match (B,Kmax) int32 for the first threshold with `want_match`, else None."""
+    if not isinstance(state, EvalState):
+        raise ValueError("eval_match: state must be an EvalState")
+    if pred.dim() != 3 or pred.shape[2] != 5 or pred.dtype != F32 or pred.shape[0] < 1:
+        raise ValueError(f"eval_match: pred must be a (B>=1,Kmax,5) float32 tensor, got {tuple(pred.shape)} {pred.dtype}")
+    B, Kmax = int(pred.shape[0]), int(pred.shape[1])
+    if not 1 <= Kmax <= EVAL_MAX_DET:
+        raise ValueError(f"eval_match: Kmax={Kmax} detections per image, 1..{EVAL_MAX_DET} are supported")
+    if tuple(pred_counts.shape) != (B,) or pred_counts.dtype != I32:
+        raise ValueError(f"eval_match: pred_counts must be a ({B},) int32 tensor, got {tuple(pred_counts.shape)} {pred_counts.dtype}")
+    if gt_rows.dim() != 2 or gt_rows.shape[1] != 5 or gt_rows.dtype != F32 or gt_rows.shape[0] < 1:
+        raise ValueError(f"eval_match: gt_rows must be a (cap>=1,5) float32 tensor, got {tuple(gt_rows.shape)} {gt_rows.dtype}")
+    if tuple(gt_offset.shape) != (B + 1,) or gt_offset.dtype != I32:
+        raise ValueError(f"eval_match: gt_offset must be a ({B + 1},) int32 tensor, got {tuple(gt_offset.shape)} {gt_offset.dtype}")
+    cap = int(gt_rows.shape[0])
+    max_gt = min(cap, EVAL_MAX_GT) if max_gt is None else int(max_gt)
+    if not 1 <= max_gt <= EVAL_MAX_GT:
+        raise ValueError(f"eval_match: max_gt={max_gt} boxes per image, 1..{EVAL_MAX_GT} are supported")
+    pred, pred_counts, gt_rows, gt_offset = pred.contiguous(), pred_counts.contiguous(), gt_rows.contiguous(), gt_offset.contiguous()
+    match = torch.empty(B, Kmax, dtype=I32, device=pred.device) if want_match else None
+    check(lib().fdet_eval_match(ptr(pred), ptr(pred_counts, I32), B, Kmax, ptr(gt_rows), ptr(gt_offset, I32), cap, max_gt,
+                                state._thr_c, state.T, state.n_bins, ptr(state.hist[0], I32), ptr(state.hist[1], I32),
+                                ptr(state.counters, torch.int64), ptr(match, I32), stream()), "fdet_eval_match")
+    return match
+
+
+# ------------------------------------------------------------------------------------------
 # SSD detection math (datasets/WIDERFace/dataset_ssd.py, losses/SSDLoss.py, datasets/utils.py:8-92)
 # ------------------------------------------------------------------------------------------
 SSD_PATCH_SIZES = (60, 30, 15, 7)

@@ -1,0 +1,110 @@
+"""Counterpart of the reference's run_validation_epoch.py: load a checkpoint, run one validation epoch, print the metrics.
+
+    python -m fdet_amd.run_validation_epoch --model poolresnet --filters 64 --checkpoint last.ckpt --json curve.json
+
+The reference prints the averaged step metrics (`format_metrics(..., training=False)`); this script prints that line and,
+below it, what the whole validation set gives through `evaluation.DetectionEvaluator`: average precision at `--iou`, the
+best F1 and the score threshold that reaches it.  `--json PATH` writes the precision/recall curve.
+
+Data: `--wider-root DIR --split val` reads DIR/wider_face_split/wider_face_val_bbx_gt.txt and DIR/WIDER_val/images (decoded
+once into a device image bank); without it a seeded synthetic bank stands in, so the script runs anywhere.  `--checkpoint`
+takes a Lightning-layout file ({"state_dict": {"model.<name>": tensor}}) or a bare state_dict archive (.pth) of the model
+class; without it the freshly initialised model is evaluated.  `--precision 16` runs the convolutions in one bf16 pass.
+"""
+import argparse
+import json
+from pathlib import Path
+
+import torch
+
+
+def load_checkpoint(model_setup, path):
+    """Lightning layout, a bare ModelMeta state_dict or a bare model state_dict -> loaded into model_setup (strict)."""
+    ck = torch.load(path, map_location="cpu", weights_only=True)
+    sd = ck["state_dict"] if isinstance(ck, dict) and "state_dict" in ck else ck
+    if not isinstance(sd, dict) or not sd:
+        raise ValueError(f"{path}: no state_dict found")
+    if all(k.startswith("model.") for k in sd):
+        model_setup.load_state_dict(sd)
+    else:
+        model_setup.model.load_state_dict(sd)
+    model_setup.model.engine.mark_params_dirty()
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--model", choices=("poolresnet", "resnet", "ssd"), default="poolresnet")
+    ap.add_argument("--filters", type=int, default=None, help="default: 128 (poolresnet), 64 (resnet), 16 (ssd)")
+    ap.add_argument("--patches", type=int, default=None, help="default: 10 (poolresnet), 15 (resnet)")
+    ap.add_argument("--size", type=int, default=480)
+    ap.add_argument("--batch-size", type=int, default=8)
+    ap.add_argument("--precision", type=int, choices=(32, 16), default=32)
+    ap.add_argument("--checkpoint", default=None)
+    ap.add_argument("--iou", type=float, nargs="+", default=[0.5], help="IoU threshold(s) of a true positive (up to 10)")
+    ap.add_argument("--score-floor", type=float, default=0.01)
+    ap.add_argument("--wider-root", default=None)
+    ap.add_argument("--split", default="val")
+    ap.add_argument("--max-faces", type=int, default=None, help="keep images with at most this many faces (reference: 2)")
+    ap.add_argument("--max-images", type=int, default=None)
+    ap.add_argument("--synthetic-images", type=int, default=64)
+    ap.add_argument("--json", default=None)
+    args = ap.parse_args(argv)
+    torch.random.manual_seed(0)
+    from . import hotpath as hp
+    from .datasets.augment import DeviceBatches, default_transform, synthetic_bank
+    from .evaluation import DetectionEvaluator
+    from .trainer import _epoch
+    shape = (3, args.size, args.size)
+    if args.model == "ssd":
+        from .models.ModelMetaSSD import ModelMetaSSD as Meta
+        from .models.SSD import SSD
+        model = SSD(filters=args.filters or 16, input_shape=shape).cuda()
+        patches, encoder = hp.SSD_PATCH_SIZES, "ssd"
+    else:
+        from .models import ModelMeta as Meta
+        if args.model == "poolresnet":
+            from .models.PoolResnet import PoolResnet
+            patches = args.patches or 10
+            model = PoolResnet(filters=args.filters or 128, input_shape=shape, num_of_patches=patches, num_of_residual_blocks=10).cuda()
+        else:
+            from .models.Resnet import Resnet
+            patches = args.patches or 15
+            model = Resnet(filters=args.filters or 64, input_shape=shape, num_of_patches=patches).cuda()
+        encoder = "yolo"
+    if args.precision == 16:
+        model.engine.set_precision("bf16")
+    log_path = Path(f"logs/out_{args.model}_single_validate.log")
+    log_path.parent.mkdir(parents=True, exist_ok=True)
+    model_setup = Meta(model=model, lr=1e-4, log_path=log_path)
+    if args.checkpoint:
+        load_checkpoint(model_setup, args.checkpoint)
+    if args.wider_root:
+        from .datasets.WIDERFace.annotations import bank_from_files, read_wider_annotations
+        paths, boxes = read_wider_annotations(args.wider_root, args.split, max_faces=args.max_faces, keep_placeholder=False)
+        if args.max_images:
+            paths, boxes = paths[:args.max_images], boxes[:args.max_images]
+        bank = bank_from_files(paths, "cuda")
+    else:
+        bank, boxes = synthetic_bank(args.synthetic_images, "cuda", seed=2)
+    if len(bank) < args.batch_size:
+        raise SystemExit(f"{len(bank)} images do not fill one batch of {args.batch_size}")
+    val = DeviceBatches(bank, boxes, args.batch_size, default_transform((args.size, args.size)), patches, encoder=encoder,
+                        shuffle=False, drop_last=False)
+    ev = DetectionEvaluator(iou_thresholds=tuple(args.iou), score_floor=args.score_floor)
+    outs = _epoch(model_setup, val, False, {}, None, ev)
+    metrics = model_setup.format_metrics(outs, training=False)
+    r = ev.compute()
+    print(f"iou: {metrics['total_iou']:5.3f}, recall {metrics['total_recall']:5.3f}, precision {metrics['total_precision']:5.3f}, "
+          f"f1_score {metrics['f1_score']:5.3f}")
+    print(f"{r.n_images} images, {r.n_gt} faces, {r.n_det} detections with score >= {args.score_floor}")
+    for t, a in zip(r.iou_thresholds, r.ap_per_threshold):
+        print(f"AP@{float(t):.2f}: {a:.4f}")
+    print(f"best F1 {r.best_f1:.4f} at score threshold {r.best_threshold:.3f}; at the model's threshold "
+          f"{model.probability_threshold}: {r.at(model.probability_threshold)}")
+    if args.json:
+        Path(args.json).write_text(json.dumps(r.to_json()))
+    return {"metrics": metrics, "result": r}
+
+
+if __name__ == "__main__":
+    main()

@@ -20,7 +20,21 @@ from .datasets.feed import U8BatchFeeder
 from .hostinfo import limit_host_threads
 
 
-def _epoch(model_meta, batches, train: bool, feeder_cache: dict, on_step: Optional[Callable]):
+def _validation_step_with_output(model_meta, batch, step):
+    """`validation_step` as it is, plus the forward output it computed (a forward hook on the wrapped model records it
+    for the duration of the call): the evaluator sees the same `y_hat` without a second forward."""
+    seen = []
+    handle = model_meta.model.register_forward_hook(lambda module, args, output: seen.append(output))
+    try:
+        out = model_meta.validation_step(batch, step)
+    finally:
+        handle.remove()
+    if len(seen) != 1:
+        raise RuntimeError(f"validation_step ran the model {len(seen)} times; the evaluator hook expects exactly one forward")
+    return out, seen[0]
+
+
+def _epoch(model_meta, batches, train: bool, feeder_cache: dict, on_step: Optional[Callable], evaluator=None):
     model = model_meta.model
     dev = next(model.parameters()).device
     size = tuple(model.input_shape[1:])
@@ -30,21 +44,22 @@ def _epoch(model_meta, batches, train: bool, feeder_cache: dict, on_step: Option
 
     def stage(batch):
         x, y = batch[0], batch[1]
+        gt = batch[2] if evaluator is not None and not train and len(batch) > 2 else None
         if x.dtype == torch.uint8 and not x.is_cuda:
             key = (tuple(x.shape), tuple(y.shape))
             fd = feeder_cache.get(key)
             if fd is None:
                 fd = feeder_cache[key] = U8BatchFeeder(tuple(x.shape), size, dev, target_shape=tuple(y.shape))
             fd.submit(x, y.float())
-            return ("feeder", fd)
-        return ("direct", (x.to(dev, non_blocking=True).float(), y.to(dev, non_blocking=True).float()))
+            return ("feeder", fd, gt)
+        return ("direct", (x.to(dev, non_blocking=True).float(), y.to(dev, non_blocking=True).float()), gt)
 
     nxt = next(it, None)
     if nxt is not None:
         pending = stage(nxt)
     step = 0
     while pending is not None:
-        kind, payload = pending
+        kind, payload, gt = pending
         if kind == "feeder":
             x_d, y_d, tok = payload.get()
         else:
@@ -59,7 +74,13 @@ def _epoch(model_meta, batches, train: bool, feeder_cache: dict, on_step: Option
         else:
             model.eval()
             with torch.no_grad():
-                out = model_meta.validation_step((x_d, y_d, None), step)
+                if evaluator is None:
+                    out = model_meta.validation_step((x_d, y_d, None), step)
+                else:
+                    if gt is None:
+                        raise ValueError("fit(evaluator=...): validation batches must carry their true boxes as batch[2]")
+                    out, y_hat = _validation_step_with_output(model_meta, (x_d, y_d, None), step)
+                    evaluator.evaluate_batch(model, y_hat, gt)
         if tok is not None:
             U8BatchFeeder.release(tok)
         nxt = next(it, None)
@@ -73,9 +94,13 @@ def _epoch(model_meta, batches, train: bool, feeder_cache: dict, on_step: Option
 
 
 def fit(model_meta, train_batches: Iterable, val_batches: Optional[Iterable] = None, epochs: int = 1,
-        torchscript_path: Optional[str] = None, on_step: Optional[Callable] = None) -> dict:
+        torchscript_path: Optional[str] = None, on_step: Optional[Callable] = None, evaluator=None) -> dict:
     """Train `model_meta` (a ModelMeta) for `epochs` passes over `train_batches` (re-iterable), validating on
-    `val_batches` after every epoch.  Returns {"train": [per-epoch metrics], "val": [...], "scripted": module or None}."""
+    `val_batches` after every epoch.  Returns {"train": [per-epoch metrics], "val": [...], "scripted": module or None}.
+
+    `evaluator` (an `evaluation.DetectionEvaluator`): the validation pass also feeds it the forward output of every
+    validation step and the batch's true boxes (batch[2]: a GtBoxes or a list of (n,5) tensors); it is reset every epoch and
+    hist["val"][e] gains "ap", "best_f1", "best_threshold" (one device-to-host copy per epoch).  Step outputs are unchanged."""
     limit_host_threads()                  # 256 OpenMP workers on a 16-core share stall the thread that feeds the GPU
     optimizers, schedulers = model_meta.configure_optimizers()
     sched = schedulers[0]
@@ -89,8 +114,13 @@ def fit(model_meta, train_batches: Iterable, val_batches: Optional[Iterable] = N
             pass
         tr = _epoch(model_meta, train_batches, True, feeder_cache, on_step)
         if val_batches is not None:
-            va = _epoch(model_meta, val_batches, False, feeder_cache, on_step)
+            if evaluator is not None:
+                evaluator.reset()
+            va = _epoch(model_meta, val_batches, False, feeder_cache, on_step, evaluator)
             hist["val"].append(model_meta.format_metrics(va, training=False))
+            if evaluator is not None:
+                r = evaluator.compute()
+                hist["val"][-1].update(ap=r.ap, best_f1=r.best_f1, best_threshold=r.best_threshold)
         hist["train"].append(model_meta.format_metrics(tr, training=True))
         sched.step()
     model_meta.model.train()
