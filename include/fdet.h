@@ -711,6 +711,44 @@ int fdet_eval_match(const float* pred, const int32_t* pred_counts, int B, int Km
                     const int32_t* gt_offset, int gt_cap, int max_gt, const float* iou_thresholds, int T,
                     int n_bins, uint32_t* tp, uint32_t* fp, uint64_t* counters, int32_t* match, void* stream);
 
+/* ---- tiled full-resolution detection (csrc/fdet_tiles.hip) ------------------------------------------
+ * Run the network on overlapping windows of a source image and merge the windows' boxes per image.  No counterpart
+ * in the reference.  bank / table / h_table: as for the augmentation above.  tiles [T] / h_tiles: the windows in
+ * device and host memory (fdet_amd.tiling.plan_tiles makes them); `image` is a row of the table. */
+typedef struct fdet_tile {
+  int32_t image, x0, y0, w, h;     /* window (x0, y0, w, h) in source pixels of table[image] */
+} fdet_tile;                       /* 20 bytes */
+
+/* Window t of the bank -> frames [T,3,Ho,Wo] planar uint8 (the frames forward_frames takes).  The sample is the one
+ * fdet_aug_warp takes with flags = 0 and the window as its crop, byte for byte: sx = (u + 0.5) * (w / Wo) + x0 - 0.5
+ * in fp64, two taps per axis clamped to the WINDOW, fp32 bilinear weights, one rint (half-to-even) + clamp; a window
+ * of exactly Ho x Wo is a copy.  h_table / h_tiles are validated before the launch: a window outside its image, a
+ * non-positive size or an image row outside the table returns FDET_EINVAL and nothing is written.  T <= 65535. */
+int fdet_tile_gather(const uint8_t* bank, const fdet_aug_image* table, const fdet_aug_image* h_table, int n_images,
+                     const fdet_tile* tiles, const fdet_tile* h_tiles, int T, int Ho, int Wo, uint8_t* frames,
+                     void* stream);
+
+/* Cross-window merge, one workgroup per source image, no host synchronisation.
+ *   rows [T,K,5] [score,x,y,w,h] in frame pixels + counts [T]: the reducers' output for the T frames
+ *   tile_offset [n_images+1]: image n owns tiles tile_offset[n]..tile_offset[n+1]-1, whose `image` must be n;
+ *        table [n_images]: only h and w are read
+ *   1. x_s = rint(x0 + x * (w_win / Wo)), w_s = rint(w * (w_win / Wo)), likewise y / h: fp32, separate multiply and
+ *      add, half-to-even
+ *   2. edge_margin > 0: a detection is dropped when x < edge_margin at a window side with x0 > 0, when
+ *      x + w > Wo - edge_margin at a side with x0 + w_win < image w, likewise y (frame pixels, fp32); sides that
+ *      are sides of the image never drop anything; 0 turns the rule off
+ *   3. greedy NMS over the image's union with the semantics of fdet_nms: stable descending score (ties: tile, then
+ *      row; a NaN score is ordered as -inf), fp32 overlap on x_s, y_s, x_s + w_s, y_s + h_s compared in double with
+ *      iou_threshold, a NaN overlap never suppresses
+ *   out [n_images,Kout,5] [score,x_s,y_s,w_s,h_s] in visiting order, rows past the count zeroed; out_counts [n_images]
+ * Limits: FDET_TILE_MAX_CANDIDATES candidates per image after step 2 and Kout survivors.  An image over either,
+ * with counts[t] outside 0..K or with inconsistent tile_offset / tiles is rejected as a whole: out_counts = 0 and
+ * rejected[0] += 1, which the caller must read as an error; nothing is ever truncated. */
+#define FDET_TILE_MAX_CANDIDATES 4864
+int fdet_tile_merge(const float* rows, const int32_t* counts, const fdet_tile* tiles, const int32_t* tile_offset,
+                    int n_images, int T, int K, int Ho, int Wo, const fdet_aug_image* table, float edge_margin,
+                    double iou_threshold, int Kout, float* out, int32_t* out_counts, uint64_t* rejected, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,98 @@
+"""Detect faces in image files at their own resolution and write the WIDER Face result text format.
+
+    python -m fdet_amd.detect_images --checkpoint CKPT --images DIR --out FILE [--model poolresnet --filters 128]
+        [--tile 480 --overlap 0.25 --no-whole --edge-margin 0 --probability-threshold P --iou-threshold T --precision 16]
+
+The images under DIR (searched recursively: .jpg .jpeg .png .bmp) are decoded with PIL into a device image bank
+(`bank_from_files`), `tiling.TiledDetector` runs the model on overlapping windows of each image (and on the whole image
+unless --no-whole) and merges the windows' boxes, and FILE receives, per image: its path relative to DIR, the number of
+boxes, then one `x y w h score` line per box in source pixels.
+"""
+import argparse
+import os
+from pathlib import Path
+
+import torch
+
+EXTENSIONS = (".jpg", ".jpeg", ".png", ".bmp")
+
+
+def write_wider_results(path, names, rows, counts) -> None:
+    """names: n strings; rows (n,K,5) [score,x,y,w,h]; counts (n,) -> the WIDER result text format."""
+    rows, counts = rows.cpu().numpy(), counts.cpu().numpy()
+    with open(path, "w") as f:
+        for i, name in enumerate(names):
+            k = int(counts[i])
+            f.write(f"{name}\n{k}\n")
+            for s, x, y, w, h in rows[i, :k].tolist():
+                f.write(f"{x:.0f} {y:.0f} {w:.0f} {h:.0f} {s:.4f}\n")
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--model", choices=("poolresnet", "resnet", "ssd"), default="poolresnet")
+    ap.add_argument("--filters", type=int, default=None, help="default: 128 (poolresnet), 64 (resnet), 16 (ssd)")
+    ap.add_argument("--patches", type=int, default=None, help="default: 10 (poolresnet), 15 (resnet)")
+    ap.add_argument("--size", type=int, default=480)
+    ap.add_argument("--precision", type=int, choices=(32, 16), default=32)
+    ap.add_argument("--checkpoint", default=None)
+    ap.add_argument("--images", required=True)
+    ap.add_argument("--out", required=True)
+    ap.add_argument("--tile", type=int, nargs="*", default=[480], help="tile side(s) in source pixels; none: whole image only")
+    ap.add_argument("--overlap", type=float, default=0.25)
+    ap.add_argument("--no-whole", action="store_true")
+    ap.add_argument("--edge-margin", type=float, default=0.0)
+    ap.add_argument("--probability-threshold", type=float, default=0.5)
+    ap.add_argument("--iou-threshold", type=float, default=0.5)
+    ap.add_argument("--batch-images", type=int, default=64, help="source images per detect() call")
+    args = ap.parse_args(argv)
+    from .datasets.WIDERFace.annotations import bank_from_files
+    from .run_validation_epoch import load_checkpoint
+    from .tiling import TiledDetector
+    shape = (3, args.size, args.size)
+    kw = dict(probability_threshold=args.probability_threshold, iou_threshold=args.iou_threshold)
+    if args.model == "ssd":
+        from .models.ModelMetaSSD import ModelMetaSSD as Meta
+        from .models.SSD import SSD
+        model = SSD(filters=args.filters or 16, input_shape=shape, **kw).cuda()
+    else:
+        from .models import ModelMeta as Meta
+        if args.model == "poolresnet":
+            from .models.PoolResnet import PoolResnet
+            model = PoolResnet(filters=args.filters or 128, input_shape=shape, num_of_patches=args.patches or 10,
+                               num_of_residual_blocks=10, **kw).cuda()
+        else:
+            from .models.Resnet import Resnet
+            model = Resnet(filters=args.filters or 64, input_shape=shape, num_of_patches=args.patches or 15, **kw).cuda()
+    if args.precision == 16:
+        model.engine.set_precision("bf16")
+    if args.checkpoint:
+        log_path = Path("logs/out_detect_images.log")
+        log_path.parent.mkdir(parents=True, exist_ok=True)
+        load_checkpoint(Meta(model=model, lr=1e-4, log_path=log_path), args.checkpoint)
+    model.eval()
+    root = Path(args.images)
+    paths = sorted(p for p in root.rglob("*") if p.suffix.lower() in EXTENSIONS)
+    if not paths:
+        raise SystemExit(f"no image under {root}")
+    det = TiledDetector(model, tile_sizes=tuple(args.tile), overlap=args.overlap, include_whole=not args.no_whole,
+                        edge_margin=args.edge_margin)
+    names, all_rows, all_counts = [], [], []
+    for a in range(0, len(paths), args.batch_images):
+        chunk = paths[a:a + args.batch_images]
+        bank = bank_from_files(chunk, "cuda")
+        rows, counts = det.detect(bank, range(len(bank)))
+        kmax = max(int(counts.max()), 1)
+        all_rows.append(rows[:, :kmax].cpu())
+        all_counts.append(counts.cpu())
+        names += [os.path.relpath(p, root) for p in chunk]
+    kmax = max(r.shape[1] for r in all_rows)
+    rows = torch.cat([torch.nn.functional.pad(r, (0, 0, 0, kmax - r.shape[1])) for r in all_rows])
+    counts = torch.cat(all_counts)
+    write_wider_results(args.out, names, rows, counts)
+    print(f"{len(names)} images, {int(counts.sum())} boxes -> {args.out}")
+    return {"names": names, "rows": rows, "counts": counts}
+
+
+if __name__ == "__main__":
+    main()

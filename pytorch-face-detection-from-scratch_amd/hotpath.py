@@ -215,6 +215,67 @@ def eval_match(pred: torch.Tensor, pred_counts: torch.Tensor, gt_rows: torch.Ten
 
 
 # ------------------------------------------------------------------------------------------
+# tiled full-resolution detection (csrc/fdet_tiles.hip)
+# ------------------------------------------------------------------------------------------
+TILE_MAX_CANDIDATES = 4864                                   # FDET_TILE_MAX_CANDIDATES of include/fdet.h
+
+
+def _tile_records(h_tiles):
+    import numpy as np
+    if not isinstance(h_tiles, np.ndarray) or h_tiles.dtype.itemsize != 20 or h_tiles.ndim != 1 or not h_tiles.flags.c_contiguous:
+        raise ValueError("tiles: expected a contiguous (T,) numpy record array of fdet_tile {image,x0,y0,w,h} int32")
+    return h_tiles
+
+
+def tile_gather(bank_data: torch.Tensor, d_table: torch.Tensor, h_table, d_tiles: torch.Tensor, h_tiles, out_hw,
+                out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Windows of a device image bank -> (T,3,Ho,Wo) planar uint8 frames (fdet_tile_gather).  bank_data: the bank's byte
+    buffer; d_table / h_table: its fdet_aug_image table on the device (uint8 view) and as the numpy record array;
+    d_tiles / h_tiles: the windows likewise (tiling.TILE_DTYPE).  Bad windows raise FdetError before anything is written."""
+    h_tiles = _tile_records(h_tiles)
+    T, n_images = len(h_tiles), len(h_table)
+    Ho, Wo = int(out_hw[0]), int(out_hw[1])
+    if d_tiles.numel() != T * 20 or d_table.numel() != n_images * 16:
+        raise ValueError("tile_gather: device and host copies of the tiles / table differ in size")
+    if out is None:
+        out = torch.empty(T, 3, Ho, Wo, dtype=torch.uint8, device=bank_data.device)
+    elif tuple(out.shape) != (T, 3, Ho, Wo):
+        raise ValueError(f"tile_gather: out must be ({T},3,{Ho},{Wo}), got {tuple(out.shape)}")
+    U8 = torch.uint8
+    check(lib().fdet_tile_gather(ptr(bank_data, U8), ptr(d_table, U8), h_table.ctypes.data, n_images, ptr(d_tiles, U8),
+                                 h_tiles.ctypes.data, T, Ho, Wo, ptr(out, U8), stream()), "fdet_tile_gather")
+    return out
+
+
+def tile_merge(rows: torch.Tensor, counts: torch.Tensor, d_tiles: torch.Tensor, tile_offset: torch.Tensor, d_table: torch.Tensor,
+               frame_hw, edge_margin: float, iou_threshold: float, max_out: int, rejected: Optional[torch.Tensor] = None):
+    """fdet_tile_merge: rows (T,K,5) [score,x,y,w,h] in frame pixels + counts (T,) int32 of the T windows d_tiles,
+    tile_offset (n+1,) int32, d_table the n images' table -> (out (n,max_out,5) in source pixels, out_counts (n,) int32,
+    rejected (1,) int64 counter, += 1 per image over a limit).  One launch, no host synchronisation."""
+    if rows.dim() != 3 or rows.shape[2] != 5 or rows.dtype != F32:
+        raise ValueError(f"tile_merge: rows must be (T,K,5) float32, got {tuple(rows.shape)} {rows.dtype}")
+    T, K = int(rows.shape[0]), int(rows.shape[1])
+    n = int(tile_offset.numel()) - 1
+    if tuple(counts.shape) != (T,) or counts.dtype != I32 or tile_offset.dtype != I32 or n < 1:
+        raise ValueError("tile_merge: counts must be (T,) int32 and tile_offset (n+1,) int32")
+    if d_tiles.numel() != T * 20 or d_table.numel() != n * 16:
+        raise ValueError("tile_merge: tiles / table do not match T / n")
+    if int(max_out) < 1:
+        raise ValueError("tile_merge: max_out must be positive")
+    dev = rows.device
+    out = torch.empty(n, int(max_out), 5, dtype=F32, device=dev)
+    out_counts = torch.empty(n, dtype=I32, device=dev)
+    if rejected is None:
+        rejected = torch.zeros(1, dtype=torch.int64, device=dev)
+    U8 = torch.uint8
+    check(lib().fdet_tile_merge(ptr(rows.contiguous()), ptr(counts.contiguous(), I32), ptr(d_tiles, U8),
+                                ptr(tile_offset.contiguous(), I32), n, T, K, int(frame_hw[0]), int(frame_hw[1]), ptr(d_table, U8),
+                                float(edge_margin), float(iou_threshold), int(max_out), ptr(out), ptr(out_counts, I32),
+                                ptr(rejected, torch.int64), stream()), "fdet_tile_merge")
+    return out, out_counts, rejected
+
+
+# ------------------------------------------------------------------------------------------
 # SSD detection math (datasets/WIDERFace/dataset_ssd.py, losses/SSDLoss.py, datasets/utils.py:8-92)
 # ------------------------------------------------------------------------------------------
 SSD_PATCH_SIZES = (60, 30, 15, 7)

@@ -10,6 +10,8 @@ Data: `--wider-root DIR --split val` reads DIR/wider_face_split/wider_face_val_b
 once into a device image bank); without it a seeded synthetic bank stands in, so the script runs anywhere.  `--checkpoint`
 takes a Lightning-layout file ({"state_dict": {"model.<name>": tensor}}) or a bare state_dict archive (.pth) of the model
 class; without it the freshly initialised model is evaluated.  `--precision 16` runs the convolutions in one bf16 pass.
+`--tiled` adds a second report: the same evaluator numbers from `tiling.TiledDetector` on the UNRESIZED bank (windows of
+`--tile` source pixels with `--overlap`, plus the whole image unless `--no-whole`) against the source-pixel boxes.
 """
 import argparse
 import json
@@ -48,6 +50,10 @@ def main(argv=None):
     ap.add_argument("--max-images", type=int, default=None)
     ap.add_argument("--synthetic-images", type=int, default=64)
     ap.add_argument("--json", default=None)
+    ap.add_argument("--tiled", action="store_true", help="also evaluate tiled detection on the unresized images")
+    ap.add_argument("--tile", type=int, nargs="*", default=[480])
+    ap.add_argument("--overlap", type=float, default=0.25)
+    ap.add_argument("--no-whole", action="store_true")
     args = ap.parse_args(argv)
     torch.random.manual_seed(0)
     from . import hotpath as hp
@@ -103,7 +109,34 @@ def main(argv=None):
           f"{model.probability_threshold}: {r.at(model.probability_threshold)}")
     if args.json:
         Path(args.json).write_text(json.dumps(r.to_json()))
-    return {"metrics": metrics, "result": r}
+    out = {"metrics": metrics, "result": r}
+    if args.tiled:
+        out["tiled"] = tiled_report(model, bank, boxes, args)
+    return out
+
+
+def tiled_report(model, bank, boxes, args):
+    """The evaluator's numbers from TiledDetector on the unresized bank against the source-pixel boxes."""
+    from .datasets.augment import DeviceBoxes
+    from .evaluation import DetectionEvaluator
+    from .tiling import TiledDetector, boxes_for
+    model.eval()
+    ev = DetectionEvaluator(iou_thresholds=tuple(args.iou), score_floor=args.score_floor)
+    det = TiledDetector(model, tile_sizes=tuple(args.tile), overlap=args.overlap, include_whole=not args.no_whole,
+                        reducer=ev.reducer_for(model))
+    gt = DeviceBoxes(boxes, "cuda")
+    step = max(1, args.batch_size)
+    for a in range(0, len(bank), step):
+        idx = list(range(a, min(a + step, len(bank))))
+        rows, counts = det.detect(bank, idx)
+        ev.update(rows, counts, boxes_for(gt, idx), max_gt=max(gt.max_per_image, 1))
+    r = ev.compute()
+    print(f"tiled (tile {list(args.tile)}, overlap {args.overlap}, whole image {not args.no_whole}): {r.n_images} images, "
+          f"{r.n_gt} faces, {r.n_det} detections with score >= {args.score_floor}")
+    for t, a in zip(r.iou_thresholds, r.ap_per_threshold):
+        print(f"tiled AP@{float(t):.2f}: {a:.4f}")
+    print(f"tiled best F1 {r.best_f1:.4f} at score threshold {r.best_threshold:.3f}")
+    return r
 
 
 if __name__ == "__main__":
