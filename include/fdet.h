@@ -711,6 +711,41 @@ int fdet_eval_match(const float* pred, const int32_t* pred_counts, int B, int Km
                     const int32_t* gt_offset, int gt_cap, int max_gt, const float* iou_thresholds, int T,
                     int n_bins, uint32_t* tp, uint32_t* fp, uint64_t* counters, int32_t* match, void* stream);
 
+/* ---- WIDER Face protocol evaluation (csrc/fdet_eval_wider.hip) ---------------------------------------
+ * The matching rule of the WIDER Face evaluation protocol for one batch, for up to FDET_EVAL_WIDER_MAX_SUBSETS subsets
+ * (Easy / Medium / Hard) in one pass, accumulated (+=) into per-(subset, score threshold) histograms.  It is not the VOC
+ * rule of fdet_eval_match: boxes outside a subset are ignored, not missed; there is no uniqueness rule; overlaps use
+ * inclusive pixel coordinates.  No counterpart in the reference.
+ *   pred [B,Kmax,5] rows [score,x,y,w,h] + pred_counts [B]: as for fdet_eval_match
+ *   pred_scale [B,2] (sx, sy) or NULL (= 1): detections are taken to source pixels as x*sx, y*sy, w*sx, h*sy, four
+ *        separate fp32 multiplies, nothing rounded to integers
+ *   gt_rows [gt_cap,5] + gt_offset [B+1]: ALL boxes of the images, source pixels, the layout of fdet_eval_match
+ *   gt_subsets [gt_cap] uint32: bit s set = the box is kept in subset s (bits >= n_subsets are not read)
+ *   score_norm: DEVICE [2] doubles (min, max - min) or NULL (= 0, 1); n = ((double)score - min) / (max - min)
+ *   proposals, hits [n_subsets,n_bins] uint32
+ *   counters [n_subsets + FDET_EVAL_WIDER_N_COUNTERS] uint64: kept boxes per subset, then images, detections,
+ *        rejected images
+ * Per image: detections in descending raw score (ties: ascending row; NaN last).  Everything below in fp64, fixed
+ * operation order, no contraction: x1 = x, y1 = y, x2 = x + w, y2 = y + h for detections and boxes alike;
+ * iw = min(x2) - max(x1) + 1, ih likewise (min(a,b) = a < b ? a : b, max(a,b) = a > b ? a : b, detection first);
+ * overlap = iw*ih / (area_d + area_g - iw*ih) with area = (x2-x1+1)*(y2-y1+1) when iw > 0 and ih > 0, else 0.
+ * The candidate of a detection is the box of highest overlap among ALL boxes (ties: lowest row; a NaN overlap is never
+ * a candidate).  For subset s: overlap >= iou_threshold on a candidate that s does not keep drops the detection from s;
+ * every other detection is a proposal; overlap >= iou_threshold on a kept candidate that no earlier detection has
+ * recalled recalls it.  bin b = the smallest t in 0..n_bins-1 with n >= 1.0 - (double)(t+1)/n_bins (n < 0 and NaN:
+ * counted nowhere); proposals[s][b] += 1 per proposal, hits[s][b] += 1 per recalled box at the bin of the detection
+ * that recalled it first.  The sums over bins <= t are the protocol's proposal and recall counts at threshold t.
+ * Limits and rejection: as fdet_eval_match (FDET_EVAL_MAX_DET, FDET_EVAL_MAX_GT, FDET_EVAL_MAX_BINS). */
+#define FDET_EVAL_WIDER_MAX_SUBSETS 8
+#define FDET_EVAL_WIDER_N_IMAGES 0
+#define FDET_EVAL_WIDER_N_DET 1
+#define FDET_EVAL_WIDER_N_REJECTED 2
+#define FDET_EVAL_WIDER_N_COUNTERS 3
+int fdet_eval_wider(const float* pred, const int32_t* pred_counts, int B, int Kmax, const float* pred_scale,
+                    const float* gt_rows, const int32_t* gt_offset, int gt_cap, const uint32_t* gt_subsets,
+                    int n_subsets, int max_gt, double iou_threshold, const double* score_norm, int n_bins,
+                    uint32_t* proposals, uint32_t* hits, uint64_t* counters, void* stream);
+
 /* ---- tiled full-resolution detection (csrc/fdet_tiles.hip) ------------------------------------------
  * Run the network on overlapping windows of a source image and merge the windows' boxes per image.  No counterpart
  * in the reference.  bank / table / h_table: as for the augmentation above.  tiles [T] / h_tiles: the windows in

@@ -167,6 +167,7 @@ SIGNATURES = {
     "fdet_aug_finish": (_I, [_P, _P, _P, _I, _I, _I, _U32, _P, _P, _P]),
     "fdet_aug_boxes": (_I, [_P, _P, _P, _P, _I, _P, _P, _I, _I, _I, _I, _P, _P, _P]),
     "fdet_eval_match": (_I, [_P, _P, _I, _I, _P, _P, _I, _I, _P, _I, _I, _P, _P, _P, _P, _P]),
+    "fdet_eval_wider": (_I, [_P, _P, _I, _I, _P, _P, _P, _I, _P, _I, _I, _D, _P, _I, _P, _P, _P, _P]),
     "fdet_tile_gather": (_I, [_P, _P, _P, _I, _P, _P, _I, _I, _I, _P, _P]),
     "fdet_tile_merge": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _F, _D, _I, _P, _P, _P, _P]),
 }

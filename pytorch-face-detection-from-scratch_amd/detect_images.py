@@ -6,7 +6,8 @@
 The images under DIR (searched recursively: .jpg .jpeg .png .bmp) are decoded with PIL into a device image bank
 (`bank_from_files`), `tiling.TiledDetector` runs the model on overlapping windows of each image (and on the whole image
 unless --no-whole) and merges the windows' boxes, and FILE receives, per image: its path relative to DIR, the number of
-boxes, then one `x y w h score` line per box in source pixels.
+boxes, then one `x y w h score` line per box in source pixels.  `--pred-dir DIR` additionally writes the per-event directory
+the WIDER protocol's tools read (`DIR/<event>/<image>.txt`, `evaluation_wider.write_wider_pred_dir`).
 """
 import argparse
 import os
@@ -44,6 +45,7 @@ def main(argv=None):
     ap.add_argument("--edge-margin", type=float, default=0.0)
     ap.add_argument("--probability-threshold", type=float, default=0.5)
     ap.add_argument("--iou-threshold", type=float, default=0.5)
+    ap.add_argument("--pred-dir", default=None, help="also write DIR/<event>/<image>.txt, the WIDER protocol's layout")
     ap.add_argument("--batch-images", type=int, default=64, help="source images per detect() call")
     args = ap.parse_args(argv)
     from .datasets.WIDERFace.annotations import bank_from_files
@@ -90,6 +92,9 @@ def main(argv=None):
     rows = torch.cat([torch.nn.functional.pad(r, (0, 0, 0, kmax - r.shape[1])) for r in all_rows])
     counts = torch.cat(all_counts)
     write_wider_results(args.out, names, rows, counts)
+    if args.pred_dir:
+        from .evaluation_wider import write_wider_pred_dir
+        write_wider_pred_dir(args.pred_dir, names, rows, counts)
     print(f"{len(names)} images, {int(counts.sum())} boxes -> {args.out}")
     return {"names": names, "rows": rows, "counts": counts}
 

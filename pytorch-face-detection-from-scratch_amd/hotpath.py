@@ -215,6 +215,71 @@ def eval_match(pred: torch.Tensor, pred_counts: torch.Tensor, gt_rows: torch.Ten
 
 
 # ------------------------------------------------------------------------------------------
+# WIDER Face protocol evaluation (csrc/fdet_eval_wider.hip)
+# ------------------------------------------------------------------------------------------
+EVAL_WIDER_MAX_SUBSETS = 8                                    # FDET_EVAL_WIDER_* of include/fdet.h
+EVAL_WIDER_N_IMAGES, EVAL_WIDER_N_DET, EVAL_WIDER_N_REJECTED, EVAL_WIDER_N_COUNTERS = 0, 1, 2, 3
+
+
+class WiderState:
+    """The accumulators of fdet_eval_wider: `hist` (2,S,n_bins) int32 holding the uint32 bit patterns of the proposal
+    (hist[0]) and hit (hist[1]) histograms, `counters` (S+3,) int64 [kept boxes per subset, images, detections, rejected
+    images]."""
+
+    def __init__(self, n_subsets: int = 3, iou_threshold: float = 0.5, n_bins: int = 1000, device="cuda"):
+        if not 1 <= int(n_subsets) <= EVAL_WIDER_MAX_SUBSETS:
+            raise ValueError(f"eval_wider: {n_subsets} subsets, 1..{EVAL_WIDER_MAX_SUBSETS} are supported")
+        if not 1 <= int(n_bins) <= EVAL_MAX_BINS:
+            raise ValueError(f"eval_wider: n_bins={n_bins}, 1..{EVAL_MAX_BINS} are supported")
+        self.n_subsets, self.n_bins, self.iou_threshold = int(n_subsets), int(n_bins), float(iou_threshold)
+        self.device = torch.device(device)
+        self.hist = torch.zeros(2, self.n_subsets, self.n_bins, dtype=I32, device=self.device)
+        self.counters = torch.zeros(self.n_subsets + EVAL_WIDER_N_COUNTERS, dtype=torch.int64, device=self.device)
+
+    def zero_(self) -> None:
+        self.hist.zero_()
+        self.counters.zero_()
+
+
+def eval_wider(pred: torch.Tensor, pred_counts: torch.Tensor, gt_rows: torch.Tensor, gt_offset: torch.Tensor,
+               gt_subsets: torch.Tensor, state: WiderState, pred_scale: Optional[torch.Tensor] = None,
+               score_norm: Optional[torch.Tensor] = None, max_gt: Optional[int] = None) -> None:
+    """Add one batch to `state` (fdet_eval_wider): pred / pred_counts / gt_rows / gt_offset as for `eval_match`, with ALL
+    boxes of the images in source pixels; gt_subsets (cap,) int32 holding the uint32 subset masks; pred_scale (B,2) fp32
+    (sx, sy) or None; score_norm (2,) float64 [min, max - min] on the device or None.  One launch, no host
+    synchronisation."""
+    if not isinstance(state, WiderState):
+        raise ValueError("eval_wider: state must be a WiderState")
+    if pred.dim() != 3 or pred.shape[2] != 5 or pred.dtype != F32 or pred.shape[0] < 1:
+        raise ValueError(f"eval_wider: pred must be a (B>=1,Kmax,5) float32 tensor, got {tuple(pred.shape)} {pred.dtype}")
+    B, Kmax = int(pred.shape[0]), int(pred.shape[1])
+    if not 1 <= Kmax <= EVAL_MAX_DET:
+        raise ValueError(f"eval_wider: Kmax={Kmax} detections per image, 1..{EVAL_MAX_DET} are supported")
+    if tuple(pred_counts.shape) != (B,) or pred_counts.dtype != I32:
+        raise ValueError(f"eval_wider: pred_counts must be a ({B},) int32 tensor, got {tuple(pred_counts.shape)} {pred_counts.dtype}")
+    if gt_rows.dim() != 2 or gt_rows.shape[1] != 5 or gt_rows.dtype != F32 or gt_rows.shape[0] < 1:
+        raise ValueError(f"eval_wider: gt_rows must be a (cap>=1,5) float32 tensor, got {tuple(gt_rows.shape)} {gt_rows.dtype}")
+    cap = int(gt_rows.shape[0])
+    if tuple(gt_offset.shape) != (B + 1,) or gt_offset.dtype != I32:
+        raise ValueError(f"eval_wider: gt_offset must be a ({B + 1},) int32 tensor, got {tuple(gt_offset.shape)} {gt_offset.dtype}")
+    if tuple(gt_subsets.shape) != (cap,) or gt_subsets.dtype != I32:
+        raise ValueError(f"eval_wider: gt_subsets must be a ({cap},) int32 tensor, got {tuple(gt_subsets.shape)} {gt_subsets.dtype}")
+    if pred_scale is not None and (tuple(pred_scale.shape) != (B, 2) or pred_scale.dtype != F32):
+        raise ValueError(f"eval_wider: pred_scale must be a ({B},2) float32 tensor, got {tuple(pred_scale.shape)} {pred_scale.dtype}")
+    if score_norm is not None and (tuple(score_norm.shape) != (2,) or score_norm.dtype != torch.float64):
+        raise ValueError("eval_wider: score_norm must be a (2,) float64 tensor")
+    max_gt = min(cap, EVAL_MAX_GT) if max_gt is None else int(max_gt)
+    if not 1 <= max_gt <= EVAL_MAX_GT:
+        raise ValueError(f"eval_wider: max_gt={max_gt} boxes per image, 1..{EVAL_MAX_GT} are supported")
+    pred, pred_counts, gt_rows, gt_offset, gt_subsets = (t.contiguous() for t in (pred, pred_counts, gt_rows, gt_offset, gt_subsets))
+    check(lib().fdet_eval_wider(ptr(pred), ptr(pred_counts, I32), B, Kmax,
+                                ptr(None if pred_scale is None else pred_scale.contiguous()), ptr(gt_rows),
+                                ptr(gt_offset, I32), cap, ptr(gt_subsets, I32), state.n_subsets, max_gt, state.iou_threshold,
+                                ptr(score_norm, torch.float64), state.n_bins, ptr(state.hist[0], I32), ptr(state.hist[1], I32),
+                                ptr(state.counters, torch.int64), stream()), "fdet_eval_wider")
+
+
+# ------------------------------------------------------------------------------------------
 # tiled full-resolution detection (csrc/fdet_tiles.hip)
 # ------------------------------------------------------------------------------------------
 TILE_MAX_CANDIDATES = 4864                                   # FDET_TILE_MAX_CANDIDATES of include/fdet.h

@@ -12,6 +12,10 @@ takes a Lightning-layout file ({"state_dict": {"model.<name>": tensor}}) or a ba
 class; without it the freshly initialised model is evaluated.  `--precision 16` runs the convolutions in one bf16 pass.
 `--tiled` adds a second report: the same evaluator numbers from `tiling.TiledDetector` on the UNRESIZED bank (windows of
 `--tile` source pixels with `--overlap`, plus the whole image unless `--no-whole`) against the source-pixel boxes.
+`--wider-gt DIR` (the directory holding wider_face_val.mat and wider_{easy,medium,hard}_val.mat) adds the Easy / Medium /
+Hard AP of the WIDER Face protocol (`evaluation_wider.WiderEvaluator`): the resized pass's detections are taken back to
+source pixels, and with `--tiled` the tiled rows are evaluated too.  `--json` then gains the keys "wider" / "wider_tiled".
+Images are matched to the .mat files by `<event>/<image>`; the synthetic bank's images are called `synthetic/00000`, ...
 """
 import argparse
 import json
@@ -31,6 +35,36 @@ def load_checkpoint(model_setup, path):
     else:
         model_setup.model.load_state_dict(sd)
     model_setup.model.engine.mark_params_dirty()
+
+
+def synthetic_names(n: int):
+    """The names the synthetic bank's images go by in `--wider-gt` files."""
+    return [f"synthetic/{i:05d}" for i in range(n)]
+
+
+class _WithWider:
+    """What `_epoch` takes as its evaluator: feeds the `DetectionEvaluator` exactly as its own `evaluate_batch` does, and
+    the same rows, scaled back to source pixels, to a `WiderEvaluator`.  The batches come in bank order."""
+
+    def __init__(self, ev, wider, subsets, gt, bank, out_hw):
+        self.ev, self.wider, self.subsets, self.gt, self.next = ev, wider, subsets, gt, 0
+        hw = bank.sizes.astype("float32")
+        scale = torch.from_numpy(hw[:, ::-1].copy())                       # (W, H)
+        scale = scale / torch.tensor([float(out_hw[1]), float(out_hw[0])], dtype=torch.float32)
+        self.scale = scale.to(bank.device)
+
+    @torch.no_grad()
+    def evaluate_batch(self, model, y_hat, gt):
+        rows, counts = self.ev.reducer_for(model).forward_batch(y_hat.detach())
+        self.ev.update(rows, counts, gt)
+        idx = list(range(self.next, self.next + int(rows.shape[0])))
+        self.next = idx[-1] + 1
+        self.wider.update(rows, counts, self.subsets.batch(self.gt, idx), scale=self.scale[idx[0]:idx[-1] + 1].contiguous())
+
+
+def print_wider(r, prefix=""):
+    print(f"{prefix}WIDER protocol ({r.n_images} images, {r.n_det} detections, scores normalised by min {r.score_min:.4g} "
+          f"range {r.score_range:.4g}): " + ", ".join(f"{k} AP {r.ap[k]:.4f} ({r.n_faces[k]} faces)" for k in r.subset_names))
 
 
 def main(argv=None):
@@ -54,6 +88,7 @@ def main(argv=None):
     ap.add_argument("--tile", type=int, nargs="*", default=[480])
     ap.add_argument("--overlap", type=float, default=0.25)
     ap.add_argument("--no-whole", action="store_true")
+    ap.add_argument("--wider-gt", default=None, help="directory of the WIDER protocol's four .mat files: report Easy/Medium/Hard AP")
     args = ap.parse_args(argv)
     torch.random.manual_seed(0)
     from . import hotpath as hp
@@ -97,7 +132,15 @@ def main(argv=None):
     val = DeviceBatches(bank, boxes, args.batch_size, default_transform((args.size, args.size)), patches, encoder=encoder,
                         shuffle=False, drop_last=False)
     ev = DetectionEvaluator(iou_thresholds=tuple(args.iou), score_floor=args.score_floor)
-    outs = _epoch(model_setup, val, False, {}, None, ev)
+    wider = None
+    if args.wider_gt:
+        from .datasets.augment import DeviceBoxes
+        from .evaluation_wider import WiderEvaluator, WiderSubsets
+        names = [str(p) for p in paths] if args.wider_root else synthetic_names(len(bank))
+        subsets, wider_boxes = WiderSubsets.from_mat(args.wider_gt, names)
+        wider_gt = DeviceBoxes(wider_boxes, "cuda")
+        wider = _WithWider(ev, WiderEvaluator(subsets.subset_names), subsets, wider_gt, bank, (args.size, args.size))
+    outs = _epoch(model_setup, val, False, {}, None, wider or ev)
     metrics = model_setup.format_metrics(outs, training=False)
     r = ev.compute()
     print(f"iou: {metrics['total_iou']:5.3f}, recall {metrics['total_recall']:5.3f}, precision {metrics['total_precision']:5.3f}, "
@@ -107,16 +150,29 @@ def main(argv=None):
         print(f"AP@{float(t):.2f}: {a:.4f}")
     print(f"best F1 {r.best_f1:.4f} at score threshold {r.best_threshold:.3f}; at the model's threshold "
           f"{model.probability_threshold}: {r.at(model.probability_threshold)}")
-    if args.json:
-        Path(args.json).write_text(json.dumps(r.to_json()))
     out = {"metrics": metrics, "result": r}
+    doc = r.to_json()
+    if wider is not None:
+        out["wider"] = wider.wider.compute()
+        print_wider(out["wider"])
+        doc["wider"] = out["wider"].to_json()
     if args.tiled:
-        out["tiled"] = tiled_report(model, bank, boxes, args)
+        tiled_wider = None
+        if wider is not None:
+            tiled_wider = (WiderEvaluator(subsets.subset_names), subsets, wider_gt)
+        out["tiled"] = tiled_report(model, bank, boxes, args, tiled_wider)
+        if tiled_wider is not None:
+            out["wider_tiled"] = tiled_wider[0].compute()
+            print_wider(out["wider_tiled"], "tiled ")
+            doc["wider_tiled"] = out["wider_tiled"].to_json()
+    if args.json:
+        Path(args.json).write_text(json.dumps(doc))
     return out
 
 
-def tiled_report(model, bank, boxes, args):
-    """The evaluator's numbers from TiledDetector on the unresized bank against the source-pixel boxes."""
+def tiled_report(model, bank, boxes, args, wider=None):
+    """The evaluator's numbers from TiledDetector on the unresized bank against the source-pixel boxes.  `wider`: a
+    (WiderEvaluator, WiderSubsets, DeviceBoxes) triple that is fed the same rows."""
     from .datasets.augment import DeviceBoxes
     from .evaluation import DetectionEvaluator
     from .tiling import TiledDetector, boxes_for
@@ -130,6 +186,8 @@ def tiled_report(model, bank, boxes, args):
         idx = list(range(a, min(a + step, len(bank))))
         rows, counts = det.detect(bank, idx)
         ev.update(rows, counts, boxes_for(gt, idx), max_gt=max(gt.max_per_image, 1))
+        if wider is not None:
+            wider[0].update(rows, counts, wider[1].batch(wider[2], idx))
     r = ev.compute()
     print(f"tiled (tile {list(args.tile)}, overlap {args.overlap}, whole image {not args.no_whole}): {r.n_images} images, "
           f"{r.n_gt} faces, {r.n_det} detections with score >= {args.score_floor}")
