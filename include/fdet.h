@@ -784,6 +784,31 @@ int fdet_tile_merge(const float* rows, const int32_t* counts, const fdet_tile* t
                     int n_images, int T, int K, int Ho, int Wo, const fdet_aug_image* table, float edge_margin,
                     double iou_threshold, int Kout, float* out, int32_t* out_counts, uint64_t* rejected, void* stream);
 
+/* Depthwise-separable residual block (models/SeparableCNN.py:40-51; none of its three convs has a bias):
+ *   a = lrelu(W1 x)   b = lrelu(dw3x3(a), pad 1)   c = W2 b   e = c * drop_scale[n,c] + x   out = maxpool2x2(e) | e
+ * fdet_sepblock_fwd runs the whole block in ONE kernel on fp32 NCHW tensors: both 1x1 convs as bf16x3 GEMMs on the matrix
+ * cores, the depthwise conv and both LeakyReLUs in LDS between them (csrc/fdet_sepblock.hip).
+ *   x [N,F,H,W]; w1_pk / w2_pk: FORWARD panels of fdet_pack_pointwise_weights_bf16x3 (Cout = Cin = F); wd [F,1,3,3];
+ *   drop_scale [N,F] or NULL (eval); pool 1 | 2 (2: even H and W); out [N,F,H/pool,W/pool]
+ *   training: a_save, b_save [N,F,H,W] (both or neither) receive a and b; route [N,F,H/2,W/2] uint8 (pooled training
+ *   passes; else NULL) receives bits 4-5 = index of the window's maximum in scan order (first maximum wins, NaN is a
+ *   maximum) with bits 0-3 set, which makes fdet_pool_route_bwd return unpool(dout) * drop_scale for this block.
+ * Supported: F % 8 == 0, 8 <= F <= 128, any map that has a tiling within the LDS (fdet_sepblock_plan returns 1 and writes
+ * {rows, columns of a tile, bands, column segments, LDS bytes, haloed positions per tile} to out[0..n-1]; launches
+ * nothing).  Everything else returns FDET_EINVAL and computes nothing.
+ * Backward is composed from fdet_pointwise_{dgrad,wgrad}_bf16x3, fdet_mbt_dw_bwd, fdet_pool_route_bwd and
+ *   fdet_sepblock_gate_bwd: out[n,f,p] = g[n,f,p] * drop_scale[n,f] * lrelu'(act[n,f,p])   (act / drop_scale may be NULL:
+ *   factor 1; lrelu' = 1 where act > 0 else slope: act is the POST-activation value, whose sign is the pre-activation's;
+ *   out may alias g).
+ * fdet_sepblock_lrelu: y = lrelu(z) over n floats (the composed forward's activation after the depthwise conv). */
+int fdet_sepblock_plan(int F, int H, int W, int pool, int* out, int n);
+int fdet_sepblock_fwd(const float* x, const void* w1_pk, const float* wd, const void* w2_pk, const float* drop_scale,
+                      float* out, float* a_save, float* b_save, unsigned char* route, int N, int F, int H, int W,
+                      int pool, float slope, void* stream);
+int fdet_sepblock_gate_bwd(const float* g, const float* act, const float* drop_scale, float* out, int N, int F, int P,
+                           float slope, void* stream);
+int fdet_sepblock_lrelu(const float* z, float* y, size_t n, float slope, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

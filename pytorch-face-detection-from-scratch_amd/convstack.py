@@ -38,6 +38,7 @@ class StackGeometry:
     head_k: int
     head_p: int
     pool_mult: int          # pool iff H > pool_mult*S  (PoolResnet.py:41: 2, Resnet.py:38: 1)
+    strict_grid: bool = True   # False: the head's grid may differ from S (models/SeparableCNN.py fixes S = 16 and returns what comes)
 
     def levels(self):
         """[(H_in, pool)] per block and the stem output size."""
@@ -53,10 +54,12 @@ class StackGeometry:
             out.append((h, pool))
             h //= pool
         s_out = h + 2 * self.head_p - self.head_k + 1
-        if s_out != self.S:
+        if s_out != self.S and self.strict_grid:
             # the reference only fails later, in yolo_loss, with a shape mismatch
             raise ValueError(f"input {self.H}x{self.W} with this stem/head reaches a {s_out}x{s_out} grid, "
                              f"not num_of_patches={self.S}")
+        if s_out <= 0:
+            raise ValueError(f"input {self.H}x{self.W} with this stem/head leaves no output grid")
         return h0, out
 
 

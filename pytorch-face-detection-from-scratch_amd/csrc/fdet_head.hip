@@ -257,13 +257,16 @@ extern "C" int fdet_head_fwd(const float* x, const float* drop_scale, const floa
   HeadGeo g;
   const int So = H + 2 * pad - k + 1, Wo = W + 2 * pad - k + 1;
   FDET_REQUIRE(So > 0 && Wo > 0 && So * Wo <= 4096, "head_fwd: unsupported output size %dx%d", So, Wo);
-  FDET_REQUIRE(k == 6 || k == 3, "head_fwd: kernel size %d not built (6 and 3 are)", k);
+  FDET_REQUIRE(k == 6 || k == 3 || k == 1, "head_fwd: kernel size %d not built (6, 3 and 1 are)", k);
   const size_t part = (size_t)16 * 5 * 64;
   FDET_REQUIRE(head_geo(F, H, W, k, pad, g, part), "head_fwd: activation %dx%d too large for LDS staging", H, W);
   const size_t lds = ((size_t)g.FC * g.HP * g.WP + part) * 4;
   if (k == 6) {
     if (lds > 64 * 1024) { if (int rc_ = set_lds_attr((const void*)k_head_fwd<6>, (size_t)(lds), __func__)) return rc_; }
     hipLaunchKernelGGL(k_head_fwd<6>, dim3(N), dim3(HT), lds, (hipStream_t)stream, x, drop_scale, w, bias, y, g);
+  } else if (k == 1) {                                   // models/SeparableCNN.py with output_kernel_size=1 (a 16x16 map)
+    if (lds > 64 * 1024) { if (int rc_ = set_lds_attr((const void*)k_head_fwd<1>, (size_t)(lds), __func__)) return rc_; }
+    hipLaunchKernelGGL(k_head_fwd<1>, dim3(N), dim3(HT), lds, (hipStream_t)stream, x, drop_scale, w, bias, y, g);
   } else {
     if (lds > 64 * 1024) { if (int rc_ = set_lds_attr((const void*)k_head_fwd<3>, (size_t)(lds), __func__)) return rc_; }
     hipLaunchKernelGGL(k_head_fwd<3>, dim3(N), dim3(HT), lds, (hipStream_t)stream, x, drop_scale, w, bias, y, g);
@@ -290,7 +293,7 @@ extern "C" int fdet_head_bwd(const float* x, const float* drop_scale, const floa
   const size_t extra = (((size_t)5 * (So + 2 * km1) * (Wo + 2 * km1) + 3) & ~(size_t)3) + (size_t)So * Wo * 8;
   FDET_REQUIRE(head_geo(F, H, W, k, pad, g, extra), "head_bwd: activation %dx%d too large for LDS staging", H, W);
   const size_t lds = ((((size_t)g.FC * g.HP * g.WP + 3) & ~(size_t)3) + extra) * 4;
-  FDET_REQUIRE(k == 6 || k == 3, "head_bwd: kernel size %d not built (6 and 3 are)", k);
+  FDET_REQUIRE(k == 6 || k == 3 || k == 1, "head_bwd: kernel size %d not built (6, 3 and 1 are)", k);
   const int kk = k * k;
   float* wsW = (float*)ws;
   float* wsb = wsW + (size_t)N * 5 * F * kk;
@@ -300,6 +303,9 @@ extern "C" int fdet_head_bwd(const float* x, const float* drop_scale, const floa
   if (k == 6) {
     if (lds > 64 * 1024) { if (int rc_ = set_lds_attr((const void*)k_head_bwd<6>, (size_t)(lds), __func__)) return rc_; }
     hipLaunchKernelGGL(k_head_bwd<6>, dim3(N), dim3(HT), lds, st, x, drop_scale, wT, y, dy, dx, wsW, wsb, g);
+  } else if (k == 1) {
+    if (lds > 64 * 1024) { if (int rc_ = set_lds_attr((const void*)k_head_bwd<1>, (size_t)(lds), __func__)) return rc_; }
+    hipLaunchKernelGGL(k_head_bwd<1>, dim3(N), dim3(HT), lds, st, x, drop_scale, wT, y, dy, dx, wsW, wsb, g);
   } else {
     if (lds > 64 * 1024) { if (int rc_ = set_lds_attr((const void*)k_head_bwd<3>, (size_t)(lds), __func__)) return rc_; }
     hipLaunchKernelGGL(k_head_bwd<3>, dim3(N), dim3(HT), lds, st, x, drop_scale, wT, y, dy, dx, wsW, wsb, g);

@@ -31,9 +31,9 @@ def write_wider_results(path, names, rows, counts) -> None:
 
 def main(argv=None):
     ap = argparse.ArgumentParser()
-    ap.add_argument("--model", choices=("poolresnet", "resnet", "ssd"), default="poolresnet")
-    ap.add_argument("--filters", type=int, default=None, help="default: 128 (poolresnet), 64 (resnet), 16 (ssd)")
-    ap.add_argument("--patches", type=int, default=None, help="default: 10 (poolresnet), 15 (resnet)")
+    ap.add_argument("--model", choices=("poolresnet", "resnet", "separablecnn", "ssd"), default="poolresnet")
+    ap.add_argument("--filters", type=int, default=None, help="default: 128 (poolresnet, separablecnn), 64 (resnet), 16 (ssd)")
+    ap.add_argument("--patches", type=int, default=None, help="default: 10 (poolresnet), 15 (resnet); separablecnn fixes 16")
     ap.add_argument("--size", type=int, default=480)
     ap.add_argument("--precision", type=int, choices=(32, 16), default=32)
     ap.add_argument("--checkpoint", default=None)
@@ -63,6 +63,9 @@ def main(argv=None):
             from .models.PoolResnet import PoolResnet
             model = PoolResnet(filters=args.filters or 128, input_shape=shape, num_of_patches=args.patches or 10,
                                num_of_residual_blocks=10, **kw).cuda()
+        elif args.model == "separablecnn":
+            from .models.SeparableCNN import SeparableCNN
+            model = SeparableCNN(filters=args.filters or 128, input_shape=shape, **SeparableCNN.coherent_head(args.size), **kw).cuda()
         else:
             from .models.Resnet import Resnet
             model = Resnet(filters=args.filters or 64, input_shape=shape, num_of_patches=args.patches or 15, **kw).cuda()

@@ -100,8 +100,8 @@ class ModelMeta(_Base):
         G = {n: sp.view(sp.grad, i) for i, n in enumerate(names)}
         if self._reducer is None or self._reducer.flat.data_ptr() != sp.grad.data_ptr():
             split_block = min(2, len(model.residual_blocks))
-            split = sp.offsets[names.index(f"residual_blocks.{split_block}.conv1.weight")] \
-                if split_block < len(model.residual_blocks) else sp.offsets[names.index("out.weight")]
+            first = next((i for i, n in enumerate(names) if n.startswith(f"residual_blocks.{split_block}.")), names.index("out.weight"))
+            split = sp.offsets[first]
             self._reducer = GradBucketReducer(sp.grad, split)
             self._split_block = split_block
             if self._reducer.enabled:

@@ -69,9 +69,9 @@ def print_wider(r, prefix=""):
 
 def main(argv=None):
     ap = argparse.ArgumentParser()
-    ap.add_argument("--model", choices=("poolresnet", "resnet", "ssd"), default="poolresnet")
-    ap.add_argument("--filters", type=int, default=None, help="default: 128 (poolresnet), 64 (resnet), 16 (ssd)")
-    ap.add_argument("--patches", type=int, default=None, help="default: 10 (poolresnet), 15 (resnet)")
+    ap.add_argument("--model", choices=("poolresnet", "resnet", "separablecnn", "ssd"), default="poolresnet")
+    ap.add_argument("--filters", type=int, default=None, help="default: 128 (poolresnet, separablecnn), 64 (resnet), 16 (ssd)")
+    ap.add_argument("--patches", type=int, default=None, help="default: 10 (poolresnet), 15 (resnet); separablecnn fixes 16")
     ap.add_argument("--size", type=int, default=480)
     ap.add_argument("--batch-size", type=int, default=8)
     ap.add_argument("--precision", type=int, choices=(32, 16), default=32)
@@ -107,6 +107,10 @@ def main(argv=None):
             from .models.PoolResnet import PoolResnet
             patches = args.patches or 10
             model = PoolResnet(filters=args.filters or 128, input_shape=shape, num_of_patches=patches, num_of_residual_blocks=10).cuda()
+        elif args.model == "separablecnn":
+            from .models.SeparableCNN import SeparableCNN
+            patches = 16                                   # fixed by the model; coherent_head picks the head that reaches it
+            model = SeparableCNN(filters=args.filters or 128, input_shape=shape, **SeparableCNN.coherent_head(args.size)).cuda()
         else:
             from .models.Resnet import Resnet
             patches = args.patches or 15

@@ -286,7 +286,11 @@ def to_torchscript(model, file_path=None) -> torch.jit.ScriptModule:
     `LightningModule.to_torchscript(file_path)` contract, train_model.py:61)."""
     from .models.MobilenetV3Backbone import MobilenetV3Backbone
     from .models.SSD import SSD
-    wrapper = ScriptableMobilenet(model) if isinstance(model, MobilenetV3Backbone) else (ScriptableSSD(model) if isinstance(model, SSD) else ScriptableDetector(model))
+    from .models.SeparableCNN import SeparableCNN
+    if isinstance(model, SeparableCNN):                  # every route here: the model's, ModelMeta's and trainer.fit's
+        raise hp.N.FdetError("TorchScript export is not built for SeparableCNN (the scripted twin covers PoolResnet / Resnet / SSD / "
+                             "MobilenetV3Backbone); keep the state dict instead")
+    wrapper =ScriptableMobilenet(model) if isinstance(model, MobilenetV3Backbone) else (ScriptableSSD(model) if isinstance(model, SSD) else ScriptableDetector(model))
     scripted = torch.jit.script(wrapper.eval())
     if file_path is not None:
         torch.jit.save(scripted, str(file_path))

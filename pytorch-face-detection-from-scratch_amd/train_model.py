@@ -37,8 +37,9 @@ def synthetic_loader(n_batches, batch_size, size, S, seed):
 
 def main(argv=None):
     ap = argparse.ArgumentParser()
+    ap.add_argument("--model", choices=("poolresnet", "separablecnn"), default="poolresnet")
     ap.add_argument("--filters", type=int, default=128)          # train_model.py:17
-    ap.add_argument("--patches", type=int, default=10)
+    ap.add_argument("--patches", type=int, default=10, help="poolresnet only; separablecnn fixes its grid at 16")
     ap.add_argument("--size", type=int, default=480)
     ap.add_argument("--lr", type=float, default=1e-4)
     ap.add_argument("--epochs", type=int, default=70)
@@ -54,12 +55,22 @@ def main(argv=None):
     from .models import ModelMeta
     from .models.PoolResnet import PoolResnet
     from .trainer import fit
-    name = f"custom_poolresnet_{args.filters}_{args.patches}x{args.patches}_{args.size}x{args.size}"
+    if args.model == "separablecnn":
+        args.patches = 16                                        # fixed by the model (models/SeparableCNN.py:71)
+        if args.save is not None:                                # refuse before training, not after the last epoch
+            ap.error("--save writes TorchScript, which is not built for --model separablecnn")
+    name = f"custom_{args.model}_{args.filters}_{args.patches}x{args.patches}_{args.size}x{args.size}"
     log_path = Path(f"logs/out_{name}.log")
     log_path.parent.mkdir(parents=True, exist_ok=True)
     log_path.unlink(missing_ok=True)
-    model = PoolResnet(filters=args.filters, input_shape=(3, args.size, args.size), num_of_patches=args.patches,
-                       num_of_residual_blocks=10).cuda()
+    if args.model == "separablecnn":
+        # the head that gives the 16x16 grid num_of_patches=16 decodes: k=6, p=3 at 480x480, k=1, p=0 at 512x512
+        from .models.SeparableCNN import SeparableCNN
+        model = SeparableCNN(filters=args.filters, input_shape=(3, args.size, args.size), num_of_residual_blocks=10,
+                             **SeparableCNN.coherent_head(args.size)).cuda()
+    else:
+        model = PoolResnet(filters=args.filters, input_shape=(3, args.size, args.size), num_of_patches=args.patches,
+                           num_of_residual_blocks=10).cuda()
     if args.precision == 16:
         model.engine.set_precision("bf16")
     model.summary()
