@@ -809,6 +809,76 @@ int fdet_sepblock_gate_bwd(const float* g, const float* act, const float* drop_s
                            float slope, void* stream);
 int fdet_sepblock_lrelu(const float* z, float* y, size_t n, float slope, void* stream);
 
+/* ---- baseline JPEG decode into the device image bank (csrc/fdet_jpeg.hip) ----------------------------
+ * The hybrid split of GPU JPEG decoders: the host does the serial work (marker parsing, Huffman decoding), the device
+ * the arithmetic (dequantisation, 8x8 inverse DCT, chroma upsampling, colour conversion) and writes HWC uint8 RGB
+ * straight into the bank.  Every device step is integer arithmetic in libjpeg, so the result is byte-identical to
+ * libjpeg-turbo's default decode (accurate-integer "islow" IDCT, "fancy" upsampling, 16-bit fixed-point YCbCr -> RGB), which
+ * is what PIL's Image.open(...).convert("RGB") returns.  Replaces the PIL decode behind datasets/WIDERFace/annotations.py
+ * bank_from_files (the reference decodes with cv2.imread in DataLoader workers, datasets/WIDERFace/dataset.py).
+ *
+ * Supported: 8-bit baseline sequential DCT (SOF0; SOF1 with 8-bit samples), Huffman coding, ONE interleaved scan; 1 component
+ * (grey: R = G = B) or 3 components YCbCr with luma sampling 1x1, 2x1 or 2x2 and chroma 1x1; 8- or 16-bit DQT entries;
+ * optional DRI; APPn / COM skipped.  Everything else that is a well-formed JPEG (progressive, arithmetic, lossless, 12-bit,
+ * CMYK / 4 components, an Adobe APP14 segment declaring RGB or components named R G B, multi-scan baseline, other sampling
+ * ratios) returns FDET_JPEG_UNSUPPORTED so that a caller can fall back to another decoder; a truncated or corrupt stream
+ * returns FDET_JPEG_ECORRUPT.
+ *
+ * The two host functions are plain C++ without a HIP call or mutable global state: any number of threads may call them at
+ * once.  `bytes` is HOST memory here, as are `out` and `coef`. */
+#define FDET_JPEG_UNSUPPORTED (-4) /* a JPEG outside the supported subset (fall back to another decoder) */
+#define FDET_JPEG_ECORRUPT (-5)    /* not a JPEG, truncated or corrupt */
+
+typedef struct fdet_jpeg_info_t {
+  int32_t width, height, ncomp;    /* ncomp 1 | 3 */
+  int32_t restart_interval;        /* MCUs between RSTn markers, 0 = none */
+  int32_t hs[3], vs[3];            /* sampling factors per component (a single component is reported as 1x1) */
+  int32_t blocks_w[3], blocks_h[3];/* 8x8 block grid per component INCLUDING the padding blocks of the last MCUs */
+  int32_t mcus_x, mcus_y;
+  int64_t coef_count;              /* int16 coefficients of the image = 64 * sum of blocks_w * blocks_h */
+  uint16_t qt[3][64];              /* dequantisation table per component, natural (row-major) order */
+} fdet_jpeg_info_t;                /* 464 bytes */
+
+/* Parse the markers up to the first SOS.  Nothing of `out` is meaningful unless 0 is returned. */
+int fdet_jpeg_info(const uint8_t* bytes, size_t n, fdet_jpeg_info_t* out);
+
+/* Huffman-decode the scan (DC prediction, byte stuffing, restart markers) into quantised coefficients in natural,
+ * de-zigzagged order: component c is one [blocks_h[c]][blocks_w[c]][64] int16 plane, planes in component order, padding
+ * blocks included (they are coded in the stream).  capacity = int16 elements at `coef`; fewer than coef_count returns
+ * FDET_EWORKSPACE.  No read goes past bytes + n and no write past coef + capacity, whatever the stream holds. */
+int fdet_jpeg_entropy_decode(const uint8_t* bytes, size_t n, int16_t* coef, size_t capacity);
+
+/* One image of a reconstruct call.  Offsets are the caller's choice (the planes of different images must not overlap). */
+typedef struct fdet_jpeg_desc {
+  int64_t bank_offset;             /* byte offset of pixel (0,0) in the bank; the image takes height * width * 3 bytes */
+  int64_t coef_offset[3];          /* first int16 of component c's plane in `coef` (multiple of 8: 16-byte loads) */
+  int64_t plane_offset[3];         /* first byte of component c's sample plane [blocks_h*8][blocks_w*8] in the workspace
+                                      (multiple of 8) */
+  int32_t width, height, ncomp;
+  int32_t hs, vs;                  /* luma sampling 1x1 | 2x1 | 2x2 (chroma is 1x1); 1x1 for ncomp = 1 */
+  int32_t blocks_w[3], blocks_h[3];
+  int32_t reserved;
+  uint16_t qt[3][64];
+} fdet_jpeg_desc;                  /* 488 bytes */
+
+/* coef (DEVICE, coef_count int16) -> RGB in the bank, two kernels on `stream`:
+ *   1. dequantise + libjpeg's jpeg_idct_islow (13-bit constants, 2 pass-1 bits), level shift and range limit through the
+ *      masked limit table (index & 1023: 0..127 -> +128, 128..511 -> 255, 512..895 -> 0, 896..1023 -> -896), one wave per eight
+ *      blocks, into the uint8 sample planes of `workspace`.  32-bit arithmetic: exact whenever the dequantised
+ *      coefficients fit in 16 bits, which is also the domain of libjpeg-turbo's SIMD IDCT
+ *   2. chroma upsampling + colour conversion + crop to width x height.  A chroma plane of downsampled width dw =
+ *      ceil(width / hs) > 2 takes the "fancy" triangle filter: 2x1 out[2i] = (3 in[i] + in[i-1] + 1) >> 2, out[2i+1] =
+ *      (3 in[i] + in[i+1] + 2) >> 2; 2x2 the same on column sums 3 * near row + far row with (… + 8) >> 4 and (… + 7) >> 4;
+ *      columns clamp to 0..dw-1 and the far row to 0..ceil(height / vs)-1 (edge replication; padding samples are read
+ *      only where they lie inside those bounds).  dw <= 2 replicates, as the library does.  R = Y + ((91881 Cr' + 32768) >> 16),
+ *      G = Y + ((-22554 Cb' - 46802 Cr' + 32768) >> 16), B = Y + ((116130 Cb' + 32768) >> 16), clamped, with Cb' = Cb - 128.
+ * descs (DEVICE) / h_descs (HOST copy, validated before anything is enqueued): blocks that do not cover the image,
+ * sampling outside the supported set, a misaligned offset or a plane / coefficient / bank range outside the given sizes
+ * return FDET_EINVAL.  bank must be 16-byte aligned.  n_images <= 65535. */
+int fdet_jpeg_reconstruct(const int16_t* coef, size_t coef_count, const fdet_jpeg_desc* descs, const fdet_jpeg_desc* h_descs,
+                          int n_images, uint8_t* workspace, size_t workspace_bytes, uint8_t* bank, size_t bank_bytes,
+                          void* stream);
+
 #ifdef __cplusplus
 }
 #endif

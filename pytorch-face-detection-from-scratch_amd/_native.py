@@ -174,6 +174,9 @@ SIGNATURES = {
     "fdet_sepblock_fwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _P]),
     "fdet_sepblock_gate_bwd": (_I, [_P, _P, _P, _P, _I, _I, _I, _F, _P]),
     "fdet_sepblock_lrelu": (_I, [_P, _P, _SZ, _F, _P]),
+    "fdet_jpeg_info": (_I, [_P, _SZ, _P]),
+    "fdet_jpeg_entropy_decode": (_I, [_P, _SZ, _P, _SZ]),
+    "fdet_jpeg_reconstruct": (_I, [_P, _SZ, _P, _P, _I, _P, _SZ, _P, _SZ, _P]),
 }
 
 

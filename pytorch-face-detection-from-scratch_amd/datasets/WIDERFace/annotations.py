@@ -5,7 +5,8 @@
 line, then one `x y w h blur expression illumination invalid occlusion pose` line per face, of which the first four
 numbers are kept as a row [1, x, y, w, h].  An image without faces carries the placeholder line `0 0 0 0 0 0 0 0 0 0`,
 which the reference keeps as a box of zero size; `keep_placeholder=False` drops it (what an evaluation wants: a box of
-zero area can never be matched).  `bank_from_files` decodes the images with PIL into a `DeviceImageBank`.
+zero area can never be matched).  `bank_from_files` decodes the images into a `DeviceImageBank`: with PIL (the default) or,
+`decoder="device"`, with the hybrid JPEG decoder of datasets/jpeg.py, which gives the same bytes.
 """
 from concurrent.futures import ThreadPoolExecutor
 from pathlib import Path
@@ -58,9 +59,16 @@ def _decode(path) -> np.ndarray:
         return np.ascontiguousarray(np.asarray(im.convert("RGB"), dtype=np.uint8))
 
 
-def bank_from_files(paths: Sequence, device, workers: int = 16):
-    """Decode `paths` with PIL on at most 16 threads into a DeviceImageBank on `device` (RGB, HWC uint8).  A once-per-run
-    cost: the bank stays resident."""
+def bank_from_files(paths: Sequence, device, workers: int = 16, decoder: str = "pil"):
+    """Decode `paths` on at most 16 threads into a DeviceImageBank on `device` (RGB, HWC uint8).  A once-per-run cost: the
+    bank stays resident.  decoder="pil" decodes on the host with PIL; decoder="device" Huffman-decodes on the host and
+    reconstructs on the device (datasets/jpeg.py DeviceJpegDecoder; files outside its JPEG subset still go through PIL).
+    Both give the same bank, byte for byte."""
+    if decoder not in ("pil", "device"):
+        raise ValueError(f"decoder must be 'pil' or 'device', got {decoder!r}")
+    if decoder == "device":
+        from ..jpeg import DeviceJpegDecoder
+        return DeviceJpegDecoder(device, workers=workers).decode_files(paths)
     from ..augment import DeviceImageBank
     workers = max(1, min(16, int(workers), len(paths) or 1))
     with ThreadPoolExecutor(max_workers=workers) as ex:

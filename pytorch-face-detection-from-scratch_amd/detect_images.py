@@ -4,7 +4,7 @@
         [--tile 480 --overlap 0.25 --no-whole --edge-margin 0 --probability-threshold P --iou-threshold T --precision 16]
 
 The images under DIR (searched recursively: .jpg .jpeg .png .bmp) are decoded with PIL into a device image bank
-(`bank_from_files`), `tiling.TiledDetector` runs the model on overlapping windows of each image (and on the whole image
+(`bank_from_files`; `--device-jpeg`: baseline JPEGs are reconstructed on the device instead, with the same bytes), `tiling.TiledDetector` runs the model on overlapping windows of each image (and on the whole image
 unless --no-whole) and merges the windows' boxes, and FILE receives, per image: its path relative to DIR, the number of
 boxes, then one `x y w h score` line per box in source pixels.  `--pred-dir DIR` additionally writes the per-event directory
 the WIDER protocol's tools read (`DIR/<event>/<image>.txt`, `evaluation_wider.write_wider_pred_dir`).
@@ -47,6 +47,8 @@ def main(argv=None):
     ap.add_argument("--iou-threshold", type=float, default=0.5)
     ap.add_argument("--pred-dir", default=None, help="also write DIR/<event>/<image>.txt, the WIDER protocol's layout")
     ap.add_argument("--batch-images", type=int, default=64, help="source images per detect() call")
+    ap.add_argument("--device-jpeg", action="store_true",
+                    help="decode baseline JPEGs with the device decoder (datasets/jpeg.py) instead of PIL; same bytes")
     args = ap.parse_args(argv)
     from .datasets.WIDERFace.annotations import bank_from_files
     from .run_validation_epoch import load_checkpoint
@@ -85,7 +87,7 @@ def main(argv=None):
     names, all_rows, all_counts = [], [], []
     for a in range(0, len(paths), args.batch_images):
         chunk = paths[a:a + args.batch_images]
-        bank = bank_from_files(chunk, "cuda")
+        bank = bank_from_files(chunk, "cuda", decoder="device" if args.device_jpeg else "pil")
         rows, counts = det.detect(bank, range(len(bank)))
         kmax = max(int(counts.max()), 1)
         all_rows.append(rows[:, :kmax].cpu())

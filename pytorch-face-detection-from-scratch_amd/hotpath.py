@@ -341,6 +341,61 @@ def tile_merge(rows: torch.Tensor, counts: torch.Tensor, d_tiles: torch.Tensor, 
 
 
 # ------------------------------------------------------------------------------------------
+# Baseline JPEG decode (csrc/fdet_jpeg.hip; datasets/jpeg.py drives these)
+# ------------------------------------------------------------------------------------------
+JPEG_UNSUPPORTED, JPEG_ECORRUPT = -4, -5                     # FDET_JPEG_* of include/fdet.h
+
+
+def _jpeg_dtypes():
+    import numpy as np
+    info = np.dtype([("width", "<i4"), ("height", "<i4"), ("ncomp", "<i4"), ("restart_interval", "<i4"), ("hs", "<i4", (3,)),
+                     ("vs", "<i4", (3,)), ("blocks_w", "<i4", (3,)), ("blocks_h", "<i4", (3,)), ("mcus_x", "<i4"),
+                     ("mcus_y", "<i4"), ("coef_count", "<i8"), ("qt", "<u2", (3, 64))], align=True)          # fdet_jpeg_info_t
+    desc = np.dtype([("bank_offset", "<i8"), ("coef_offset", "<i8", (3,)), ("plane_offset", "<i8", (3,)), ("width", "<i4"),
+                     ("height", "<i4"), ("ncomp", "<i4"), ("hs", "<i4"), ("vs", "<i4"), ("blocks_w", "<i4", (3,)),
+                     ("blocks_h", "<i4", (3,)), ("reserved", "<i4"), ("qt", "<u2", (3, 64))], align=True)    # fdet_jpeg_desc
+    assert info.itemsize == 464 and desc.itemsize == 488
+    return info, desc
+
+
+JPEG_INFO_DTYPE, JPEG_DESC_DTYPE = _jpeg_dtypes()
+
+
+def jpeg_info(data: bytes):
+    """fdet_jpeg_info on the bytes of one file (host only, thread-safe) -> (rc, info record | None, message).  rc 0: a
+    baseline JPEG of the supported subset; JPEG_UNSUPPORTED: a JPEG another decoder must take; JPEG_ECORRUPT / -1: broken."""
+    import numpy as np
+    L = lib()
+    out = np.zeros(1, dtype=JPEG_INFO_DTYPE)
+    rc = L.fdet_jpeg_info(data, len(data), out.ctypes.data)
+    if rc != 0:
+        return rc, None, L.fdet_last_error().decode(errors="replace")       # the message is thread-local: read it here
+    return 0, out[0], ""
+
+
+def jpeg_entropy_decode(data: bytes, coef_ptr: int, capacity: int):
+    """fdet_jpeg_entropy_decode (host only, thread-safe; ctypes releases the GIL): the scan of `data` -> `capacity` int16
+    coefficients at host address `coef_ptr`.  -> (rc, message)."""
+    L = lib()
+    rc = L.fdet_jpeg_entropy_decode(data, len(data), coef_ptr, capacity)
+    return rc, ("" if rc == 0 else L.fdet_last_error().decode(errors="replace"))
+
+
+def jpeg_reconstruct(coef: torch.Tensor, d_descs: torch.Tensor, h_descs, workspace: torch.Tensor, bank_data: torch.Tensor) -> None:
+    """fdet_jpeg_reconstruct: device int16 coefficients + one fdet_jpeg_desc per image (device uint8 view and the numpy record
+    array) -> RGB written into the bank's byte buffer, on the current stream.  Bad descriptors raise before anything runs."""
+    import numpy as np
+    if not isinstance(h_descs, np.ndarray) or h_descs.dtype != JPEG_DESC_DTYPE or h_descs.ndim != 1 or not h_descs.flags.c_contiguous:
+        raise ValueError("jpeg_reconstruct: h_descs must be a contiguous (n,) record array of JPEG_DESC_DTYPE")
+    if d_descs.numel() != len(h_descs) * JPEG_DESC_DTYPE.itemsize:
+        raise ValueError("jpeg_reconstruct: device and host copies of the descriptors differ in size")
+    U8 = torch.uint8
+    check(lib().fdet_jpeg_reconstruct(ptr(coef, torch.int16), coef.numel(), ptr(d_descs, U8), h_descs.ctypes.data, len(h_descs),
+                                      ptr(workspace, U8), workspace.numel(), ptr(bank_data, U8), bank_data.numel(), stream()),
+          "fdet_jpeg_reconstruct")
+
+
+# ------------------------------------------------------------------------------------------
 # SSD detection math (datasets/WIDERFace/dataset_ssd.py, losses/SSDLoss.py, datasets/utils.py:8-92)
 # ------------------------------------------------------------------------------------------
 SSD_PATCH_SIZES = (60, 30, 15, 7)

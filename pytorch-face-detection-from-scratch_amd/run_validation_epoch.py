@@ -89,6 +89,8 @@ def main(argv=None):
     ap.add_argument("--overlap", type=float, default=0.25)
     ap.add_argument("--no-whole", action="store_true")
     ap.add_argument("--wider-gt", default=None, help="directory of the WIDER protocol's four .mat files: report Easy/Medium/Hard AP")
+    ap.add_argument("--device-jpeg", action="store_true",
+                    help="--wider-root: decode baseline JPEGs with the device decoder (datasets/jpeg.py) instead of PIL; same bytes")
     args = ap.parse_args(argv)
     torch.random.manual_seed(0)
     from . import hotpath as hp
@@ -128,7 +130,7 @@ def main(argv=None):
         paths, boxes = read_wider_annotations(args.wider_root, args.split, max_faces=args.max_faces, keep_placeholder=False)
         if args.max_images:
             paths, boxes = paths[:args.max_images], boxes[:args.max_images]
-        bank = bank_from_files(paths, "cuda")
+        bank = bank_from_files(paths, "cuda", decoder="device" if args.device_jpeg else "pil")
     else:
         bank, boxes = synthetic_bank(args.synthetic_images, "cuda", seed=2)
     if len(bank) < args.batch_size:

@@ -14,6 +14,11 @@ own training recipe.  `--precision 32` (default) keeps the fp32-grade bf16x3 ari
 `--augment` trains instead on a device-resident bank of seeded synthetic images of WIDER-like ragged sizes through the
 reference's training_transform (datamodule.py:105-124) run on the GPU (datasets/augment.py); validation uses
 default_transform (Resize alone).
+
+`--wider-root DIR` trains on the real dataset the same way: the train and val splits under DIR (wider_face_split/ and
+WIDER_{train,val}/images, the reference's filter of at most two faces per image) are decoded once into two device image
+banks and go through the same training_transform / default_transform.  `--device-jpeg` decodes them with the device
+JPEG decoder (datasets/jpeg.py) instead of PIL; the banks are the same bytes.
 """
 import argparse
 from pathlib import Path
@@ -35,7 +40,7 @@ def synthetic_loader(n_batches, batch_size, size, S, seed):
     return out
 
 
-def main(argv=None):
+def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser()
     ap.add_argument("--model", choices=("poolresnet", "separablecnn"), default="poolresnet")
     ap.add_argument("--filters", type=int, default=128)          # train_model.py:17
@@ -50,6 +55,24 @@ def main(argv=None):
     ap.add_argument("--precision", type=int, choices=(32, 16), default=32)   # train_model.py:50 Trainer(precision=...)
     ap.add_argument("--augment", action="store_true", help="on-device training_transform over a synthetic image bank")
     ap.add_argument("--bank-size", type=int, default=None, help="--augment: images in the bank (default: one epoch's worth)")
+    ap.add_argument("--wider-root", default=None, help="train on the WIDER Face tree under DIR (train and val splits)")
+    ap.add_argument("--device-jpeg", action="store_true", help="--wider-root: decode the JPEGs with the device decoder, not PIL")
+    return ap
+
+
+def wider_batches(root, split, batch_size, transform, patches, decoder, **kw):
+    """DeviceBatches over one split of a WIDER Face tree, filtered as the reference filters it (at most two faces)."""
+    from .datasets.augment import DeviceBatches
+    from .datasets.WIDERFace.annotations import bank_from_files, read_wider_annotations
+    paths, boxes = read_wider_annotations(root, split, max_faces=2)
+    if len(paths) < batch_size:
+        raise SystemExit(f"{root}: the {split} split holds {len(paths)} images with at most two faces, a batch needs {batch_size}")
+    bank = bank_from_files(paths, "cuda", decoder=decoder)
+    return DeviceBatches(bank, boxes, batch_size, transform, patches, **kw)
+
+
+def main(argv=None):
+    ap = build_parser()
     args = ap.parse_args(argv)
     torch.random.manual_seed(0)                                  # train_model.py:13
     from .models import ModelMeta
@@ -75,7 +98,15 @@ def main(argv=None):
         model.engine.set_precision("bf16")
     model.summary()
     model_setup = ModelMeta(model=model, lr=args.lr, log_path=log_path)
-    if args.augment:
+    if args.wider_root:
+        from .datasets.augment import default_transform, training_transform
+        shape = (args.size, args.size)
+        decoder = "device" if args.device_jpeg else "pil"
+        train = wider_batches(args.wider_root, "train", args.batch_size, training_transform(shape, seed=1), args.patches, decoder,
+                              seed=1)
+        val = wider_batches(args.wider_root, "val", args.batch_size, default_transform(shape), args.patches, decoder,
+                            shuffle=False)
+    elif args.augment:
         from .datasets.augment import DeviceBatches, default_transform, synthetic_bank, training_transform
         shape = (args.size, args.size)
         n_train = args.bank_size or args.steps_per_epoch * args.batch_size
