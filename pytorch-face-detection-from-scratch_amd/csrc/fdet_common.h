@@ -40,6 +40,16 @@ inline int set_lds_attr(const void* kern, size_t lds, const char* what) {
 // environment switch read once per call site (launch paths are hot on the launch-bound demo path)
 #define FDET_ENV_ONCE(NAME) ([]() -> const char* { static const char* v_ = getenv(NAME); return v_; }())
 
+// compute units of the current device, asked once per process (256 where the query fails)
+inline int num_cus() {
+  static int ncu = 0;
+  if (ncu == 0) {
+    int dev = 0, v = 0;
+    ncu = (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) ? v : 256;
+  }
+  return ncu;
+}
+
 constexpr int WAVE = 64;
 
 __device__ __forceinline__ float wave_sum(float v) {

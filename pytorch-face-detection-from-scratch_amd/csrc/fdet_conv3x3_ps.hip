@@ -644,15 +644,6 @@ k_conv3x3_ps(const PsConvArgs p) {
 #undef PS_ROWOFF
 }
 
-int ps_num_cus() {
-  static int ncu = 0;
-  if (ncu == 0) {
-    int dev = 0, v = 0;
-    ncu = (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) ? v : 256;
-  }
-  return ncu;
-}
-
 // One translation unit per (mode, row width, precision): the woven kernels take a minute or more each to compile, so the
 // Makefile builds this source 17 times -- -DPS_TU=<8*P16 + 2*mode + (WP == 64)> emits ONE kernel instantiation behind
 // fdet_ps_launch_<n>(), and the plain build keeps the host logic and the C-ABI.
@@ -761,7 +752,7 @@ int run_ps(int mode, const void* x, const void* wpk, const float* bias, const vo
   p.magic_hp = magic_of(gi.HP);
   p.slope = slope;
   const size_t lds = (size_t)2 * (2 * PSA + 4 * PT) * 16;
-  const int grid = std::min(p.ntiles, ps_num_cus());
+  const int grid = std::min(p.ntiles, num_cus());
   const bool w64 = gi.WP == 64;
   switch (mode) {
     case PSE_FWD_FULL:

@@ -46,7 +46,7 @@ __device__ __forceinline__ void split8(const float (&f)[8], bf16x8& hi, bf16x8& 
 }  // namespace
 
 namespace fdet {
-// pooled-block fusion of the ping-pong kernel (fdet_conv3x3_x3_pp.hip); all null = plain epilogue modes
+// pooled-block fusion of the aligned-band small-tile kernel (fdet_x3_sb_pool_run); all null = plain epilogue modes
 struct PoolArgs {
   float* pool_out;                  // EPI_FWD_POOL: [N,Cout,H/2,W/2] = maxpool2x2(lrelu(conv+bias)*scale + skip)
   unsigned char* mask_out;          // EPI_FWD_POOL (training): [N,Cout,H/2,W/2] routing bytes, may be null
@@ -55,12 +55,9 @@ struct PoolArgs {
 };
 }  // namespace fdet
 
-// ping-pong variant for rows of <= 63 columns (fdet_conv3x3_x3_pp.hip); returns 1 when it has no tiling
-int fdet_x3_pp_run(fdet::ConvArgs a, fdet::PoolArgs q, hipStream_t st);
-
 // diagnostic record of the kernel the last fwd / dgrad / pooled launch on this thread went to (fdet_conv3x3_x3_last_route):
 // each runner notes its route where it launches; the C entry points clear it first, so a refused call leaves zeros
-enum { X3_ROUTE_PP = 1, X3_ROUTE_AL = 2, X3_ROUTE_SB = 3, X3_ROUTE_GENERAL = 4 };
+enum { X3_ROUTE_AL = 2, X3_ROUTE_SB = 3, X3_ROUTE_GENERAL = 4 };     // (1 was a retired kernel family; recorded route files keep these ids)
 void x3_note_route(int family, int vw, int mt, int mode, bool seg, bool p16);
 void x3_clear_route();
 
@@ -69,10 +66,10 @@ int fdet_x3_sb_run(fdet::ConvArgs a, hipStream_t st);
 // ... its aligned-band variant with the pooled-block epilogues
 int fdet_x3_sb_pool_run(fdet::ConvArgs a, fdet::PoolArgs q, hipStream_t st);
 
-// one translation unit per epilogue mode (fdet_conv3x3_x3_m<MODE>.hip): picks the kernel
+// one translation unit per epilogue mode (fdet_conv3x3_x3_tu.hip, -DX3_TU=<MODE>): picks the kernel
 // instantiation for (MT, NW, NT, VW, seg) and launches it
 #define X3_DECL_LAUNCH(M_) int fdet_x3_launch_m##M_(const X3Args& p, int MT, int NW, int NT, int VW, bool seg, size_t lds, int grid, hipStream_t st);
 X3_DECL_LAUNCH(0) X3_DECL_LAUNCH(1) X3_DECL_LAUNCH(2) X3_DECL_LAUNCH(3) X3_DECL_LAUNCH(4) X3_DECL_LAUNCH(5)
-// ... and their precision16 (one bf16 pass) forms, fdet_conv3x3_x3_m<MODE>_bf16.hip
+// ... and their precision16 (one bf16 pass) forms, -DX3_TU=<6 + MODE>
 X3_DECL_LAUNCH(0_bf16) X3_DECL_LAUNCH(1_bf16) X3_DECL_LAUNCH(2_bf16) X3_DECL_LAUNCH(3_bf16) X3_DECL_LAUNCH(4_bf16) X3_DECL_LAUNCH(5_bf16)
 #undef X3_DECL_LAUNCH

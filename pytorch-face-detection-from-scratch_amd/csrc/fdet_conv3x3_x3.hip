@@ -6,7 +6,7 @@
 // f32 MFMA: three passes are ~5x faster, which moves the 3x3 convs from MFMA-bound to HBM-bound.
 //
 // This file: weight-panel packing, tile selection and the C-ABI entry points.  The kernels live in
-// fdet_conv3x3_x3_kernel.inc, compiled once per epilogue mode (fdet_conv3x3_x3_m*.hip).
+// fdet_conv3x3_x3_kernel.inc, compiled once per epilogue mode and precision (fdet_conv3x3_x3_tu.hip).
 #include "fdet_conv3x3_x3.h"
 #include <algorithm>
 
@@ -23,9 +23,8 @@ struct PackBatch { const float* w[PACK_MAXL]; bf16x8* fwd[PACK_MAXL]; bf16x8* bw
 // Each panel is [hi units | lo units]; both halves together are exactly as large as the fp32
 // panel of fdet_pack_conv3x3_weights, so callers size one buffer for either precision.
 // ---------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(256)
-k_pack3x3_x3(const float* __restrict__ w, int Cout, int Cin, int CoP, int CiP, bf16x8* __restrict__ fwd,
-             bf16x8* __restrict__ bwd) {
+__device__ __forceinline__ void pack3x3_x3(const float* __restrict__ w, int Cout, int Cin, int CoP, int CiP,
+                                           bf16x8* __restrict__ fwd, bf16x8* __restrict__ bwd) {
   const int nf = (Cin / 16) * 9 * 2 * CoP, nb = (Cout / 16) * 9 * 2 * CiP;
   const int t = blockIdx.x * 256 + threadIdx.x;
   if (fwd && t < nf) {
@@ -52,40 +51,33 @@ k_pack3x3_x3(const float* __restrict__ w, int Cout, int Cin, int CoP, int CiP, b
   }
 }
 
-int num_cus() {
-  static int n = 0;
-  if (n == 0) {
-    int dev = 0, v = 0;
-    if (hipGetDevice(&dev) == hipSuccess &&
-        hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) n = v;
-    else n = 256;
-  }
-  return n;
+__global__ void __launch_bounds__(256)
+k_pack3x3_x3(const float* __restrict__ w, int Cout, int Cin, int CoP, int CiP, bf16x8* __restrict__ fwd,
+             bf16x8* __restrict__ bwd) {
+  pack3x3_x3(w, Cout, Cin, CoP, CiP, fwd, bwd);
+}
+
+// ... one layer per blockIdx.y
+__global__ void __launch_bounds__(256)
+k_pack3x3_x3_batched(const PackBatch b, int Cout, int Cin, int CoP, int CiP) {
+  pack3x3_x3(b.w[blockIdx.y], Cout, Cin, CoP, CiP, b.fwd[blockIdx.y], b.bwd[blockIdx.y]);
 }
 
 int run_x3(ConvArgs a, hipStream_t st) {
-  // rows of up to 64 columns: the small-tile kernel (two workgroups per CU) is the faster one
+  // rows of up to 64 columns: the small-tile kernels (two workgroups per CU) are the faster ones
   // (FDET_CONV_KERNEL=general forces the persistent kernel)
-  {
-    static const char kernel_choice = [] { const char* e = getenv("FDET_CONV_KERNEL"); return e ? e[0] : '\0'; }();
-    if (a.W <= 64 && kernel_choice != 'g') {
-      // ping-pong kernel first (one 8-wave workgroup per CU, barrier-enforced MFMA / memory alternation), then the
-      // round-1 small-tile kernel (FDET_CONV_KERNEL=s), then the general persistent kernel (=g)
-      if (kernel_choice != 's' && !a.p16) {           // (the ping-pong kernel has no precision16 form)
-        const int rc = fdet_x3_pp_run(a, PoolArgs{nullptr, nullptr, nullptr, nullptr}, st);
-        if (rc != 1) return rc;
-      }
-      // aligned-band variant of the small-tile kernel (no separator rows, shared epilogue with two-instruction quad
-      // exchanges): measured -6 % / -7 % on the 60x60 forward / data-gradient launches, a wash at 30x30 (bands of 8 rows
-      // cover 32 of 30): default for rows of 33..63 columns; FDET_SB_AL=0 / 1 forces it off / on for every width
-      static const int sb_al = [] { const char* e = getenv("FDET_SB_AL"); return e ? (e[0] == '1' ? 1 : 0) : -1; }();
-      if (sb_al == 1 || (sb_al < 0 && a.W >= 33)) {
-        const int rc = fdet_x3_sb_pool_run(a, PoolArgs{nullptr, nullptr, nullptr, nullptr}, st);
-        if (rc != 1) return rc;
-      }
-      const int rc = fdet_x3_sb_run(a, st);
+  static const char kernel_choice = [] { const char* e = getenv("FDET_CONV_KERNEL"); return e ? e[0] : '\0'; }();
+  if (a.W <= 64 && kernel_choice != 'g') {
+    // aligned-band variant of the small-tile kernel (no separator rows, epilogue with two-instruction quad
+    // exchanges): measured -6 % / -7 % on the 60x60 forward / data-gradient launches, a wash at 30x30 (bands of 8 rows
+    // cover 32 of 30): default for rows of 33..63 columns; FDET_SB_AL=0 / 1 forces it off / on for every width
+    static const int sb_al = [] { const char* e = getenv("FDET_SB_AL"); return e ? (e[0] == '1' ? 1 : 0) : -1; }();
+    if (sb_al == 1 || (sb_al < 0 && a.W >= 33)) {
+      const int rc = fdet_x3_sb_pool_run(a, PoolArgs{nullptr, nullptr, nullptr, nullptr}, st);
       if (rc != 1) return rc;
     }
+    const int rc = fdet_x3_sb_run(a, st);
+    if (rc != 1) return rc;
   }
   a.VR = a.N * (a.H + 1) + 1;
   if (a.VR >= (1 << 20)) return fail(FDET_EINVAL, "conv3x3_bf16x3: N*(H+1)=%d virtual rows exceed the index range", a.VR);
@@ -239,37 +231,6 @@ extern "C" int fdet_pack_conv3x3_weights_bf16x3(const float* w, int Cout, int Ci
   return check_launch("fdet_pack_conv3x3_weights_bf16x3");
 }
 
-__global__ void __launch_bounds__(256)
-k_pack3x3_x3_batched(const PackBatch b, int Cout, int Cin, int CoP, int CiP) {
-  const float* __restrict__ w = b.w[blockIdx.y];
-  bf16x8* __restrict__ fwd = b.fwd[blockIdx.y];
-  bf16x8* __restrict__ bwd = b.bwd[blockIdx.y];
-  const int nf = (Cin / 16) * 9 * 2 * CoP, nb = (Cout / 16) * 9 * 2 * CiP;
-  const int t = blockIdx.x * 256 + threadIdx.x;
-  if (fwd && t < nf) {
-    const int co = t % CoP, r = t / CoP;
-    const int h = r & 1, r2 = r >> 1, tap = r2 % 9, c16 = r2 / 9;
-    float f[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) f[j] = (co < Cout) ? w[((size_t)co * Cin + c16 * 16 + 8 * h + j) * 9 + tap] : 0.f;
-    bf16x8 hi, lo;
-    split8(f, hi, lo);
-    fwd[t] = hi;
-    fwd[nf + t] = lo;
-  }
-  if (bwd && t < nb) {
-    const int ci = t % CiP, r = t / CiP;
-    const int h = r & 1, r2 = r >> 1, tap = r2 % 9, o16 = r2 / 9;
-    float f[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) f[j] = (ci < Cin) ? w[((size_t)(o16 * 16 + 8 * h + j) * Cin + ci) * 9 + (8 - tap)] : 0.f;
-    bf16x8 hi, lo;
-    split8(f, hi, lo);
-    bwd[t] = hi;
-    bwd[nb + t] = lo;
-  }
-}
-
 extern "C" int fdet_pack_conv3x3_weights_bf16x3_batched(const float* const* h_w, int L, int Cout, int Cin,
                                                         void* const* h_wpk_fwd, void* const* h_wpk_bwd, void* stream) {
   FDET_REQUIRE(h_w && L >= 1 && Cout > 0 && Cin > 0 && (h_wpk_fwd || h_wpk_bwd), "pack_conv3x3_weights_bf16x3_batched: bad arguments");
@@ -319,17 +280,6 @@ extern "C" int fdet_conv3x3_fwd_bf16(const float* x, const void* wpk, const floa
   return conv3x3_fwd_x3(x, wpk, bias, y_full, skip, drop_scale, y_out, N, Cin, Cout, H, W, pool, slope, 1, stream);
 }
 
-// pooled-block modes: aligned-band small-tile kernel (two workgroups per CU), or the ping-pong kernel (FDET_POOL_KERNEL=pp)
-// (precision16 always takes the aligned-band kernel: the ping-pong kernel has no one-pass form)
-static int run_x3_pooled(const ConvArgs& a, const PoolArgs& q, hipStream_t st) {
-  static const bool use_pp = [] { const char* e = getenv("FDET_POOL_KERNEL"); return e && e[0] == 'p'; }();
-  if (!use_pp || a.p16) {
-    const int rc = fdet_x3_sb_pool_run(a, q, st);
-    if (rc != 1 || a.p16) return rc;
-  }
-  return fdet_x3_pp_run(a, q, st);
-}
-
 // 1 when the fused pooled-block kernels (fdet_conv3x3_fwd_pool_bf16x3 / fdet_conv3x3_dgrad_unpool_bf16x3) have a tiling
 // for the shape -- the same conditions fdet_x3_sb_pool_run checks before it launches (even map of <= 62 columns, channel
 // multiples, 32-bit element offsets, < 2^20 (image, band) tiles) -- so a caller can choose the separate conv + tail
@@ -354,7 +304,7 @@ static int conv3x3_fwd_pool_x3(const float* x, const void* wpk, const float* bia
   a.x = x; a.wpk = (const float*)wpk; a.bias = bias; a.y_full = nullptr; a.skip = skip; a.scale = drop_scale;
   a.y_out = nullptr; a.act = nullptr; a.N = N; a.Cin = Cin; a.Cout = Cout; a.H = H; a.W = W; a.dgrad = 0; a.slope = slope;
   a.p16 = p16;
-  const int rc = run_x3_pooled(a, PoolArgs{out_pooled, route, nullptr, nullptr}, (hipStream_t)stream);
+  const int rc = fdet_x3_sb_pool_run(a, PoolArgs{out_pooled, route, nullptr, nullptr}, (hipStream_t)stream);   // the aligned-band kernel
   return rc == 1 ? fail(FDET_EINVAL, "conv3x3_fwd_pool_bf16%s: no tiling for H=%d W=%d", p16 ? "" : "x3", H, W) : rc;
 }
 
@@ -380,7 +330,7 @@ static int conv3x3_dgrad_unpool_x3(const float* dz, const void* wpk, const float
   a.x = dz; a.wpk = (const float*)wpk; a.bias = nullptr; a.y_full = dx; a.skip = nullptr; a.scale = nullptr; a.y_out = nullptr;
   a.act = nullptr; a.N = N; a.Cin = Cout; a.Cout = Cin; a.H = H; a.W = W; a.dgrad = 1; a.slope = slope;
   a.p16 = p16;
-  const int rc = run_x3_pooled(a, PoolArgs{nullptr, nullptr, dout_pooled, route}, (hipStream_t)stream);
+  const int rc = fdet_x3_sb_pool_run(a, PoolArgs{nullptr, nullptr, dout_pooled, route}, (hipStream_t)stream);
   return rc == 1 ? fail(FDET_EINVAL, "conv3x3_dgrad_unpool_bf16%s: no tiling for H=%d W=%d", p16 ? "" : "x3", H, W) : rc;
 }
 

@@ -1,5 +1,4 @@
-// Tile epilogue shared by the ping-pong kernel (fdet_conv3x3_x3_pp.hip) and the aligned-band variant of the small-tile
-// kernel (fdet_conv3x3_x3_sb.hip): image-aligned bands, a wave owns two 32-position blocks n = 0,1 (row-pair mapping: the
+// Tile epilogue of the aligned-band variant of the small-tile kernel (fdet_conv3x3_x3_sb.hip): image-aligned bands, a wave owns two 32-position blocks n = 0,1 (row-pair mapping: the
 // same 32 columns of two adjacent rows, so whole 2x2 pooling windows sit in one lane after the quad transpose).
 // ARGS must provide: ConvArgs c; PoolArgs q; unsigned magic_wp.
 #pragma once

@@ -24,9 +24,9 @@
 // tiles: while chunk s is in the MFMA loop the global loads of chunk s+1 (possibly the next tile's
 // first chunk) are in flight, and their fp32 -> (hi,lo) split + LDS writes are interleaved with
 // the MFMAs of the later taps.  One barrier per chunk.
-// This file is included by fdet_conv3x3_x3_m<MODE>.hip with X3_MODE defined (one translation unit
+// This file is included by fdet_conv3x3_x3_tu.hip with X3_MODE defined (one translation unit
 // per epilogue mode keeps each kernel's register allocation independent and the build parallel).
-// X3_P16 = 1 (fdet_conv3x3_x3_m<MODE>_bf16.hip) instantiates the precision16 form instead: one bf16 pass (P16 below).
+// X3_P16 = 1 instantiates the precision16 form instead: one bf16 pass (P16 below).
 #include "fdet_conv3x3_x3.h"
 #ifndef X3_P16
 #define X3_P16 0

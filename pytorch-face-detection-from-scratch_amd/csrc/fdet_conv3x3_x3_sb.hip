@@ -464,15 +464,6 @@ int launch_sb_pool(const X3SbArgs& p, int VW, size_t lds, dim3 grid, hipStream_t
   return check_launch("fdet_conv3x3_bf16x3(sb, pooled)");
 }
 
-int sb_num_cus() {
-  static int ncu = 0;
-  if (ncu == 0) {
-    int dev = 0, v = 0;
-    ncu = (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) ? v : 256;
-  }
-  return ncu;
-}
-
 }  // namespace
 
 // Returns 1 when this kernel family has no tiling for the shape (the caller then uses the general
@@ -538,7 +529,7 @@ int fdet_x3_sb_run(ConvArgs a, hipStream_t st) {
   p.ntiles = a.nbands * p.ncob;
   // persistent: two workgroups per CU walk the tiles (the zero fill and the first-chunk latency are
   // paid once per workgroup, later tiles prefetch their first chunk under the previous tile's tail)
-  int gsz = 2 * sb_num_cus();
+  int gsz = 2 * num_cus();
   if (force.grid >= 0) gsz = force.grid > 0 ? force.grid : p.ntiles;
   dim3 grid(p.ntiles < gsz ? p.ntiles : gsz, 1);
   p.c.stagger = 0;
@@ -604,7 +595,7 @@ int fdet_x3_sb_pool_run(ConvArgs a, PoolArgs q, hipStream_t st) {
   if (lds > 80 * 1024) return 1;
   p.ncob = a.CoP / (MT * 32);
   p.ntiles = (int)nbt * p.ncob;
-  const int gsz = 2 * sb_num_cus();
+  const int gsz = 2 * num_cus();
   dim3 grid(p.ntiles < gsz ? p.ntiles : gsz, 1);
   x3_note_route(X3_ROUTE_AL, VW, MT, a.mode, false, a.p16);
   if (a.p16) return MT == 2 ? launch_sb_pool<2, true>(p, VW, lds, grid, st) : launch_sb_pool<1, true>(p, VW, lds, grid, st);

@@ -60,8 +60,8 @@ enum { EPI_GENERIC = 0,
        EPI_FWD_OUT,     // y_out = z + skip                          (eval, un-pooled block tail)
        EPI_DGRAD_ACT,   // dx = acc * lrelu'(act)
        EPI_DGRAD_ADD,   // dx = acc + add
-       EPI_FWD_POOL,    // pool_out = maxpool2x2(z*scale + skip) + routing bytes   (pooled block tail; ping-pong kernel only)
-       EPI_DGRAD_ADDPOOL }; // dx = acc + unpool(dout) through the routing bytes  (ping-pong kernel only)
+       EPI_FWD_POOL,    // pool_out = maxpool2x2(z*scale + skip) + routing bytes   (pooled block tail; aligned-band kernel only)
+       EPI_DGRAD_ADDPOOL }; // dx = acc + unpool(dout) through the routing bytes  (aligned-band kernel only)
 
 // precision16 (one bf16 MFMA pass, P16 template flag of the bf16x3 kernels): every activation / activation gradient the
 // epilogue stores is rounded once to bf16 (RNE) and stored in its fp32 word; the epilogue arithmetic itself stays fp32

@@ -320,15 +320,6 @@ k_pw_wgrad_reduce(const float* __restrict__ ws, int nslab, int CoP32, int CiP32,
   }
 }
 
-int pw_num_cus() {
-  static int ncu = 0;
-  if (ncu == 0) {
-    int dev = 0, v = 0;
-    ncu = (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) ? v : 256;
-  }
-  return ncu;
-}
-
 template <bool P16>
 int run_pw(const float* x, const void* wpk, const float* bias, const float* add, float* y, int N, int Cin, int Cout, int P,
            float slope, hipStream_t st, const char* what) {

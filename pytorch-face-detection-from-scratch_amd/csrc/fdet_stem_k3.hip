@@ -216,15 +216,6 @@ k_stem3_fwd_ps(const float* __restrict__ x, const float* __restrict__ w, const f
   }
 }
 
-int s3_num_cus() {
-  static int ncu = 0;
-  if (ncu == 0) {
-    int dev = 0, v = 0;
-    ncu = (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) ? v : 256;
-  }
-  return ncu;
-}
-
 }  // namespace
 
 namespace fdet {
@@ -238,7 +229,7 @@ bool stem3_wgrad_ok(int Cin, int F, int H, int W, int k, int stride, int pad) {
 // slabs the workspace must hold: [F/64 blocks][grid][64][32] floats
 size_t stem3_wgrad_ws_floats(int N, int F, int H, int W) {
   (void)N; (void)H; (void)W;
-  return (size_t)((F + 63) / 64) * (size_t)(3 * s3_num_cus()) * 2048;
+  return (size_t)((F + 63) / 64) * (size_t)(3 * num_cus()) * 2048;
 }
 
 int stem3_wgrad(const float* x, const float* dz, float* dW, float* db, float* ws, size_t ws_floats, int N, int F, int H, int W,
@@ -250,7 +241,7 @@ int stem3_wgrad(const float* x, const float* dz, float* dW, float* db, float* ws
   a.pitch = ((W + 4 + 59) / 64) * 64 + 4;                 // >= W + 4, == 4 (mod 64)
   a.ksteps = a.Wo / 16;
   const int fblk = (F + 63) / 64;
-  int grid = std::min(a.nrows, 3 * s3_num_cus());
+  int grid = std::min(a.nrows, 3 * num_cus());
   grid = (int)std::min<size_t>((size_t)grid, ws_floats / ((size_t)fblk * 2048));
   if (grid < 1) return fail(FDET_EWORKSPACE, "stem_wgrad_bf16x3 (k3): workspace too small");
   const size_t lds = std::max<size_t>((size_t)9 * a.pitch * 4, (size_t)4 * 2048 * 4);

@@ -1,7 +1,8 @@
 // Elementwise tails of the residual block (HBM-bound): dropout scale + skip add + 2x2 max
 // pool forward, and their backward fused with the second LeakyReLU's derivative.
 // models/PoolResnet.py:37-42 (models/Resnet.py:34-39) and ATen's max_pool2d backward
-// (first maximum in window scan order wins; NaN is a maximum).
+// (first maximum in window scan order wins; NaN is a maximum).  Last: the tail backward of the fused pooled
+// block, which reads the routing bytes of the conv kernel's EPI_FWD_POOL epilogue instead of c and x.
 #include "fdet_common.h"
 
 using namespace fdet;
@@ -100,4 +101,79 @@ extern "C" int fdet_block_tail_bwd(const float* dout, const float* c, const floa
   hipLaunchKernelGGL(k_tail_bwd, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, dout, c, x, drop_scale,
                      dz2, de, N * F, H, W, pool, slope);
   return check_launch("fdet_block_tail_bwd");
+}
+
+// ---- pooled residual block, backward of the tail: dz2 = unpool(dout) * drop_scale * lrelu'(c), everything read
+// from the pooled gradient and the routing bytes written by EPI_FWD_POOL (c and the block input are not needed).
+namespace {
+__global__ void __launch_bounds__(256)
+k_pool_route_bwd(const float* __restrict__ dout, const unsigned char* __restrict__ mask, const float* __restrict__ scale,
+                 float* __restrict__ dz2, int NF, int Hp, int Wp, float slope) {
+  const int W = 2 * Wp;
+  const size_t total = (size_t)NF * Hp * (Wp >> 1);             // one thread per TWO windows (16-byte row stores)
+  for (size_t t = (size_t)blockIdx.x * 256 + threadIdx.x; t < total; t += (size_t)gridDim.x * 256) {
+    const int oxp = (int)(t % (Wp >> 1));
+    const size_t r = t / (Wp >> 1);
+    const int oy = (int)(r % Hp);
+    const size_t nf = r / Hp;
+    const float sc = scale ? scale[nf] : 1.f;
+    const size_t pi = (nf * Hp + oy) * Wp + 2 * oxp;
+    const float g0 = dout[pi], g1 = dout[pi + 1];
+    const unsigned m0 = mask[pi], m1 = mask[pi + 1];
+    float row0[4], row1[4];
+#pragma unroll
+    for (int pc = 0; pc < 2; ++pc) {
+      const unsigned mk = pc ? m1 : m0;
+      const float g = (pc ? g1 : g0) * sc;
+      const int arg = (mk >> 4) & 3;
+      row0[2 * pc] = arg == 0 ? g * ((mk & 1) ? 1.f : slope) : 0.f;
+      row0[2 * pc + 1] = arg == 1 ? g * ((mk & 2) ? 1.f : slope) : 0.f;
+      row1[2 * pc] = arg == 2 ? g * ((mk & 4) ? 1.f : slope) : 0.f;
+      row1[2 * pc + 1] = arg == 3 ? g * ((mk & 8) ? 1.f : slope) : 0.f;
+    }
+    float* o = dz2 + (nf * (2 * Hp) + 2 * (size_t)oy) * W + 4 * (size_t)oxp;
+    __builtin_memcpy(o, row0, 16);
+    __builtin_memcpy(o + W, row1, 16);
+  }
+}
+// odd pooled width: the last window of a row has no partner
+__global__ void __launch_bounds__(256)
+k_pool_route_bwd_last(const float* __restrict__ dout, const unsigned char* __restrict__ mask, const float* __restrict__ scale,
+                      float* __restrict__ dz2, int NF, int Hp, int Wp, float slope) {
+  const int W = 2 * Wp;
+  const size_t total = (size_t)NF * Hp;
+  for (size_t t = (size_t)blockIdx.x * 256 + threadIdx.x; t < total; t += (size_t)gridDim.x * 256) {
+    const int oy = (int)(t % Hp);
+    const size_t nf = t / Hp;
+    const float sc = scale ? scale[nf] : 1.f;
+    const size_t pi = (nf * Hp + oy) * Wp + (Wp - 1);
+    const unsigned mk = mask[pi];
+    const float g = dout[pi] * sc;
+    const int arg = (mk >> 4) & 3;
+    float* o = dz2 + (nf * (2 * Hp) + 2 * (size_t)oy) * W + 2 * (size_t)(Wp - 1);
+    o[0] = arg == 0 ? g * ((mk & 1) ? 1.f : slope) : 0.f;
+    o[1] = arg == 1 ? g * ((mk & 2) ? 1.f : slope) : 0.f;
+    o[W] = arg == 2 ? g * ((mk & 4) ? 1.f : slope) : 0.f;
+    o[W + 1] = arg == 3 ? g * ((mk & 8) ? 1.f : slope) : 0.f;
+  }
+}
+}  // namespace
+
+extern "C" int fdet_pool_route_bwd(const float* dout, const unsigned char* mask, const float* drop_scale, float* dz2,
+                                   int N, int F, int H, int W, float slope, void* stream) {
+  FDET_REQUIRE(dout && mask && dz2 && N > 0 && F > 0 && H >= 2 && W >= 2 && !(H & 1) && !(W & 1),
+               "pool_route_bwd: bad arguments (even H, W >= 2 required; H=%d W=%d)", H, W);
+  const int Hp = H / 2, Wp = W / 2;
+  const size_t total = (size_t)N * F * Hp * (Wp >> 1);
+  if (total) {
+    size_t blocks = (total + 255) / 256; if (blocks > 8192) blocks = 8192;
+    hipLaunchKernelGGL(k_pool_route_bwd, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, dout, mask, drop_scale,
+                       dz2, N * F, Hp, Wp, slope);
+  }
+  if (Wp & 1) {
+    size_t blocks = ((size_t)N * F * Hp + 255) / 256; if (blocks > 8192) blocks = 8192;
+    hipLaunchKernelGGL(k_pool_route_bwd_last, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, dout, mask,
+                       drop_scale, dz2, N * F, Hp, Wp, slope);
+  }
+  return check_launch("fdet_pool_route_bwd");
 }

@@ -325,22 +325,13 @@ k_wgrad_ps_reduce(const float* __restrict__ ws, const float* __restrict__ wsb, i
   }
 }
 
-int wg_num_cus() {
-  static int ncu = 0;
-  if (ncu == 0) {
-    int dev = 0, v = 0;
-    ncu = (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) ? v : 256;
-  }
-  return ncu;
-}
-
 int wg_plan(int L, int N, int H, int W, PsGeo& g, int& nslab, int& lpw) {
   PsStrips sp;                                           // wide maps: column strips (fdet_ps.h); g.N counts strip-images
   if (!ps_geo_strips(N, 64, H, W, g, sp) || L < 1 || L > WG_MAXL) return 0;
   const int lpi = g.HP * g.WP / 64;
   const long nlines = (long)g.N * lpi;
   if (nlines + 2 * lpi >= (1 << 20) || (size_t)(g.N + 2) * g.img * 16 >= ((size_t)1 << 32)) return 0;   // 32-bit DMA byte offsets
-  nslab = std::max(1, std::min((int)nlines, wg_num_cus() / L));
+  nslab = std::max(1, std::min((int)nlines, num_cus() / L));
   lpw = (int)((nlines + nslab - 1) / nslab);
   nslab = (int)((nlines + lpw - 1) / lpw);
   return 1;

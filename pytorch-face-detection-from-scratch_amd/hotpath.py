@@ -693,12 +693,12 @@ def conv3x3_dgrad(dz, wpk_bwd, cin: int, dx, act=None, add=None, slope: float = 
 
 
 X3_ROUTE_FIELDS = ("family", "vw", "mt", "mode", "seg", "p16")
-X3_FAMILIES = {1: "pp", 2: "al", 3: "sb", 4: "general"}
+X3_FAMILIES = {2: "al", 3: "sb", 4: "general"}
 
 
 def conv3x3_x3_last_route() -> dict:
     """Kernel route of the last bf16x3 / precision16 conv3x3 forward, data-gradient or pooled launch on this thread
-    (fdet_conv3x3_x3_last_route): family ("pp", "al", "sb", "general"; None after a refused call), vector width VW, MT,
+    (fdet_conv3x3_x3_last_route): family ("al", "sb", "general"; None after a refused call), vector width VW, MT,
     epilogue mode (EPI_*), column-segmented rows and precision16."""
     import ctypes
     out = (ctypes.c_int * len(X3_ROUTE_FIELDS))()

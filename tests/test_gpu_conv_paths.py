@@ -1,8 +1,8 @@
 """Every dispatch path of the bf16x3 / precision16 3x3 convolution (csrc/fdet_conv3x3_x3*.hip, fdet_wgrad3x3_x3.hip)
 against a float64 CPU reference of the same operation.
 
-The runners choose among four kernel families (ping-pong "pp", aligned-band small-tile "al", small-tile "sb", general
-persistent "general"), and inside a family among vector widths (from W % 4 and the pointers' alignment), MT (Cout padded
+The runners choose among three kernel families (aligned-band small-tile "al", small-tile "sb", general persistent
+"general"), and inside a family among vector widths (from W % 4 and the pointers' alignment), MT (Cout padded
 to 32, CoP % 64), epilogue modes, column segmentation and the precision.  Each case below states the route it must reach
 (`expected_route`, a restatement of those rules) and checks it through fdet_conv3x3_x3_last_route /
 fdet_conv3x3_wgrad_bf16x3_plan, so a shape list that drifts off its branch fails instead of testing nothing.  Tile sizes
@@ -13,8 +13,8 @@ Bounds: bf16x3 max|got - ref| <= 1e-4 * max(1, max|ref|); precision16 reference 
 within close_bf16's bound (one bf16 rounding of the stored value), weight gradients within 1e-4 of the scale.
 Outputs start as NaN inside a sentinel band that must survive; every launch runs twice and must repeat bit for bit.
 
-The environment switches the runners read once per process (FDET_CONV_KERNEL, FDET_SB_AL, FDET_CONV_PP,
-FDET_POOL_KERNEL, FDET_WGRAD_PIPE, FDET_WGRAD_PK4, FDET_WGRAD_PACK) are covered by re-running subsets of this file in
+The environment switches the runners read once per process (FDET_CONV_KERNEL, FDET_SB_AL, FDET_WGRAD_PIPE,
+FDET_WGRAD_PK4, FDET_WGRAD_PACK) are covered by re-running subsets of this file in
 child processes (test_switch_groups); FDET_CONV_TILE is read at every call and covered in-process."""
 import os
 import subprocess
@@ -49,18 +49,18 @@ def close(got, ref, tol=1e-4, what=""):
 
 
 # ----------------------------------------------------------------------------------------------------------------------
-# expected routes: a restatement of run_x3 / fdet_x3_pp_run / fdet_x3_sb_pool_run / fdet_x3_sb_run / plan_x3
+# expected routes: a restatement of run_x3 / fdet_x3_sb_pool_run / fdet_x3_sb_run / plan_x3
 # ----------------------------------------------------------------------------------------------------------------------
 def _aligned(p, b):
     return p is None or p % b == 0
 
 
 def _vw(W, x):
-    """Vector width of the pp / sb / al runners: from W and the input pointer only."""
+    """Vector width of the sb / al runners: from W and the input pointer only."""
     return 4 if W % 4 == 0 and _aligned(x, 16) else (2 if W % 2 == 0 and _aligned(x, 8) else 1)
 
 
-def _nbs_small(vw):          # nbs_sb / nbs_pp: staging slots per thread
+def _nbs_small(vw):          # nbs_sb: staging slots per thread
     return 1 if vw == 4 else (2 if vw == 2 else 3)
 
 
@@ -83,29 +83,6 @@ def _plain_mode(dgrad, p):
         if not p["act"] and p["skip"]:
             return EPI_DGRAD_ADD
     return None
-
-
-def _route_pp(N, ci, co, H, W, p, dgrad, pooled, p16):
-    if W > 63 or co % 32 or ci % 16:
-        return None
-    if pooled:
-        mode = EPI_DGRAD_ADDPOOL if dgrad else EPI_FWD_POOL
-        WP = 32 if W <= 31 else 64
-    else:
-        mode = _plain_mode(dgrad, p)
-        WP = (W + 4) // 4 * 4
-    if mode is None:
-        return None
-    vw = _vw(W, p["x"])
-    rowpair = WP in (32, 64)
-    if pooled and (not rowpair or H % 2 or W % 2):
-        return None
-    R = 256 // WP
-    if R > H:
-        R = (H + 1) & ~1 if rowpair else H
-    if 2 * (R + 2) * (W // vw) > _nbs_small(vw) * 256:
-        return None
-    return {("pp", vw, 2 if co % 64 == 0 else 1, mode, 0, 0)}
 
 
 def _route_al(N, ci, co, H, W, p, dgrad, pooled, p16):
@@ -213,18 +190,9 @@ def expected_route(kind, N, ci, co, H, W, p, p16):
     dgrad = kind in ("dgrad", "dgrad_unpool")
     env = os.environ
     if kind in ("fwd_pool", "dgrad_unpool"):
-        use_pp = env.get("FDET_POOL_KERNEL", "")[:1] == "p"
-        if not use_pp or p16:
-            r = _route_al(N, ci, co, H, W, p, dgrad, True, p16)
-            if r or p16:
-                return r or set()
-        return _route_pp(N, ci, co, H, W, p, dgrad, True, p16) or set()
+        return _route_al(N, ci, co, H, W, p, dgrad, True, p16) or set()
     kc = env.get("FDET_CONV_KERNEL", "")[:1]
     if W <= 64 and kc != "g":
-        if kc != "s" and not p16 and env.get("FDET_CONV_PP", "")[:1] == "1":
-            r = _route_pp(N, ci, co, H, W, p, dgrad, False, p16)
-            if r:
-                return r
         e = env.get("FDET_SB_AL")
         sb_al = -1 if e is None else (1 if e[:1] == "1" else 0)
         if sb_al == 1 or (sb_al < 0 and W >= 33):
@@ -638,7 +606,7 @@ def test_wgrad_refusals(hp, shape):
 def test_tables_reach_their_branches():
     """Without switches the width table reaches every family the defaults use, VW 4 / 2 / 1 in each, both MT, and
     segmented rows; every listed refusal is refused by the rules (checked on the GPU by test_*_refusals)."""
-    for k in ("FDET_CONV_KERNEL", "FDET_SB_AL", "FDET_CONV_PP", "FDET_CONV_TILE"):
+    for k in ("FDET_CONV_KERNEL", "FDET_SB_AL", "FDET_CONV_TILE"):
         if k in os.environ:
             pytest.skip("the defaults only")
     reach = set()
@@ -764,7 +732,6 @@ SWITCH_GROUPS = [
     ({"FDET_CONV_KERNEL": "general", "FDET_WGRAD_PIPE": "0"}, "test_conv_path and (W6 or W3 or W1-)"),
     ({"FDET_SB_AL": "0", "FDET_WGRAD_PK4": "0"}, "test_conv_path and (W3 or W4 or W1)"),
     ({"FDET_SB_AL": "1", "FDET_WGRAD_PACK": "1"}, "test_conv_path and (W1 or W2 or W3)"),
-    ({"FDET_CONV_PP": "1", "FDET_POOL_KERNEL": "pp"}, "(test_conv_path and (W3 or W4 or W6)) or test_pooled_path"),
 ]
 
 
