@@ -784,6 +784,41 @@ int fdet_tile_merge(const float* rows, const int32_t* counts, const fdet_tile* t
                     int n_images, int T, int K, int Ho, int Wo, const fdet_aug_image* table, float edge_margin,
                     double iou_threshold, int Kout, float* out, int32_t* out_counts, uint64_t* rejected, void* stream);
 
+/* Test-time augmentation for the two entries above: a mirrored second pass and box voting.
+ *
+ * fdet_tile_gather_flags: fdet_tile_gather plus flags [T] (device) / h_flags (host copy, validated with the windows).
+ *   Bit 0 set: the frame is written mirrored left to right; output pixel (v, u) holds exactly what the unflagged
+ *   frame holds at (v, Wo-1-u) (the same sample arithmetic on column Wo-1-u; one pass, the taps are read in reversed
+ *   order, the stores keep their order).  An unflagged window gives fdet_tile_gather's bytes.  A flag byte with any
+ *   other bit set returns FDET_EINVAL and nothing is written. */
+int fdet_tile_gather_flags(const uint8_t* bank, const fdet_aug_image* table, const fdet_aug_image* h_table, int n_images,
+                           const fdet_tile* tiles, const fdet_tile* h_tiles, const uint8_t* flags, const uint8_t* h_flags,
+                           int T, int Ho, int Wo, uint8_t* frames, void* stream);
+
+/* fdet_tile_merge with un-mirroring and box voting.  Launch, limits and rejection are fdet_tile_merge's (one workgroup
+ * per image, FDET_TILE_MAX_CANDIDATES candidates and Kout survivors, an image over either rejected as a whole).
+ *   flags [T] device, NULL = all zero; out_votes [n_images,Kout] int32; min_votes >= 1; vote 0 | 1
+ *   0. a row of a tile with flags bit 0 set: x <- ((float)Wo - x) - w, two fp32 subtractions in that order; y, w, h
+ *      unchanged
+ *   1., 2. as fdet_tile_merge, on the un-mirrored row
+ *   3. the visiting loop of fdet_tile_merge (same order, same overlap test) with ownership: a live candidate i that is
+ *      visited becomes a keeper and owns itself; every live j after it whose overlap with i exceeds iou_threshold dies
+ *      and is owned by i, the first keeper that suppresses it, and by no other
+ *   4. vote = 1: member weight q = llrint((double)min(score, 1.0f) * 1048576.0); q = 0 when the score is NaN or <= 0,
+ *      or when any of the member's x1 = x_s, y1 = y_s, x2 = x_s + w_s, y2 = y_s + h_s (fp32) is not finite or exceeds
+ *      2^24 in magnitude.  Per keeper, over its members, in int64: Q = sum q, sum q*x1, sum q*y1, sum q*x2, sum q*y2
+ *      (the coordinates are integer-valued).  Q > 0: X1 = rint((double)sum q*x1 / (double)Q) (half to even), likewise
+ *      Y1, X2, Y2; the row is [score of the keeper, X1, Y1, X2 - X1, Y2 - Y1] as fp32.  Q == 0 or vote = 0: the
+ *      keeper's own [score, x_s, y_s, w_s, h_s].  votes = the number of members, the keeper included.  The sums are
+ *      integers, so no order of addition changes a result.
+ *   5. keepers with votes < min_votes are not written and do not count towards Kout (they still suppressed in 3);
+ *      survivors in visiting order; rows of out and out_votes past the count are zeroed
+ * With flags all zero, vote = 0 and min_votes = 1, out and out_counts are fdet_tile_merge's, byte for byte. */
+int fdet_tile_merge_vote(const float* rows, const int32_t* counts, const fdet_tile* tiles, const uint8_t* flags,
+                         const int32_t* tile_offset, int n_images, int T, int K, int Ho, int Wo,
+                         const fdet_aug_image* table, float edge_margin, double iou_threshold, int min_votes, int vote,
+                         int Kout, float* out, int32_t* out_votes, int32_t* out_counts, uint64_t* rejected, void* stream);
+
 /* Depthwise-separable residual block (models/SeparableCNN.py:40-51; none of its three convs has a bias):
  *   a = lrelu(W1 x)   b = lrelu(dw3x3(a), pad 1)   c = W2 b   e = c * drop_scale[n,c] + x   out = maxpool2x2(e) | e
  * fdet_sepblock_fwd runs the whole block in ONE kernel on fp32 NCHW tensors: both 1x1 convs as bf16x3 GEMMs on the matrix

@@ -2,12 +2,15 @@
 
     python -m fdet_amd.detect_images --checkpoint CKPT --images DIR --out FILE [--model poolresnet --filters 128]
         [--tile 480 --overlap 0.25 --no-whole --edge-margin 0 --probability-threshold P --iou-threshold T --precision 16]
+        [--flip --vote --min-votes N]
 
 The images under DIR (searched recursively: .jpg .jpeg .png .bmp) are decoded with PIL into a device image bank
 (`bank_from_files`; `--device-jpeg`: baseline JPEGs are reconstructed on the device instead, with the same bytes), `tiling.TiledDetector` runs the model on overlapping windows of each image (and on the whole image
 unless --no-whole) and merges the windows' boxes, and FILE receives, per image: its path relative to DIR, the number of
 boxes, then one `x y w h score` line per box in source pixels.  `--pred-dir DIR` additionally writes the per-event directory
 the WIDER protocol's tools read (`DIR/<event>/<image>.txt`, `evaluation_wider.write_wider_pred_dir`).
+`--flip` runs every window a second time mirrored, `--vote` merges with box voting and `--min-votes N` leaves out boxes that
+fewer than N detections agree on.
 """
 import argparse
 import os
@@ -30,6 +33,7 @@ def write_wider_results(path, names, rows, counts) -> None:
 
 
 def main(argv=None):
+    """Parse and check the options, then `run` them."""
     ap = argparse.ArgumentParser()
     ap.add_argument("--model", choices=("poolresnet", "resnet", "separablecnn", "ssd"), default="poolresnet")
     ap.add_argument("--filters", type=int, default=None, help="default: 128 (poolresnet, separablecnn), 64 (resnet), 16 (ssd)")
@@ -49,7 +53,19 @@ def main(argv=None):
     ap.add_argument("--batch-images", type=int, default=64, help="source images per detect() call")
     ap.add_argument("--device-jpeg", action="store_true",
                     help="decode baseline JPEGs with the device decoder (datasets/jpeg.py) instead of PIL; same bytes")
+    ap.add_argument("--flip", action="store_true", help="every window a second time, mirrored left to right")
+    ap.add_argument("--vote", action="store_true", help="box voting: a kept box is the score-weighted mean of its cluster")
+    ap.add_argument("--min-votes", type=int, default=1, help="with --vote: leave out boxes with fewer members than this")
     args = ap.parse_args(argv)
+    if args.min_votes < 1:
+        ap.error("--min-votes must be >= 1")
+    if args.min_votes > 1 and not args.vote:
+        ap.error("--min-votes above 1 needs --vote")
+    return run(args)
+
+
+def run(args):
+    """What `main` does with its parsed options."""
     from .datasets.WIDERFace.annotations import bank_from_files
     from .run_validation_epoch import load_checkpoint
     from .tiling import TiledDetector
@@ -83,7 +99,7 @@ def main(argv=None):
     if not paths:
         raise SystemExit(f"no image under {root}")
     det = TiledDetector(model, tile_sizes=tuple(args.tile), overlap=args.overlap, include_whole=not args.no_whole,
-                        edge_margin=args.edge_margin)
+                        edge_margin=args.edge_margin, flip=args.flip, vote=args.vote, min_votes=args.min_votes)
     names, all_rows, all_counts = [], [], []
     for a in range(0, len(paths), args.batch_images):
         chunk = paths[a:a + args.batch_images]

@@ -340,6 +340,70 @@ def tile_merge(rows: torch.Tensor, counts: torch.Tensor, d_tiles: torch.Tensor, 
     return out, out_counts, rejected
 
 
+def _tile_flags(h_flags, T):
+    import numpy as np
+    if not isinstance(h_flags, np.ndarray) or h_flags.dtype != np.uint8 or h_flags.shape != (T,) or not h_flags.flags.c_contiguous:
+        raise ValueError(f"flags: expected a contiguous ({T},) numpy uint8 array")
+    return h_flags
+
+
+def tile_gather_flags(bank_data: torch.Tensor, d_table: torch.Tensor, h_table, d_tiles: torch.Tensor, h_tiles, d_flags: torch.Tensor,
+                      h_flags, out_hw, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """`tile_gather` with a mirror flag per window (fdet_tile_gather_flags): d_flags / h_flags are (T,) uint8 on the device
+    and as a numpy array; bit 0 set writes the frame mirrored left to right, byte-equal to `flip(-1)` of the unflagged frame.
+    A flag with another bit set raises FdetError before anything is written."""
+    h_tiles = _tile_records(h_tiles)
+    T, n_images = len(h_tiles), len(h_table)
+    h_flags = _tile_flags(h_flags, T)
+    Ho, Wo = int(out_hw[0]), int(out_hw[1])
+    U8 = torch.uint8
+    if d_tiles.numel() != T * 20 or d_table.numel() != n_images * 16 or d_flags.numel() != T or d_flags.dtype != U8:
+        raise ValueError("tile_gather_flags: device and host copies of the tiles / table / flags differ in size")
+    if out is None:
+        out = torch.empty(T, 3, Ho, Wo, dtype=U8, device=bank_data.device)
+    elif tuple(out.shape) != (T, 3, Ho, Wo):
+        raise ValueError(f"tile_gather_flags: out must be ({T},3,{Ho},{Wo}), got {tuple(out.shape)}")
+    check(lib().fdet_tile_gather_flags(ptr(bank_data, U8), ptr(d_table, U8), h_table.ctypes.data, n_images, ptr(d_tiles, U8),
+                                       h_tiles.ctypes.data, ptr(d_flags, U8), h_flags.ctypes.data, T, Ho, Wo, ptr(out, U8),
+                                       stream()), "fdet_tile_gather_flags")
+    return out
+
+
+def tile_merge_vote(rows: torch.Tensor, counts: torch.Tensor, d_tiles: torch.Tensor, d_flags: Optional[torch.Tensor],
+                    tile_offset: torch.Tensor, d_table: torch.Tensor, frame_hw, edge_margin: float, iou_threshold: float,
+                    max_out: int, vote: bool = True, min_votes: int = 1, rejected: Optional[torch.Tensor] = None):
+    """fdet_tile_merge_vote: `tile_merge` that first un-mirrors the rows of the windows flagged in d_flags ((T,) uint8 on
+    the device, None = no window is mirrored) and, with `vote`, writes each kept box as the score-weighted mean of the boxes
+    it suppressed; `vote=False` writes the kept boxes themselves.  Kept boxes with fewer than min_votes members are left out.
+    -> (out (n,max_out,5), out_votes (n,max_out) int32, out_counts (n,) int32, rejected (1,) int64)."""
+    if rows.dim() != 3 or rows.shape[2] != 5 or rows.dtype != F32:
+        raise ValueError(f"tile_merge_vote: rows must be (T,K,5) float32, got {tuple(rows.shape)} {rows.dtype}")
+    T, K = int(rows.shape[0]), int(rows.shape[1])
+    n = int(tile_offset.numel()) - 1
+    if tuple(counts.shape) != (T,) or counts.dtype != I32 or tile_offset.dtype != I32 or n < 1:
+        raise ValueError("tile_merge_vote: counts must be (T,) int32 and tile_offset (n+1,) int32")
+    if d_tiles.numel() != T * 20 or d_table.numel() != n * 16:
+        raise ValueError("tile_merge_vote: tiles / table do not match T / n")
+    U8 = torch.uint8
+    if d_flags is not None and (d_flags.numel() != T or d_flags.dtype != U8):
+        raise ValueError("tile_merge_vote: flags must be (T,) uint8")
+    if int(max_out) < 1 or int(min_votes) < 1:
+        raise ValueError("tile_merge_vote: max_out and min_votes must be positive")
+    dev = rows.device
+    out = torch.empty(n, int(max_out), 5, dtype=F32, device=dev)
+    out_votes = torch.empty(n, int(max_out), dtype=I32, device=dev)
+    out_counts = torch.empty(n, dtype=I32, device=dev)
+    if rejected is None:
+        rejected = torch.zeros(1, dtype=torch.int64, device=dev)
+    check(lib().fdet_tile_merge_vote(ptr(rows.contiguous()), ptr(counts.contiguous(), I32), ptr(d_tiles, U8),
+                                     ptr(None if d_flags is None else d_flags.contiguous(), U8), ptr(tile_offset.contiguous(), I32),
+                                     n, T, K, int(frame_hw[0]), int(frame_hw[1]), ptr(d_table, U8), float(edge_margin),
+                                     float(iou_threshold), int(min_votes), int(bool(vote)), int(max_out), ptr(out),
+                                     ptr(out_votes, I32), ptr(out_counts, I32), ptr(rejected, torch.int64), stream()),
+          "fdet_tile_merge_vote")
+    return out, out_votes, out_counts, rejected
+
+
 # ------------------------------------------------------------------------------------------
 # Baseline JPEG decode (csrc/fdet_jpeg.hip; datasets/jpeg.py drives these)
 # ------------------------------------------------------------------------------------------

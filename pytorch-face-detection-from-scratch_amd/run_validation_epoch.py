@@ -12,6 +12,8 @@ takes a Lightning-layout file ({"state_dict": {"model.<name>": tensor}}) or a ba
 class; without it the freshly initialised model is evaluated.  `--precision 16` runs the convolutions in one bf16 pass.
 `--tiled` adds a second report: the same evaluator numbers from `tiling.TiledDetector` on the UNRESIZED bank (windows of
 `--tile` source pixels with `--overlap`, plus the whole image unless `--no-whole`) against the source-pixel boxes.
+With `--flip`, `--vote` or `--min-votes N` the tiled pass runs with test-time augmentation and its AP lines
+name the options that ran.
 `--wider-gt DIR` (the directory holding wider_face_val.mat and wider_{easy,medium,hard}_val.mat) adds the Easy / Medium /
 Hard AP of the WIDER Face protocol (`evaluation_wider.WiderEvaluator`): the resized pass's detections are taken back to
 source pixels, and with `--tiled` the tiled rows are evaluated too.  `--json` then gains the keys "wider" / "wider_tiled".
@@ -67,7 +69,14 @@ def print_wider(r, prefix=""):
           f"range {r.score_range:.4g}): " + ", ".join(f"{k} AP {r.ap[k]:.4f} ({r.n_faces[k]} faces)" for k in r.subset_names))
 
 
+def tta_label(args) -> str:
+    """' [flip, vote, min-votes 2]' for the tiled report lines; empty when none of the three options is set"""
+    on = (["flip"] if args.flip else []) + (["vote"] if args.vote else []) + ([f"min-votes {args.min_votes}"] if args.min_votes > 1 else [])
+    return f" [{', '.join(on)}]" if on else ""
+
+
 def main(argv=None):
+    """Parse and check the options, then `run` them."""
     ap = argparse.ArgumentParser()
     ap.add_argument("--model", choices=("poolresnet", "resnet", "separablecnn", "ssd"), default="poolresnet")
     ap.add_argument("--filters", type=int, default=None, help="default: 128 (poolresnet, separablecnn), 64 (resnet), 16 (ssd)")
@@ -91,7 +100,21 @@ def main(argv=None):
     ap.add_argument("--wider-gt", default=None, help="directory of the WIDER protocol's four .mat files: report Easy/Medium/Hard AP")
     ap.add_argument("--device-jpeg", action="store_true",
                     help="--wider-root: decode baseline JPEGs with the device decoder (datasets/jpeg.py) instead of PIL; same bytes")
+    ap.add_argument("--flip", action="store_true", help="--tiled: every window a second time, mirrored left to right")
+    ap.add_argument("--vote", action="store_true", help="--tiled: box voting instead of plain NMS across windows")
+    ap.add_argument("--min-votes", type=int, default=1, help="--tiled --vote: leave out boxes with fewer members than this")
     args = ap.parse_args(argv)
+    if args.min_votes < 1:
+        ap.error("--min-votes must be >= 1")
+    if (args.flip or args.vote or args.min_votes > 1) and not args.tiled:
+        ap.error("--flip, --vote and --min-votes apply to the tiled pass: add --tiled")
+    if args.min_votes > 1 and not args.vote:
+        ap.error("--min-votes above 1 needs --vote")
+    return run(args)
+
+
+def run(args):
+    """What `main` does with its parsed options."""
     torch.random.manual_seed(0)
     from . import hotpath as hp
     from .datasets.augment import DeviceBatches, default_transform, synthetic_bank
@@ -169,7 +192,7 @@ def main(argv=None):
         out["tiled"] = tiled_report(model, bank, boxes, args, tiled_wider)
         if tiled_wider is not None:
             out["wider_tiled"] = tiled_wider[0].compute()
-            print_wider(out["wider_tiled"], "tiled ")
+            print_wider(out["wider_tiled"], f"tiled{tta_label(args)} ")
             doc["wider_tiled"] = out["wider_tiled"].to_json()
     if args.json:
         Path(args.json).write_text(json.dumps(doc))
@@ -185,7 +208,7 @@ def tiled_report(model, bank, boxes, args, wider=None):
     model.eval()
     ev = DetectionEvaluator(iou_thresholds=tuple(args.iou), score_floor=args.score_floor)
     det = TiledDetector(model, tile_sizes=tuple(args.tile), overlap=args.overlap, include_whole=not args.no_whole,
-                        reducer=ev.reducer_for(model))
+                        reducer=ev.reducer_for(model), flip=args.flip, vote=args.vote, min_votes=args.min_votes)
     gt = DeviceBoxes(boxes, "cuda")
     step = max(1, args.batch_size)
     for a in range(0, len(bank), step):
@@ -198,7 +221,7 @@ def tiled_report(model, bank, boxes, args, wider=None):
     print(f"tiled (tile {list(args.tile)}, overlap {args.overlap}, whole image {not args.no_whole}): {r.n_images} images, "
           f"{r.n_gt} faces, {r.n_det} detections with score >= {args.score_floor}")
     for t, a in zip(r.iou_thresholds, r.ap_per_threshold):
-        print(f"tiled AP@{float(t):.2f}: {a:.4f}")
+        print(f"tiled AP@{float(t):.2f}{tta_label(args)}: {a:.4f}")
     print(f"tiled best F1 {r.best_f1:.4f} at score threshold {r.best_threshold:.3f}")
     return r
 
