@@ -819,6 +819,32 @@ int fdet_tile_merge_vote(const float* rows, const int32_t* counts, const fdet_ti
                          const fdet_aug_image* table, float edge_margin, double iou_threshold, int min_votes, int vote,
                          int Kout, float* out, int32_t* out_votes, int32_t* out_counts, uint64_t* rejected, void* stream);
 
+/* ---- rendering detections into a second bank (csrc/fdet_render.hip) ----------------------
+ * dst image i = src image i with the first counts[i] rows of rows[i] rendered into it.  src / src_table / h_src_table
+ * and dst / dst_table / h_dst_table: two banks as above, image i of the one and of the other of equal h and w.
+ * rows [n_images,K,5] fp32 [score,x,y,w,h] in source pixels (NULL only with K = 0); counts [n_images] int32 on the
+ * device, h_counts the same values in host memory; ws [n_images+1] int32 device scratch.  The source is never written.
+ *   1. the destination image starts as a copy of the source image (device-to-device copies: one per run of images
+ *      that follow each other in both banks)
+ *   2. box -> pixels, fp32 then truncation toward zero: x0 = (int)x, y0 = (int)y, x1 = (int)(x + w), y1 = (int)(y + h),
+ *      both ends inclusive.  A box is skipped when x, y, w or h is not finite, w < 1 or h < 1, or |x|, |y|, |x + w| or
+ *      |y + h| exceeds 2^24, or when x1 == x0 or y1 == y0 (zero width or height in pixels: with w, h >= 1 only where
+ *      the truncation folds a start in (-1, 0) and an end in [0, 1) onto pixel 0).  Rows at index >= counts[i] are
+ *      never read.
+ *   3. pixelate = 1: cell = max(1, ceil(max(x1-x0+1, y1-y0+1) / blocks)); cell (i, j) covers
+ *      [x0+i*cell, x0+(i+1)*cell-1] n [x0, x1] n [0, W-1], likewise y; every pixel of a non-empty cell becomes
+ *      (sum + cnt/2) / cnt per channel, in integers, over the cell's pixels of the SOURCE image; a pixel that several
+ *      boxes cover takes the value of the box with the lowest row index
+ *   4. outline = 1, after 3: t = (w <= 15 || h <= 15) ? 1 : 3 on the fp32 w and h (datasets/utils.py:198-201); a pixel
+ *      inside the image takes (red, green, blue) when it lies in [x0,x1] x [y0,y1] and not in [x0+t,x1-t] x [y0+t,y1-t].
+ *      This is the set of pixels PIL's ImageDraw.rectangle(outline=..., width=t) paints.
+ * Validated on the host, FDET_EINVAL and nothing written: the byte ranges the two tables span overlap; h / w differ
+ * between the tables; K < 0; blocks < 1; h_counts[i] outside 0..K; a flag that is not 0 | 1; a colour outside 0..255. */
+int fdet_render_boxes(const uint8_t* src, const fdet_aug_image* src_table, const fdet_aug_image* h_src_table,
+                      const float* rows, const int32_t* counts, const int32_t* h_counts, int n_images, int K, uint8_t* dst,
+                      const fdet_aug_image* dst_table, const fdet_aug_image* h_dst_table, int outline, int pixelate,
+                      int blocks, int red, int green, int blue, int32_t* ws, void* stream);
+
 /* Depthwise-separable residual block (models/SeparableCNN.py:40-51; none of its three convs has a bias):
  *   a = lrelu(W1 x)   b = lrelu(dw3x3(a), pad 1)   c = W2 b   e = c * drop_scale[n,c] + x   out = maxpool2x2(e) | e
  * fdet_sepblock_fwd runs the whole block in ONE kernel on fp32 NCHW tensors: both 1x1 convs as bf16x3 GEMMs on the matrix

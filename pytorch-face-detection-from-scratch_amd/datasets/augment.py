@@ -105,6 +105,37 @@ class DeviceImageBank:
                 torch.cuda.current_stream(device).synchronize()  # the staging buffer is refilled next
         return cls(data, table)
 
+    def to_arrays(self, indices=None, chunk_bytes: int = 256 << 20) -> List[np.ndarray]:
+        """The inverse of `from_arrays`: the images `indices` (all when None) as (H,W,3) uint8 arrays of their own, through
+        one pinned staging buffer per chunk (images that follow each other in the bank share a copy)."""
+        idx = np.arange(len(self)) if indices is None else np.asarray(list(indices), dtype=np.int64).reshape(-1)
+        if idx.size and (idx.min() < 0 or idx.max() >= len(self)):
+            raise IndexError(f"to_arrays: indices outside the bank of {len(self)} images")
+        t = self.table[idx]
+        sizes = t["h"].astype(np.int64) * t["w"] * 3
+        if idx.size == 0:
+            return []
+        stage = torch.empty(int(min(max(int(sizes.sum()), 1), max(int(chunk_bytes), int(sizes.max())))), dtype=torch.uint8).pin_memory()
+        sn = stage.numpy()
+        out: List[np.ndarray] = []
+        i, n = 0, len(idx)
+        while i < n:
+            first, fill = i, 0
+            while i < n and fill + int(sizes[i]) <= stage.numel():
+                run_off, run_fill, run_bytes = int(t["offset"][i]), fill, 0
+                while (i < n and fill + int(sizes[i]) <= stage.numel()
+                       and int(t["offset"][i]) == run_off + run_bytes):           # the run goes on in the bank
+                    run_bytes += int(sizes[i])
+                    fill += int(sizes[i])
+                    i += 1
+                stage[run_fill:run_fill + run_bytes].copy_(self.data[run_off:run_off + run_bytes], non_blocking=True)
+            torch.cuda.current_stream(self.device).synchronize()                 # the staging buffer is refilled next
+            pos = 0
+            for k in range(first, i):
+                out.append(sn[pos:pos + int(sizes[k])].reshape(int(t["h"][k]), int(t["w"][k]), 3).copy())
+                pos += int(sizes[k])
+        return out
+
     def __len__(self) -> int:
         return len(self.table)
 

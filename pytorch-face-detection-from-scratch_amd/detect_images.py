@@ -2,7 +2,7 @@
 
     python -m fdet_amd.detect_images --checkpoint CKPT --images DIR --out FILE [--model poolresnet --filters 128]
         [--tile 480 --overlap 0.25 --no-whole --edge-margin 0 --probability-threshold P --iou-threshold T --precision 16]
-        [--flip --vote --min-votes N]
+        [--flip --vote --min-votes N] [--draw DIR [--anonymize pixelate] [--blocks N] [--draw-format png|jpg] [--no-outline]]
 
 The images under DIR (searched recursively: .jpg .jpeg .png .bmp) are decoded with PIL into a device image bank
 (`bank_from_files`; `--device-jpeg`: baseline JPEGs are reconstructed on the device instead, with the same bytes), `tiling.TiledDetector` runs the model on overlapping windows of each image (and on the whole image
@@ -11,6 +11,10 @@ boxes, then one `x y w h score` line per box in source pixels.  `--pred-dir DIR`
 the WIDER protocol's tools read (`DIR/<event>/<image>.txt`, `evaluation_wider.write_wider_pred_dir`).
 `--flip` runs every window a second time mirrored, `--vote` merges with box voting and `--min-votes N` leaves out boxes that
 fewer than N detections agree on.
+`--draw DIR` also writes every input image with its boxes rendered into it (`render.render_detections`) to
+`DIR/<path relative to --images>` with the suffix replaced by `--draw-format`: blue outlines of the reference's width unless
+`--no-outline`, and with `--anonymize pixelate` every box flattened to at most `--blocks` x `--blocks` cells.  The images are
+rendered on the device, chunk by chunk, from the bank the detector just read.
 """
 import argparse
 import os
@@ -56,7 +60,19 @@ def main(argv=None):
     ap.add_argument("--flip", action="store_true", help="every window a second time, mirrored left to right")
     ap.add_argument("--vote", action="store_true", help="box voting: a kept box is the score-weighted mean of its cluster")
     ap.add_argument("--min-votes", type=int, default=1, help="with --vote: leave out boxes with fewer members than this")
+    ap.add_argument("--draw", default=None, metavar="DIR", help="also write every image, rendered, under DIR")
+    ap.add_argument("--anonymize", choices=("pixelate",), default=None, help="with --draw: pixelate every box")
+    ap.add_argument("--blocks", type=int, default=None, help="with --draw --anonymize: cells along the longer side of a box (8)")
+    ap.add_argument("--draw-format", choices=("png", "jpg"), default=None, help="with --draw: the files' format (png)")
+    ap.add_argument("--no-outline", action="store_true", help="with --draw: no outlines")
     args = ap.parse_args(argv)
+    if args.draw is None:
+        for flag, given in (("--anonymize", args.anonymize is not None), ("--blocks", args.blocks is not None),
+                            ("--draw-format", args.draw_format is not None), ("--no-outline", args.no_outline)):
+            if given:
+                ap.error(f"{flag} needs --draw")
+    if args.blocks is not None and args.blocks < 1:
+        ap.error("--blocks must be >= 1")
     if args.min_votes < 1:
         ap.error("--min-votes must be >= 1")
     if args.min_votes > 1 and not args.vote:
@@ -105,6 +121,12 @@ def run(args):
         chunk = paths[a:a + args.batch_images]
         bank = bank_from_files(chunk, "cuda", decoder="device" if args.device_jpeg else "pil")
         rows, counts = det.detect(bank, range(len(bank)))
+        if args.draw is not None:
+            from .render import render_detections, save_images
+            drawn = render_detections(bank, rows, counts, outline=not args.no_outline, anonymize=args.anonymize,
+                                      blocks=8 if args.blocks is None else args.blocks)
+            save_images(drawn, [(Path(args.draw) / os.path.relpath(p, root)).with_suffix("." + (args.draw_format or "png"))
+                                for p in chunk])
         kmax = max(int(counts.max()), 1)
         all_rows.append(rows[:, :kmax].cpu())
         all_counts.append(counts.cpu())

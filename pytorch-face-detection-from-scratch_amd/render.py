@@ -1,0 +1,84 @@
+"""Render detections into a second device image bank: outlines as PIL draws them, and pixelation for anonymisation.
+
+    rows, counts = TiledDetector(model).detect(bank, idx)
+    drawn = render_detections(bank, rows, counts, idx)                                   # blue outlines, reference widths
+    anon = render_detections(bank, rows, counts, idx, outline=False, anonymize="pixelate")
+    save_images(drawn, [f"out/{i}.png" for i in range(len(drawn))])
+
+The pixels never leave the device between the detector and the rendered bank: `fdet_render_boxes` (csrc/fdet_render.hip)
+copies the chosen images device to device and works on the boxes alone.  The only host read is `counts` (n int32), which
+sizes the launches and is validated before anything is written.  Rules, limits and measurements: DESIGN.md 5g;
+tests/render_cpu_ref.py restates the rules in numpy.
+"""
+from __future__ import annotations
+
+import os
+from concurrent.futures import ThreadPoolExecutor
+from typing import Optional, Sequence
+
+import numpy as np
+import torch
+
+from ._native import check, lib, ptr, stream
+from .datasets.augment import IMAGE_DTYPE, DeviceImageBank
+
+ANONYMIZERS = (None, "pixelate")
+
+
+def render_detections(bank: DeviceImageBank, rows: torch.Tensor, counts: torch.Tensor, indices=None, outline: bool = True,
+                      anonymize: Optional[str] = None, blocks: int = 8, color=(0, 0, 255)) -> DeviceImageBank:
+    """-> a new bank over its own buffer holding the images `indices` of `bank` (all of them when None), renumbered
+    0..len(indices)-1, with the first counts[i] boxes of rows[i] rendered into image i.  rows (n,K,5) fp32 [score,x,y,w,h] in
+    source pixels and counts (n,) int32 on the bank's device, row-aligned with `indices`, as `TiledDetector.detect` returns
+    them.  anonymize="pixelate": every box becomes at most `blocks` x `blocks` flat cells (the mean of the source pixels of
+    each cell); outline: a `color` outline of the reference's width on top.  `bank` is never written."""
+    if anonymize not in ANONYMIZERS:
+        raise ValueError(f"render_detections: anonymize must be None or 'pixelate', got {anonymize!r}")
+    if int(blocks) < 1:
+        raise ValueError(f"render_detections: blocks={blocks} must be >= 1")
+    col = tuple(int(c) for c in color)
+    if len(col) != 3 or any(not 0 <= c <= 255 for c in col):
+        raise ValueError(f"render_detections: color must be three values in 0..255, got {color!r}")
+    src = bank if indices is None else bank.subset(np.asarray(list(indices), dtype=np.int64).reshape(-1))
+    n = len(src)
+    if n == 0:
+        raise ValueError("render_detections: no image")
+    if rows.dim() != 3 or rows.shape[0] != n or rows.shape[2] != 5 or rows.dtype != torch.float32:
+        raise ValueError(f"render_detections: rows must be ({n},K,5) float32, got {tuple(rows.shape)} {rows.dtype}")
+    if tuple(counts.shape) != (n,) or counts.dtype != torch.int32:
+        raise ValueError(f"render_detections: counts must be ({n},) int32, got {tuple(counts.shape)} {counts.dtype}")
+    table = np.zeros(n, dtype=IMAGE_DTYPE)
+    sizes = src.table["h"].astype(np.int64) * src.table["w"] * 3
+    table["offset"][1:] = np.cumsum(sizes)[:-1]
+    table["h"], table["w"] = src.table["h"], src.table["w"]
+    dev = bank.device
+    out = DeviceImageBank(torch.empty(int(sizes.sum()), dtype=torch.uint8, device=dev), table)
+    rows, counts = rows.contiguous(), counts.contiguous()
+    h_counts = np.ascontiguousarray(counts.cpu().numpy())
+    ws = torch.empty(n + 1, dtype=torch.int32, device=dev)
+    U8, I32 = torch.uint8, torch.int32
+    K = int(rows.shape[1])
+    check(lib().fdet_render_boxes(ptr(src.data, U8), ptr(src.d_table, U8), src.table.ctypes.data, ptr(rows) if K else None,
+                                  ptr(counts, I32), h_counts.ctypes.data, n, K, ptr(out.data, U8), ptr(out.d_table, U8),
+                                  out.table.ctypes.data, int(bool(outline)), int(anonymize == "pixelate"), int(blocks), col[0],
+                                  col[1], col[2], ptr(ws, I32), stream()), "fdet_render_boxes")
+    return out
+
+
+def save_images(bank: DeviceImageBank, paths: Sequence, threads: int = 16) -> None:
+    """Write image i of `bank` to paths[i] with PIL, PNG or JPEG by the suffix, on at most 16 threads.  Parent directories
+    are created."""
+    from PIL import Image
+    paths = [os.fspath(p) for p in paths]
+    if len(paths) != len(bank):
+        raise ValueError(f"save_images: {len(paths)} paths for a bank of {len(bank)} images")
+    for d in sorted({os.path.dirname(p) for p in paths}):
+        if d:
+            os.makedirs(d, exist_ok=True)
+    arrays = bank.to_arrays()
+
+    def save(job):
+        Image.fromarray(job[0]).save(job[1])
+
+    with ThreadPoolExecutor(max_workers=max(1, min(16, int(threads), len(paths) or 1))) as ex:
+        list(ex.map(save, zip(arrays, paths)))

@@ -73,6 +73,9 @@ def wider_batches(root, split, batch_size, transform, patches, decoder, **kw):
 
 def main(argv=None):
     ap = build_parser()
+    # not a training option: build_parser() stays the set of options that shape the run
+    ap.add_argument("--draw-dir", default=None,
+                    help="write {train|validation}_epoch_{E}.png (image 0 of the first batch, predicted boxes) there")
     args = ap.parse_args(argv)
     torch.random.manual_seed(0)                                  # train_model.py:13
     from .models import ModelMeta
@@ -117,7 +120,7 @@ def main(argv=None):
     else:
         train = synthetic_loader(args.steps_per_epoch, args.batch_size, args.size, args.patches, seed=1)
         val = synthetic_loader(args.val_steps, args.batch_size, args.size, args.patches, seed=2)
-    hist = fit(model_setup, train, val, epochs=args.epochs, torchscript_path=args.save)
+    hist = fit(model_setup, train, val, epochs=args.epochs, torchscript_path=args.save, draw_dir=args.draw_dir)
     print(f"\nfinal training loss {float(hist['train'][-1]['loss']):.3f}")
     return hist
 

@@ -46,6 +46,8 @@ def parser():
     ap.add_argument("--precision", type=int, choices=(32, 16), default=32)   # train_model_ssd.py:49 Trainer(precision=...)
     ap.add_argument("--augment", action="store_true", help="on-device default_transform over a synthetic image bank")
     ap.add_argument("--bank-size", type=int, default=None, help="--augment: images in the bank (default: one epoch's worth)")
+    ap.add_argument("--draw-dir", default=None,
+                    help="write {train|validation}_epoch_{E}.png (image 0 of the first batch, predicted boxes) there")
     return ap
 
 
@@ -76,7 +78,7 @@ def main(argv=None):
     else:
         train = synthetic_loader(args.steps_per_epoch, args.batch_size, args.size, seed=1)
         val = synthetic_loader(args.val_steps, args.batch_size, args.size, seed=2)
-    hist = fit(model_setup, train, val, epochs=args.epochs, torchscript_path=args.save)
+    hist = fit(model_setup, train, val, epochs=args.epochs, torchscript_path=args.save, draw_dir=args.draw_dir)
     print(f"\nfinal training loss {float(hist['train'][-1]['loss']):.3f}")
     return hist
 

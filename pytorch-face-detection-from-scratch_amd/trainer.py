@@ -34,7 +34,18 @@ def _validation_step_with_output(model_meta, batch, step):
     return out, seen[0]
 
 
-def _epoch(model_meta, batches, train: bool, feeder_cache: dict, on_step: Optional[Callable], evaluator=None):
+def _draw_first(model_meta, x0, y_hat, draw_dir, train: bool) -> None:
+    """The reference's side effect of step(batch_idx == 0) (models/ModelMeta.py:144-157): image 0 of the batch with the boxes
+    the model predicts for it, as `{train|validation}_epoch_{E}.png` under draw_dir."""
+    from .datasets.utils import draw_bbx
+    model = model_meta.model
+    with torch.no_grad():
+        pred = model.non_max_suppression(y_hat[:1].detach())[0]
+    draw_bbx(img=x0, bbx=pred, input_shape=model.input_shape,
+             save_name=f"{'train' if train else 'validation'}_epoch_{model_meta.current_epoch}", save_dir=str(draw_dir))
+
+
+def _epoch(model_meta, batches, train: bool, feeder_cache: dict, on_step: Optional[Callable], evaluator=None, draw_dir=None):
     model = model_meta.model
     dev = next(model.parameters()).device
     size = tuple(model.input_shape[1:])
@@ -71,10 +82,19 @@ def _epoch(model_meta, batches, train: bool, feeder_cache: dict, on_step: Option
             model.train()
             lsum, y_hat, tot = model_meta.fused_train_step(x_d, y_d, with_metrics=True)
             out = {"loss": lsum.detach().reshape(()), "total_iou": tot[0], "total_recall": tot[1], "total_precision": tot[2]}
+            if draw_dir is not None and step == 0:
+                _draw_first(model_meta, x_d[0], y_hat, draw_dir, True)
         else:
             model.eval()
             with torch.no_grad():
-                if evaluator is None:
+                if draw_dir is not None and step == 0:
+                    out, y_hat = _validation_step_with_output(model_meta, (x_d, y_d, None), step)
+                    _draw_first(model_meta, x_d[0], y_hat, draw_dir, False)
+                    if evaluator is not None:
+                        if gt is None:
+                            raise ValueError("fit(evaluator=...): validation batches must carry their true boxes as batch[2]")
+                        evaluator.evaluate_batch(model, y_hat, gt)
+                elif evaluator is None:
                     out = model_meta.validation_step((x_d, y_d, None), step)
                 else:
                     if gt is None:
@@ -94,13 +114,17 @@ def _epoch(model_meta, batches, train: bool, feeder_cache: dict, on_step: Option
 
 
 def fit(model_meta, train_batches: Iterable, val_batches: Optional[Iterable] = None, epochs: int = 1,
-        torchscript_path: Optional[str] = None, on_step: Optional[Callable] = None, evaluator=None) -> dict:
+        torchscript_path: Optional[str] = None, on_step: Optional[Callable] = None, evaluator=None, draw_dir=None) -> dict:
     """Train `model_meta` (a ModelMeta) for `epochs` passes over `train_batches` (re-iterable), validating on
     `val_batches` after every epoch.  Returns {"train": [per-epoch metrics], "val": [...], "scripted": module or None}.
 
     `evaluator` (an `evaluation.DetectionEvaluator`): the validation pass also feeds it the forward output of every
     validation step and the batch's true boxes (batch[2]: a GtBoxes or a list of (n,5) tensors); it is reset every epoch and
-    hist["val"][e] gains "ap", "best_f1", "best_threshold" (one device-to-host copy per epoch).  Step outputs are unchanged."""
+    hist["val"][e] gains "ap", "best_f1", "best_threshold" (one device-to-host copy per epoch).  Step outputs are unchanged.
+
+    `draw_dir` (a directory, created when missing): image 0 of the first training and of the first validation batch of every
+    epoch is written there with the boxes predicted for it, as `train_epoch_{E}.png` / `validation_epoch_{E}.png`, the
+    reference's `draw_bbx` side effect (models/ModelMeta.py:144-157), rendered on the device.  None (default): nothing."""
     limit_host_threads()                  # 256 OpenMP workers on a 16-core share stall the thread that feeds the GPU
     optimizers, schedulers = model_meta.configure_optimizers()
     sched = schedulers[0]
@@ -112,11 +136,11 @@ def fit(model_meta, train_batches: Iterable, val_batches: Optional[Iterable] = N
             # Lightning runs the validation loop inside the training epoch and calls validation_epoch_end first, which is
             # why the reference's training line in the log quotes the validation metrics of the same epoch (ModelMeta.py:268-289)
             pass
-        tr = _epoch(model_meta, train_batches, True, feeder_cache, on_step)
+        tr = _epoch(model_meta, train_batches, True, feeder_cache, on_step, draw_dir=draw_dir)
         if val_batches is not None:
             if evaluator is not None:
                 evaluator.reset()
-            va = _epoch(model_meta, val_batches, False, feeder_cache, on_step, evaluator)
+            va = _epoch(model_meta, val_batches, False, feeder_cache, on_step, evaluator, draw_dir)
             hist["val"].append(model_meta.format_metrics(va, training=False))
             if evaluator is not None:
                 r = evaluator.compute()
