@@ -521,6 +521,19 @@ int fdet_stem_wgrad_bf16(const float* x, const float* dy, float* dW, float* db, 
  * chunks; its weight gradient sums the per-workgroup partials of every chunk in one reduction (fdet_stem_ws_bytes). */
 int fdet_stem_fwd_ps_ok(int N, int Cin, int F, int H, int W, int k, int stride, int pad, int precision16, int u8);
 int fdet_stem_wgrad_x3_ok(int N, int Cin, int F, int H, int W, int k, int stride, int pad, int precision16);
+/* Diagnostic: what the last fdet_stem_{fwd,wgrad}* call on the calling thread launched, recorded where the launch was
+ * issued: out[0..min(n,8)-1] = kernel family (FDET_STEM_*), pass (1 forward, 2 weight gradient), precision16 (0/1), uint8
+ * input (0/1), PS output (0/1), launches of the main kernel (image chunks), gridDim.x and work items (output rows, or
+ * row x 64-column segment items of the scalar-fed kernel) of the first launch.  All zero after a refused call. */
+#define FDET_STEM_VALU_K10 1         /* fp32 VALU, k10 s8 p2 */
+#define FDET_STEM_VALU_K3_GENERIC 2  /* fp32 VALU, k3 s2 p1 (any H, W) */
+#define FDET_STEM_VALU_K3_SCALAR 3   /* fp32 VALU, k3 s2 p1 weight gradient fed by scalar loads (H, W even, Wo % 4 == 0) */
+#define FDET_STEM_MFMA 4             /* fp32 MFMA, k10 */
+#define FDET_STEM_X3_SINGLE 5        /* bf16x3 k10, one LDS tile */
+#define FDET_STEM_X3_PIPE 6          /* bf16x3 / precision16 k10, pipelined */
+#define FDET_STEM_K3_MATRIX 7        /* bf16x3 / precision16 k3 weight gradient on the matrix cores */
+#define FDET_STEM_K3_PS_FWD 8        /* k3 forward with a PS (column-strip) output */
+int fdet_stem_last_route(int* out, int n);
 int fdet_conv3x3_wgrad_ps_batched_p16(const void* const* h_x, const void* const* h_dz, float* const* h_dW,
                                       float* const* h_db, int L, int N, int C, int H, int W, void* ws,
                                       size_t ws_bytes, void* stream);

@@ -77,6 +77,7 @@ SIGNATURES = {
     "fdet_conv3x3_x3_last_route": (_I, [_P, _I]),
     "fdet_conv3x3_ps_ok": (_I, [_I, _I, _I, _I, _I, _I]),
     "fdet_stem_fwd_ps_ok": (_I, [_I, _I, _I, _I, _I, _I, _I, _I, _I, _I]),
+    "fdet_stem_last_route": (_I, [_P, _I]),
     "fdet_stem_wgrad_x3_ok": (_I, [_I, _I, _I, _I, _I, _I, _I, _I, _I]),
     "fdet_ps_bytes": (_SZ, [_I, _I, _I, _I]),
     "fdet_ps_image0_offset": (_SZ, [_I, _I, _I, _I]),

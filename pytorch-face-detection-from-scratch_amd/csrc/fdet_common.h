@@ -50,6 +50,13 @@ inline int num_cus() {
   return ncu;
 }
 
+// record of the kernels a stem call launched (fdet_stem_last_route, fdet_stem.hip); the first launch of a call sets the fields
+enum { STEM_VALU_K10 = FDET_STEM_VALU_K10, STEM_VALU_K3_GENERIC = FDET_STEM_VALU_K3_GENERIC, STEM_VALU_K3_SCALAR = FDET_STEM_VALU_K3_SCALAR,
+       STEM_MFMA = FDET_STEM_MFMA, STEM_X3_SINGLE = FDET_STEM_X3_SINGLE, STEM_X3_PIPE = FDET_STEM_X3_PIPE,
+       STEM_K3_MATRIX = FDET_STEM_K3_MATRIX, STEM_K3_PS_FWD = FDET_STEM_K3_PS_FWD, STEM_PASS_FWD = 1, STEM_PASS_WGRAD = 2 };
+void stem_note_route(int family, int pass, bool p16, bool u8, bool ps, int grid, int items);
+void stem_clear_route();
+
 constexpr int WAVE = 64;
 
 __device__ __forceinline__ float wave_sum(float v) {

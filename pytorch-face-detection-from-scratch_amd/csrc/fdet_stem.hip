@@ -34,6 +34,26 @@ bool stem3_fwd_ps_ok(int Cin, int F, int H, int W, int k, int stride, int pad);
 int stem3_fwd_ps(const float* x, const float* w, const float* bias, void* y_ps, int N, int F, int H, int W, hipStream_t st, bool p16);
 }
 
+// diagnostic record of the kernels the last stem call on this thread launched (fdet_stem_last_route): family, pass,
+// precision16, uint8 input, PS output, launches of the main kernel, gridDim.x and work items of the first one
+namespace {
+thread_local int g_stem_route[8];
+}
+namespace fdet {
+void stem_note_route(int family, int pass, bool p16, bool u8, bool ps, int grid, int items) {
+  int* r = g_stem_route;
+  if (r[5] == 0) { r[0] = family; r[1] = pass; r[2] = p16 ? 1 : 0; r[3] = u8 ? 1 : 0; r[4] = ps ? 1 : 0; r[6] = grid; r[7] = items; }
+  r[5] += 1;
+}
+void stem_clear_route() { for (int& v : g_stem_route) v = 0; }
+}
+
+extern "C" int fdet_stem_last_route(int* out, int n) {
+  FDET_REQUIRE(out && n >= 0, "stem_last_route: bad arguments");
+  for (int i = 0; i < n && i < 8; ++i) out[i] = g_stem_route[i];
+  return FDET_OK;
+}
+
 namespace {
 
 template <int KS, int ST, int PD, int CIN>
@@ -345,6 +365,7 @@ extern "C" size_t fdet_stem_ws_bytes(int N, int Cin, int F, int H, int W, int k,
 
 extern "C" int fdet_stem_fwd(const float* x, const float* w, const float* bias, float* y, void* ws, size_t ws_bytes,
                              int N, int Cin, int F, int H, int W, int k, int stride, int pad, void* stream) {
+  stem_clear_route();
   FDET_REQUIRE(x && w && bias && y && ws && N > 0 && F > 0, "stem_fwd: bad arguments");
   StemPlan p;
   FDET_REQUIRE(stem_plan(N, Cin, F, H, W, k, stride, pad, p),
@@ -358,9 +379,11 @@ extern "C" int fdet_stem_fwd(const float* x, const float* w, const float* bias, 
   dim3 grid(N * p.Ho);
   if (k == 10) {
     if (p.lds_fwd > 64 * 1024) { if (int rc_ = set_lds_attr((const void*)k_stem_fwd<10, 8, 2, 3>, (size_t)p.lds_fwd, __func__)) return rc_; }
+    stem_note_route(STEM_VALU_K10, STEM_PASS_FWD, false, false, false, (int)grid.x, N * p.Ho);
     hipLaunchKernelGGL((k_stem_fwd<10, 8, 2, 3>), grid, dim3(256), p.lds_fwd, st, x, wpk, bias, y, F, p.FP, H, W, p.Ho, p.Wo, p.BXS);
   } else {
     if (p.lds_fwd > 64 * 1024) { if (int rc_ = set_lds_attr((const void*)k_stem_fwd<3, 2, 1, 3>, (size_t)p.lds_fwd, __func__)) return rc_; }
+    stem_note_route(STEM_VALU_K3_GENERIC, STEM_PASS_FWD, false, false, false, (int)grid.x, N * p.Ho);
     hipLaunchKernelGGL((k_stem_fwd<3, 2, 1, 3>), grid, dim3(256), p.lds_fwd, st, x, wpk, bias, y, F, p.FP, H, W, p.Ho, p.Wo, p.BXS);
   }
   return check_launch("fdet_stem_fwd");
@@ -369,6 +392,7 @@ extern "C" int fdet_stem_fwd(const float* x, const float* w, const float* bias, 
 extern "C" int fdet_stem_fwd_bf16x3(const float* x, const float* w, const float* bias, float* y, void* ws, size_t ws_bytes,
                                     int N, int Cin, int F, int H, int W, int k, int stride, int pad, void* stream) {
   (void)ws; (void)ws_bytes;
+  stem_clear_route();
   FDET_REQUIRE(x && w && bias && y && N > 0 && F > 0, "stem_fwd_bf16x3: bad arguments");
   FDET_REQUIRE(stem_mfma_ok(Cin, F, H, W, k, stride, pad),
                "stem_fwd_bf16x3: only the PoolResnet stem (3ch k10 s8 p2, W%%4==0, W<=512) is built; got Cin=%d k=%d s=%d p=%d W=%d",
@@ -406,6 +430,7 @@ extern "C" int fdet_stem_wgrad_x3_ok(int N, int Cin, int F, int H, int W, int k,
 // the PoolResnet stem with a pre-split (PS) output: y_ps = image-0 pointer of a PS tensor (N, 64, Ho, Wo)
 extern "C" int fdet_stem_fwd_ps(const float* x, const float* w, const float* bias, void* y_ps, int N, int Cin, int F, int H,
                                 int W, int k, int stride, int pad, void* stream) {
+  stem_clear_route();
   FDET_REQUIRE(x && w && bias && y_ps && N > 0, "stem_fwd_ps: bad arguments");
   FDET_REQUIRE(stem_fwd_ps_plan_ok(N, Cin, F, H, W, k, stride, pad, false),
                "stem_fwd_ps: no PS stem plan for N=%d Cin=%d F=%d %dx%d k=%d s=%d p=%d", N, Cin, F, H, W, k, stride, pad);
@@ -420,6 +445,7 @@ extern "C" int fdet_stem_fwd_ps(const float* x, const float* w, const float* bia
 // precision16: one MFMA pass on bf16(x) x bf16(w), hi plane of the PS output only (see fdet_conv3x3_ps_fwd_p16)
 extern "C" int fdet_stem_fwd_ps_p16(const float* x, const float* w, const float* bias, void* y_ps, int N, int Cin, int F, int H,
                                     int W, int k, int stride, int pad, void* stream) {
+  stem_clear_route();
   FDET_REQUIRE(x && w && bias && y_ps && N > 0, "stem_fwd_ps_p16: bad arguments");
   FDET_REQUIRE(stem_fwd_ps_plan_ok(N, Cin, F, H, W, k, stride, pad, false),
                "stem_fwd_ps_p16: no PS stem plan for N=%d Cin=%d F=%d %dx%d k=%d s=%d p=%d", N, Cin, F, H, W, k, stride, pad);
@@ -436,6 +462,7 @@ extern "C" int fdet_stem_fwd_ps_p16(const float* x, const float* w, const float*
 // written).  frames: [N][3][H][W] uint8, W % 4 == 0.  precision16: one MFMA pass, hi plane only.
 extern "C" int fdet_stem_fwd_ps_u8(const unsigned char* frames, const float* w, const float* bias, void* y_ps, int N, int Cin, int F,
                                    int H, int W, int k, int stride, int pad, int precision16, void* stream) {
+  stem_clear_route();
   FDET_REQUIRE(frames && w && bias && y_ps && N > 0 && F == 64, "stem_fwd_ps_u8: bad arguments (F must be 64)");
   FDET_REQUIRE(stem_mfma_ok(Cin, F, H, W, k, stride, pad) && ((uintptr_t)frames % 4) == 0,
                "stem_fwd_ps_u8: only the PoolResnet stem (3ch k10 s8 p2, W%%4==0, W<=512) on 4-byte aligned frames; got Cin=%d k=%d s=%d p=%d W=%d",
@@ -446,6 +473,7 @@ extern "C" int fdet_stem_fwd_ps_u8(const unsigned char* frames, const float* w, 
 
 extern "C" int fdet_stem_wgrad_bf16x3(const float* x, const float* dy, float* dW, float* db, void* ws, size_t ws_bytes,
                                       int N, int Cin, int F, int H, int W, int k, int stride, int pad, void* stream) {
+  stem_clear_route();
   FDET_REQUIRE(x && dy && dW && db && ws && N > 0 && F > 0, "stem_wgrad_bf16x3: bad arguments");
   if (stem3_wgrad_ok(Cin, F, H, W, k, stride, pad))       // the Resnet stem (k3 s2 p1), fdet_stem_k3.hip
     return stem3_wgrad(x, dy, dW, db, (float*)ws, ws_bytes / 4, N, F, H, W, (hipStream_t)stream, false);
@@ -460,6 +488,7 @@ extern "C" int fdet_stem_wgrad_bf16x3(const float* x, const float* dy, float* dW
 // precision16: one MFMA pass on bf16(dy) x bf16(x), fp32 accumulation; same workspace as fdet_stem_wgrad_bf16x3
 extern "C" int fdet_stem_wgrad_bf16(const float* x, const float* dy, float* dW, float* db, void* ws, size_t ws_bytes,
                                     int N, int Cin, int F, int H, int W, int k, int stride, int pad, void* stream) {
+  stem_clear_route();
   FDET_REQUIRE(x && dy && dW && db && ws && N > 0 && F > 0, "stem_wgrad_bf16: bad arguments");
   if (stem3_wgrad_ok(Cin, F, H, W, k, stride, pad))       // the Resnet / SSD stem (k3 s2 p1), fdet_stem_k3.hip
     return stem3_wgrad(x, dy, dW, db, (float*)ws, ws_bytes / 4, N, F, H, W, (hipStream_t)stream, true);
@@ -473,6 +502,7 @@ extern "C" int fdet_stem_wgrad_bf16(const float* x, const float* dy, float* dW, 
 
 extern "C" int fdet_stem_wgrad(const float* x, const float* dy, float* dW, float* db, void* ws, size_t ws_bytes,
                                int N, int Cin, int F, int H, int W, int k, int stride, int pad, void* stream) {
+  stem_clear_route();
   FDET_REQUIRE(x && dy && dW && db && ws && N > 0 && F > 0, "stem_wgrad: bad arguments");
   StemPlan p;
   FDET_REQUIRE(stem_plan(N, Cin, F, H, W, k, stride, pad, p), "stem_wgrad: unsupported stem k=%d stride=%d pad=%d", k, stride, pad);
@@ -487,6 +517,7 @@ extern "C" int fdet_stem_wgrad(const float* x, const float* dy, float* dW, float
   dim3 grid(p.nblk, p.FP / 64);
   if (k == 10) {
     if (p.lds_wg > 64 * 1024) { if (int rc_ = set_lds_attr((const void*)k_stem_wgrad<10, 8, 2, 3>, (size_t)p.lds_wg, __func__)) return rc_; }
+    stem_note_route(STEM_VALU_K10, STEM_PASS_WGRAD, false, false, false, p.nblk, N * p.Ho);
     hipLaunchKernelGGL((k_stem_wgrad<10, 8, 2, 3>), grid, dim3(256), p.lds_wg, st, x, dy, wsW, wsb, N, F, p.FP, H, W, p.Ho, p.Wo, p.XS, p.DS);
   } else if (H % 2 == 0 && W % 2 == 0 && p.Wo % 4 == 0 && !FDET_ENV_ONCE("FDET_STEM_K3_GENERIC")) {
     // scalar-fed kernel: items = (row, 64-column segment), four 8-wave workgroups per CU, one slab per workgroup
@@ -495,12 +526,14 @@ extern "C" int fdet_stem_wgrad(const float* x, const float* dy, float* dW, float
     int ncu = 256;
     { int dev = 0, v = 0; if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) ncu = v; }
     const int nb = std::min(std::min(nitems, 4 * ncu), p.nblk);            // the workspace holds p.nblk slabs
+    stem_note_route(STEM_VALU_K3_SCALAR, STEM_PASS_WGRAD, false, false, false, nb, nitems);
     hipLaunchKernelGGL(k_stem_wgrad_k3, dim3(nb, p.FP / 64), dim3(512), 0, st, x, dy, wsW, wsb, N, F, p.FP, H, W, p.Ho, p.Wo, nseg);
     if (int rc = check_launch("fdet_stem_wgrad(k3)")) return rc;
     hipLaunchKernelGGL(k_stem_reduce, dim3((p.KK * p.FP + p.FP + 15) / 16), dim3(256), 0, st, wsW, wsb, nb, p.KK, F, p.FP, dW, db);
     return check_launch("fdet_stem_wgrad(reduce)");
   } else {
     if (p.lds_wg > 64 * 1024) { if (int rc_ = set_lds_attr((const void*)k_stem_wgrad<3, 2, 1, 3>, (size_t)p.lds_wg, __func__)) return rc_; }
+    stem_note_route(STEM_VALU_K3_GENERIC, STEM_PASS_WGRAD, false, false, false, p.nblk, N * p.Ho);
     hipLaunchKernelGGL((k_stem_wgrad<3, 2, 1, 3>), grid, dim3(256), p.lds_wg, st, x, dy, wsW, wsb, N, F, p.FP, H, W, p.Ho, p.Wo, p.XS, p.DS);
   }
   if (int rc = check_launch("fdet_stem_wgrad")) return rc;

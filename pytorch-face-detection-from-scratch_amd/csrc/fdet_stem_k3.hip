@@ -255,6 +255,7 @@ int stem3_wgrad(const float* x, const float* dz, float* dW, float* db, float* ws
     attr[p16] = true;
   }
   if (lds > 64 * 1024) return fail(FDET_EINVAL, "stem_wgrad_bf16x3 (k3): rows of %d columns do not fit the LDS plan", W);
+  stem_note_route(STEM_K3_MATRIX, STEM_PASS_WGRAD, p16, false, false, grid, a.nrows);
   if (p16) hipLaunchKernelGGL(k_stem3_wgrad_x3<true>, dim3(grid, fblk), dim3(256), lds, st, a);
   else hipLaunchKernelGGL(k_stem3_wgrad_x3<false>, dim3(grid, fblk), dim3(256), lds, st, a);
   if (int rc = check_launch("fdet_stem_wgrad_bf16x3(k3)")) return rc;
@@ -271,6 +272,7 @@ int stem3_fwd_ps(const float* x, const float* w, const float* bias, void* y_ps, 
   PsStrips sp;
   const int Ho = H / 2, Wo = W / 2;
   if (!ps_geo_strips(N, F, Ho, Wo, g, sp)) return fail(FDET_EINVAL, "stem_fwd_ps (k3): the %dx%d output has no PS layout", Ho, Wo);
+  stem_note_route(STEM_K3_PS_FWD, STEM_PASS_FWD, p16, false, true, N * Ho, N * Ho);
   if (p16)
     hipLaunchKernelGGL(k_stem3_fwd_ps<true>, dim3(N * Ho), dim3(256), 0, st, x, w, bias, reinterpret_cast<ps_bf16x8*>(y_ps), g, sp, F, H, W, Ho, Wo);
   else

@@ -261,6 +261,7 @@ int stem_mfma_fwd(const float* x, const float* w, const float* bias, float* y, i
   const int nblk = a.nrows < 256 ? a.nrows : 256;
   const size_t lds = (size_t)XT * 4;
   { if (int rc_ = set_lds_attr((const void*)k_stem_fwd_mfma, (size_t)(lds), __func__)) return rc_; }
+  stem_note_route(STEM_MFMA, STEM_PASS_FWD, false, false, false, nblk, a.nrows);
   hipLaunchKernelGGL(k_stem_fwd_mfma, dim3(nblk, FP / 64), dim3(256), lds, st, a);
   return check_launch("fdet_stem_fwd(mfma)");
 }
@@ -275,6 +276,7 @@ int stem_mfma_wgrad(const float* x, const float* dy, float* dW, float* db, float
   a.ws = ws; a.wsb = ws + (size_t)nblk * FP * 320;
   const size_t lds = (size_t)(XT + 64 * DYS) * 4;
   { if (int rc_ = set_lds_attr((const void*)k_stem_wgrad_mfma, (size_t)(lds), __func__)) return rc_; }
+  stem_note_route(STEM_MFMA, STEM_PASS_WGRAD, false, false, false, nblk, a.nrows);
   hipLaunchKernelGGL(k_stem_wgrad_mfma, dim3(nblk, FP / 64), dim3(256), lds, st, a);
   if (int rc = check_launch("fdet_stem_wgrad(mfma)")) return rc;
   hipLaunchKernelGGL(k_stem_mfma_reduce, dim3(5, F), dim3(256), 0, st, a.ws, a.wsb, nblk, F, FP, dW, db);

@@ -844,10 +844,12 @@ int stem_x3_fwd(const float* x, const float* w, const float* bias, float* y, int
       (void)hipGetLastError();
       return fail(FDET_ELAUNCH, "stem_fwd(bf16x3): cannot reserve %zu bytes of LDS", 2 * lds + 256);
     }
+    stem_note_route(STEM_X3_PIPE, STEM_PASS_FWD, false, false, false, nblk, a.nrows);
     hipLaunchKernelGGL(k_stem_fwd_x3_pipe<false>, dim3(nblk, FP / 64), dim3(256), 2 * lds + 256, st, a);
     return check_launch("fdet_stem_fwd(bf16x3 pipelined)");
   }
   { if (int rc_ = set_lds_attr((const void*)k_stem_fwd_x3, (size_t)(lds), __func__)) return rc_; }
+  stem_note_route(STEM_X3_SINGLE, STEM_PASS_FWD, false, false, false, nblk, a.nrows);
   hipLaunchKernelGGL(k_stem_fwd_x3, dim3(nblk, FP / 64), dim3(256), lds, st, a);
   return check_launch("fdet_stem_fwd(bf16x3)");
 }
@@ -895,6 +897,7 @@ int stem_x3_fwd_ps(const void* xin, const float* w, const float* bias, void* y_p
     a.Ho = Ho; a.Wo = Wo; a.nrows = a.N * Ho;
     a.ps_hp = g.HP; a.ps_wp = g.WP; a.ps_plane = g.plane; a.ps_img = g.img;
     const int nblk = a.nrows < 256 ? a.nrows : 256;
+    stem_note_route(STEM_X3_PIPE, STEM_PASS_FWD, p16, u8, true, nblk, a.nrows);
     if (u8 && p16) hipLaunchKernelGGL((k_stem_fwd_x3_pipe<true, true, true>), dim3(nblk, 1), dim3(256), ldsb, st, a);
     else if (u8) hipLaunchKernelGGL((k_stem_fwd_x3_pipe<true, false, true>), dim3(nblk, 1), dim3(256), ldsb, st, a);
     else if (p16) hipLaunchKernelGGL((k_stem_fwd_x3_pipe<true, true>), dim3(nblk, 1), dim3(256), ldsb, st, a);
@@ -942,6 +945,7 @@ int stem_x3_wgrad(const float* x, const float* dy, float* dW, float* db, float* 
       a.x = x + (size_t)n0 * CIN * H * W; a.dy = dy + (size_t)n0 * F * Ho * Wo;
       const int nblk = a.nrows < 256 ? a.nrows : 256;
       a.ws = ws + (size_t)slabs * FP * 320; a.wsb = ws + tot * FP * 320 + (size_t)slabs * FP;
+      stem_note_route(STEM_X3_PIPE, STEM_PASS_WGRAD, p16, false, false, nblk, a.nrows);
       if (p16) hipLaunchKernelGGL(k_stem_wgrad_x3_pipe<true>, dim3(nblk, FP / 64), dim3(256), lds2, st, a);
       else hipLaunchKernelGGL(k_stem_wgrad_x3_pipe<false>, dim3(nblk, FP / 64), dim3(256), lds2, st, a);
       if (int rc = check_launch("fdet_stem_wgrad(bf16x3)")) return rc;
@@ -954,6 +958,7 @@ int stem_x3_wgrad(const float* x, const float* dy, float* dW, float* db, float* 
     slabs = a.nrows < 256 ? a.nrows : 256;
     a.ws = ws; a.wsb = ws + (size_t)slabs * FP * 320;
     { if (int rc_ = set_lds_attr((const void*)k_stem_wgrad_x3, (size_t)(lds), __func__)) return rc_; }
+    stem_note_route(STEM_X3_SINGLE, STEM_PASS_WGRAD, false, false, false, slabs, a.nrows);
     hipLaunchKernelGGL(k_stem_wgrad_x3, dim3(slabs, FP / 64), dim3(256), lds, st, a);
     if (int rc = check_launch("fdet_stem_wgrad(bf16x3)")) return rc;
   }

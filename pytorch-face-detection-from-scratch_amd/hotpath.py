@@ -1064,6 +1064,25 @@ def stem_wgrad_x3_ok(N, cin, F_, H, W, k, stride, pad, p16: bool = False) -> boo
     return bool(lib().fdet_stem_wgrad_x3_ok(int(N), int(cin), int(F_), int(H), int(W), int(k), int(stride), int(pad), int(p16)))
 
 
+STEM_ROUTE_FIELDS = ("family", "pass", "p16", "u8", "ps", "launches", "grid", "items")
+STEM_FAMILIES = {1: "valu_k10", 2: "valu_k3_generic", 3: "valu_k3_scalar", 4: "mfma", 5: "x3_single", 6: "x3_pipe", 7: "k3_matrix",
+                 8: "k3_ps_fwd"}
+STEM_PASSES = {1: "fwd", 2: "wgrad"}
+
+
+def stem_last_route() -> dict:
+    """What the last stem forward / weight-gradient call on this thread launched (fdet_stem_last_route): kernel family
+    (None after a refused call), pass ("fwd" / "wgrad"), precision16, uint8 input, PS output, launches of the main kernel
+    (image chunks), and gridDim.x and work items of the first launch."""
+    import ctypes
+    out = (ctypes.c_int * len(STEM_ROUTE_FIELDS))()
+    check(lib().fdet_stem_last_route(out, len(out)), "fdet_stem_last_route")
+    r = dict(zip(STEM_ROUTE_FIELDS, list(out)))
+    r["family"] = STEM_FAMILIES.get(r["family"])
+    r["pass"] = STEM_PASSES.get(r["pass"])
+    return r
+
+
 def stem_wgrad(x, dy, dW, db, ws, k, stride, pad, x3: bool = False, p16: bool = False):
     Nn, cin, H, W = x.shape
     F_ = dW.shape[0]
