@@ -858,6 +858,70 @@ int fdet_render_boxes(const uint8_t* src, const fdet_aug_image* src_table, const
                       const fdet_aug_image* dst_table, const fdet_aug_image* h_dst_table, int outline, int pixelate,
                       int blocks, int red, int green, int blue, int32_t* ws, void* stream);
 
+/* ---- tracking faces across frame sequences (csrc/fdet_track.hip) --------------------------
+ * Associates the detections of consecutive frames with a table of FDET_TRACK_SLOTS tracks per sequence: identity
+ * (an id per track, never reused) and gap bridging (a track the detector misses is still emitted for emit_misses
+ * frames).  No counterpart in the reference.  One workgroup per sequence walks its frames in order; no host
+ * synchronisation.  Integer arithmetic throughout; the only floating-point operations are the fp32 sums of step 1 and
+ * the one double multiply of step 3.
+ *
+ * State: per sequence one fdet_track_seq followed by FDET_TRACK_SLOTS fdet_track, in device memory; all-zero bytes are
+ * a fresh state.  A slot is live when its id != 0; a free slot is all zero.  Corners are kept in 1/16 pixel. */
+#define FDET_TRACK_SLOTS     128     /* live tracks per sequence */
+#define FDET_TRACK_MAX_DETS  256     /* valid detections per frame */
+#define FDET_TRACK_MAX_COORD 16384   /* |corner| bound, keeps every product below 2^62 */
+
+typedef struct fdet_track {
+  int32_t id, x1q, y1q, x2q, y2q, hits, misses, born;
+  float score;
+  int32_t reserved[3];
+} fdet_track;                        /* 48 bytes */
+typedef struct fdet_track_seq {
+  int32_t next_id, frame, dropped, reserved;
+} fdet_track_seq;                    /* 16 bytes, followed by FDET_TRACK_SLOTS fdet_track */
+
+/* n_seq * (16 + 128 * 48) bytes; 0 for n_seq < 1. */
+size_t fdet_track_state_bytes(int n_seq);
+
+/* rows [T,K,5] fp32 [score,x,y,w,h] + counts [T] int32: what the reducers and TiledDetector.detect return, one row of
+ * `rows` per frame.  seq_offset [n_seq+1] int32 (device) / h_seq_offset (the same values in host memory): sequence s
+ * owns frames seq_offset[s]..seq_offset[s+1]-1 in time order.  state: fdet_track_state_bytes(n_seq) bytes, updated in
+ * place.  Per frame t of a sequence, in order:
+ *   1. valid detections.  Only the first counts[t] rows are read.  A row is valid when score, x, y, w, h are finite,
+ *      every corner X1 = rint(x), Y1 = rint(y), X2 = rint(x + w), Y2 = rint(y + h) (fp32 sums, half to even, then
+ *      converted to int) has |c| <= FDET_TRACK_MAX_COORD, and X2 - X1 >= 1 and Y2 - Y1 >= 1.  An invalid row takes
+ *      no part in anything below and gets det_ids = 0.
+ *   2. track box in pixels: P = (q + 8) >> 4 per corner (arithmetic shift: floor).
+ *   3. overlap of a live track and a valid detection: iw = min(P.x2, X2) - max(P.x1, X1), ih likewise,
+ *      inter = (iw > 0 && ih > 0) ? iw * ih : 0, uni = areaT + areaD - inter, all int64.  The pair is eligible when
+ *      (double)inter > iou_threshold * (double)uni.
+ *   4. greedy matching: until no eligible pair remains among unmatched tracks and unmatched detections, the pair with
+ *      the largest IoU is matched; two IoUs compare exactly, as inter_a * uni_b against inter_b * uni_a in int64; ties
+ *      go to the lower slot, then to the lower row index.
+ *   5. matched track: q <- (alpha256 * 16 * D + (256 - alpha256) * q + 128) >> 8 per corner with D the detection's
+ *      corner (int64, arithmetic shift); hits += 1; misses = 0; score = the detection's score.  alpha256 = 256 copies
+ *      the detection.  x2q - x1q >= 16 and y2q - y1q >= 16 always hold, so P never degenerates.
+ *   6. unmatched live track: misses += 1; when misses > max_misses the slot is freed (all zero).  Frees come before
+ *      births: a freed slot can be taken in the same frame.
+ *   7. births: the unmatched valid detections in row order; one gives birth when score >= birth_score (fp32).  It takes
+ *      the lowest free slot: id = ++next_id, q = 16 * D, hits = 1, misses = 0, born = frame, score = its score.  With
+ *      no free slot the detection is dropped and dropped += 1; that is not an error.
+ *   8. det_ids [T,K] int32: det_ids[t][j] = the id row j was matched to or born as, else 0 (rows >= counts[t] too).
+ *   9. emit, in slot order, every live track with hits >= min_hits and misses <= emit_misses:
+ *      out_rows [T,128,5] fp32 [score, P.x1, P.y1, P.x2 - P.x1, P.y2 - P.y1], out_ids [T,128], out_misses [T,128],
+ *      out_counts [T]; rows past out_counts[t] are zeroed.  Then frame += 1.
+ * Rejection: a sequence with a counts[t] outside 0..K or a frame with more than FDET_TRACK_MAX_DETS valid rows is
+ * rejected as a whole: its state stays as it was before the call, all its frames get out_counts = 0 and zeroed
+ * out_rows / out_ids / out_misses / det_ids, and rejected[0] += 1, which the caller must read as an error.  Other
+ * sequences are unaffected; nothing is ever truncated.
+ * Validated on the host, FDET_EINVAL and nothing launched: h_seq_offset not monotone from 0 to T; n_seq < 1, T < 0 or
+ * K < 0; alpha256 outside 1..256; max_misses < 0, min_hits < 1, emit_misses outside 0..max_misses; iou_threshold not
+ * in [0, 1); a required pointer NULL (rows and det_ids are required when T * K > 0, counts and the out_* when T > 0). */
+int fdet_track_update(const float* rows, const int32_t* counts, const int32_t* seq_offset, const int32_t* h_seq_offset,
+                      int n_seq, int T, int K, double iou_threshold, int alpha256, int max_misses, int min_hits,
+                      int emit_misses, float birth_score, void* state, float* out_rows, int32_t* out_ids,
+                      int32_t* out_misses, int32_t* out_counts, int32_t* det_ids, uint64_t* rejected, void* stream);
+
 /* Depthwise-separable residual block (models/SeparableCNN.py:40-51; none of its three convs has a bias):
  *   a = lrelu(W1 x)   b = lrelu(dw3x3(a), pad 1)   c = W2 b   e = c * drop_scale[n,c] + x   out = maxpool2x2(e) | e
  * fdet_sepblock_fwd runs the whole block in ONE kernel on fp32 NCHW tensors: both 1x1 convs as bf16x3 GEMMs on the matrix

@@ -36,36 +36,36 @@ def write_wider_results(path, names, rows, counts) -> None:
                 f.write(f"{x:.0f} {y:.0f} {w:.0f} {h:.0f} {s:.4f}\n")
 
 
-def main(argv=None):
-    """Parse and check the options, then `run` them."""
-    ap = argparse.ArgumentParser()
+def add_model_arguments(ap) -> None:
+    """The options that choose and load the network (shared with track_frames)."""
     ap.add_argument("--model", choices=("poolresnet", "resnet", "separablecnn", "ssd"), default="poolresnet")
     ap.add_argument("--filters", type=int, default=None, help="default: 128 (poolresnet, separablecnn), 64 (resnet), 16 (ssd)")
     ap.add_argument("--patches", type=int, default=None, help="default: 10 (poolresnet), 15 (resnet); separablecnn fixes 16")
     ap.add_argument("--size", type=int, default=480)
     ap.add_argument("--precision", type=int, choices=(32, 16), default=32)
     ap.add_argument("--checkpoint", default=None)
-    ap.add_argument("--images", required=True)
-    ap.add_argument("--out", required=True)
+    ap.add_argument("--probability-threshold", type=float, default=0.5)
+    ap.add_argument("--iou-threshold", type=float, default=0.5)
+
+
+def add_tile_arguments(ap) -> None:
+    """The options of `TiledDetector`'s windows (shared with track_frames)."""
     ap.add_argument("--tile", type=int, nargs="*", default=[480], help="tile side(s) in source pixels; none: whole image only")
     ap.add_argument("--overlap", type=float, default=0.25)
     ap.add_argument("--no-whole", action="store_true")
     ap.add_argument("--edge-margin", type=float, default=0.0)
-    ap.add_argument("--probability-threshold", type=float, default=0.5)
-    ap.add_argument("--iou-threshold", type=float, default=0.5)
-    ap.add_argument("--pred-dir", default=None, help="also write DIR/<event>/<image>.txt, the WIDER protocol's layout")
-    ap.add_argument("--batch-images", type=int, default=64, help="source images per detect() call")
-    ap.add_argument("--device-jpeg", action="store_true",
-                    help="decode baseline JPEGs with the device decoder (datasets/jpeg.py) instead of PIL; same bytes")
-    ap.add_argument("--flip", action="store_true", help="every window a second time, mirrored left to right")
-    ap.add_argument("--vote", action="store_true", help="box voting: a kept box is the score-weighted mean of its cluster")
-    ap.add_argument("--min-votes", type=int, default=1, help="with --vote: leave out boxes with fewer members than this")
+
+
+def add_draw_arguments(ap) -> None:
+    """--draw and the options that need it (shared with track_frames); `check_draw_arguments` checks them."""
     ap.add_argument("--draw", default=None, metavar="DIR", help="also write every image, rendered, under DIR")
     ap.add_argument("--anonymize", choices=("pixelate",), default=None, help="with --draw: pixelate every box")
     ap.add_argument("--blocks", type=int, default=None, help="with --draw --anonymize: cells along the longer side of a box (8)")
     ap.add_argument("--draw-format", choices=("png", "jpg"), default=None, help="with --draw: the files' format (png)")
     ap.add_argument("--no-outline", action="store_true", help="with --draw: no outlines")
-    args = ap.parse_args(argv)
+
+
+def check_draw_arguments(ap, args) -> None:
     if args.draw is None:
         for flag, given in (("--anonymize", args.anonymize is not None), ("--blocks", args.blocks is not None),
                             ("--draw-format", args.draw_format is not None), ("--no-outline", args.no_outline)):
@@ -73,6 +73,25 @@ def main(argv=None):
                 ap.error(f"{flag} needs --draw")
     if args.blocks is not None and args.blocks < 1:
         ap.error("--blocks must be >= 1")
+
+
+def main(argv=None):
+    """Parse and check the options, then `run` them."""
+    ap = argparse.ArgumentParser()
+    add_model_arguments(ap)
+    ap.add_argument("--images", required=True)
+    ap.add_argument("--out", required=True)
+    add_tile_arguments(ap)
+    ap.add_argument("--pred-dir", default=None, help="also write DIR/<event>/<image>.txt, the WIDER protocol's layout")
+    ap.add_argument("--batch-images", type=int, default=64, help="source images per detect() call")
+    ap.add_argument("--device-jpeg", action="store_true",
+                    help="decode baseline JPEGs with the device decoder (datasets/jpeg.py) instead of PIL; same bytes")
+    ap.add_argument("--flip", action="store_true", help="every window a second time, mirrored left to right")
+    ap.add_argument("--vote", action="store_true", help="box voting: a kept box is the score-weighted mean of its cluster")
+    ap.add_argument("--min-votes", type=int, default=1, help="with --vote: leave out boxes with fewer members than this")
+    add_draw_arguments(ap)
+    args = ap.parse_args(argv)
+    check_draw_arguments(ap, args)
     if args.min_votes < 1:
         ap.error("--min-votes must be >= 1")
     if args.min_votes > 1 and not args.vote:
@@ -80,11 +99,9 @@ def main(argv=None):
     return run(args)
 
 
-def run(args):
-    """What `main` does with its parsed options."""
-    from .datasets.WIDERFace.annotations import bank_from_files
+def load_model(args):
+    """The network the model options describe, on the GPU, in eval mode, with the checkpoint loaded."""
     from .run_validation_epoch import load_checkpoint
-    from .tiling import TiledDetector
     shape = (3, args.size, args.size)
     kw = dict(probability_threshold=args.probability_threshold, iou_threshold=args.iou_threshold)
     if args.model == "ssd":
@@ -109,7 +126,14 @@ def run(args):
         log_path = Path("logs/out_detect_images.log")
         log_path.parent.mkdir(parents=True, exist_ok=True)
         load_checkpoint(Meta(model=model, lr=1e-4, log_path=log_path), args.checkpoint)
-    model.eval()
+    return model.eval()
+
+
+def run(args):
+    """What `main` does with its parsed options."""
+    from .datasets.WIDERFace.annotations import bank_from_files
+    from .tiling import TiledDetector
+    model = load_model(args)
     root = Path(args.images)
     paths = sorted(p for p in root.rglob("*") if p.suffix.lower() in EXTENSIONS)
     if not paths:

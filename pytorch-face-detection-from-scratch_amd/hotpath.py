@@ -405,6 +405,57 @@ def tile_merge_vote(rows: torch.Tensor, counts: torch.Tensor, d_tiles: torch.Ten
 
 
 # ------------------------------------------------------------------------------------------
+# Tracking across frame sequences (csrc/fdet_track.hip; tracking.py drives this)
+# ------------------------------------------------------------------------------------------
+TRACK_SLOTS, TRACK_MAX_DETS, TRACK_MAX_COORD = 128, 256, 16384      # FDET_TRACK_* of include/fdet.h
+TRACK_STATE_BYTES = 16 + TRACK_SLOTS * 48                           # per sequence
+
+
+def track_state_bytes(n_seq: int) -> int:
+    return int(lib().fdet_track_state_bytes(int(n_seq)))
+
+
+def track_update(rows: torch.Tensor, counts: torch.Tensor, seq_offset: torch.Tensor, h_seq_offset, state: torch.Tensor,
+                 iou_threshold: float, alpha256: int, max_misses: int, min_hits: int, emit_misses: int, birth_score: float,
+                 rejected: Optional[torch.Tensor] = None):
+    """fdet_track_update: rows (T,K,5) [score,x,y,w,h] + counts (T,) int32 of T frames; seq_offset (n_seq+1,) int32 on the
+    device and h_seq_offset, the same values as a numpy int32 array: sequence s owns frames seq_offset[s]..seq_offset[s+1]-1
+    in time order; state: (n_seq * 6160,) uint8 on the device, updated in place (zeros = fresh) ->
+    (out_rows (T,128,5), out_ids (T,128) int32, out_misses (T,128) int32, out_counts (T,) int32, det_ids (T,K) int32,
+    rejected (1,) int64 counter, += 1 per rejected sequence).  One launch, no host synchronisation."""
+    import numpy as np
+    if rows.dim() != 3 or rows.shape[2] != 5 or rows.dtype != F32:
+        raise ValueError(f"track_update: rows must be (T,K,5) float32, got {tuple(rows.shape)} {rows.dtype}")
+    T, K = int(rows.shape[0]), int(rows.shape[1])
+    if not isinstance(h_seq_offset, np.ndarray) or h_seq_offset.dtype != np.int32 or h_seq_offset.ndim != 1 or \
+            not h_seq_offset.flags.c_contiguous or h_seq_offset.size < 2:
+        raise ValueError("track_update: h_seq_offset must be a contiguous (n_seq+1,) numpy int32 array")
+    n = int(h_seq_offset.size) - 1
+    if tuple(counts.shape) != (T,) or counts.dtype != I32 or tuple(seq_offset.shape) != (n + 1,) or seq_offset.dtype != I32:
+        raise ValueError("track_update: counts must be (T,) int32 and seq_offset (n_seq+1,) int32")
+    if state.dtype != torch.uint8 or state.numel() != n * TRACK_STATE_BYTES:
+        raise ValueError(f"track_update: state must be {n * TRACK_STATE_BYTES} uint8 for {n} sequence(s), got {state.numel()}")
+    dev = rows.device
+    out_rows = torch.empty(T, TRACK_SLOTS, 5, dtype=F32, device=dev)
+    out_ids = torch.empty(T, TRACK_SLOTS, dtype=I32, device=dev)
+    out_misses = torch.empty(T, TRACK_SLOTS, dtype=I32, device=dev)
+    out_counts = torch.empty(T, dtype=I32, device=dev)
+    det_ids = torch.empty(T, K, dtype=I32, device=dev)
+    if rejected is None:
+        rejected = torch.zeros(1, dtype=torch.int64, device=dev)
+
+    def p(t, dtype=F32):                                     # an empty tensor has no storage to point at
+        return ptr(t, dtype) if t.numel() else None
+
+    check(lib().fdet_track_update(p(rows.contiguous()), p(counts.contiguous(), I32), ptr(seq_offset.contiguous(), I32),
+                                  h_seq_offset.ctypes.data, n, T, K, float(iou_threshold), int(alpha256), int(max_misses),
+                                  int(min_hits), int(emit_misses), float(birth_score), ptr(state, torch.uint8), p(out_rows),
+                                  p(out_ids, I32), p(out_misses, I32), p(out_counts, I32), p(det_ids, I32),
+                                  ptr(rejected, torch.int64), stream()), "fdet_track_update")
+    return out_rows, out_ids, out_misses, out_counts, det_ids, rejected
+
+
+# ------------------------------------------------------------------------------------------
 # Baseline JPEG decode (csrc/fdet_jpeg.hip; datasets/jpeg.py drives these)
 # ------------------------------------------------------------------------------------------
 JPEG_UNSUPPORTED, JPEG_ECORRUPT = -4, -5                     # FDET_JPEG_* of include/fdet.h

@@ -1,0 +1,118 @@
+"""Detect and track faces through a directory of video frames and write MOTChallenge text.
+
+    python -m fdet_amd.track_frames --checkpoint CKPT --frames DIR --out FILE [--model poolresnet --filters 128]
+        [--tiled --tile 480 --overlap 0.25] [--iou 0.3 --alpha 0.5 --max-misses 5 --min-hits 2 --emit-misses N]
+        [--draw DIR [--anonymize pixelate] [--blocks N] [--draw-format png|jpg] [--no-outline]]
+
+The images directly under DIR (.jpg .jpeg .png .bmp), sorted by name, are the frames of ONE sequence and must all have the
+same size.  They are detected in chunks of --max-frames: without --tiled each frame is resized whole to the network's input,
+with --tiled `TiledDetector` also runs the --tile windows.  `tracking.FaceTracker` carries its state from chunk to chunk.
+FILE receives one line per emitted track and frame, `frame,id,x,y,w,h,score,-1,-1,-1` with frames counted from 1 and the box
+in source pixels.  `--draw DIR` writes every frame with the TRACKER's boxes rendered into it (`render.render_detections`), so
+with `--anonymize pixelate` a face the detector misses for up to --emit-misses frames stays covered.  The model options are
+those of `detect_images`.  Files only: there is no camera or video-container input.
+"""
+import argparse
+import os
+from pathlib import Path
+
+from .detect_images import EXTENSIONS, add_draw_arguments, add_model_arguments, add_tile_arguments, check_draw_arguments
+
+
+def frame_paths(root):
+    """The frames of DIR in name order."""
+    return sorted((p for p in Path(root).iterdir() if p.is_file() and p.suffix.lower() in EXTENSIONS), key=lambda p: p.name)
+
+
+def frame_size(paths):
+    """(w, h) shared by every file (read from the headers), or ValueError naming the first that differs."""
+    from PIL import Image
+    first = None
+    for p in paths:
+        with Image.open(p) as im:
+            size = im.size
+        if first is None:
+            first = size
+        elif size != first:
+            raise ValueError(f"{p.name} is {size[0]}x{size[1]}, {paths[0].name} is {first[0]}x{first[1]}")
+    return first
+
+
+def write_mot(f, first_frame, rows, counts, ids) -> int:
+    """Append the tracks of consecutive frames (host arrays) to the open text file; first_frame counts from 1."""
+    n = 0
+    for t in range(len(counts)):
+        for k in range(int(counts[t])):
+            s, x, y, w, h = rows[t, k].tolist()
+            f.write(f"{first_frame + t},{int(ids[t, k])},{x:.0f},{y:.0f},{w:.0f},{h:.0f},{s:.4f},-1,-1,-1\n")
+            n += 1
+    return n
+
+
+def main(argv=None):
+    """Parse and check the options (the frames' sizes included), then `run` them."""
+    ap = argparse.ArgumentParser()
+    add_model_arguments(ap)
+    ap.add_argument("--frames", required=True, metavar="DIR")
+    ap.add_argument("--out", required=True)
+    ap.add_argument("--tiled", action="store_true", help="also run the --tile windows of every frame (TiledDetector)")
+    add_tile_arguments(ap)
+    ap.add_argument("--max-frames", type=int, default=256, help="frames per detection chunk")
+    ap.add_argument("--iou", type=float, default=0.3, help="least overlap of a track and a detection")
+    ap.add_argument("--alpha", type=float, default=0.5, help="weight of the new detection in a track's box")
+    ap.add_argument("--max-misses", type=int, default=5)
+    ap.add_argument("--min-hits", type=int, default=2)
+    ap.add_argument("--emit-misses", type=int, default=None, help="frames a missed track is still emitted (--max-misses)")
+    ap.add_argument("--birth-score", type=float, default=0.0)
+    add_draw_arguments(ap)
+    args = ap.parse_args(argv)
+    check_draw_arguments(ap, args)
+    if args.max_frames < 1:
+        ap.error("--max-frames must be >= 1")
+    if not os.path.isdir(args.frames):
+        ap.error(f"--frames: {args.frames} is not a directory")
+    args.paths = frame_paths(args.frames)
+    if not args.paths:
+        ap.error(f"--frames: no image in {args.frames}")
+    try:
+        args.frame_size = frame_size(args.paths)
+    except ValueError as e:
+        ap.error(f"--frames: the frames of a sequence must have one size, but {e}")
+    return run(args)
+
+
+def run(args):
+    """What `main` does with its parsed options."""
+    from .datasets.WIDERFace.annotations import bank_from_files
+    from .detect_images import load_model
+    from .tiling import TiledDetector
+    from .tracking import FaceTracker
+    tracker = FaceTracker(1, iou_threshold=args.iou, alpha=args.alpha, max_misses=args.max_misses, min_hits=args.min_hits,
+                          emit_misses=args.emit_misses, birth_score=args.birth_score)         # checks its options first
+    model = load_model(args)
+    det = TiledDetector(model, tile_sizes=tuple(args.tile) if args.tiled else (), overlap=args.overlap,
+                        include_whole=not (args.tiled and args.no_whole), edge_margin=args.edge_margin,
+                        max_out=256)                        # fdet_track_update takes at most 256 valid rows per frame
+    paths, lines = args.paths, 0
+    out = Path(args.out)
+    if out.parent != Path(""):
+        out.parent.mkdir(parents=True, exist_ok=True)
+    with open(out, "w") as f:
+        for a in range(0, len(paths), args.max_frames):
+            chunk = paths[a:a + args.max_frames]
+            bank = bank_from_files(chunk, "cuda")
+            rows, counts = det.detect(bank, range(len(bank)))
+            res = tracker.update(rows, counts)
+            if args.draw is not None:
+                from .render import render_detections, save_images
+                drawn = render_detections(bank, res.rows, res.counts, outline=not args.no_outline, anonymize=args.anonymize,
+                                          blocks=8 if args.blocks is None else args.blocks)
+                save_images(drawn, [(Path(args.draw) / p.name).with_suffix("." + (args.draw_format or "png")) for p in chunk])
+            lines += write_mot(f, a + 1, res.rows.cpu().numpy(), res.counts.cpu().numpy(), res.ids.cpu().numpy())
+    snap = tracker.snapshot()
+    print(f"{len(paths)} frames, {int(snap['seq']['next_id'][0])} tracks, {lines} lines -> {args.out}")
+    return {"frames": len(paths), "tracks": int(snap["seq"]["next_id"][0]), "lines": lines, "dropped": tracker.dropped}
+
+
+if __name__ == "__main__":
+    main()

@@ -1,0 +1,110 @@
+"""Track faces across frame sequences on the device: identity from frame to frame, and bridging of the detector's gaps.
+
+    tr = FaceTracker(max_misses=3, min_hits=1)
+    rows, counts = model.reduce_bounding_boxes.forward_batch(model.forward_frames(frames))     # or TiledDetector.detect
+    res = tr.update(rows, counts)                   # the frames of one call are consecutive; the state is carried on
+    res.ids[t, :res.counts[t]]                      # the same face keeps its id from frame to frame
+
+A per-frame anonymiser shows a face in every frame the detector misses it.  The tracker goes on emitting a missed track
+for `emit_misses` frames at its last box, so rendering the tracker's rows instead of the detector's closes those gaps:
+
+    anon = render_detections(bank, res.rows, res.counts, anonymize="pixelate", outline=False)
+
+`fdet_track_update` (csrc/fdet_track.hip) does the association in one launch per call, one workgroup per sequence, with
+exact integer arithmetic; include/fdet.h states the rule step by step, tests/track_cpu_ref.py restates it in numpy and
+DESIGN.md 5h gives the limits and the measurements.  The reference project has no counterpart.
+"""
+from __future__ import annotations
+
+from collections import namedtuple
+from typing import Optional
+
+import numpy as np
+import torch
+
+from . import hotpath as hp
+from ._native import FdetError
+
+TRACK_DTYPE = np.dtype([("id", "<i4"), ("x1q", "<i4"), ("y1q", "<i4"), ("x2q", "<i4"), ("y2q", "<i4"), ("hits", "<i4"),
+                        ("misses", "<i4"), ("born", "<i4"), ("score", "<f4"), ("reserved", "<i4", (3,))])     # fdet_track
+SEQ_DTYPE = np.dtype([("next_id", "<i4"), ("frame", "<i4"), ("dropped", "<i4"), ("reserved", "<i4")])         # fdet_track_seq
+STATE_DTYPE = np.dtype([("seq", SEQ_DTYPE), ("tracks", TRACK_DTYPE, (hp.TRACK_SLOTS,))])
+assert TRACK_DTYPE.itemsize == 48 and SEQ_DTYPE.itemsize == 16 and STATE_DTYPE.itemsize == hp.TRACK_STATE_BYTES
+
+TrackResult = namedtuple("TrackResult", "rows counts ids misses det_ids")
+TrackResult.__doc__ = """rows (T,128,5) fp32 [score,x,y,w,h] and counts (T,) int32: the tracks emitted per frame, in the
+shape `render_detections` takes; ids / misses (T,128) int32: each emitted track's id and the frames since it was last
+detected (0 = detected in this frame); det_ids (T,K) int32: the id each input row was matched to or born as, 0 = none."""
+
+
+def alpha_to_256(alpha: float) -> int:
+    """round(alpha * 256), which must lie in 1..256."""
+    a = int(round(float(alpha) * 256))
+    if not 1 <= a <= 256:
+        raise ValueError(f"FaceTracker: alpha={alpha} gives alpha256={a}, 1..256 are supported (alpha in (0, 1])")
+    return a
+
+
+class FaceTracker:
+    """n_seq independent sequences (cameras, files), each with 128 track slots.  iou_threshold: least overlap of a track and a
+    detection that may be matched, in [0, 1).  alpha: weight of the new detection in a matched track's box (1 = take the
+    detection, smaller = smoother).  max_misses: a track that goes unmatched for more frames than this dies.  min_hits: a
+    track is emitted from its min_hits-th detection on (2 keeps one-frame false positives out).  emit_misses: an unmatched
+    track is emitted for this many frames (None = max_misses, 0 = never).  birth_score: least score that starts a track."""
+
+    def __init__(self, n_seq: int = 1, iou_threshold: float = 0.3, alpha: float = 0.5, max_misses: int = 5, min_hits: int = 2,
+                 emit_misses: Optional[int] = None, birth_score: float = 0.0, device="cuda"):
+        self.n_seq = int(n_seq)
+        if self.n_seq < 1:
+            raise ValueError(f"FaceTracker: n_seq={n_seq} must be >= 1")
+        self.iou_threshold = float(iou_threshold)
+        if not 0.0 <= self.iou_threshold < 1.0:
+            raise ValueError(f"FaceTracker: iou_threshold={iou_threshold} must be in [0, 1)")
+        self.alpha256 = alpha_to_256(alpha)
+        self.max_misses, self.min_hits = int(max_misses), int(min_hits)
+        self.emit_misses = self.max_misses if emit_misses is None else int(emit_misses)
+        if self.max_misses < 0 or self.min_hits < 1 or not 0 <= self.emit_misses <= self.max_misses:
+            raise ValueError(f"FaceTracker: max_misses={max_misses} must be >= 0, min_hits={min_hits} >= 1 and "
+                             f"emit_misses={emit_misses} in 0..max_misses")
+        self.birth_score = float(birth_score)
+        self.device = torch.device(device)
+        self.state = torch.zeros(self.n_seq * hp.TRACK_STATE_BYTES, dtype=torch.uint8, device=self.device)
+
+    def reset(self) -> None:
+        """Forget every track; ids start again from 1."""
+        self.state.zero_()
+
+    def snapshot(self) -> np.ndarray:
+        """Host copy of the state: (n_seq,) records {seq: fdet_track_seq, tracks: (128,) fdet_track}."""
+        return self.state.cpu().numpy().view(STATE_DTYPE).copy()
+
+    @property
+    def dropped(self) -> int:
+        """Detections that found no free slot so far, over all sequences (a host read)."""
+        return int(self.snapshot()["seq"]["dropped"].astype(np.int64).sum())
+
+    def update(self, rows: torch.Tensor, counts: torch.Tensor, seq_offset=None) -> TrackResult:
+        """rows (T,K,5) [score,x,y,w,h] and counts (T,) int32 on the tracker's device, as the reducers' `forward_batch` and
+        `TiledDetector.detect` return them, one row per frame.  seq_offset: n_seq + 1 integers, sequence s owns frames
+        seq_offset[s]..seq_offset[s+1]-1 in time order (a sequence may own none); None with n_seq == 1: all T frames.
+        Raises FdetError when a sequence is rejected (a count outside 0..K, or more than 256 valid rows in a frame): the
+        state of such a sequence is as it was before the call, the others have advanced.  That counter is the only host
+        read."""
+        T = int(rows.shape[0])
+        if seq_offset is None:
+            if self.n_seq != 1:
+                raise ValueError(f"FaceTracker.update: seq_offset is needed with n_seq={self.n_seq}")
+            seq_offset = (0, T)
+        h_off = np.ascontiguousarray(np.asarray(seq_offset.cpu() if isinstance(seq_offset, torch.Tensor) else seq_offset,
+                                                dtype=np.int64).reshape(-1).astype(np.int32))
+        if h_off.size != self.n_seq + 1:
+            raise ValueError(f"FaceTracker.update: seq_offset must hold n_seq + 1 = {self.n_seq + 1} values, got {h_off.size}")
+        d_off = torch.from_numpy(h_off).to(self.device)
+        out_rows, out_ids, out_misses, out_counts, det_ids, rejected = hp.track_update(
+            rows, counts, d_off, h_off, self.state, self.iou_threshold, self.alpha256, self.max_misses, self.min_hits,
+            self.emit_misses, self.birth_score)
+        n_rej = int(rejected.item())
+        if n_rej:
+            raise FdetError(f"FaceTracker.update: {n_rej} sequence(s) rejected by fdet_track_update (a count outside 0..K={int(rows.shape[1])}, "
+                            f"or more than {hp.TRACK_MAX_DETS} valid detections in one frame); their state is unchanged")
+        return TrackResult(out_rows, out_counts, out_ids, out_misses, det_ids)
