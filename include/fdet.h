@@ -922,6 +922,90 @@ int fdet_track_update(const float* rows, const int32_t* counts, const int32_t* s
                       int emit_misses, float birth_score, void* state, float* out_rows, int32_t* out_ids,
                       int32_t* out_misses, int32_t* out_counts, int32_t* det_ids, uint64_t* rejected, void* stream);
 
+/* ---- face chips and the sharpest chip of each track (csrc/fdet_chips.hip) ------------------
+ * fdet_chip_extract cuts one fixed-size square crop ("chip") per detection row out of the image bank;
+ * fdet_chip_best_update keeps, per track id, the sharpest chip seen so far.  No counterpart in the reference.  Integer
+ * arithmetic throughout; the only floating-point operations are the fp32 sums and roundings of step 1. */
+#define FDET_CHIP_MIN_SIZE 8
+#define FDET_CHIP_MAX_SIZE 256
+#define FDET_CHIP_MAX_SIDE 8192      /* source window side; bounds the work per chip (S*S taps) */
+#define FDET_CHIP_MAX_CHIPS (1 << 20)
+
+typedef struct fdet_chip_info {
+  int32_t image, row;        /* rows[image][row] */
+  int32_t wx0, wy0, S;       /* source window [wx0, wx0+S) x [wy0, wy0+S) in pixels of table[image] */
+  int32_t inside256;         /* floor(256 * window pixels inside the image / S^2) */
+  int32_t flags;             /* bit 0: valid */
+  int32_t reserved;
+  int64_t sharp;
+} fdet_chip_info;            /* 40 bytes */
+
+/* bank / table / h_table: an image bank as above.  rows [n_images,K,5] fp32 [score,x,y,w,h] in source pixels (NULL only
+ * with K = 0) and counts [n_images] int32 on the device: what the reducers, TiledDetector.detect and the tracker return;
+ * h_counts: the same values in host memory.  chip_offset [n_images+1] int32 (device) / h_chip_offset (host): the
+ * exclusive prefix sum of h_counts.  Chip chip_offset[i] + j belongs to row j of image i; M = h_chip_offset[n_images].
+ * chips: [M,C,C,3] uint8 (planar = 0, the bank's HWC layout) or [M,3,C,C] (planar = 1); info [M].  Per chip:
+ *   1. corners as step 1 of fdet_track_update: X1 = rint(x), Y1 = rint(y), X2 = rint(x + w), Y2 = rint(y + h) (fp32 sums,
+ *      half to even).  The row is valid when score, x, y, w, h are finite, every |corner| <= 16384, X2 - X1 >= 1 and
+ *      Y2 - Y1 >= 1, the box meets the image (X2 > 0, X1 < W, Y2 > 0, Y1 < H) and the S of step 2 is <=
+ *      FDET_CHIP_MAX_SIDE.  An invalid row gives an all-zero chip and an info of zeros except image and row; that is
+ *      not an error.
+ *   2. square window with margin: side = max(X2 - X1, Y2 - Y1); m = (side * margin256 + 128) >> 8; S = side + 2 * m;
+ *      wx0 = (X1 + X2 - S) >> 1, wy0 = (Y1 + Y2 - S) >> 1 (arithmetic shift: floor).
+ *   3. per-axis taps of chip column u of C (rows alike): pairs (window index i in 0..S-1, integer weight) whose weights
+ *      sum to D.  S >= C, exact area averaging, D = S: every i with w = min((i+1)*C, (u+1)*S) - max(i*C, u*S) > 0, weight
+ *      w (S == C: one tap, a copy).  S < C, bilinear in integers, D = 2*C: t = (2*u + 1)*S - C, i0 = floor(t / (2*C))
+ *      (may be -1), f = t - i0*2*C; the taps are (i0, 2*C - f) and (i0 + 1, f), indices clamped to 0..S-1.
+ *   4. window index i reads image column clamp(wx0 + i, 0, W-1), rows alike (edge replication).  Per channel
+ *      value = (sum_y sum_x wy*wx*p + D*D/2) / (D*D) in int64, integer division; D*D*255 < 2^35.
+ *   5. inside = max(0, min(wx0+S, W) - max(wx0, 0)) * (the same in y); inside256 = (inside * 256) / (S*S) in int64.
+ *   6. sharpness of the chip as written: L = (77*R + 150*G + 29*B + 128) >> 8;
+ *      sharp = sum over 1 <= v,u <= C-2 of (4*L(v,u) - L(v-1,u) - L(v+1,u) - L(v,u-1) - L(v,u+1))^2 in int64
+ *      (at C = 256 at most 254^2 * 1020^2 = 67 122 446 400 < 2^40).
+ * Validated on the host, FDET_EINVAL and nothing written: C outside 8..256; margin256 outside 0..256; planar not 0 | 1;
+ * K < 0; n_images < 1; an h_counts[i] outside 0..K; h_chip_offset not the prefix sum of h_counts; M >
+ * FDET_CHIP_MAX_CHIPS; a table row of non-positive size; a required pointer NULL (chips and info are required when
+ * M > 0).  M = 0 is success with no launch. */
+int fdet_chip_extract(const uint8_t* bank, const fdet_aug_image* table, const fdet_aug_image* h_table, int n_images,
+                      const float* rows, const int32_t* counts, const int32_t* h_counts,
+                      const int32_t* chip_offset, const int32_t* h_chip_offset, int K, int C, int margin256,
+                      int planar, uint8_t* chips, fdet_chip_info* info, void* stream);
+
+/* The best-shot gallery: n_seq * G entries in device memory, carried from call to call like the tracker state; all-zero
+ * bytes are an empty gallery.  Entry k - 1 of sequence s belongs to track id k (the tracker's ids are dense from 1 per
+ * sequence and never reused). */
+typedef struct fdet_chip_best {
+  int32_t id;                /* 0 = empty */
+  int32_t frame, image_wx0, image_wy0, S, inside256, seen, reserved;
+  int64_t sharp;
+} fdet_chip_best;            /* 40 bytes */
+
+/* n_seq * G * 40; 0 for bad arguments. */
+size_t fdet_chip_gallery_bytes(int n_seq, int G);
+
+/* chips / info [M]: what fdet_chip_extract wrote (either layout: a chip is C*C*3 bytes).  ids [n_images,K] int32,
+ * row-aligned with the rows the chips were cut from: the id of chip i is ids[info[i].image * K + info[i].row].
+ * seq_offset [n_seq+1] int32 (device) / h_seq_offset (host): frame t = info[i].image belongs to the sequence s with
+ * seq_offset[s] <= t < seq_offset[s+1]; the recorded frame number is frame_base[s] + t - seq_offset[s] (frame_base
+ * [n_seq] int32, device).  gallery: fdet_chip_gallery_bytes(n_seq, G) bytes; gallery_chips [n_seq,G,C*C*3] uint8;
+ * scratch [n_seq*G] uint64 (cleared by the call); overflow [1] uint64 counter.
+ *   1. a chip is a candidate when it is valid, id >= 1, S >= min_side and inside256 >= min_inside256 (and its sharp lies
+ *      in 0..2^40-1, which fdet_chip_extract guarantees).  A candidate with id > G adds one to overflow[0] and takes no
+ *      further part; that is not an error.
+ *   2. among the candidates of one (sequence, id) in this call the winner has the largest sharp; ties go to the lowest
+ *      chip index.
+ *   3. the winner replaces the entry when the entry is empty or when sharp > entry.sharp, strictly: id, frame,
+ *      image_wx0 = wx0, image_wy0 = wy0, S, inside256 and sharp are set and the chip's C*C*3 bytes are copied.
+ *   4. seen += the number of candidates of that id in this call, whether or not the winner replaced anything.
+ * Ties and strictness make the result independent of how a sequence is cut into calls.
+ * Validated on the host, FDET_EINVAL and nothing written: G < 1; M outside 0..FDET_CHIP_MAX_CHIPS; C outside 8..256;
+ * h_seq_offset not monotone from 0; n_seq < 1; K < 0; min_side < 0; min_inside256 outside 0..256; a required pointer
+ * NULL (chips, info and ids are required when M > 0).  M = 0 is success with no launch. */
+int fdet_chip_best_update(const uint8_t* chips, const fdet_chip_info* info, int M, int C, const int32_t* ids, int K,
+                          const int32_t* seq_offset, const int32_t* h_seq_offset, int n_seq, const int32_t* frame_base,
+                          int G, int min_side, int min_inside256, void* gallery, uint8_t* gallery_chips,
+                          uint64_t* scratch, uint64_t* overflow, void* stream);
+
 /* Depthwise-separable residual block (models/SeparableCNN.py:40-51; none of its three convs has a bias):
  *   a = lrelu(W1 x)   b = lrelu(dw3x3(a), pad 1)   c = W2 b   e = c * drop_scale[n,c] + x   out = maxpool2x2(e) | e
  * fdet_sepblock_fwd runs the whole block in ONE kernel on fp32 NCHW tensors: both 1x1 convs as bf16x3 GEMMs on the matrix

@@ -3,6 +3,7 @@
     python -m fdet_amd.detect_images --checkpoint CKPT --images DIR --out FILE [--model poolresnet --filters 128]
         [--tile 480 --overlap 0.25 --no-whole --edge-margin 0 --probability-threshold P --iou-threshold T --precision 16]
         [--flip --vote --min-votes N] [--draw DIR [--anonymize pixelate] [--blocks N] [--draw-format png|jpg] [--no-outline]]
+        [--chips DIR [--chip-size N] [--chip-margin F]]
 
 The images under DIR (searched recursively: .jpg .jpeg .png .bmp) are decoded with PIL into a device image bank
 (`bank_from_files`; `--device-jpeg`: baseline JPEGs are reconstructed on the device instead, with the same bytes), `tiling.TiledDetector` runs the model on overlapping windows of each image (and on the whole image
@@ -15,6 +16,9 @@ fewer than N detections agree on.
 `DIR/<path relative to --images>` with the suffix replaced by `--draw-format`: blue outlines of the reference's width unless
 `--no-outline`, and with `--anonymize pixelate` every box flattened to at most `--blocks` x `--blocks` cells.  The images are
 rendered on the device, chunk by chunk, from the bank the detector just read.
+`--chips DIR` also writes every detected face as a `--chip-size` x `--chip-size` crop (112) around its box widened by
+`--chip-margin` of its longer side (0.25), cut on the device (`chips.extract_chips`), to
+`DIR/<path relative to --images without its suffix>_<row>.png`.
 """
 import argparse
 import os
@@ -75,6 +79,26 @@ def check_draw_arguments(ap, args) -> None:
         ap.error("--blocks must be >= 1")
 
 
+def add_chip_arguments(ap, flag, what) -> None:
+    """`flag` DIR and the chip options that need it (shared with track_frames); `check_chip_arguments` checks them."""
+    ap.add_argument(flag, dest="chips_dir", default=None, metavar="DIR", help=what)
+    ap.add_argument("--chip-size", type=int, default=None, help=f"with {flag}: side of a chip in pixels, 8..256 (112)")
+    ap.add_argument("--chip-margin", type=float, default=None, help=f"with {flag}: margin as a share of the box's longer side, 0..1 (0.25)")
+
+
+def check_chip_arguments(ap, args, flag) -> None:
+    if args.chips_dir is None:
+        for name, given in (("--chip-size", args.chip_size is not None), ("--chip-margin", args.chip_margin is not None)):
+            if given:
+                ap.error(f"{name} needs {flag}")
+    if args.chip_size is not None and not 8 <= args.chip_size <= 256:
+        ap.error("--chip-size must be in 8..256")
+    if args.chip_margin is not None and not 0.0 <= args.chip_margin <= 1.0:
+        ap.error("--chip-margin must be in 0..1")
+    args.chip_size = 112 if args.chip_size is None else args.chip_size
+    args.chip_margin = 0.25 if args.chip_margin is None else args.chip_margin
+
+
 def main(argv=None):
     """Parse and check the options, then `run` them."""
     ap = argparse.ArgumentParser()
@@ -90,8 +114,10 @@ def main(argv=None):
     ap.add_argument("--vote", action="store_true", help="box voting: a kept box is the score-weighted mean of its cluster")
     ap.add_argument("--min-votes", type=int, default=1, help="with --vote: leave out boxes with fewer members than this")
     add_draw_arguments(ap)
+    add_chip_arguments(ap, "--chips", "also write every detected face as a square crop under DIR")
     args = ap.parse_args(argv)
     check_draw_arguments(ap, args)
+    check_chip_arguments(ap, args, "--chips")
     if args.min_votes < 1:
         ap.error("--min-votes must be >= 1")
     if args.min_votes > 1 and not args.vote:
@@ -151,6 +177,13 @@ def run(args):
                                       blocks=8 if args.blocks is None else args.blocks)
             save_images(drawn, [(Path(args.draw) / os.path.relpath(p, root)).with_suffix("." + (args.draw_format or "png"))
                                 for p in chunk])
+        if getattr(args, "chips_dir", None) is not None:
+            from .chips import extract_chips
+            from .render import save_images
+            cs = extract_chips(bank, rows, counts, size=args.chip_size, margin=args.chip_margin)
+            stems = [(Path(args.chips_dir) / os.path.relpath(p, root)).with_suffix("") for p in chunk]
+            if len(cs):
+                save_images(cs.as_bank(), [f"{stems[i]}_{j}.png" for i in range(len(chunk)) for j in range(int(cs.offset[i + 1] - cs.offset[i]))])
         kmax = max(int(counts.max()), 1)
         all_rows.append(rows[:, :kmax].cpu())
         all_counts.append(counts.cpu())

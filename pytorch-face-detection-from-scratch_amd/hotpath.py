@@ -456,6 +456,96 @@ def track_update(rows: torch.Tensor, counts: torch.Tensor, seq_offset: torch.Ten
 
 
 # ------------------------------------------------------------------------------------------
+# Face chips and the best-shot gallery (csrc/fdet_chips.hip; chips.py drives these)
+# ------------------------------------------------------------------------------------------
+CHIP_MIN_SIZE, CHIP_MAX_SIZE, CHIP_MAX_SIDE, CHIP_MAX_CHIPS = 8, 256, 8192, 1 << 20      # FDET_CHIP_* of include/fdet.h
+CHIP_INFO_BYTES = CHIP_BEST_BYTES = 40                                # fdet_chip_info, fdet_chip_best
+
+
+def chip_extract(bank_data: torch.Tensor, d_table: torch.Tensor, h_table, rows: torch.Tensor, counts: torch.Tensor, h_counts,
+                 size: int, margin256: int, planar: bool = False):
+    """fdet_chip_extract: one size x size chip per row j < counts[i] of rows (n,K,5) [score,x,y,w,h], cut from image i of the
+    bank (bank_data / d_table / h_table as `tile_gather` takes them).  h_counts: the values of counts as a contiguous (n,)
+    numpy int32 array -> (chips (M,size,size,3) uint8, or (M,3,size,size) when planar; info (M * 40,) uint8, M fdet_chip_info;
+    h_chip_offset (n+1,) numpy int32, chip h_chip_offset[i] + j is row j of image i).  One launch, no host synchronisation."""
+    import numpy as np
+    n = len(h_table)
+    if rows.dim() != 3 or rows.shape[0] != n or rows.shape[2] != 5 or rows.dtype != F32:
+        raise ValueError(f"chip_extract: rows must be ({n},K,5) float32, got {tuple(rows.shape)} {rows.dtype}")
+    K, C = int(rows.shape[1]), int(size)
+    if tuple(counts.shape) != (n,) or counts.dtype != I32:
+        raise ValueError(f"chip_extract: counts must be ({n},) int32, got {tuple(counts.shape)} {counts.dtype}")
+    if not isinstance(h_counts, np.ndarray) or h_counts.dtype != np.int32 or h_counts.shape != (n,) or not h_counts.flags.c_contiguous:
+        raise ValueError(f"chip_extract: h_counts must be a contiguous ({n},) numpy int32 array")
+    if d_table.numel() != n * 16:
+        raise ValueError("chip_extract: device and host copies of the table differ in size")
+    h_off = np.zeros(n + 1, np.int64)
+    np.cumsum(np.clip(h_counts.astype(np.int64), 0, max(K, 0)), out=h_off[1:])          # a count outside 0..K is refused below
+    M = int(h_off[-1])
+    if M > CHIP_MAX_CHIPS:
+        raise ValueError(f"chip_extract: {M} chips in one call, at most {CHIP_MAX_CHIPS}")
+    h_off = np.ascontiguousarray(h_off.astype(np.int32))
+    dev, U8 = bank_data.device, torch.uint8
+    d_off = torch.from_numpy(h_off).to(dev)
+    chips = torch.empty((M, 3, C, C) if planar else (M, C, C, 3), dtype=U8, device=dev)
+    info = torch.empty(M * CHIP_INFO_BYTES, dtype=U8, device=dev)
+
+    def p(t, dtype=U8):                                      # an empty tensor has no storage to point at
+        return ptr(t, dtype) if t.numel() else None
+
+    check(lib().fdet_chip_extract(ptr(bank_data, U8), ptr(d_table, U8), h_table.ctypes.data, n, p(rows.contiguous(), F32),
+                                  ptr(counts.contiguous(), I32), h_counts.ctypes.data, ptr(d_off, I32), h_off.ctypes.data, K, C,
+                                  int(margin256), int(bool(planar)), p(chips), p(info), stream()), "fdet_chip_extract")
+    return chips, info, h_off
+
+
+def chip_gallery_bytes(n_seq: int, capacity: int) -> int:
+    return int(lib().fdet_chip_gallery_bytes(int(n_seq), int(capacity)))
+
+
+def chip_best_update(chips: torch.Tensor, info: torch.Tensor, ids: torch.Tensor, seq_offset: torch.Tensor, h_seq_offset,
+                     frame_base: torch.Tensor, capacity: int, min_side: int, min_inside256: int, gallery: torch.Tensor,
+                     gallery_chips: torch.Tensor, scratch: torch.Tensor, overflow: torch.Tensor) -> None:
+    """fdet_chip_best_update: chips (M,...) uint8 and info (M * 40,) uint8 as `chip_extract` returns them; ids (n,K) int32
+    row-aligned with the rows the chips were cut from; seq_offset (n_seq+1,) int32 on the device and h_seq_offset, the same
+    values as a numpy int32 array; frame_base (n_seq,) int32.  Updated in place: gallery (n_seq * capacity * 40,) uint8
+    (zeros = empty), gallery_chips (n_seq, capacity, size*size*3) uint8, overflow (1,) int64 counter; scratch (n_seq *
+    capacity,) int64 is cleared by the call.  Two launches, no host synchronisation."""
+    import numpy as np
+    if not isinstance(h_seq_offset, np.ndarray) or h_seq_offset.dtype != np.int32 or h_seq_offset.ndim != 1 or \
+            not h_seq_offset.flags.c_contiguous or h_seq_offset.size < 2:
+        raise ValueError("chip_best_update: h_seq_offset must be a contiguous (n_seq+1,) numpy int32 array")
+    n_seq, G = int(h_seq_offset.size) - 1, int(capacity)
+    M = int(chips.shape[0])
+    if chips.dim() != 4 or chips.dtype != torch.uint8 or chips.shape[1:].numel() % 3 or info.dtype != torch.uint8 or \
+            info.numel() != M * CHIP_INFO_BYTES:
+        raise ValueError(f"chip_best_update: chips must be (M,C,C,3) or (M,3,C,C) uint8 and info M * {CHIP_INFO_BYTES} uint8")
+    C = int(max(chips.shape[1:]))
+    if chips.shape[1:].numel() != C * C * 3:
+        raise ValueError(f"chip_best_update: chips of shape {tuple(chips.shape)} are not square RGB chips")
+    if ids.dim() != 2 or ids.dtype != I32:
+        raise ValueError(f"chip_best_update: ids must be (n_images,K) int32, got {tuple(ids.shape)} {ids.dtype}")
+    if int(ids.shape[0]) != int(h_seq_offset[-1]):
+        raise ValueError(f"chip_best_update: ids holds {int(ids.shape[0])} frames, seq_offset ends at {int(h_seq_offset[-1])}")
+    if tuple(seq_offset.shape) != (n_seq + 1,) or seq_offset.dtype != I32 or tuple(frame_base.shape) != (n_seq,) or frame_base.dtype != I32:
+        raise ValueError("chip_best_update: seq_offset must be (n_seq+1,) int32 and frame_base (n_seq,) int32")
+    if G < 1 or gallery.dtype != torch.uint8 or gallery.numel() != n_seq * G * CHIP_BEST_BYTES or gallery_chips.dtype != torch.uint8 or \
+            gallery_chips.numel() != n_seq * G * C * C * 3:
+        raise ValueError(f"chip_best_update: gallery must be {n_seq} x {G} x {CHIP_BEST_BYTES} uint8 and gallery_chips {n_seq} x {G} x {C * C * 3}")
+    if scratch.dtype != torch.int64 or scratch.numel() != n_seq * G or overflow.dtype != torch.int64 or overflow.numel() != 1:
+        raise ValueError(f"chip_best_update: scratch must be {n_seq * G} int64 and overflow one int64")
+    U8, I64 = torch.uint8, torch.int64
+
+    def p(t, dtype=U8):
+        return ptr(t, dtype) if t.numel() else None
+
+    check(lib().fdet_chip_best_update(p(chips.contiguous()), p(info), M, C, p(ids.contiguous(), I32), int(ids.shape[1]),
+                                      ptr(seq_offset.contiguous(), I32), h_seq_offset.ctypes.data, n_seq, ptr(frame_base, I32), G,
+                                      int(min_side), int(min_inside256), ptr(gallery, U8), ptr(gallery_chips, U8),
+                                      ptr(scratch, I64), ptr(overflow, I64), stream()), "fdet_chip_best_update")
+
+
+# ------------------------------------------------------------------------------------------
 # Baseline JPEG decode (csrc/fdet_jpeg.hip; datasets/jpeg.py drives these)
 # ------------------------------------------------------------------------------------------
 JPEG_UNSUPPORTED, JPEG_ECORRUPT = -4, -5                     # FDET_JPEG_* of include/fdet.h

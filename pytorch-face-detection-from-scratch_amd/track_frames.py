@@ -3,6 +3,7 @@
     python -m fdet_amd.track_frames --checkpoint CKPT --frames DIR --out FILE [--model poolresnet --filters 128]
         [--tiled --tile 480 --overlap 0.25] [--iou 0.3 --alpha 0.5 --max-misses 5 --min-hits 2 --emit-misses N]
         [--draw DIR [--anonymize pixelate] [--blocks N] [--draw-format png|jpg] [--no-outline]]
+        [--best-shots DIR [--chip-size N] [--chip-margin F]]
 
 The images directly under DIR (.jpg .jpeg .png .bmp), sorted by name, are the frames of ONE sequence and must all have the
 same size.  They are detected in chunks of --max-frames: without --tiled each frame is resized whole to the network's input,
@@ -10,13 +11,16 @@ with --tiled `TiledDetector` also runs the --tile windows.  `tracking.FaceTracke
 FILE receives one line per emitted track and frame, `frame,id,x,y,w,h,score,-1,-1,-1` with frames counted from 1 and the box
 in source pixels.  `--draw DIR` writes every frame with the TRACKER's boxes rendered into it (`render.render_detections`), so
 with `--anonymize pixelate` a face the detector misses for up to --emit-misses frames stays covered.  The model options are
-those of `detect_images`.  Files only: there is no camera or video-container input.
+those of `detect_images`.  `--best-shots DIR` writes one picture per track, `DIR/seq0_track<id>.png`: the sharpest
+`--chip-size` x `--chip-size` crop (112) among the frames in which the detector saw the track, cut with `--chip-margin` (0.25)
+and kept on the device from chunk to chunk (`chips.BestShots`).  Files only: there is no camera or video-container input.
 """
 import argparse
 import os
 from pathlib import Path
 
-from .detect_images import EXTENSIONS, add_draw_arguments, add_model_arguments, add_tile_arguments, check_draw_arguments
+from .detect_images import (EXTENSIONS, add_chip_arguments, add_draw_arguments, add_model_arguments, add_tile_arguments,
+                            check_chip_arguments, check_draw_arguments)
 
 
 def frame_paths(root):
@@ -65,8 +69,10 @@ def main(argv=None):
     ap.add_argument("--emit-misses", type=int, default=None, help="frames a missed track is still emitted (--max-misses)")
     ap.add_argument("--birth-score", type=float, default=0.0)
     add_draw_arguments(ap)
+    add_chip_arguments(ap, "--best-shots", "also write the sharpest crop of every track under DIR")
     args = ap.parse_args(argv)
     check_draw_arguments(ap, args)
+    check_chip_arguments(ap, args, "--best-shots")
     if args.max_frames < 1:
         ap.error("--max-frames must be >= 1")
     if not os.path.isdir(args.frames):
@@ -93,6 +99,10 @@ def run(args):
     det = TiledDetector(model, tile_sizes=tuple(args.tile) if args.tiled else (), overlap=args.overlap,
                         include_whole=not (args.tiled and args.no_whole), edge_margin=args.edge_margin,
                         max_out=256)                        # fdet_track_update takes at most 256 valid rows per frame
+    best = None
+    if getattr(args, "chips_dir", None) is not None:
+        from .chips import BestShots
+        best = BestShots(1, size=args.chip_size, margin=args.chip_margin)
     paths, lines = args.paths, 0
     out = Path(args.out)
     if out.parent != Path(""):
@@ -108,7 +118,13 @@ def run(args):
                 drawn = render_detections(bank, res.rows, res.counts, outline=not args.no_outline, anonymize=args.anonymize,
                                           blocks=8 if args.blocks is None else args.blocks)
                 save_images(drawn, [(Path(args.draw) / p.name).with_suffix("." + (args.draw_format or "png")) for p in chunk])
+            if best is not None:
+                best.update(bank, res)
             lines += write_mot(f, a + 1, res.rows.cpu().numpy(), res.counts.cpu().numpy(), res.ids.cpu().numpy())
+    if best is not None:
+        shots = best.save(args.chips_dir)
+        print(f"{len(shots)} best shots -> {args.chips_dir}" + (f" ({best.overflow} detections of tracks beyond id {best.capacity} left out)"
+                                                                if best.overflow else ""))
     snap = tracker.snapshot()
     print(f"{len(paths)} frames, {int(snap['seq']['next_id'][0])} tracks, {lines} lines -> {args.out}")
     return {"frames": len(paths), "tracks": int(snap["seq"]["next_id"][0]), "lines": lines, "dropped": tracker.dropped}
