@@ -50,14 +50,6 @@ __device__ __forceinline__ float aug_normal(uint32_t seed, uint32_t key, int c, 
   return sqrtf(-2.0f * logf(u1)) * cosf(6.283185307179586f * u2);
 }
 
-// x / 255 for an integer 0 <= x <= 255, bit-identical to the IEEE division (same as fdet_u8_to_f32_norm, fdet_detect.hip)
-__device__ __forceinline__ float u8_over_255(float x) {
-  const float r = 1.0f / 255.0f;
-  const float q = x * r;
-  const float rem = __builtin_fmaf(-q, 255.0f, x);
-  return __builtin_fmaf(rem, r, q);
-}
-
 // continuous reflect-101 of an index-space coordinate into [0, n-1]
 __device__ __forceinline__ double reflect101d(double t, int n) {
   if (n == 1) return 0.0;

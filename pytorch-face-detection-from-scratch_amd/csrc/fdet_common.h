@@ -70,6 +70,16 @@ __device__ __forceinline__ float wave_sum_all(float v) {
   return v;
 }
 
+// x / 255 for an integer 0 <= x <= 255, bit-identical to the IEEE division: q = x * fl(1/255) is off by an ulp for 126 of the
+// 256 values, one residual correction (two FMAs) makes all 256 exact (tests/test_gpu_detect.py::test_u8_norm_bit_exact covers
+// every value).  fdet_u8_to_f32_norm (fdet_detect.hip) and fdet_aug_finish (fdet_augment.hip) share it.
+__device__ __forceinline__ float u8_over_255(float x) {
+  const float r = 1.0f / 255.0f;
+  const float q = x * r;
+  const float rem = __builtin_fmaf(-q, 255.0f, x);
+  return __builtin_fmaf(rem, r, q);
+}
+
 }  // namespace fdet
 
 #define FDET_REQUIRE(cond, ...) \

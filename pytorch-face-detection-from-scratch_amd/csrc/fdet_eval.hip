@@ -9,7 +9,7 @@
 //   2. per threshold: winner[box] = min rank over the detections that claim it (LDS atomicMin); a detection is a true
 //      positive iff it is that winner; the workgroup's tp/fp bins are counted in LDS and the non-zero ones added to the
 //      global histograms with vector atomics.
-#include "fdet_common.h"
+#include "fdet_boxes.h"
 #include <cfloat>
 #include <cmath>
 
@@ -60,20 +60,12 @@ k_eval_match(const float* __restrict__ pred, const int32_t* __restrict__ pred_co
     return;
   }
   const float* P = pred + (size_t)n * Kmax * 5;
-  for (int d = tid; d < K; d += EVAL_THREADS) {
-    const float s = P[d * 5];
-    sc[d] = (s == s) ? s + 0.0f : -INFINITY;          // NaN sorts last, -0 == +0
-  }
+  for (int d = tid; d < K; d += EVAL_THREADS) sc[d] = nan_last_key(P[d * 5]);
   for (int b = tid; b < 2 * n_bins; b += EVAL_THREADS) htp[b] = 0u;      // htp and hfp are contiguous
   __syncthreads();
 
   for (int d = tid; d < K; d += EVAL_THREADS) {
-    const float s = sc[d];
-    uint32_t r = 0;
-    for (int e = 0; e < K; ++e) {
-      const float se = sc[e];
-      r += (se > s) || (se == s && e < d);
-    }
+    const uint32_t r = (uint32_t)box_rank(sc, K, d);
     const float px1 = P[d * 5 + 1], py1 = P[d * 5 + 2], px2 = P[d * 5 + 3] + px1, py2 = P[d * 5 + 4] + py1;
     const float a2 = (px2 - px1) * (py2 - py1);
     float best = -INFINITY;
@@ -82,10 +74,7 @@ k_eval_match(const float* __restrict__ pred, const int32_t* __restrict__ pred_co
       const float* ga = gt_rows + (size_t)(g0 + g) * 5;
       const float gx1 = ga[1], gy1 = ga[2], gx2 = ga[3] + ga[1], gy2 = ga[4] + ga[2];
       const float a1 = (gx2 - gx1) * (gy2 - gy1);
-      const float w = fmaxf(fminf(gx2, px2) - fmaxf(gx1, px1), 0.f);
-      const float h = fmaxf(fminf(gy2, py2) - fmaxf(gy1, py1), 0.f);
-      const float inter = w * h;
-      const float iou = inter / (a1 + a2 - inter);
+      const float iou = box_overlap(gx1, gy1, gx2, gy2, a1, px1, py1, px2, py2, a2);
       if (iou > best) { best = iou; bidx = g; }
     }
     rk[d] = r;

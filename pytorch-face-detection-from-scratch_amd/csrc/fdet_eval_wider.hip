@@ -13,7 +13,7 @@
 // The cumulative sums of the two histograms over bins <= t are the protocol's (proposals, recalled boxes) at threshold t.
 //
 // Overlaps are fp64 with a fixed operation order; contraction is off for the whole file (and in the Makefile).
-#include "fdet_common.h"
+#include "fdet_boxes.h"
 #include <cfloat>
 #include <cmath>
 
@@ -73,10 +73,7 @@ k_eval_wider(const float* __restrict__ pred, const int32_t* __restrict__ pred_co
   const float sx = pred_scale ? pred_scale[n * 2] : 1.f, sy = pred_scale ? pred_scale[n * 2 + 1] : 1.f;
   const double smin = score_norm ? score_norm[0] : 0.0, srange = score_norm ? score_norm[1] : 1.0;
   const uint32_t all = n_subsets >= 32 ? 0xFFFFFFFFu : ((1u << n_subsets) - 1u);
-  for (int d = tid; d < K; d += WIDER_THREADS) {
-    const float s = P[d * 5];
-    sc[d] = (s == s) ? s + 0.0f : -INFINITY;          // NaN sorts last, -0 == +0
-  }
+  for (int d = tid; d < K; d += WIDER_THREADS) sc[d] = nan_last_key(P[d * 5]);
   for (int g = tid; g < G; g += WIDER_THREADS) winner[g] = 0xFFFFFFFFu;
   if (tid < FDET_EVAL_WIDER_MAX_SUBSETS) kept[tid] = 0u;
   __syncthreads();
@@ -94,12 +91,7 @@ k_eval_wider(const float* __restrict__ pred, const int32_t* __restrict__ pred_co
   }
 
   for (int d = tid; d < K; d += WIDER_THREADS) {
-    const float s = sc[d];
-    uint32_t r = 0;
-    for (int e = 0; e < K; ++e) {
-      const float se = sc[e];
-      r += (se > s) || (se == s && e < d);
-    }
+    const uint32_t r = (uint32_t)box_rank(sc, K, d);
     // source pixels: four fp32 multiplies, everything after them in fp64
     const float fx = P[d * 5 + 1] * sx, fy = P[d * 5 + 2] * sy, fw = P[d * 5 + 3] * sx, fh = P[d * 5 + 4] * sy;
     const double dx1 = (double)fx, dy1 = (double)fy, dx2 = dx1 + (double)fw, dy2 = dy1 + (double)fh;

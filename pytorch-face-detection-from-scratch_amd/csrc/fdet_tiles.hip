@@ -16,7 +16,7 @@
 //                     it suppressed).  Both are template instances; the plain entries compile to what they were.
 //
 // tests/tiles_cpu_ref.py and tests/tta_cpu_ref.py restate them in numpy.  Built with -ffp-contract=off like every file here.
-#include "fdet_common.h"
+#include "fdet_boxes.h"
 #include <cstdint>
 
 using namespace fdet;
@@ -141,32 +141,10 @@ k_tile_gather(const uint8_t* __restrict__ bank, int64_t bank_bytes, const fdet_a
 }
 
 // ------------------------------------------------------------------------------------------------------------------
-// merge: one workgroup per source image; 33 bytes of LDS per candidate, as fdet_nms
+// merge: one workgroup per source image; 33 bytes of LDS per candidate, the carve of fdet_nms (fdet_boxes.h) with plane 5
+// holding src: candidate -> row of `rows` (tile * K + r), so that the sweep computes the areas from the corners
 // ------------------------------------------------------------------------------------------------------------------
 constexpr int MERGE_CAP = 4864;
-
-struct MergeLds {
-  float* x1; float* y1; float* x2; float* y2; float* key;
-  int* src;              // candidate -> row of `rows` (tile * K + r)
-  int* order;            // sorted position -> candidate
-  int* keep;             // visiting order -> candidate
-  unsigned char* dead;   // by sorted position
-  int* ctl;              // [0] running count, [1..4] per-wave counts, [5] kept
-};
-
-__host__ __device__ inline size_t merge_lds_bytes(int cap) { return (size_t)cap * 32 + (size_t)((cap + 15) / 16) * 16 + 64; }
-
-__device__ __forceinline__ MergeLds merge_carve(char* smem, int cap) {
-  MergeLds L;
-  float* f = reinterpret_cast<float*>(smem);
-  L.x1 = f; L.y1 = f + cap; L.x2 = f + 2 * cap; L.y2 = f + 3 * cap; L.key = f + 4 * cap;
-  L.src = reinterpret_cast<int*>(f + 5 * cap);
-  L.order = reinterpret_cast<int*>(f + 6 * cap);
-  L.keep = reinterpret_cast<int*>(f + 7 * cap);
-  L.dead = reinterpret_cast<unsigned char*>(f + 8 * cap);
-  L.ctl = reinterpret_cast<int*>(smem + merge_lds_bytes(cap) - 64);
-  return L;
-}
 
 // one detection row in frame pixels -> source pixels: fp32, separate multiply and add, then half-to-even
 __device__ __forceinline__ void to_source(const float* d, const fdet_tile& Tl, float kx, float ky, float& x, float& y, float& w,
@@ -202,6 +180,66 @@ __device__ __forceinline__ long long vote_weight(float key, float x1, float y1, 
   return llrint((double)fminf(key, 1.f) * 1048576.0);
 }
 
+// what box voting does per suppression and per keeper in the shared sweep (box_greedy_nms of fdet_boxes.h)
+struct VoteHook {
+  const BoxLds& L;
+  unsigned long long* acc;                           // the two accumulator sets
+  const MergeTta& A;
+  int par = 0;
+  unsigned long long* S = nullptr;                   // the accumulator set of this keeper
+  float* mine = nullptr;                             // the plane that lane e of wave 0 writes in settle: x, y, w or h
+
+  __device__ __forceinline__ void begin() {
+    if (threadIdx.x < 2 * VOTE_ACC) acc[threadIdx.x] = 0ull;
+    const int e = threadIdx.x & 3;                   // chosen once: a per-keeper choice costs 4 % on the vote=1 path
+    mine = e == 0 ? L.x1 : e == 1 ? L.y1 : e == 2 ? L.x2 : L.y2;
+  }
+  __device__ __forceinline__ void visit(int) { S = acc + par * VOTE_ACC; }
+  // j dies here and nowhere else: the current keeper owns it.  Integer sums in LDS, so the order of the additions cannot
+  // change them
+  __device__ __forceinline__ void suppress(int j, float jx1, float jy1, float jx2, float jy2) const {
+    atomicAdd(&S[5], 1ull);
+    const long long q = A.vote ? vote_weight(L.key[j], jx1, jy1, jx2, jy2) : 0;
+    if (q) {
+      atomicAdd(&S[0], (unsigned long long)q);
+      atomicAdd(&S[1], (unsigned long long)(q * (long long)jx1));
+      atomicAdd(&S[2], (unsigned long long)(q * (long long)jy1));
+      atomicAdd(&S[3], (unsigned long long)(q * (long long)jx2));
+      atomicAdd(&S[4], (unsigned long long)(q * (long long)jy2));
+    }
+  }
+  // 4: lanes 0..3 of wave 0 turn the sums into x, y, w, h.  Candidate i is never read again by the sweep, so its box
+  // slots take the voted box and its key slot the member count (bit 31: voted); the other waves go on meanwhile
+  __device__ __forceinline__ void settle(int i, float ix1, float iy1, float ix2, float iy2) {
+    if (threadIdx.x < 4) {
+      const int e = threadIdx.x, ax = e & 1;
+      const unsigned long long sq = S[0], sl = S[1 + ax], sh = S[3 + ax], sn = S[5];
+      __builtin_amdgcn_wave_barrier();           // the four lanes' reads are issued before lane 0's clears
+      if (e == 0) {
+#pragma unroll
+        for (int k = 0; k < VOTE_ACC; ++k) S[k] = 0ull;
+      }
+      const long long members = (long long)sn + 1;
+      const long long qi = A.vote ? vote_weight(L.key[i], ix1, iy1, ix2, iy2) : 0;
+      const long long Q = (long long)sq + qi;
+      const long long slo = (long long)sl + (qi ? qi * (long long)(ax ? iy1 : ix1) : 0);
+      const long long shi = (long long)sh + (qi ? qi * (long long)(ax ? iy2 : ix2) : 0);
+      if (Q > 0) {
+        const double lo = rint((double)slo / (double)Q);
+        const float v = e < 2 ? (float)lo : (float)(rint((double)shi / (double)Q) - lo);
+        mine[i] = v;
+      }
+      if (e == 0) {
+        // lanes 0..3 read L.key[i] (vote_weight above) before this store by program order inside one wave; a read
+        // of the key moved below this line, or into another wave, would see the member count instead
+        L.key[i] = __int_as_float((int)members | (Q > 0 ? (int)0x80000000 : 0));
+        if (members >= A.min_votes) { L.keep[L.ctl[5]] = i; L.ctl[5] += 1; }       // 5: the others only suppressed
+      }
+    }
+    par ^= 1;                                        // two sets, used alternately: one barrier per keeper stays enough
+  }
+};
+
 template <bool TTA>
 __global__ void __launch_bounds__(256)
 k_tile_merge(const float* __restrict__ rows, const int32_t* __restrict__ counts, const fdet_tile* __restrict__ tiles,
@@ -209,9 +247,9 @@ k_tile_merge(const float* __restrict__ rows, const int32_t* __restrict__ counts,
              float margin, double thr, int cap, int Kout, float* __restrict__ out, int32_t* __restrict__ out_counts,
              unsigned long long* __restrict__ rejected, MergeTta A) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  const MergeLds L = merge_carve(smem, cap);
-  unsigned long long* const acc = reinterpret_cast<unsigned long long*>(smem + merge_lds_bytes(cap));      // TTA only
-  const int n = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const BoxLds L = box_carve(smem, cap, true, false);
+  unsigned long long* const acc = reinterpret_cast<unsigned long long*>(smem + box_lds_bytes(cap, true));  // TTA only
+  const int n = blockIdx.x, tid = threadIdx.x;
   const int t0 = tile_offset[n], t1 = tile_offset[n + 1];
   const fdet_aug_image img = table[n];
   bool bad = t0 < 0 || t1 < t0 || t1 > T;
@@ -235,106 +273,32 @@ k_tile_merge(const float* __restrict__ rows, const int32_t* __restrict__ counts,
         if ((cl && d[1] < margin) || (cr && bx2 > (float)Wo - margin) || (ct && d[2] < margin) || (cb && by2 > (float)Ho - margin))
           hit = false;
       }
-      const unsigned long long bal = __ballot(hit);
-      const int before = __popcll(bal & ((1ull << lane) - 1ull));
-      if (lane == 0) L.ctl[1 + wid] = __popcll(bal);
-      __syncthreads();
-      int base = L.ctl[0];
-      for (int w = 0; w < wid; ++w) base += L.ctl[1 + w];
-      const int k = base + before;
+      const int k = compact_slot(hit, L.ctl);
       if (hit && k < cap) {
         float x, y, w, h;
         to_source(d, Tl, kx, ky, x, y, w, h);
-        L.key[k] = d[0] != d[0] ? -INFINITY : d[0];      // a NaN score is ordered as -inf (visited last), as fdet_eval_match does
+        // a NaN score is ordered as -inf (visited last), as fdet_eval_match does.  The shared key also turns -0 into +0:
+        // the key never reaches an output (v[0] below is read from the row again) and -0 compares equal to +0 in the rank,
+        // in vote_weight's `key > 0` and in its fminf, so no result changes with it
+        L.key[k] = nan_last_key(d[0]);
         L.x1[k] = x; L.y1[k] = y; L.x2[k] = x + w; L.y2[k] = y + h;
         L.src[k] = t * K + r;
       }
-      __syncthreads();
-      if (tid == 0) L.ctl[0] += L.ctl[1] + L.ctl[2] + L.ctl[3] + L.ctl[4];
-      __syncthreads();
     }
   }
+  __syncthreads();                                   // the candidates and the total are visible
   const int C = L.ctl[0];
   bad = bad || C > MERGE_CAP || C > cap;
   int nk = 0;
   if (!bad) {
-    // 3: greedy NMS (torchvision 0.11.2 nms_kernel.cpp as restated by fdet_nms): stable descending rank, fp32 overlap
-    for (int i = tid; i < C; i += 256) {
-      const float si = L.key[i];
-      int rk = 0;
-      for (int j = 0; j < C; ++j) { const float sj = L.key[j]; rk += (sj > si) || (sj == si && j < i); }
-      L.order[rk] = i;
+    // 3: greedy NMS (torchvision 0.11.2 nms_kernel.cpp, the sweep of fdet_nms): stable descending rank, fp32 overlap
+    if (TTA) {
+      VoteHook vote{L, acc, A};
+      nk = box_greedy_nms(L, C, thr, vote);
+    } else {
+      KeepEvery every{L};
+      nk = box_greedy_nms(L, C, thr, every);
     }
-    for (int i = tid; i < C; i += 256) L.dead[i] = 0;
-    if (tid == 0) L.ctl[5] = 0;
-    if (TTA && tid < 2 * VOTE_ACC) acc[tid] = 0ull;
-    __syncthreads();
-    int par = 0;                                     // TTA: the accumulator set of this keeper
-    for (int a = 0; a < C; ++a) {
-      if (L.dead[a]) continue;                       // uniform: written before the last barrier
-      const int i = L.order[a];
-      if (!TTA && tid == 0) { L.keep[L.ctl[5]] = i; L.ctl[5] += 1; }
-      unsigned long long* const S = acc + par * VOTE_ACC;
-      const float ix1 = L.x1[i], iy1 = L.y1[i], ix2 = L.x2[i], iy2 = L.y2[i];
-      const float ia = (ix2 - ix1) * (iy2 - iy1);
-      for (int bq = a + 1 + tid; bq < C; bq += 256) {
-        if (L.dead[bq]) continue;
-        const int j = L.order[bq];
-        const float jx1 = L.x1[j], jy1 = L.y1[j], jx2 = L.x2[j], jy2 = L.y2[j];
-        const float ja = (jx2 - jx1) * (jy2 - jy1);
-        const float w = fmaxf(0.f, fminf(ix2, jx2) - fmaxf(ix1, jx1));
-        const float h = fmaxf(0.f, fminf(iy2, jy2) - fmaxf(iy1, jy1));
-        const float inter = w * h;
-        const float ovr = inter / (ia + ja - inter);                 // 0/0 = NaN -> not suppressed
-        if ((double)ovr > thr) {
-          L.dead[bq] = 1;
-          if (TTA) {                                 // j dies here and nowhere else: keeper i owns it.  Integer sums in
-            atomicAdd(&S[5], 1ull);                  // LDS, so the order of the additions cannot change them
-            const long long q = A.vote ? vote_weight(L.key[j], jx1, jy1, jx2, jy2) : 0;
-            if (q) {
-              atomicAdd(&S[0], (unsigned long long)q);
-              atomicAdd(&S[1], (unsigned long long)(q * (long long)jx1));
-              atomicAdd(&S[2], (unsigned long long)(q * (long long)jy1));
-              atomicAdd(&S[3], (unsigned long long)(q * (long long)jx2));
-              atomicAdd(&S[4], (unsigned long long)(q * (long long)jy2));
-            }
-          }
-        }
-      }
-      __syncthreads();
-      if (TTA) {
-        // 4: lanes 0..3 of wave 0 turn the sums into x, y, w, h.  Candidate i is never read again by the loop, so its box
-        // slots take the voted box and its key slot the member count (bit 31: voted); the other waves go on meanwhile
-        if (tid < 4) {
-          const int e = tid, ax = e & 1;
-          const unsigned long long sq = S[0], sl = S[1 + ax], sh = S[3 + ax], sn = S[5];
-          __builtin_amdgcn_wave_barrier();           // the four lanes' reads are issued before lane 0's clears
-          if (e == 0) {
-#pragma unroll
-            for (int k = 0; k < VOTE_ACC; ++k) S[k] = 0ull;
-          }
-          const long long members = (long long)sn + 1;
-          const long long qi = A.vote ? vote_weight(L.key[i], ix1, iy1, ix2, iy2) : 0;
-          const long long Q = (long long)sq + qi;
-          const long long slo = (long long)sl + (qi ? qi * (long long)(ax ? iy1 : ix1) : 0);
-          const long long shi = (long long)sh + (qi ? qi * (long long)(ax ? iy2 : ix2) : 0);
-          if (Q > 0) {
-            const double lo = rint((double)slo / (double)Q);
-            const float v = e < 2 ? (float)lo : (float)(rint((double)shi / (double)Q) - lo);
-            (e == 0 ? L.x1 : e == 1 ? L.y1 : e == 2 ? L.x2 : L.y2)[i] = v;
-          }
-          if (e == 0) {
-            // lanes 0..3 read L.key[i] (vote_weight above) before this store by program order inside one wave; a read
-            // of the key moved below this line, or into another wave, would see the member count instead
-            L.key[i] = __int_as_float((int)members | (Q > 0 ? (int)0x80000000 : 0));
-            if (members >= A.min_votes) { L.keep[L.ctl[5]] = i; L.ctl[5] += 1; }       // 5: the others only suppressed
-          }
-        }
-        par ^= 1;
-      }
-    }
-    __syncthreads();
-    nk = L.ctl[5];
     bad = nk > Kout;
   }
   // 4: an image over a limit is rejected as a whole
@@ -427,7 +391,7 @@ static int tile_merge_launch(const char* what, const float* rows, const int32_t*
   FDET_REQUIRE(edge_margin >= 0.f, "%s: edge_margin=%g must be >= 0", what, (double)edge_margin);
   const int64_t most = (int64_t)T * K;
   const int cap = most < MERGE_CAP ? (int)most : MERGE_CAP;
-  const size_t lds = merge_lds_bytes(cap) + (tta ? VOTE_LDS : 0);
+  const size_t lds = box_lds_bytes(cap, true) + (tta ? VOTE_LDS : 0);
   const void* kern = tta ? reinterpret_cast<const void*>(k_tile_merge<true>) : reinterpret_cast<const void*>(k_tile_merge<false>);
   if (lds > 64 * 1024)
     if (int rc = set_lds_attr(kern, lds, what)) return rc;

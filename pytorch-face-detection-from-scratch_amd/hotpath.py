@@ -183,6 +183,27 @@ class EvalState:
         self.counters.zero_()
 
 
+def _eval_common_args(name: str, pred, pred_counts, gt_rows, gt_offset, max_gt):
+    """The shape and dtype checks that eval_match and eval_wider share, `name` being the entry the messages speak for
+    -> (B, Kmax, cap, max_gt), max_gt defaulting to min(cap, EVAL_MAX_GT)."""
+    if pred.dim() != 3 or pred.shape[2] != 5 or pred.dtype != F32 or pred.shape[0] < 1:
+        raise ValueError(f"{name}: pred must be a (B>=1,Kmax,5) float32 tensor, got {tuple(pred.shape)} {pred.dtype}")
+    B, Kmax = int(pred.shape[0]), int(pred.shape[1])
+    if not 1 <= Kmax <= EVAL_MAX_DET:
+        raise ValueError(f"{name}: Kmax={Kmax} detections per image, 1..{EVAL_MAX_DET} are supported")
+    if tuple(pred_counts.shape) != (B,) or pred_counts.dtype != I32:
+        raise ValueError(f"{name}: pred_counts must be a ({B},) int32 tensor, got {tuple(pred_counts.shape)} {pred_counts.dtype}")
+    if gt_rows.dim() != 2 or gt_rows.shape[1] != 5 or gt_rows.dtype != F32 or gt_rows.shape[0] < 1:
+        raise ValueError(f"{name}: gt_rows must be a (cap>=1,5) float32 tensor, got {tuple(gt_rows.shape)} {gt_rows.dtype}")
+    cap = int(gt_rows.shape[0])
+    if tuple(gt_offset.shape) != (B + 1,) or gt_offset.dtype != I32:
+        raise ValueError(f"{name}: gt_offset must be a ({B + 1},) int32 tensor, got {tuple(gt_offset.shape)} {gt_offset.dtype}")
+    max_gt = min(cap, EVAL_MAX_GT) if max_gt is None else int(max_gt)
+    if not 1 <= max_gt <= EVAL_MAX_GT:
+        raise ValueError(f"{name}: max_gt={max_gt} boxes per image, 1..{EVAL_MAX_GT} are supported")
+    return B, Kmax, cap, max_gt
+
+
 def eval_match(pred: torch.Tensor, pred_counts: torch.Tensor, gt_rows: torch.Tensor, gt_offset: torch.Tensor,
                state: EvalState, max_gt: Optional[int] = None, want_match: bool = False):
     """Match one batch and add it to `state` (fdet_eval_match): pred (B,Kmax,5) [score,x,y,w,h] with pred_counts (B,) as
@@ -191,21 +212,7 @@ def eval_match(pred: torch.Tensor, pred_counts: torch.Tensor, gt_rows: torch.Ten
     synchronisation.  -> match (B,Kmax) int32 for the first threshold with `want_match`, else None."""
     if not isinstance(state, EvalState):
         raise ValueError("eval_match: state must be an EvalState")
-    if pred.dim() != 3 or pred.shape[2] != 5 or pred.dtype != F32 or pred.shape[0] < 1:
-        raise ValueError(f"eval_match: pred must be a (B>=1,Kmax,5) float32 tensor, got {tuple(pred.shape)} {pred.dtype}")
-    B, Kmax = int(pred.shape[0]), int(pred.shape[1])
-    if not 1 <= Kmax <= EVAL_MAX_DET:
-        raise ValueError(f"eval_match: Kmax={Kmax} detections per image, 1..{EVAL_MAX_DET} are supported")
-    if tuple(pred_counts.shape) != (B,) or pred_counts.dtype != I32:
-        raise ValueError(f"eval_match: pred_counts must be a ({B},) int32 tensor, got {tuple(pred_counts.shape)} {pred_counts.dtype}")
-    if gt_rows.dim() != 2 or gt_rows.shape[1] != 5 or gt_rows.dtype != F32 or gt_rows.shape[0] < 1:
-        raise ValueError(f"eval_match: gt_rows must be a (cap>=1,5) float32 tensor, got {tuple(gt_rows.shape)} {gt_rows.dtype}")
-    if tuple(gt_offset.shape) != (B + 1,) or gt_offset.dtype != I32:
-        raise ValueError(f"eval_match: gt_offset must be a ({B + 1},) int32 tensor, got {tuple(gt_offset.shape)} {gt_offset.dtype}")
-    cap = int(gt_rows.shape[0])
-    max_gt = min(cap, EVAL_MAX_GT) if max_gt is None else int(max_gt)
-    if not 1 <= max_gt <= EVAL_MAX_GT:
-        raise ValueError(f"eval_match: max_gt={max_gt} boxes per image, 1..{EVAL_MAX_GT} are supported")
+    B, Kmax, cap, max_gt = _eval_common_args("eval_match", pred, pred_counts, gt_rows, gt_offset, max_gt)
     pred, pred_counts, gt_rows, gt_offset = pred.contiguous(), pred_counts.contiguous(), gt_rows.contiguous(), gt_offset.contiguous()
     match = torch.empty(B, Kmax, dtype=I32, device=pred.device) if want_match else None
     check(lib().fdet_eval_match(ptr(pred), ptr(pred_counts, I32), B, Kmax, ptr(gt_rows), ptr(gt_offset, I32), cap, max_gt,
@@ -250,27 +257,13 @@ def eval_wider(pred: torch.Tensor, pred_counts: torch.Tensor, gt_rows: torch.Ten
     synchronisation."""
     if not isinstance(state, WiderState):
         raise ValueError("eval_wider: state must be a WiderState")
-    if pred.dim() != 3 or pred.shape[2] != 5 or pred.dtype != F32 or pred.shape[0] < 1:
-        raise ValueError(f"eval_wider: pred must be a (B>=1,Kmax,5) float32 tensor, got {tuple(pred.shape)} {pred.dtype}")
-    B, Kmax = int(pred.shape[0]), int(pred.shape[1])
-    if not 1 <= Kmax <= EVAL_MAX_DET:
-        raise ValueError(f"eval_wider: Kmax={Kmax} detections per image, 1..{EVAL_MAX_DET} are supported")
-    if tuple(pred_counts.shape) != (B,) or pred_counts.dtype != I32:
-        raise ValueError(f"eval_wider: pred_counts must be a ({B},) int32 tensor, got {tuple(pred_counts.shape)} {pred_counts.dtype}")
-    if gt_rows.dim() != 2 or gt_rows.shape[1] != 5 or gt_rows.dtype != F32 or gt_rows.shape[0] < 1:
-        raise ValueError(f"eval_wider: gt_rows must be a (cap>=1,5) float32 tensor, got {tuple(gt_rows.shape)} {gt_rows.dtype}")
-    cap = int(gt_rows.shape[0])
-    if tuple(gt_offset.shape) != (B + 1,) or gt_offset.dtype != I32:
-        raise ValueError(f"eval_wider: gt_offset must be a ({B + 1},) int32 tensor, got {tuple(gt_offset.shape)} {gt_offset.dtype}")
+    B, Kmax, cap, max_gt = _eval_common_args("eval_wider", pred, pred_counts, gt_rows, gt_offset, max_gt)
     if tuple(gt_subsets.shape) != (cap,) or gt_subsets.dtype != I32:
         raise ValueError(f"eval_wider: gt_subsets must be a ({cap},) int32 tensor, got {tuple(gt_subsets.shape)} {gt_subsets.dtype}")
     if pred_scale is not None and (tuple(pred_scale.shape) != (B, 2) or pred_scale.dtype != F32):
         raise ValueError(f"eval_wider: pred_scale must be a ({B},2) float32 tensor, got {tuple(pred_scale.shape)} {pred_scale.dtype}")
     if score_norm is not None and (tuple(score_norm.shape) != (2,) or score_norm.dtype != torch.float64):
         raise ValueError("eval_wider: score_norm must be a (2,) float64 tensor")
-    max_gt = min(cap, EVAL_MAX_GT) if max_gt is None else int(max_gt)
-    if not 1 <= max_gt <= EVAL_MAX_GT:
-        raise ValueError(f"eval_wider: max_gt={max_gt} boxes per image, 1..{EVAL_MAX_GT} are supported")
     pred, pred_counts, gt_rows, gt_offset, gt_subsets = (t.contiguous() for t in (pred, pred_counts, gt_rows, gt_offset, gt_subsets))
     check(lib().fdet_eval_wider(ptr(pred), ptr(pred_counts, I32), B, Kmax,
                                 ptr(None if pred_scale is None else pred_scale.contiguous()), ptr(gt_rows),

@@ -90,6 +90,51 @@ def test_decode_and_reduce_golden_bit_exact(hp, golden):
         assert torch.equal(out[0, :Ko].cpu(), g["out"][c, :Ko]), c
 
 
+def _multi_chunk_maps(S):
+    """(3,5,S,S) maps for the 256-wide compaction chunks of decode: scores from a set of 20 values (k/20, so equal scores
+    are frequent and 10/20 sits exactly on the threshold 0.5).  Map 0 mixes hits and misses, map 1 has every cell above
+    the threshold, map 2 none (its largest score equals the threshold: the comparison is strict)."""
+    g = torch.Generator().manual_seed(100 + S)
+    x = torch.rand(3, 5, S, S, generator=g)
+    x[:, 3:] = x[:, 3:] * 0.28 + 0.02                      # boxes of 2..30 % of the image: plenty of overlap
+    x[0, 0] = torch.randint(0, 20, (S, S), generator=g).float() / 20
+    x[1, 0] = torch.randint(11, 20, (S, S), generator=g).float() / 20
+    x[2, 0] = torch.randint(0, 11, (S, S), generator=g).float() / 20
+    return x
+
+
+@pytest.mark.parametrize("S", [16, 17, 23])
+def test_decode_and_reduce_multi_chunk_bit_exact(hp, S):
+    """decode and reduce_bounding_boxes past one 256-cell compaction chunk: 256 cells (exactly one full chunk), 289 (a
+    second chunk that ends inside a wave) and 529 (three chunks), bit for bit against the oracle's decode_pre_nms
+    followed by its nms."""
+    from oracle import yolo_oracle as Y
+    size, pt, iou, C = 480, 0.5, 0.3, S * S
+    x = _multi_chunk_maps(S)
+    ref = [Y.decode_pre_nms(x[n], pt, (3, size, size), S)[:2] for n in range(3)]
+    # the oracle alone, before anything is compared with it: the counts these inputs were built for
+    hit = (x[0, 0] > pt).flatten()
+    assert [r[0].numel() for r in ref] == [int(hit.sum()), C, 0] and 0 < int(hit.sum()) < C
+    for w0 in range(0, C, 64):                              # hits and misses in every wave of every chunk
+        assert 0 < int(hit[w0:w0 + 64].sum()) < hit[w0:w0 + 64].numel(), w0
+    assert ref[0][0].unique().numel() < ref[0][0].numel() and float(x[2, 0].max()) == pt
+    keeps = [Y.nms(rb, rs, iou) for rs, rb in ref]
+    assert all(0 < keeps[n].numel() < ref[n][0].numel() for n in (0, 1)) and keeps[2].numel() == 0   # the NMS has work
+
+    xb = x.cuda()
+    scores, boxes, counts = hp.decode(xb, pt, size, size)
+    out, oc = hp.reduce_bounding_boxes(xb, pt, iou, size, size)
+    assert counts.cpu().tolist() == [r[0].numel() for r in ref]
+    assert oc.cpu().tolist() == [k.numel() for k in keeps]
+    for n, ((rs, rb), keep) in enumerate(zip(ref, keeps)):
+        K = rs.numel()
+        assert torch.equal(scores[n, :K].cpu(), rs) and torch.equal(boxes[n, :K].cpu(), rb), (S, n)
+        want = torch.cat([rs.view(-1, 1), rb.view(-1, 4)], 1)[keep]
+        want[:, 3] -= want[:, 1]                            # utils.py:148-149
+        want[:, 4] -= want[:, 2]
+        assert torch.equal(out[n, :keep.numel()].cpu(), want), (S, n)
+
+
 @pytest.mark.parametrize("thr", [0.01, 0.3, 0.5])
 def test_nms_keep_sets_bit_exact(hp, thr):
     """torchvision.ops.nms semantics are restated (PARITY UNPINNED by the reference); the HIP
