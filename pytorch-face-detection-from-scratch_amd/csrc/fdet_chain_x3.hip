@@ -501,12 +501,19 @@ k_block_chain_x3(const ChainArgs a) {
 
 // ---- PS flavour, epilogue pipelined across the layer boundary --------------------------------------------------
 // Layer L+1's chunk c only reads the 16-channel group c of layer L's output, and there is a workgroup barrier at the end
-// of every chunk anyway.  So layer L's epilogue does its arithmetic, writes group 0 (X in LDS + the PS tensor in HBM) and
-// passes the barrier; groups 1, 2, 3 wait in 48 registers and are split / written as four "jobs" per chunk (taps 1, 3,
-// 5, 7) of layer L+1's chunks 0, 1, 2, behind its MFMAs.  Everything a job does is branch-free so that it can sit in one
+// of every chunk anyway.  Even and odd layers accumulate into two alternating accumulator sets (the layer loop is unrolled
+// by two so that both are static registers).  After its last MFMA a layer turns only group 0 of its sums into outputs (the
+// epilogue arithmetic, X in LDS, the PS tensor in HBM) -- before the barrier that ends chunk 3, since group 0 of X has
+// been free since chunk 0: ONE barrier per layer boundary.  Groups 1, 2, 3 stay in the finished set as raw sums and are
+// read, transformed (LeakyReLU / scale + skip / lrelu' mask, element by element as before), split and written as four
+// "jobs" per chunk (taps 1, 3, 5, 7) of layer L+1's chunks 0, 1, 2.  A job is written in stages that stand between the
+// tap's MFMAs in source order (sched_group_barrier left them in one lump behind the MFMAs).  During chunk 3 the idle set
+// is seeded with the next layer's bias.  Everything a job does is branch-free so that it can sit in one
 // scheduling region with the MFMAs: lanes of pad positions write LDS to a per-lane dummy slot and HBM through a buffer
-// descriptor at an out-of-range offset (dropped); a tensor that is not kept has an EMPTY descriptor.  Store counts are
-// therefore exact -- 12 per piece -- and the waits for the weight ring are counted (vmcnt 12 / 24), not drains.
+// descriptor at an out-of-range offset (dropped); a tensor that is not kept has an EMPTY descriptor; the first layer's
+// jobs (no producer) write to the dummy slot and an empty descriptor and leave the skip registers alone.  Store counts
+// are therefore exact -- SJ per chunk and per boundary, + 4 where c's hi plane rides along -- and the waits for the
+// weight ring are counted, not drains.
 // P16 (precision16, see fdet_conv3x3_ps.hip): one MFMA pass on the hi planes; the lo planes are neither moved, kept in
 // LDS nor written: a job is one LDS store and one buffer store, SJ = 4 stores per hand-over group instead of 8.
 template <bool BWD, bool P16 = false>
@@ -569,46 +576,111 @@ k_block_chain_ps(const ChainArgs a) {
   }
 
   // one job: four values (position tile J, 16-channel group P, k half HH) -> hi / lo split -> X, PS tensor, c's hi plane
-#define CHP_SUB(F0, F1, F2, F3, J, P, HH)                                                     \
+#define CHP_SUB(F0, F1, F2, F3, J, P, HH, OK)                                                  \
   {                                                                                                \
     const float f_[4] = {F0, F1, F2, F3};                                                          \
     unsigned hi_[2], lo_[2];                                                                       \
     if (P16) ps_hi4(f_, hi_); else ps_split4(f_, hi_, lo_);                                        \
     const unsigned ah_ = (unsigned)((((P) * 2 + 0) * 2 + (HH)) * PT) * 16u, al_ = (unsigned)((((P) * 2 + 1) * 2 + (HH)) * PT) * 16u; \
-    *reinterpret_cast<u32x2*>(smem + (valid[J] ? ah_ + xw[J] : dmy)) = u32x2{hi_[0], hi_[1]};      \
-    if (!P16) *reinterpret_cast<u32x2*>(smem + (valid[J] ? al_ + xw[J] : dmy)) = u32x2{lo_[0], lo_[1]}; \
+    *reinterpret_cast<u32x2*>(smem + ((OK) ? ah_ + xw[J] : dmy)) = u32x2{hi_[0], hi_[1]};      \
+    if (!P16) *reinterpret_cast<u32x2*>(smem + ((OK) ? al_ + xw[J] : dmy)) = u32x2{lo_[0], lo_[1]}; \
     const unsigned go_ = pso[J] + (unsigned)(4 * ((P) >> 1) + 2 * ((P) & 1) + (HH)) * ps_g;        \
     __builtin_amdgcn_raw_buffer_store_b64(u32x2{hi_[0], hi_[1]}, tgt_rs, go_, 0, 0);               \
     if (!P16) __builtin_amdgcn_raw_buffer_store_b64(u32x2{lo_[0], lo_[1]}, tgt_rs, go_, ps_lo, 0); \
   }
-  // group 0 of a finished tile now; groups 1..3 into the pending registers
-#define CHP_HAND_OVER(V)                                                                           \
+  // every group of a tile at once (the chain input)
+#define CHP_WRITE_ALL(V)                                                                           \
   {                                                                                                \
     _Pragma("unroll") for (int j_ = 0; j_ < NT; ++j_)                                              \
-      _Pragma("unroll") for (int h_ = 0; h_ < 2; ++h_)                                             \
-        CHP_SUB(V[j_][0][4 * h_], V[j_][0][4 * h_ + 1], V[j_][0][4 * h_ + 2], V[j_][0][4 * h_ + 3], j_, 0, h_) \
-    _Pragma("unroll") for (int j_ = 0; j_ < NT; ++j_)                                              \
-      _Pragma("unroll") for (int p_ = 1; p_ < 4; ++p_)                                             \
-        _Pragma("unroll") for (int i_ = 0; i_ < 8; ++i_) pend[j_][p_ - 1][i_] = V[j_][p_ >> 1][8 * (p_ & 1) + i_]; \
+      _Pragma("unroll") for (int p_ = 0; p_ < 4; ++p_)                                             \
+        _Pragma("unroll") for (int h_ = 0; h_ < 2; ++h_)                                           \
+          CHP_SUB(V[j_][p_ >> 1][8 * (p_ & 1) + 4 * h_], V[j_][p_ >> 1][8 * (p_ & 1) + 4 * h_ + 1], \
+                  V[j_][p_ >> 1][8 * (p_ & 1) + 4 * h_ + 2], V[j_][p_ >> 1][8 * (p_ & 1) + 4 * h_ + 3], j_, p_, h_, valid[j_]) \
   }
-  __amdgpu_buffer_rsrc_t tgt_rs = __builtin_amdgcn_make_buffer_rsrc((void*)nullptr, 0, 0, 0x00020000);
+  // One lazy job: the four sums of (tile J, group P, k half HH) leave the finished accumulator set ACC, get the epilogue
+  // arithmetic of the layer that produced them (PODD: its parity; AUX: its lrelu' operand; LROW: its row of the scale
+  // table), are split and go to X, the PS tensor and c's hi plane.  KEEP (the jobs of the first layer, which has no
+  // producer): Hreg stays as it is.  The job is written in ten stages S so that a tap can place them BETWEEN its MFMAs
+  // in source order: 0 scale read, 1..4 one value each, 5 c's hi plane, 6 / 7 split of one value pair, 8 X, 9 PS tensor.
+#define CHP_JOB_VARS                                                                               \
+  float fj_[4], cj_[4] = {0.f, 0.f, 0.f, 0.f};                                                     \
+  unsigned jh_[2] = {0u, 0u}, jl_[2] = {0u, 0u};                                                   \
+  f32x4 sv_ = {1.f, 1.f, 1.f, 1.f};
+#define CHP_JOB_ST(S, ACC, AUX, J, P, HH, PODD, LROW, KEEP, OK)                                    \
+  {                                                                                                \
+    typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));                                   \
+    const int m_ = (P) >> 1, r0_ = 8 * ((P) & 1) + 4 * (HH);                                        \
+    if ((S) == 0) {                                                                                \
+      if (PODD) sv_ = *reinterpret_cast<const f32x4*>(Ls + (LROW) * FCH + 32 * m_ + 2 * r0_ + 4 * half); \
+    } else if ((S) <= 4) {                                                                         \
+      const int i_ = ((S) - 1) & 3;                                                                \
+      const float s_ = ACC[J][m_][r0_ + i_];                                                       \
+      if (!BWD) {                                                                                  \
+        const float v_ = s_ > 0.f ? s_ : s_ * a.slope;                                             \
+        cj_[i_] = v_;                                                                              \
+        if (PODD) {                                                                                \
+          const float hn_ = v_ * sv_[i_] + Hreg[J][m_][r0_ + i_];                                  \
+          Hreg[J][m_][r0_ + i_] = (KEEP) ? Hreg[J][m_][r0_ + i_] : hn_;                            \
+          fj_[i_] = Hreg[J][m_][r0_ + i_];                                                         \
+        } else {                                                                                   \
+          fj_[i_] = v_;                                                                            \
+        }                                                                                          \
+      } else if (!(PODD)) {                                                                        \
+        fj_[i_] = s_ * (CH_POS(AUX, J, m_, r0_ + i_) ? 1.f : a.slope);                             \
+      } else {                                                                                     \
+        const float hn_ = Hreg[J][m_][r0_ + i_] + s_;                                              \
+        Hreg[J][m_][r0_ + i_] = (KEEP) ? Hreg[J][m_][r0_ + i_] : hn_;                              \
+        fj_[i_] = Hreg[J][m_][r0_ + i_] * sv_[i_] * (CH_POS(AUX, J, m_, r0_ + i_) ? 1.f : a.slope); \
+      }                                                                                            \
+    } else if ((S) == 5) {                                                                         \
+      if (!BWD && (PODD)) {                                     /* c: only its hi plane (its signs) is kept */ \
+        const bf16x2_t h0_ = {(__bf16)cj_[0], (__bf16)cj_[1]}, h1_ = {(__bf16)cj_[2], (__bf16)cj_[3]}; \
+        __builtin_amdgcn_raw_buffer_store_b64(u32x2{__builtin_bit_cast(unsigned, h0_), __builtin_bit_cast(unsigned, h1_)}, crs, \
+                                              pso[J] + (unsigned)(4 * m_ + (r0_ >> 2)) * ps_g, 0, 0); \
+      }                                                                                            \
+    } else if ((S) <= 7) {                                      /* as ps_split4 / ps_hi4 (fdet_ps.h), one pair */ \
+      const int k_ = (S) & 1;                                                                      \
+      const bf16x2_t h_ = {(__bf16)fj_[2 * k_], (__bf16)fj_[2 * k_ + 1]};                          \
+      jh_[k_] = __builtin_bit_cast(unsigned, h_);                                                  \
+      if (!P16) {                                                                                  \
+        const float h0_ = __builtin_bit_cast(float, jh_[k_] << 16), h1_ = __builtin_bit_cast(float, jh_[k_] & 0xffff0000u); \
+        const bf16x2_t l_ = {(__bf16)(fj_[2 * k_] - h0_), (__bf16)(fj_[2 * k_ + 1] - h1_)};        \
+        jl_[k_] = __builtin_bit_cast(unsigned, l_);                                                \
+      }                                                                                            \
+    } else if ((S) == 8) {                                                                         \
+      const unsigned ah_ = (unsigned)((((P) * 2 + 0) * 2 + (HH)) * PT) * 16u, al_ = (unsigned)((((P) * 2 + 1) * 2 + (HH)) * PT) * 16u; \
+      *reinterpret_cast<u32x2*>(smem + ((OK) ? ah_ + xw[J] : dmy)) = u32x2{jh_[0], jh_[1]};        \
+      if (!P16) *reinterpret_cast<u32x2*>(smem + ((OK) ? al_ + xw[J] : dmy)) = u32x2{jl_[0], jl_[1]}; \
+    } else {                                                                                       \
+      const unsigned go_ = pso[J] + (unsigned)(4 * ((P) >> 1) + 2 * ((P) & 1) + (HH)) * ps_g;      \
+      __builtin_amdgcn_raw_buffer_store_b64(u32x2{jh_[0], jh_[1]}, tgt_rs, go_, 0, 0);             \
+      if (!P16) __builtin_amdgcn_raw_buffer_store_b64(u32x2{jl_[0], jl_[1]}, tgt_rs, go_, ps_lo, 0); \
+    }                                                                                              \
+  }
+#define CHP_JOB(ACC, AUX, J, P, HH, PODD, LROW, KEEP, OK)                                          \
+  {                                                                                                \
+    CHP_JOB_VARS                                                                                   \
+    _Pragma("unroll") for (int s_j = 0; s_j < 10; ++s_j) CHP_JOB_ST(s_j, ACC, AUX, J, P, HH, PODD, LROW, KEEP, OK) \
+  }
+#define CHP_EMPTY __builtin_amdgcn_make_buffer_rsrc((void*)nullptr, 0, 0, 0x00020000)
 #define CHP_TARGET(PTR) __builtin_amdgcn_make_buffer_rsrc((void*)(PTR), 0, (PTR) ? ps_bytes : 0, 0x00020000)
-  float pend[NT][3][8];
-  int young = 0;                                                // stores issued after the DMA of the next layer's chunk 1
+  __amdgpu_buffer_rsrc_t tgt_rs = CHP_EMPTY, crs = CHP_EMPTY;   // targets of the jobs: the kept tensor, c's hi plane
 
   f32x16 Hreg[NT][2];                                           // skip connection / running gradient
-  u32x2 auxb[NT][2][4];                                         // raw PS hi pieces of the lrelu' operand (bwd)
+  f32x16 accS[2][NT][2];                                        // the sums of even / odd layers
+  u32x2 auxS[2][NT][2][4];                                      // raw PS hi pieces of the lrelu' operand of even / odd layers (bwd)
   if (a.psio & 2) CH_LOAD_PS(Hreg, a.in) else CH_LOAD_TILE(Hreg, a.in)
-  if (BWD) CH_LOAD_HI(auxb, a.pre_ld)
+  if (BWD) CH_LOAD_HI(auxS[1], a.pre_ld)
   __syncthreads();                                              // zero fill done
   if (!BWD) {
-    CHP_HAND_OVER(Hreg)
+    CHP_WRITE_ALL(Hreg)
   } else {                                                      // dz2 of the first block to run = dout * scale * lrelu'(c)
     f32x16 t[NT][2], s2[2];
     CH_SCALE_TILE(s2, a.pre_sc)
-    CH_FOR_ALL t[j][m][r] = Hreg[j][m][r] * s2[m][r] * (CH_POS(auxb, j, m, r) ? 1.f : a.slope);
+    CH_FOR_ALL t[j][m][r] = Hreg[j][m][r] * s2[m][r] * (CH_POS(auxS[1], j, m, r) ? 1.f : a.slope);
     tgt_rs = CHP_TARGET(a.pre_st);
-    CHP_HAND_OVER(t)
+    CHP_WRITE_ALL(t)
+    tgt_rs = CHP_EMPTY;
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");             // first weight chunk landed
   __syncthreads();
@@ -620,112 +692,124 @@ k_block_chain_ps(const ChainArgs a) {
   const int w_off = half * FCH + l31;
   const int x_off = half * PT + wid * (32 * NT) + l31;
 
-  for (int L = 0; L < a.nlayers; ++L) {
-    f32x16 acc[NT][2];
-    const bool odd = L & 1, last = L + 1 == a.nlayers;
-    if (!BWD) {                                                 // the sums start from the bias
-      f32x16 b0[2];
-      CHP_LDS_TILE(b0, Lb + L * FCH)
-      CH_FOR_ALL acc[j][m][r] = b0[m][r];
-    } else {
-      CH_FOR_ALL acc[j][m][r] = 0.f;
-    }
-    if (BWD && a.ld[L]) CH_LOAD_HI(auxb, a.ld[L])               // the lrelu' operand of this layer's epilogue
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      // weight ring (buffer c & 1 holds chunk c): chunk 1 of a layer was issued before the previous epilogue
-      if (!(P16 && wid >= 2)) {                                 // P16: the lo-plane waves move nothing
-        if (c == 1 || c == 2) CH_DMA_W(L, c + 1, (c & 1) ^ 1)
-        else if (c == 3 && !last) CH_DMA_W(L + 1, 0, 0)
-      }
-      const bf16x8* Ww = Wb + (c & 1) * 2 * A_UNITS + w_off;
-      const bf16x8* Xh = X + (c * 2 + 0) * 2 * PT + x_off;
-      const bf16x8* Xl = X + (c * 2 + 1) * 2 * PT + x_off;
-      bf16x8 wh[2][2], wl[2][2], xh[2][NT], xl[2][NT];
-#pragma unroll
-      for (int m = 0; m < 2; ++m) { wh[0][m] = Ww[m * 32]; if (!P16) wl[0][m] = Ww[A_UNITS + m * 32]; }
-#pragma unroll
-      for (int j = 0; j < NT; ++j) { xh[0][j] = Xh[tapoff[0] + j * 32]; if (!P16) xl[0][j] = Xl[tapoff[0] + j * 32]; }
-#pragma unroll
-      for (int t = 0; t < 9; ++t) {
-        const int cur = t & 1, nxt = cur ^ 1;
-        if (t + 1 < 9) {
-#pragma unroll
-          for (int m = 0; m < 2; ++m) {
-            wh[nxt][m] = Ww[(t + 1) * 2 * FCH + m * 32];
-            if (!P16) wl[nxt][m] = Ww[A_UNITS + (t + 1) * 2 * FCH + m * 32];
-          }
-#pragma unroll
-          for (int j = 0; j < NT; ++j) {
-            xh[nxt][j] = Xh[tapoff[t + 1] + j * 32];
-            if (!P16) xl[nxt][j] = Xl[tapoff[t + 1] + j * 32];
-          }
-        }
-        __builtin_amdgcn_sched_barrier(0);                      // keep the fragment reads one tap ahead of their MFMAs
-        if (CH_DBG & 4) { acc[0][0][0] += (float)wh[cur][0][0] + (float)xh[cur][0][0] + (float)wh[cur][1][0] + (float)xh[cur][1][0]; } else {
-        if (!P16) {
-#pragma unroll
-        for (int j = 0; j < NT; ++j)
-#pragma unroll
-          for (int m = 0; m < 2; ++m) acc[j][m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wh[cur][m], xl[cur][j], acc[j][m], 0, 0, 0);
-#pragma unroll
-        for (int j = 0; j < NT; ++j)
-#pragma unroll
-          for (int m = 0; m < 2; ++m) acc[j][m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wl[cur][m], xh[cur][j], acc[j][m], 0, 0, 0);
-        }
-#pragma unroll
-        for (int j = 0; j < NT; ++j)
-#pragma unroll
-          for (int m = 0; m < 2; ++m) acc[j][m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wh[cur][m], xh[cur][j], acc[j][m], 0, 0, 0);
-        }
-        if (!(CH_DBG & 2) && c < 3 && (t & 1)) {                // a pending job of the previous layer's group c + 1
-          constexpr int dummy_ = 0; (void)dummy_;
-          const int jj = (t - 1) >> 2, hh = ((t - 1) >> 1) & 1;
-          CHP_SUB(pend[jj][c][4 * hh], pend[jj][c][4 * hh + 1], pend[jj][c][4 * hh + 2], pend[jj][c][4 * hh + 3], jj, c + 1, hh)
-          if (!P16) {
-#pragma unroll
-          for (int i = 0; i < 12; ++i) {
-            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-            __builtin_amdgcn_sched_group_barrier(0x002, 3, 0);
-            if (i == 8 || i == 9) __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);
-            if (i >= 10) __builtin_amdgcn_sched_group_barrier(0x040, 1, 0);
-          }
-          } else {
-#pragma unroll
-          for (int i = 0; i < 4; ++i) {
-            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-            __builtin_amdgcn_sched_group_barrier(0x002, 5, 0);
-            if (i == 2) __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);
-            if (i == 3) __builtin_amdgcn_sched_group_barrier(0x040, 1, 0);
-          }
-          }
-        }
-        __builtin_amdgcn_sched_barrier(0);
-      }
-      // this wave's pieces of the next chunk have landed: everything issued after them is the 8 job stores of this chunk
-      // (chunks 0..2) and, after chunk 0, the `young` stores of the previous epilogue (8 of group 0, 16 more for c's hi plane)
-      if (c == 0) {
-        if (young == 0) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(SJ) : "memory");
-        else if (young == SJ) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * SJ) : "memory");
-        else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * SJ + 16) : "memory");
-      }
-      else if (c < 3) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(SJ) : "memory");
-      else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __syncthreads();                                          // chunk consumed by every wave; next one visible
-    }
-    if (!last && !(P16 && wid >= 2)) CH_DMA_W(L + 1, 1, 1)      // buffer of chunk 3 is free: next layer's chunk 1
+  // layer 0 starts from its bias; the other set is what layer 0's jobs read (nothing they make of it is kept)
+  CH_FOR_ALL accS[1][j][m][r] = 0.f;
+  if (!BWD) {
+    f32x16 b0[2];
+    CHP_LDS_TILE(b0, Lb)
+    CH_FOR_ALL accS[0][j][m][r] = b0[m][r];
+  } else {
+    CH_FOR_ALL accS[0][j][m][r] = 0.f;
+  }
 
-    // ---- epilogue arithmetic for the whole tile (in place), then group 0 now and groups 1..3 handed to the next layer
-    young = SJ;
-    if (CH_DBG & 1) {
-    } else if (!BWD) {
-      CH_FOR_ALL { const float t = acc[j][m][r]; acc[j][m][r] = t > 0.f ? t : t * a.slope; }
-      if (!odd) {
-        tgt_rs = CHP_TARGET(a.st[L]);
-        CHP_HAND_OVER(acc)
-      } else {
-        // c: only its hi plane (its signs) is kept -- stored here for the whole tile, 16 exact-count stores
-        const __amdgpu_buffer_rsrc_t crs = CHP_TARGET(a.st[L]);
+  for (int L0 = 0; L0 < a.nlayers; L0 += 2) {
+#pragma unroll
+    for (int par = 0; par < 2; ++par) {                         // static accumulator sets: even layers in set 0, odd in set 1
+      const int L = L0 + par;
+      const bool last = par == 1 && L + 1 == a.nlayers;
+      const bool first = par == 0 && L0 == 0;
+      const bool jok[NT] = {valid[0] && !first, valid[1] && !first};
+      const int lrow = first ? 0 : (L - 1) >> 1;
+      f32x16 (&acc)[NT][2] = accS[par];
+      f32x16 (&prv)[NT][2] = accS[par ^ 1];
+      if (BWD && a.ld[L]) CH_LOAD_HI(auxS[par], a.ld[L])         // the lrelu' operand of this layer's epilogue
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        // weight ring (buffer c & 1 holds chunk c): chunk 1 of a layer is issued behind the barrier of the layer boundary
+        if (!(P16 && wid >= 2)) {                               // P16: the lo-plane waves move nothing
+          if (c == 1 || c == 2) CH_DMA_W(L, c + 1, (c & 1) ^ 1)
+          else if (c == 3 && !last) CH_DMA_W(L + 1, 0, 0)
+        }
+        const bf16x8* Ww = Wb + (c & 1) * 2 * A_UNITS + w_off;
+        const bf16x8* Xh = X + (c * 2 + 0) * 2 * PT + x_off;
+        const bf16x8* Xl = X + (c * 2 + 1) * 2 * PT + x_off;
+        bf16x8 wh[2][2], wl[2][2], xh[2][NT], xl[2][NT];
+#pragma unroll
+        for (int m = 0; m < 2; ++m) { wh[0][m] = Ww[m * 32]; if (!P16) wl[0][m] = Ww[A_UNITS + m * 32]; }
+#pragma unroll
+        for (int j = 0; j < NT; ++j) { xh[0][j] = Xh[tapoff[0] + j * 32]; if (!P16) xl[0][j] = Xl[tapoff[0] + j * 32]; }
+#pragma unroll
+        for (int t = 0; t < 9; ++t) {
+          const int cur = t & 1, nxt = cur ^ 1;
+          if (t + 1 < 9) {
+#pragma unroll
+            for (int m = 0; m < 2; ++m) {
+              wh[nxt][m] = Ww[(t + 1) * 2 * FCH + m * 32];
+              if (!P16) wl[nxt][m] = Ww[A_UNITS + (t + 1) * 2 * FCH + m * 32];
+            }
+#pragma unroll
+            for (int j = 0; j < NT; ++j) {
+              xh[nxt][j] = Xh[tapoff[t + 1] + j * 32];
+              if (!P16) xl[nxt][j] = Xl[tapoff[t + 1] + j * 32];
+            }
+          }
+          __builtin_amdgcn_sched_barrier(0);                    // keep the fragment reads one tap ahead of their MFMAs
+          // MFMA K of a tap (product-major: consecutive MFMAs go to different accumulators) and, at taps 1, 3, 5, 7 of
+          // chunks 0..2, stage S of a job of the previous layer's group c + 1 out of the other set.  The stages stand
+          // BETWEEN the MFMAs in source order, which is the order the matrix and vector pipes then see.
+          const bool jobtap = !(CH_DBG & 2) && c < 3 && (t & 1);
+          const int jj = (t >> 2) & 1, hh = (t >> 1) & 1;
+          CHP_JOB_VARS
+#define CH_MF(K)                                                                                   \
+  {                                                                                                \
+    const int j_ = ((K) >> 1) & 1, m_ = (K) & 1;                                                   \
+    if ((K) < 4) acc[j_][m_] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wh[cur][m_], xl[cur][j_], acc[j_][m_], 0, 0, 0);      \
+    else if ((K) < 8) acc[j_][m_] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wl[cur][m_], xh[cur][j_], acc[j_][m_], 0, 0, 0); \
+    else acc[j_][m_] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wh[cur][m_], xh[cur][j_], acc[j_][m_], 0, 0, 0);              \
+  }
+#define CH_JS(S) if (jobtap) CHP_JOB_ST(S, prv, auxS[par ^ 1], jj, c + 1, hh, par == 0, lrow, first, jok[jj])
+          if (CH_DBG & 4) {
+            acc[0][0][0] += (float)wh[cur][0][0] + (float)xh[cur][0][0] + (float)wh[cur][1][0] + (float)xh[cur][1][0];
+          } else if (!P16) {
+            CH_JS(0) CH_MF(0) CH_JS(1) CH_MF(1) CH_JS(2) CH_MF(2) CH_JS(3) CH_MF(3) CH_JS(4) CH_MF(4) CH_JS(5) CH_JS(6)
+            CH_MF(5) CH_JS(7) CH_MF(6) CH_JS(8) CH_MF(7) CH_JS(9) CH_MF(8) CH_MF(9) CH_MF(10) CH_MF(11)
+          } else {
+            CH_JS(0) CH_MF(8) CH_JS(1) CH_JS(2) CH_MF(9) CH_JS(3) CH_JS(4) CH_JS(5) CH_MF(10) CH_JS(6) CH_JS(7) CH_JS(8)
+            CH_MF(11) CH_JS(9)
+          }
+          if (c == 3 && (t & 1)) {                              // the idle set is free: seed one tile of the next layer's sums
+            const int sj = (t - 1) >> 2, sm = ((t - 1) >> 1) & 1;
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+              f32x4 v = {0.f, 0.f, 0.f, 0.f};
+              if (!BWD) v = *reinterpret_cast<const f32x4*>(Lb + (L + 1) * FCH + 32 * sm + 8 * g + 4 * half);
+#pragma unroll
+              for (int i = 0; i < 4; ++i) prv[sj][sm][4 * g + i] = v[i];
+            }
+          }
+          __builtin_amdgcn_sched_barrier(0);
+        }
+        // this wave's pieces of the next chunk have landed: everything issued after them is the job stores of this chunk
+        // (after chunk 0 also the lrelu' loads of this layer, which only add slack).  Chunk 3 ends behind the hand-over.
+        if (c < 3) {
+          if (!BWD && par == 0) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(SJ + 4) : "memory");   // + c's hi plane, one store per job
+          else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(SJ) : "memory");
+          __syncthreads();                                      // chunk consumed by every wave; next one visible
+        }
+      }
+
+      // ---- layer boundary.  Chunk c reads X group c only, so group 0 has been free since the barrier of chunk 0: its
+      // new values are written BEFORE the barrier that ends chunk 3, and that one barrier also publishes them.  Groups
+      // 1..3 stay in this layer's accumulator set for the next layer's jobs.
+      if (!last) {
+        if (par == 0) {
+          tgt_rs = CHP_TARGET(a.st[L]);
+        } else {
+          tgt_rs = CHP_TARGET(a.st2[L]);
+          if (!BWD) crs = CHP_TARGET(a.st[L]);
+        }
+        if (!(CH_DBG & 1)) {
+#pragma unroll
+          for (int j = 0; j < NT; ++j)
+#pragma unroll
+            for (int h = 0; h < 2; ++h) CHP_JOB(acc, auxS[par], j, 0, h, par == 1, L >> 1, false, valid[j])
+        }
+        // the next layer's chunk 0 has landed: only the stores above are younger
+        if (!BWD && par == 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(SJ + 4) : "memory");
+        else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(SJ) : "memory");
+      } else if (!BWD) {                                        // last layer: the whole tile now
+        CH_FOR_ALL { const float t = acc[j][m][r]; acc[j][m][r] = t > 0.f ? t : t * a.slope; }
+        crs = CHP_TARGET(a.st[L]);
 #pragma unroll
         for (int j = 0; j < NT; ++j)
 #pragma unroll
@@ -740,33 +824,22 @@ k_block_chain_ps(const ChainArgs a) {
         f32x16 s2[2];
         CHP_LDS_TILE(s2, Ls + (L >> 1) * FCH)
         CH_FOR_ALL Hreg[j][m][r] = acc[j][m][r] * s2[m][r] + Hreg[j][m][r];
-        if (last) {
-          CH_STORE_TILE(a.st2[L], Hreg)                         // chain output, fp32 NCHW
-        } else {
-          tgt_rs = CHP_TARGET(a.st2[L]);
-          CHP_HAND_OVER(Hreg)
-          young = SJ + 16;
-        }
-      }
-    } else {
-      if (!odd) {                                               // conv2^T: dz1 = acc * lrelu'(a)
-        CH_FOR_ALL acc[j][m][r] *= (CH_POS(auxb, j, m, r) ? 1.f : a.slope);
-        tgt_rs = CHP_TARGET(a.st[L]);
-        CHP_HAND_OVER(acc)
-      } else {                                                  // conv1^T: dx = acc + dout
+        CH_STORE_TILE(a.st2[L], Hreg)                           // chain output, fp32 NCHW
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      } else {
         CH_FOR_ALL Hreg[j][m][r] += acc[j][m][r];
-        if (last) {
-          CH_STORE_TILE(a.st2[L], Hreg)                         // gradient w.r.t. the chain input, fp32 NCHW
-        } else {                                                // dz2 of the next block to run
-          f32x16 s2[2];
-          CHP_LDS_TILE(s2, Ls + (L >> 1) * FCH)
-          CH_FOR_ALL acc[j][m][r] = Hreg[j][m][r] * s2[m][r] * (CH_POS(auxb, j, m, r) ? 1.f : a.slope);
-          tgt_rs = CHP_TARGET(a.st2[L]);
-          CHP_HAND_OVER(acc)
-        }
+        CH_STORE_TILE(a.st2[L], Hreg)                           // gradient w.r.t. the chain input, fp32 NCHW
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       }
+      if (CH_DBG & 3) {                                         // (the sums stay live, or the MFMAs go with their readers)
+#pragma unroll
+        for (int j = 0; j < NT; ++j)
+#pragma unroll
+          for (int m = 0; m < 2; ++m) asm volatile("" ::"a"(acc[j][m]));
+      }
+      __syncthreads();                                          // chunk 3 consumed by every wave, group 0 of the new X visible
+      if (!last && !(P16 && wid >= 2)) CH_DMA_W(L + 1, 1, 1)    // buffer of chunk 3 is free: next layer's chunk 1
     }
-    __syncthreads();                                            // group 0 of the new X visible
   }
 }
 
