@@ -1101,6 +1101,51 @@ int fdet_jpeg_reconstruct(const int16_t* coef, size_t coef_count, const fdet_jpe
                           int n_images, uint8_t* workspace, size_t workspace_bytes, uint8_t* bank, size_t bank_bytes,
                           void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Int8 inference: the PoolResnet residual trunk post-training-quantised, on the integer matrix cores
+ * (v_mfma_i32_16x16x64_i8).  Inference only.  The reference has no such path (it ships pruner.py and ONNX / TorchScript
+ * export for deployment); the arithmetic below is this project's contract, restated in numpy by tests/q8_cpu_ref.py, and
+ * the GPU results equal that restatement bit for bit.
+ *
+ * Quantisation is symmetric: q = clamp(rintf(x * (1.0f / s)), -127, 127) (round half to even, NaN -> 0, -128 never
+ * produced), x = float(q) * s.  Activation scales are per tensor, weight scales per output channel.
+ *
+ * Activation layout ("Q8"): int8 [N][H+2][W+2][C], channel innermost, with a one-pixel halo of ZEROS round every image
+ * (0 is the real zero of a symmetric code, so a conv reads its padding from the halo and tests no bounds).  The caller
+ * zero-fills a buffer once; every producer below writes real pixels only, so a buffer reused for the SAME shape keeps its
+ * halo.  A buffer reused for another shape must be zero-filled again.  Base pointers are 16-byte aligned.
+ *
+ * Packed weights: int8 [9 taps ky*3+kx][C/64][Cout][64] -- for each tap and chunk of 64 input channels, the 64 input-channel
+ * bytes of every output channel in a row (a plain permutation of [Cout][Cin][3][3]; quantize.py does it with torch).
+ * ------------------------------------------------------------------------------------- */
+
+/* 1 when Q8 tensors and fdet_q8_conv3x3 take this shape: C a multiple of 64 up to 256, 1 <= H, W <= 4096. */
+int fdet_q8_supported(int C, int H, int W);
+
+/* Bytes of a Q8 tensor, N * (H+2) * (W+2) * C; 0 for an unsupported shape or 2^31 bytes and more. */
+size_t fdet_q8_act_bytes(int N, int C, int H, int W);
+
+/* x fp32 [N,C,H,W] -> q (Q8), q = clamp(rintf(x * (1.0f / scale)), -127, 127); a NaN product (a NaN input, or 0 * inf under a
+ * scale so small that its reciprocal overflows) -> 0.  Real pixels only. */
+int fdet_q8_quantize(const float* x, float scale, int8_t* q, int N, int C, int H, int W, void* stream);
+
+/* q (Q8) -> x fp32 [N,C,H,W] = float(q) * scale (what fdet_head_fwd takes).  With scale 1 the two converters carry exact
+ * integers in and out. */
+int fdet_q8_dequantize(const int8_t* q, float scale, float* x, int N, int C, int H, int W, void* stream);
+
+/* 3x3 convolution, pad 1, C -> C channels, with the requantising epilogue in registers:
+ *     acc = bias[co] + sum x_q * w_q                       int32, exact
+ *     t   = float(acc) * mul[co]                           (int -> float RNE, one multiply)
+ *     t   = t >= 0 ? t : t * slope
+ *     t   = t + float(skip_q) * skip_mul                   (skip != NULL only; one multiply, one add, not fused)
+ *     q   = clamp(rintf(t), -127, 127)
+ *     y   = pool ? max of q over each 2x2 window : q       (pool: even H and W; y is a Q8 tensor of H/2 x W/2)
+ *   x, skip [N,C,H,W] Q8; wpk packed weights (9*C*C bytes); bias [C] int32; mul [C] fp32; y Q8, not aliasing x or skip.
+ * One kernel family for every supported shape: a wave computes 64 output channels of 4 rows x 16 columns, its block keeps
+ * the 64 channels' weights in LDS. */
+int fdet_q8_conv3x3(const int8_t* x, const int8_t* wpk, const int32_t* bias, const float* mul, const int8_t* skip,
+                    float skip_mul, int8_t* y, int N, int C, int H, int W, int pool, float slope, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -3,7 +3,7 @@
     python -m fdet_amd.detect_images --checkpoint CKPT --images DIR --out FILE [--model poolresnet --filters 128]
         [--tile 480 --overlap 0.25 --no-whole --edge-margin 0 --probability-threshold P --iou-threshold T --precision 16]
         [--flip --vote --min-votes N] [--draw DIR [--anonymize pixelate] [--blocks N] [--draw-format png|jpg] [--no-outline]]
-        [--chips DIR [--chip-size N] [--chip-margin F]]
+        [--chips DIR [--chip-size N] [--chip-margin F]] [--int8 [--calib DIR] [--calib-images N]]
 
 The images under DIR (searched recursively: .jpg .jpeg .png .bmp) are decoded with PIL into a device image bank
 (`bank_from_files`; `--device-jpeg`: baseline JPEGs are reconstructed on the device instead, with the same bytes), `tiling.TiledDetector` runs the model on overlapping windows of each image (and on the whole image
@@ -19,6 +19,9 @@ rendered on the device, chunk by chunk, from the bank the detector just read.
 `--chips DIR` also writes every detected face as a `--chip-size` x `--chip-size` crop (112) around its box widened by
 `--chip-margin` of its longer side (0.25), cut on the device (`chips.extract_chips`), to
 `DIR/<path relative to --images without its suffix>_<row>.png`.
+`--int8` (poolresnet) runs the residual trunk post-training-quantised on the integer matrix cores (`quantize.py`, DESIGN.md
+5j): the activation scales are calibrated first, with the float model, on the first `--calib-images` images (32) under
+`--calib DIR` (default: the input images), each resized whole to the model resolution.
 """
 import argparse
 import os
@@ -50,6 +53,48 @@ def add_model_arguments(ap) -> None:
     ap.add_argument("--checkpoint", default=None)
     ap.add_argument("--probability-threshold", type=float, default=0.5)
     ap.add_argument("--iou-threshold", type=float, default=0.5)
+
+
+def add_int8_arguments(ap) -> None:
+    """--int8 and the calibration options that need it (shared with run_validation_epoch); `check_int8_arguments` checks them."""
+    ap.add_argument("--int8", action="store_true", help="poolresnet: run the residual trunk in int8 (post-training quantisation)")
+    ap.add_argument("--calib", default=None, metavar="DIR", help="with --int8: calibration images (default: the first input images)")
+    ap.add_argument("--calib-images", type=int, default=None, help="with --int8: number of calibration images (32)")
+
+
+def check_int8_arguments(ap, args) -> None:
+    if not args.int8:
+        for flag, given in (("--calib", args.calib is not None), ("--calib-images", args.calib_images is not None)):
+            if given:
+                ap.error(f"{flag} needs --int8")
+        return
+    if args.precision == 16:
+        ap.error("--int8 and --precision 16 are two arithmetic modes of the same convolutions: choose one")
+    if args.model != "poolresnet":
+        ap.error("--int8 covers --model poolresnet only")
+    if args.calib_images is not None and args.calib_images < 1:
+        ap.error("--calib-images must be >= 1")
+    args.calib_images = 32 if args.calib_images is None else args.calib_images
+
+
+def image_paths(root):
+    root = Path(root)
+    return sorted(p for p in root.rglob("*") if p.suffix.lower() in EXTENSIONS)
+
+
+def quantize_loaded_model(model, args, default_bank=None, decoder="pil"):
+    """--int8: calibrate `model` on the images under --calib (or on `default_bank`) and return its Int8PoolResnet."""
+    from .quantize import Int8PoolResnet, bank_frames, calibrate
+    bank = default_bank
+    if args.calib is not None:
+        from .datasets.WIDERFace.annotations import bank_from_files
+        paths = image_paths(args.calib)[:args.calib_images]
+        if not paths:
+            raise SystemExit(f"no image under {args.calib}")
+        bank = bank_from_files(paths, "cuda", decoder=decoder)
+    qp = calibrate(model, bank_frames(bank, model.input_shape[1:], args.calib_images))
+    print(f"int8: calibrated on {qp.images_seen} images ({qp.method})")
+    return Int8PoolResnet(model, qp)
 
 
 def add_tile_arguments(ap) -> None:
@@ -115,7 +160,9 @@ def main(argv=None):
     ap.add_argument("--min-votes", type=int, default=1, help="with --vote: leave out boxes with fewer members than this")
     add_draw_arguments(ap)
     add_chip_arguments(ap, "--chips", "also write every detected face as a square crop under DIR")
+    add_int8_arguments(ap)
     args = ap.parse_args(argv)
+    check_int8_arguments(ap, args)
     check_draw_arguments(ap, args)
     check_chip_arguments(ap, args, "--chips")
     if args.min_votes < 1:
@@ -161,9 +208,13 @@ def run(args):
     from .tiling import TiledDetector
     model = load_model(args)
     root = Path(args.images)
-    paths = sorted(p for p in root.rglob("*") if p.suffix.lower() in EXTENSIONS)
+    paths = image_paths(root)
     if not paths:
         raise SystemExit(f"no image under {root}")
+    if getattr(args, "int8", False):
+        decoder = "device" if args.device_jpeg else "pil"
+        first = None if args.calib is not None else bank_from_files(paths[:args.calib_images], "cuda", decoder=decoder)
+        model = quantize_loaded_model(model, args, first, decoder)
     det = TiledDetector(model, tile_sizes=tuple(args.tile), overlap=args.overlap, include_whole=not args.no_whole,
                         edge_margin=args.edge_margin, flip=args.flip, vote=args.vote, min_votes=args.min_votes)
     names, all_rows, all_counts = [], [], []

@@ -1379,3 +1379,113 @@ def mb_head(f: torch.Tensor, w2: torch.Tensor, bias: torch.Tensor) -> torch.Tens
     ws = torch.empty(nb // 4, dtype=F32, device=f.device)
     check(lib().fdet_mb_head(ptr(f, BF16), ptr(w2, BF16), ptr(bias), ptr(y), ptr(ws), nb, Nn, S, C, stream()), "fdet_mb_head")
     return y
+
+
+# ------------------------------------------------------------------------------------------
+# int8 inference (csrc/fdet_q8.hip; include/fdet.h "Int8 inference")
+# ------------------------------------------------------------------------------------------
+I8 = torch.int8
+
+
+def q8_supported(C: int, H: int, W: int) -> bool:
+    return bool(lib().fdet_q8_supported(int(C), int(H), int(W)))
+
+
+def q8_act_bytes(Nn: int, C: int, H: int, W: int) -> int:
+    return int(lib().fdet_q8_act_bytes(int(Nn), int(C), int(H), int(W)))
+
+
+class Q8Tensor:
+    """An int8 feature map in the kernels' layout [N][H+2][W+2][C] with its halo of zeros.  The storage is zero-filled when
+    the tensor is made and whenever `reshape_` gives it another shape; producers write real pixels only, so reuse at the
+    same shape costs nothing."""
+
+    def __init__(self, Nn: int, C: int, H: int, W: int, device, storage: Optional[torch.Tensor] = None):
+        nbytes = q8_act_bytes(Nn, C, H, W)
+        if nbytes == 0:
+            raise N.FdetError(f"Q8Tensor: unsupported shape ({Nn},{C},{H},{W}) (C % 64 == 0, C <= 256, under 2 GiB)")
+        if storage is None:
+            storage = torch.zeros(nbytes, dtype=I8, device=device)
+        elif storage.dtype != I8 or storage.dim() != 1 or not storage.is_cuda or storage.numel() < nbytes:
+            raise ValueError("Q8Tensor: storage must be a flat int8 GPU tensor of at least fdet_q8_act_bytes bytes")
+        else:
+            storage.zero_()
+        self.storage = storage
+        self.shape = (int(Nn), int(C), int(H), int(W))
+
+    def reshape_(self, Nn: int, C: int, H: int, W: int) -> "Q8Tensor":
+        """The same allocation as a map of another shape (it must fit): the halo moves, so the storage is zero-filled."""
+        if (Nn, C, H, W) != self.shape:
+            nbytes = q8_act_bytes(Nn, C, H, W)
+            if nbytes == 0 or nbytes > self.storage.numel():
+                raise ValueError(f"Q8Tensor.reshape_: ({Nn},{C},{H},{W}) does not fit this allocation")
+            self.storage.zero_()
+            self.shape = (int(Nn), int(C), int(H), int(W))
+        return self
+
+    @property
+    def data(self) -> int:
+        return ptr(self.storage, I8)
+
+    @property
+    def device(self):
+        return self.storage.device
+
+    def nchw(self) -> torch.Tensor:
+        """The real pixels as an (N,C,H,W) int8 tensor (a torch copy: tests and trace())."""
+        Nn, C, H, W = self.shape
+        v = self.storage[:Nn * (H + 2) * (W + 2) * C].view(Nn, H + 2, W + 2, C)
+        return v[:, 1:-1, 1:-1, :].permute(0, 3, 1, 2).contiguous()
+
+
+def _q8_same(t, shape, name):
+    if not isinstance(t, Q8Tensor) or t.shape != tuple(shape):
+        raise ValueError(f"{name}: expected a Q8Tensor of shape {tuple(shape)}, got {getattr(t, 'shape', type(t))}")
+
+
+def q8_quantize(x: torch.Tensor, scale: float, out: Optional[Q8Tensor] = None) -> Q8Tensor:
+    """fp32 (N,C,H,W) -> Q8Tensor: q = clamp(rintf(x * (1.0f / scale)), -127, 127), NaN -> 0."""
+    if x.dim() != 4:
+        raise ValueError("q8_quantize: expected an (N,C,H,W) tensor")
+    Nn, C, H, W = x.shape
+    q = out if out is not None else Q8Tensor(Nn, C, H, W, x.device)
+    _q8_same(q, (Nn, C, H, W), "q8_quantize: out")
+    check(lib().fdet_q8_quantize(ptr(x), float(scale), q.data, Nn, C, H, W, stream()), "fdet_q8_quantize")
+    return q
+
+
+def q8_dequantize(q: Q8Tensor, scale: float, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Q8Tensor -> fp32 (N,C,H,W) = float(q) * scale."""
+    Nn, C, H, W = q.shape
+    x = out if out is not None else torch.empty(Nn, C, H, W, dtype=F32, device=q.device)
+    _chk4(x, q.shape, "q8_dequantize: out")
+    check(lib().fdet_q8_dequantize(q.data, float(scale), ptr(x), Nn, C, H, W, stream()), "fdet_q8_dequantize")
+    return x
+
+
+def q8_pack_weights(w_q: torch.Tensor) -> torch.Tensor:
+    """int8 [Cout,Cin,3,3] -> the conv's [tap][Cin/64][Cout][64] order (one-time work, a torch permutation)."""
+    if w_q.dtype != I8 or w_q.dim() != 4 or tuple(w_q.shape[2:]) != (3, 3) or w_q.shape[0] != w_q.shape[1] or w_q.shape[1] % 64:
+        raise ValueError("q8_pack_weights: expected int8 weights [C,C,3,3] with C % 64 == 0")
+    co, ci = w_q.shape[:2]
+    return w_q.permute(2, 3, 1, 0).reshape(9, ci // 64, 64, co).permute(0, 1, 3, 2).contiguous().reshape(-1)
+
+
+def q8_conv3x3(x: Q8Tensor, wpk: torch.Tensor, bias: torch.Tensor, mul: torch.Tensor, y: Q8Tensor, skip: Optional[Q8Tensor] = None,
+               skip_mul: float = 0.0, pool: bool = False, slope: float = 0.2) -> Q8Tensor:
+    """y = requantise(LeakyReLU((bias + conv3x3(x)) * mul) [+ skip * skip_mul]) [2x2 max-pooled] on the integer matrix cores."""
+    if not isinstance(x, Q8Tensor):
+        raise ValueError("q8_conv3x3: x must be a Q8Tensor")
+    Nn, C, H, W = x.shape
+    if pool and (H % 2 or W % 2):
+        raise ValueError(f"q8_conv3x3: cannot 2x2-pool an odd {H}x{W} map")
+    _q8_same(y, (Nn, C, H // 2, W // 2) if pool else (Nn, C, H, W), "q8_conv3x3: y")
+    if skip is not None:
+        _q8_same(skip, x.shape, "q8_conv3x3: skip")
+    if wpk.numel() != 9 * C * C:
+        raise ValueError("q8_conv3x3: packed weight size does not match the channel count")
+    _chk4(bias, (C,), "bias")
+    _chk4(mul, (C,), "mul")
+    check(lib().fdet_q8_conv3x3(x.data, ptr(wpk, I8), ptr(bias, torch.int32), ptr(mul), skip.data if skip is not None else None,
+                                float(skip_mul), y.data, Nn, C, H, W, int(bool(pool)), float(slope), stream()), "fdet_q8_conv3x3")
+    return y

@@ -47,3 +47,9 @@ class PoolResnet(BaseModel):
         if predict == 1:
             x = self.single_non_max_suppression(x[0])      # image 0 only, as the reference (:103-104)
         return x
+
+    def quantize(self, frames_iter, **kw):
+        """Int8 post-training quantisation for inference: calibrate the activation scales on `frames_iter` (quantize.calibrate;
+        keywords method / percentile) and return the Int8PoolResnet of this model."""
+        from ..quantize import quantize_model
+        return quantize_model(self, frames_iter, **kw)

@@ -1,0 +1,356 @@
+"""Int8 post-training quantisation of PoolResnet for inference (include/fdet.h "Int8 inference").
+
+    qp = calibrate(model, frames_iter)                  # float engine over a few frames -> activation scales
+    m8 = Int8PoolResnet(model, qp)                      # int8 weights, int32 biases, fp32 multipliers, once
+    rows, counts = m8.reduce_bounding_boxes.forward_batch(m8.forward_frames(frames))
+
+The residual trunk (every 3x3 conv, both LeakyReLUs, the skip add and the 2x2 max-pool) runs on the integer matrix cores
+(fdet_q8_conv3x3); the stem and the head keep their float kernels.  The reference has no quantised path (its deployment
+tools are pruner.py and the ONNX / TorchScript exports); the arithmetic is this project's own contract, restated in numpy by
+tests/q8_cpu_ref.py, and the kernels equal that restatement bit for bit.
+"""
+from __future__ import annotations
+
+from typing import Iterable, List, Optional, Sequence
+
+import numpy as np
+import torch
+
+from . import hotpath as hp
+from ._native import FdetError
+
+F32 = torch.float32
+NPF = np.float32
+METHODS = ("absmax", "percentile", "explicit")
+
+
+# ---------------------------------------------------------------------------------------------------------- scales
+class QuantParams:
+    """Activation scales of the int8 trunk, on the CPU: s_h[k] of block k's input (k = 0..nb; s_h[nb] is the head's input)
+    and s_a[k] of block k's first-conv output.  Symmetric, per tensor, float32."""
+
+    def __init__(self, s_h: Sequence[float], s_a: Sequence[float], method: str = "explicit", percentile: Optional[float] = None,
+                 images_seen: int = 0):
+        self.s_h = np.asarray(s_h, dtype=NPF).reshape(-1).copy()
+        self.s_a = np.asarray(s_a, dtype=NPF).reshape(-1).copy()
+        if self.s_a.size < 1 or self.s_h.size != self.s_a.size + 1:
+            raise ValueError(f"QuantParams: {self.s_h.size} block-input scales need {self.s_h.size - 1} first-conv scales, "
+                             f"got {self.s_a.size}")
+        for name, s in (("s_h", self.s_h), ("s_a", self.s_a)):
+            if not (np.all(np.isfinite(s)) and np.all(s > 0)):
+                raise ValueError(f"QuantParams: every scale in {name} must be positive and finite")
+        if method not in METHODS:
+            raise ValueError(f"QuantParams: method must be one of {METHODS}")
+        self.method = method
+        self.percentile = None if percentile is None else float(percentile)
+        self.images_seen = int(images_seen)
+
+    @property
+    def num_blocks(self) -> int:
+        return int(self.s_a.size)
+
+    def save(self, path) -> None:
+        np.savez(path, s_h=self.s_h, s_a=self.s_a, method=np.array(self.method),
+                 percentile=np.array(np.nan if self.percentile is None else self.percentile, dtype=np.float64),
+                 images_seen=np.array(self.images_seen, dtype=np.int64))
+
+    @classmethod
+    def load(cls, path) -> "QuantParams":
+        with np.load(path, allow_pickle=False) as z:
+            pct = float(z["percentile"])
+            return cls(z["s_h"], z["s_a"], str(z["method"]), None if np.isnan(pct) else pct, int(z["images_seen"]))
+
+    def __eq__(self, other):
+        return (isinstance(other, QuantParams) and np.array_equal(self.s_h, other.s_h) and np.array_equal(self.s_a, other.s_a)
+                and (self.method, self.percentile, self.images_seen) == (other.method, other.percentile, other.images_seen))
+
+    def __repr__(self):
+        return (f"QuantParams(blocks={self.num_blocks}, method={self.method!r}, percentile={self.percentile}, "
+                f"images_seen={self.images_seen})")
+
+
+class ActivationObserver:
+    """Running range of the trunk's activations over calibration batches (torch reductions: offline work).  "absmax": the
+    largest magnitude seen.  "percentile": per batch the given percentile of the magnitudes, the largest over the batches."""
+
+    def __init__(self, num_blocks: int, method: str = "absmax", percentile: Optional[float] = None):
+        if method not in ("absmax", "percentile"):
+            raise ValueError("calibration method must be 'absmax' or 'percentile'")
+        if method == "percentile" and not (percentile is not None and 50.0 <= float(percentile) <= 100.0):
+            raise ValueError("percentile calibration needs percentile in [50, 100], e.g. 99.99")
+        if method == "absmax" and percentile is not None:
+            raise ValueError("percentile is given: use method='percentile'")
+        self.method, self.percentile = method, (None if percentile is None else float(percentile))
+        self.h = [0.0] * (num_blocks + 1)
+        self.a = [0.0] * num_blocks
+        self.images = 0
+
+    def _range(self, t: torch.Tensor) -> float:
+        m = t.detach().abs().reshape(-1).float()
+        if self.method == "absmax" or m.numel() == 1:
+            return float(m.max())
+        k = min(m.numel(), max(1, int(np.ceil(self.percentile / 100.0 * m.numel()))))
+        return float(m.kthvalue(k).values)
+
+    def observe(self, h: List[torch.Tensor], a: List[torch.Tensor]) -> None:
+        """h: the nb + 1 block inputs (the last one is the head's input), a: the nb first-conv outputs, of one batch."""
+        if len(h) != len(self.h) or len(a) != len(self.a):
+            raise ValueError("ActivationObserver.observe: wrong number of tensors")
+        for i, t in enumerate(h):
+            self.h[i] = max(self.h[i], self._range(t))
+        for i, t in enumerate(a):
+            self.a[i] = max(self.a[i], self._range(t))
+        self.images += int(h[0].shape[0])
+
+    def params(self) -> QuantParams:
+        if self.images == 0:
+            raise ValueError("calibration saw no image")
+
+        def scale(v):                                      # an all-zero tensor quantises with scale 1
+            return NPF(1.0) if v == 0.0 else NPF(v) / NPF(127.0)
+        return QuantParams([scale(v) for v in self.h], [scale(v) for v in self.a], self.method, self.percentile, self.images)
+
+
+def _check_model(model):
+    from .models.PoolResnet import PoolResnet
+    if type(model) is not PoolResnet:
+        raise TypeError(f"int8 inference covers PoolResnet only, got {type(model).__name__}")
+
+
+@torch.no_grad()
+def calibrate(model, frames_iter: Iterable[torch.Tensor], method: str = "absmax", percentile: Optional[float] = None) -> QuantParams:
+    """Run the float engine (eval arithmetic: no dropout) over the calibration frames and reduce the intermediates it keeps
+    for backward to activation scales.  frames_iter yields batches of FRAMES exactly as `forward_frames` takes them: (N,3,H,W)
+    with values 0..255, uint8 or float, any size -- they go through the model's own preprocessing (resize, / 255).  Images
+    that are already normalised to [0,1] are not frames: passing them would calibrate on nearly black input."""
+    from .ps import PsTensor
+    _check_model(model)
+    if percentile is not None and method == "absmax":
+        method = "percentile"
+    eng = model.engine
+    if eng.p16:
+        raise FdetError("calibrate: run the calibration on the bf16x3 engine, not in precision16")
+    nb = len(model.residual_blocks)
+    obs = ActivationObserver(nb, method, percentile)
+    dev = next(model.parameters()).device
+    names, params = model.named_stack_params()
+    P = {n: p.detach() for n, p in zip(names, params)}
+
+    def f32(t):
+        return t.to_f32() if isinstance(t, PsTensor) else t
+    for frames in frames_iter:
+        x = model._preprocess(torch.as_tensor(frames).to(dev))
+        _, saved = eng.forward(x, P, None, save=True)
+        blocks = saved["blocks"]
+        obs.observe([f32(b[0]) for b in blocks] + [f32(saved["h_last"])], [f32(b[1]) for b in blocks])
+        saved["ps_scope"].release()
+    return obs.params()
+
+
+def bank_frames(bank, out_hw, max_images: Optional[int] = None, batch_size: int = 16):
+    """Calibration frames from a device image bank: its first `max_images` images, each resized whole to out_hw as the
+    validation transform does (datasets.augment.default_transform), in batches of uint8 frames (values 0..255, what
+    `calibrate` and `forward_frames` take; the transform's second output, not its normalised fp32 images)."""
+    from .datasets.augment import DeviceBoxes, default_transform
+    n = len(bank) if max_images is None else min(len(bank), int(max_images))
+    if n < 1:
+        raise ValueError("bank_frames: no calibration image")
+    tf = default_transform(tuple(out_hw))
+    boxes = DeviceBoxes([np.array([[1.0, 0.0, 0.0, 1.0, 1.0]], dtype=np.float32)] * len(bank), bank.device)   # (the transform wants boxes)
+    for a in range(0, n, batch_size):
+        yield tf(bank, np.arange(a, min(a + batch_size, n)), boxes, 0)[1]
+
+
+# ---------------------------------------------------------------------------------------------------------- weights
+def prepare_conv(w: np.ndarray, b: np.ndarray, s_in, s_out):
+    """One conv's integers: (w_q int8 [Co,Ci,3,3], b_q int32 [Co], mul float32 [Co]).
+    s_w[co] = absmax(w[co]) / 127 (1 for a channel of zeros), w_q = clamp(rint(w / s_w)), b_q = rint(b / (s_w * s_in)) in
+    float64, mul = (s_w * s_in) / s_out in float32, one rounding per operation."""
+    w = np.asarray(w, dtype=NPF)
+    m = np.abs(w).reshape(w.shape[0], -1).max(axis=1).astype(NPF)
+    s_w = np.where(m == 0, NPF(1.0), m / NPF(127.0)).astype(NPF)
+    w_q = np.clip(np.rint(w / s_w[:, None, None, None]), -127, 127).astype(np.int8)
+    b_q = np.rint(np.asarray(b, dtype=np.float64) / (s_w.astype(np.float64) * np.float64(NPF(s_in))))
+    b_q = np.clip(b_q, -2 ** 31, 2 ** 31 - 1).astype(np.int32)
+    mul = ((s_w * NPF(s_in)) / NPF(s_out)).astype(NPF)
+    return w_q, b_q, mul
+
+
+class _Q8Conv:
+    def __init__(self, w, b, s_in, s_out, dev):
+        w_q, b_q, mul = prepare_conv(w, b, s_in, s_out)
+        self.wpk = hp.q8_pack_weights(torch.from_numpy(w_q).to(dev))
+        self.bias = torch.from_numpy(b_q).to(dev)
+        self.mul = torch.from_numpy(mul).to(dev)
+
+
+# ---------------------------------------------------------------------------------------------------------- the model
+class Int8PoolResnet:
+    """A trained PoolResnet with its residual trunk in int8: existing stem -> quantise -> 2 x blocks int8 convs ->
+    dequantise -> existing head.  Inference only; weights and scales are those at construction.  It offers what the rest of
+    the package asks of a model (TiledDetector, DetectionEvaluator, GraphedPredict, render / tracking / chips)."""
+
+    training = False
+
+    def __init__(self, model, qparams: QuantParams):
+        _check_model(model)
+        if not isinstance(qparams, QuantParams):
+            raise TypeError("Int8PoolResnet: qparams must be a QuantParams")
+        nb = len(model.residual_blocks)
+        if qparams.num_blocks != nb:
+            raise ValueError(f"Int8PoolResnet: the model has {nb} residual blocks, the scales are for {qparams.num_blocks}")
+        dev = next(model.parameters()).device
+        if dev.type != "cuda":
+            raise FdetError("Int8PoolResnet runs on the GPU only (no CPU fallback): move the model to cuda first")
+        self.geo = model._geometry()
+        self.h0, self.lv = self.geo.levels()
+        F_ = int(model.filters)
+        for hk, _ in self.lv:
+            if not hp.q8_supported(F_, hk, hk):
+                raise FdetError(f"Int8PoolResnet: {F_} channels at {hk}x{hk} are outside the int8 kernels' range "
+                                "(fdet_q8_supported: a multiple of 64 up to 256)")
+        self.input_shape = model.input_shape
+        self.num_of_patches = model.num_of_patches
+        self.filters = F_
+        self.probability_threshold = model.probability_threshold
+        self.iou_threshold = model.iou_threshold
+        self.reduce_bounding_boxes = model.reduce_bounding_boxes
+        self.qparams = qparams
+        self.device = dev
+        self.slope = 0.2
+        self._preprocess = model._preprocess               # resize / 255 exactly as the float model
+        sd = {k: v.detach().cpu().numpy() for k, v in model.state_dict().items()}
+        s_h, s_a = qparams.s_h, qparams.s_a
+        self.blocks = []
+        for k in range(nb):
+            n = f"residual_blocks.{k}"
+            c1 = _Q8Conv(sd[n + ".conv1.weight"], sd[n + ".conv1.bias"], s_h[k], s_a[k], dev)
+            c2 = _Q8Conv(sd[n + ".conv2.weight"], sd[n + ".conv2.bias"], s_a[k], s_h[k + 1], dev)
+            self.blocks.append((c1, c2, float(NPF(s_h[k]) / NPF(s_h[k + 1]))))
+        self.stem_w = model.conv1.weight.detach().to(F32).contiguous().clone()
+        self.stem_b = model.conv1.bias.detach().to(F32).contiguous().clone()
+        self.head_w = model.out.weight.detach().to(F32).contiguous().clone()
+        self.head_b = model.out.bias.detach().to(F32).contiguous().clone()
+        g = self.geo
+        self._stem_x3 = hp.x3_supported(F_, F_) and hp.stem_x3_supported(g.in_ch, g.W, g.stem_k, g.stem_s, g.stem_p)
+        self._ws = None
+        self._pool = {}                                    # (N,C,H,W) -> free Q8Tensors; kept for the life of the model
+        self.timer = None                                  # a convstack.KernelTimer: per-kernel times (tools/q8_throughput.py)
+
+    # ------------------------------------------------------------------ nn.Module-shaped odds and ends
+    def eval(self):
+        return self
+
+    def train(self, mode: bool = True):
+        if mode:
+            raise FdetError("Int8PoolResnet is inference only")
+        return self
+
+    # ------------------------------------------------------------------ buffers
+    def _take(self, N, H, W) -> hp.Q8Tensor:
+        free = self._pool.setdefault((N, self.filters, H, W), [])
+        return free.pop() if free else hp.Q8Tensor(N, self.filters, H, W, self.device)
+
+    def _give(self, t: hp.Q8Tensor) -> None:
+        self._pool.setdefault(t.shape, []).append(t)
+
+    def _t(self, kind, h, flops=0.0, nbytes=0.0):
+        from .convstack import _NOSPAN
+        return _NOSPAN if self.timer is None else self.timer.span(f"{kind}@{h}x{h}", flops, nbytes)
+
+    # ------------------------------------------------------------------ forward
+    def _forward_f32(self, x: torch.Tensor, trace: Optional[dict] = None) -> torch.Tensor:
+        g, F_ = self.geo, self.filters
+        if not x.is_cuda:
+            raise FdetError("Int8PoolResnet runs on the GPU only (no CPU fallback): move the input to cuda")
+        if x.dim() != 4 or tuple(x.shape[1:]) != (g.in_ch, g.H, g.W):
+            raise ValueError(f"expected input (N,{g.in_ch},{g.H},{g.W}), got {tuple(x.shape)}")
+        if x.dtype != F32 or not x.is_contiguous():
+            x = x.to(F32).contiguous()
+        N, dev = x.shape[0], x.device
+        nws = hp.stem_ws_bytes(N, g.in_ch, F_, g.H, g.W, g.stem_k, g.stem_s, g.stem_p)
+        if self._ws is None or self._ws.numel() * 4 < nws:
+            self._ws = torch.empty(max((nws + 3) // 4, 4), dtype=F32, device=dev)
+        h0 = self.h0
+        hf = torch.empty(N, F_, h0, h0, dtype=F32, device=dev)
+        with self._t("stem_fwd", h0):
+            hp.stem_fwd(x, self.stem_w, self.stem_b, hf, self._ws, g.stem_k, g.stem_s, g.stem_p, x3=self._stem_x3)
+        s_h = self.qparams.s_h
+        h = self._take(N, h0, h0)
+        with self._t("q8_quantize", h0, 0.0, 5.0 * hf.numel()):
+            hp.q8_quantize(hf, float(s_h[0]), out=h)
+        if trace is not None:
+            trace["stem"], trace["blocks"] = hf, []
+        for k, (hk, pool) in enumerate(self.lv):
+            c1, c2, skip_mul = self.blocks[k]
+            flops = 2.0 * N * F_ * F_ * 9 * hk * hk
+            a = self._take(N, hk, hk)
+            with self._t("q8_conv3x3", hk, flops, 2.0 * N * F_ * hk * hk):
+                hp.q8_conv3x3(h, c1.wpk, c1.bias, c1.mul, a, slope=self.slope)
+            out = self._take(N, hk // pool, hk // pool)
+            with self._t("q8_conv3x3_pool" if pool == 2 else "q8_conv3x3_skip", hk, flops, (2.0 + 1.0 / (pool * pool)) * N * F_ * hk * hk):
+                hp.q8_conv3x3(a, c2.wpk, c2.bias, c2.mul, out, skip=h, skip_mul=skip_mul, pool=pool == 2, slope=self.slope)
+            self._give(h)
+            self._give(a)
+            h = out
+            if trace is not None:
+                trace["blocks"].append(h.nchw())
+        hl = h.shape[2]
+        hd = torch.empty(N, F_, hl, hl, dtype=F32, device=dev)
+        with self._t("q8_dequantize", hl, 0.0, 5.0 * hd.numel()):
+            hp.q8_dequantize(h, float(s_h[-1]), out=hd)
+        self._give(h)
+        y = torch.empty(N, 5, g.S, g.S, dtype=F32, device=dev)
+        with self._t("head_fwd", hl):
+            hp.head_fwd(hd, None, self.head_w, self.head_b, y, g.head_k, g.head_p)
+        if trace is not None:
+            trace["y"] = y
+        return y
+
+    @torch.no_grad()
+    def forward_frames(self, x: torch.Tensor) -> torch.Tensor:
+        """frames (uint8 or float, any size) -> the (N,5,S,S) maps, as BaseModel.forward_frames."""
+        return self._forward_f32(self._preprocess(x))
+
+    @torch.no_grad()
+    def trace(self, frames: torch.Tensor) -> dict:
+        """{"stem": fp32 stem output (N,F,h0,h0), "blocks": [int8 (N,F,h,h) output of every block], "y": (N,5,S,S)}"""
+        out = {}
+        self._forward_f32(self._preprocess(frames), trace=out)
+        return out
+
+    @torch.no_grad()
+    def __call__(self, x: torch.Tensor, predict: torch.Tensor = torch.tensor(0)):
+        """PoolResnet.forward: float images in [0,1] at the model resolution -> maps; predict=1: frames -> boxes of image 0."""
+        if predict == 1:
+            return self.single_non_max_suppression(self.forward_frames(x)[0])
+        return self._forward_f32(x)
+
+    forward = __call__
+
+    def non_max_suppression(self, x):
+        from .models.BaseModel import split_rows
+        if len(x.shape) == 4:
+            return split_rows(*self.reduce_bounding_boxes.forward_batch(x))
+        return self.reduce_bounding_boxes(x)
+
+    def single_non_max_suppression(self, x):
+        return self.reduce_bounding_boxes(x)
+
+    @torch.no_grad()
+    def predict(self, x, probability_threshold=0.5, iou_threshold=0.5):
+        from .datasets.utils import ReduceBoundingBoxes
+        self.reduce_bounding_boxes = ReduceBoundingBoxes(
+            probability_threshold=probability_threshold, iou_threshold=iou_threshold,
+            input_shape=self.input_shape, num_of_patches=self.num_of_patches)
+        image = self._preprocess(x)
+        return image, self.non_max_suppression(self._forward_f32(image))[0]
+
+    def graphed_predict(self, example: torch.Tensor):
+        from .models.BaseModel import GraphedPredict
+        return GraphedPredict(self, example)
+
+
+def quantize_model(model, frames_iter, **kw) -> Int8PoolResnet:
+    """calibrate + Int8PoolResnet (what PoolResnet.quantize does)."""
+    return Int8PoolResnet(model, calibrate(model, frames_iter, **kw))

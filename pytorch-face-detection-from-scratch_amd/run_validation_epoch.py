@@ -18,6 +18,9 @@ name the options that ran.
 Hard AP of the WIDER Face protocol (`evaluation_wider.WiderEvaluator`): the resized pass's detections are taken back to
 source pixels, and with `--tiled` the tiled rows are evaluated too.  `--json` then gains the keys "wider" / "wider_tiled".
 Images are matched to the .mat files by `<event>/<image>`; the synthetic bank's images are called `synthetic/00000`, ...
+`--int8` (poolresnet) adds the same evaluator numbers from the int8 post-training-quantised model (`quantize.py`, DESIGN.md
+5j) beside the float ones of the same run: the scales are calibrated with the float model on the first `--calib-images`
+images (32) under `--calib DIR` (default: the validation bank's first images).  `--json` then gains the key "int8".
 """
 import argparse
 import json
@@ -103,7 +106,10 @@ def main(argv=None):
     ap.add_argument("--flip", action="store_true", help="--tiled: every window a second time, mirrored left to right")
     ap.add_argument("--vote", action="store_true", help="--tiled: box voting instead of plain NMS across windows")
     ap.add_argument("--min-votes", type=int, default=1, help="--tiled --vote: leave out boxes with fewer members than this")
+    from .detect_images import add_int8_arguments, check_int8_arguments
+    add_int8_arguments(ap)
     args = ap.parse_args(argv)
+    check_int8_arguments(ap, args)
     if args.min_votes < 1:
         ap.error("--min-votes must be >= 1")
     if (args.flip or args.vote or args.min_votes > 1) and not args.tiled:
@@ -181,6 +187,9 @@ def run(args):
           f"{model.probability_threshold}: {r.at(model.probability_threshold)}")
     out = {"metrics": metrics, "result": r}
     doc = r.to_json()
+    if getattr(args, "int8", False):
+        out["int8"] = int8_report(model, val, bank, args, r)
+        doc["int8"] = out["int8"].to_json()
     if wider is not None:
         out["wider"] = wider.wider.compute()
         print_wider(out["wider"])
@@ -197,6 +206,23 @@ def run(args):
     if args.json:
         Path(args.json).write_text(json.dumps(doc))
     return out
+
+
+def int8_report(model, val, bank, args, float_result):
+    """The evaluator's numbers of the int8 model on the same batches, printed beside the float ones."""
+    from .detect_images import quantize_loaded_model
+    from .evaluation import DetectionEvaluator
+    m8 = quantize_loaded_model(model.eval(), args, bank, "device" if args.device_jpeg else "pil")
+    ev = DetectionEvaluator(iou_thresholds=tuple(args.iou), score_floor=args.score_floor)
+    with torch.no_grad():
+        for x, _, gt in val:
+            ev.evaluate_batch(m8, m8(x), gt)
+    r = ev.compute()
+    print(f"int8: {r.n_images} images, {r.n_gt} faces, {r.n_det} detections with score >= {args.score_floor}")
+    for t, a8, a in zip(r.iou_thresholds, r.ap_per_threshold, float_result.ap_per_threshold):
+        print(f"int8 AP@{float(t):.2f}: {a8:.4f} (float {a:.4f})")
+    print(f"int8 best F1 {r.best_f1:.4f} at score threshold {r.best_threshold:.3f} (float {float_result.best_f1:.4f})")
+    return r
 
 
 def tiled_report(model, bank, boxes, args, wider=None):

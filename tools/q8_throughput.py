@@ -1,0 +1,128 @@
+"""Inference throughput of the int8 post-training-quantised PoolResnet beside the two float modes.
+
+    python tools/q8_throughput.py [--images 256] [--launches 100] [--calls 10] [--out profiles/r13_q8.json]
+
+Workload: the inference leg's -- --images uint8 480x480 frames on the device (the three stored frames of
+tests/golden/g6_trained_small.npz, repeated) through the medium PoolResnet (64 filters, the trained weights of
+tests/golden/g16_trained_medium.npz) to boxes: `reduce_bounding_boxes.forward_batch(model.forward_frames(frames))`.
+Three models in ONE process, every one warmed up, alternated sample by sample; a sample is --calls back-to-back calls between
+two device events (about 10 ms of work), reported per call; median / min / max and the 5th / 95th percentile over --launches
+samples (about a second of timed work per mode):
+
+  bf16x3        the default engine (three bf16 MFMA passes)
+  precision16   engine.set_precision("bf16") (one bf16 pass)
+  int8          quantize.Int8PoolResnet, calibrated (abs-max) on the first 16 frames
+
+Then, in a second phase with a KernelTimer attached (device events around every kernel class, so launch gaps inside a class
+count as its time), the per-kernel times of the int8 path and of precision16, and from them the 20-conv trunk alone in both
+modes.  `int8_trunk_floor_share` is the trunk's MACs (119 GMAC at 256 images) over the dense int8 MFMA peak (2 x the 2.5 PF
+bf16 peak = 2.5e15 MAC/s) over the measured trunk time.  Prints one JSON line and, with --out, writes it.
+"""
+import argparse
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+INT8_PEAK_MACS = 2.5e15
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--images", type=int, default=256)
+    ap.add_argument("--launches", type=int, default=100, help="timed samples per mode")
+    ap.add_argument("--calls", type=int, default=10, help="back-to-back calls per sample")
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--kernel-runs", type=int, default=50)
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args(argv)
+    import numpy as np
+    import torch
+    import fdet_amd  # noqa: F401
+    from fdet_amd.convstack import KernelTimer
+    from fdet_amd.models.PoolResnet import PoolResnet
+    from fdet_amd.quantize import Int8PoolResnet, calibrate
+    if not torch.cuda.is_available():
+        raise SystemExit("q8_throughput needs a GPU")
+    gold = os.path.join(ROOT, "tests", "golden")
+    g = np.load(os.path.join(gold, "g16_trained_medium.npz"))
+    P = {k[len("param/"):]: torch.from_numpy(g[k]) for k in g.files if k.startswith("param/")}
+    images = torch.from_numpy(np.load(os.path.join(gold, "g6_trained_small.npz"))["images"])
+    n = args.images
+    frames = images[torch.arange(n) % images.shape[0]].contiguous().cuda()
+
+    def build(p16):
+        m = PoolResnet(filters=64, input_shape=(3, 480, 480), num_of_patches=10, probability_threshold=0.7, iou_threshold=0.01)
+        m.load_state_dict({k: v.clone() for k, v in P.items()})
+        m = m.cuda().eval()
+        if p16:
+            m.engine.set_precision("bf16")
+        return m
+    m32, m16 = build(False), build(True)
+    m8 = Int8PoolResnet(m32, calibrate(m32, [frames[:16]]))
+    models = {"bf16x3": m32, "precision16": m16, "int8": m8}
+
+    def run(m):
+        with torch.no_grad():
+            return m.reduce_bounding_boxes.forward_batch(m.forward_frames(frames))
+    boxes = {}
+    for k, m in models.items():
+        for _ in range(args.warmup):
+            rows, counts = run(m)
+        boxes[k] = int(counts.sum())
+    torch.cuda.synchronize()
+    ms = {k: [] for k in models}
+    for _ in range(args.launches):
+        for k, m in models.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(args.calls):
+                run(m)
+            e1.record()
+            e1.synchronize()
+            ms[k].append(e0.elapsed_time(e1) / args.calls)
+
+    def stats(v):
+        a = np.sort(np.asarray(v))
+        return {"median_ms": round(float(np.median(a)), 4), "min_ms": round(float(a[0]), 4), "max_ms": round(float(a[-1]), 4),
+                "p05_ms": round(float(np.percentile(a, 5)), 4), "p95_ms": round(float(np.percentile(a, 95)), 4)}
+
+    # per-kernel times (a phase of its own: the events slow the host side down a little)
+    def kernel_times(m, holder):
+        holder.timer = KernelTimer()
+        for _ in range(args.kernel_runs):
+            run(m)
+        s = holder.timer.summary()
+        holder.timer = None
+        return {name: {"launches_per_call": cnt // args.kernel_runs, "ms_per_call": round(total / args.kernel_runs, 4)}
+                for name, (cnt, total, _, _) in sorted(s.items())}
+    k8 = kernel_times(m8, m8)
+    k16 = kernel_times(m16, m16.engine)
+    trunk8 = sum(v["ms_per_call"] for k, v in k8.items() if k.startswith("q8_conv3x3"))
+    trunk16 = sum(v["ms_per_call"] for k, v in k16.items() if k.startswith(("conv3x3_fwd", "chain_fwd")))
+    # (blocks 0 and 1 are pooled: 2 convs at 60x60, 2 at 30x30; then 8 blocks = 16 convs at 15x15)
+    trunk_macs = float(n) * 64 * 64 * 9 * (2 * 60 * 60 + 2 * 30 * 30 + 16 * 15 * 15)
+    floor_ms = trunk_macs / INT8_PEAK_MACS * 1e3
+    e2e = {k: stats(v) for k, v in ms.items()}
+    res = {"tool": "q8_throughput", "device_name": torch.cuda.get_device_name(0), "images": n, "launches": args.launches,
+           "calls_per_sample": args.calls, "end_to_end": e2e, "images_per_s": {k: round(n / (v["median_ms"] * 1e-3), 1) for k, v in e2e.items()},
+           "boxes": boxes,
+           "int8_over_precision16": round(e2e["precision16"]["median_ms"] / e2e["int8"]["median_ms"], 3),
+           "int8_over_bf16x3": round(e2e["bf16x3"]["median_ms"] / e2e["int8"]["median_ms"], 3),
+           "int8_kernels": k8, "precision16_kernels": k16,
+           "trunk_20_convs_ms": {"int8": round(trunk8, 4), "precision16": round(trunk16, 4)},
+           "trunk_gmac": round(trunk_macs / 1e9, 2), "int8_trunk_floor_ms": round(floor_ms, 4),
+           "int8_trunk_floor_share": round(floor_ms / trunk8, 4) if trunk8 > 0 else None}
+    line = json.dumps(res)
+    print(line)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+    return res
+
+
+if __name__ == "__main__":
+    main()
