@@ -10,6 +10,12 @@
 //   * operand fragments are double-buffered in registers: the 12 ds_read_b128 of tap t+1 issue among the MFMAs of tap t;
 //   * tiles are bands of R "virtual rows" (fdet_ps.h: v = n*HP + y, zero rows between images), so bands run across
 //     images, every image's halo rows are real zero rows, and row pairs stay pool-aligned.
+// The fused pooled forward (PSE_FWD_POOL, bf16x3) runs by default in a second form, WG2: TWO workgroups per CU, each in
+// half the register file (128 AGPRs of accumulators + 128 VGPRs, no scratch) with ONE chunk buffer -- see the comment in
+// front of the kernel.  Its ~1700-VALU epilogue is not woven into the MFMA stream (that was built twice and did not pay);
+// with a second workgroup on the SIMD it runs under the partner's MFMAs instead.  Timing (rocprofv3 kernel stats, bs 256,
+// three passes each): 60x60 257.7 -> 225.8 us, 30x30 69.3 -> 58.4 us, results bit-identical;
+// FDET_PS_POOL_WG2=0 selects the one-workgroup form (the other modes hold two accumulator sets and cannot follow).
 // Arithmetic is that of fdet_conv3x3_x3*.hip (a_hi*b_lo + a_lo*b_hi + a_hi*b_hi, fp32 accumulate, the same K order
 // within a chunk), results agree with those kernels to the rounding of the PS format (16 significant bits).
 //
@@ -73,6 +79,22 @@ __device__ __forceinline__ void ps_keep(const f32x16& v) {
 #if defined(__HIP_DEVICE_COMPILE__)
   asm volatile("" ::"v"(v));
 #endif
+}
+
+// hides where a per-lane value came from (keeps an and/or blend from being folded back into a select)
+__device__ __forceinline__ void ps_opaque(unsigned& v) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  asm("" : "+v"(v));
+#endif
+}
+
+// the lane number, computed where this stands (two VALU; volatile: not hoisted out of a loop and kept in a register)
+__device__ __forceinline__ int ps_lane_now() {
+  int v = 0;
+#if defined(__HIP_DEVICE_COMPILE__)
+  asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(v));
+#endif
+  return v;
 }
 
 // one accumulator element -> VGPR (explicit accumulation-register read, see ps_unit)
@@ -148,9 +170,20 @@ __device__ __forceinline__ void ps_unit(const f32x16& acc, const int gp, const f
 // WOVEN (forward): the epilogue of tile i runs as 16 "units" spread over the first two chunks of tile i+1, one unit
 // behind each of taps 0..7, its ~65 VALU instructions and two stores placed two or three per MFMA gap by
 // sched_group_barrier; two accumulator sets alternate.  The other modes keep the epilogue at the end of the tile.
-template <int MODE, int WP, bool P16>
-__global__ void __launch_bounds__(256, 1)
+//
+// WG2 (PSE_FWD_POOL only): TWO workgroups per CU, each in half the register file (one accumulator set in 128 AGPRs, at
+// most 128 VGPRs, no scratch) with ONE chunk buffer (76.5 KB at WP 64), so that one workgroup's un-woven epilogue and
+// chunk-open waits run under the other's MFMAs -- the SIMD's arbiter interleaves what one in-order stream cannot.
+// Chunk protocol with one buffer: barrier (every wave is past its last fragment read), DMA of the next chunk, vmcnt(0),
+// barrier, body; the next tile's chunk 0 is requested right behind the tile's last chunk, BEFORE the epilogue, and
+// opens with the counted wait on the epilogue's stores like the two-buffer form.  The A fragments stay double-buffered
+// (32 registers), the B fragments are ONE set of 32 that rotates: block n's pair is re-read for tap t+1 right behind
+// block n's six MFMAs of tap t (n outer, m inner: the order of the products WITHIN every accumulator is unchanged, so
+// results are bit-identical); the bias is re-read per epilogue unit instead of living in 32 registers.
+template <int MODE, int WP, bool P16, bool WG2 = false>
+__global__ void __launch_bounds__(256, WG2 ? 2 : 1)
 k_conv3x3_ps(const PsConvArgs p) {
+  static_assert(!WG2 || MODE == PSE_FWD_POOL, "two workgroups per CU: the pooled forward only (one accumulator set)");
   constexpr bool WOVEN = MODE == PSE_FWD_FULL || MODE == PSE_DGRAD_ACT || MODE == PSE_DGRAD_ADDPOOL;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   bf16x8* const lds = reinterpret_cast<bf16x8*>(smem);
@@ -233,7 +266,7 @@ k_conv3x3_ps(const PsConvArgs p) {
 #pragma unroll
     for (int g = 0; g < 4; ++g)
 #pragma unroll
-      for (int i = 0; i < 4; ++i) bz[m][g][i] = (MODE == PSE_FWD_FULL || MODE == PSE_FWD_POOL) ? p.bias[32 * m + 8 * g + 4 * half + i] : 0.f;
+      for (int i = 0; i < 4; ++i) bz[m][g][i] = ((MODE == PSE_FWD_FULL || MODE == PSE_FWD_POOL) && !WG2) ? p.bias[32 * m + 8 * g + 4 * half + i] : 0.f;   // WG2: read in the epilogue
 
   const int a_off = half * 64 + l31;                     // + tap*128 + m*32 ; lo plane: + PSA
   const int b_off = 2 * PSA + half * PT + lb;            // + qn[n] + tap offset ; lo planes: + 2*PT
@@ -299,8 +332,50 @@ k_conv3x3_ps(const PsConvArgs p) {
     }                                                                                              \
     __builtin_amdgcn_sched_barrier(0);                                                             \
   }
-  bf16x8 ah[2][2], al[2][2], bh[2][4], bl[2][4];
-#define PS_FRAGS(F, T)                                                                             \
+  bf16x8 ah[2][2], al[2][2], bh[2][4], bl[2][4];         // WG2: bh[0] / bl[0] only (one rotating set)
+#define PS_FRAG_A(F, T)                                                                            \
+  {                                                                                                \
+    _Pragma("unroll") for (int m_ = 0; m_ < 2; ++m_) {                                             \
+      ah[F][m_] = Aw[(T) * 128 + m_ * 32];                                                         \
+      if (!P16) al[F][m_] = Aw[PSA + (T) * 128 + m_ * 32];                                         \
+    }                                                                                              \
+  }
+#define PS_FRAG_B(N, T)                                                                            \
+  {                                                                                                \
+    const int to_ = ((T) / 3) * WP + (T) % 3;                                                      \
+    bh[0][N] = Bw[qn[N] + to_];                                                                    \
+    if (!P16) bl[0][N] = Bw[2 * PT + qn[N] + to_];                                                 \
+  }
+  // WG2: nine taps of one chunk (the only buffer) into ACC; block n's B pair of tap t+1 is requested behind block n's
+  // MFMAs of tap t, the A fragments of tap t+1 at the head of tap t
+#define PS_BODY2(ACC, FIRST)                                                                       \
+  {                                                                                                \
+    const bf16x8* Aw = lds + a_off;                                                                \
+    const bf16x8* Bw = lds + b_off;                                                                \
+    PS_FRAG_A(0, 0)                                                                                \
+    _Pragma("unroll") for (int n = 0; n < 4; ++n) PS_FRAG_B(n, 0)                                  \
+    __builtin_amdgcn_sched_barrier(0);                                                             \
+    _Pragma("unroll") for (int t = 0; t < 9; ++t) {                                                \
+      const int F = t & 1;                                                                         \
+      if (t < 8) PS_FRAG_A(F ^ 1, t + 1)                                                           \
+      _Pragma("unroll") for (int n = 0; n < 4; ++n) {                                              \
+        if (!(PS_DBG & 2)) {                                                                       \
+          _Pragma("unroll") for (int m = 0; m < 2; ++m) {                                          \
+            const f32x16 zero_ = {};                                                               \
+            if (P16) {                                                                             \
+              ACC[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[F][m], bh[0][n], ((FIRST) && t == 0) ? zero_ : ACC[m][n], 0, 0, 0); \
+            } else {                                                                               \
+              ACC[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[F][m], bl[0][n], ((FIRST) && t == 0) ? zero_ : ACC[m][n], 0, 0, 0); \
+              ACC[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[F][m], bh[0][n], ACC[m][n], 0, 0, 0); \
+              ACC[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[F][m], bh[0][n], ACC[m][n], 0, 0, 0); \
+            }                                                                                      \
+          }                                                                                        \
+        }                                                                                          \
+        if (t < 8) PS_FRAG_B(n, t + 1)                                                             \
+      }                                                                                            \
+    }                                                                                              \
+  }
+#define PS_FRAGS(F, T)                                                                         \
   {                                                                                                \
     const int to_ = ((T) / 3) * WP + (T) % 3;                                                      \
     _Pragma("unroll") for (int m_ = 0; m_ < 2; ++m_) {                                             \
@@ -391,6 +466,9 @@ k_conv3x3_ps(const PsConvArgs p) {
       MODE == PSE_FWD_POOL ? (int)((size_t)p.N * p.img_p * 16) : (int)((size_t)p.Nimg * 64 * p.H * p.Wf * 4), 0x00020000);
   const __amdgpu_buffer_rsrc_t frs = __builtin_amdgcn_make_buffer_rsrc(p.pool_f32, 0, (int)((size_t)p.Nimg * 64 * p.Hp * p.Wpf * 4), 0x00020000);
   const __amdgpu_buffer_rsrc_t rrs = __builtin_amdgcn_make_buffer_rsrc(p.route_out, 0, (int)((size_t)p.N * 64 * p.Hp * p.Wp), 0x00020000);
+  const __amdgpu_buffer_rsrc_t srs = __builtin_amdgcn_make_buffer_rsrc((void*)p.scale, 0, (WG2 && p.scale) ? (int)((size_t)p.Nimg * 64 * 4) : 0, 0x00020000);   // WG2: dropout scales
+  const __amdgpu_buffer_rsrc_t ars = __builtin_amdgcn_make_buffer_rsrc((void*)p.aux, 0, WG2 ? (int)((size_t)p.N * p.img_i * 16) : 0, 0x00020000);   // WG2: the skip tensor
+  const __amdgpu_buffer_rsrc_t brs = __builtin_amdgcn_make_buffer_rsrc((void*)p.bias, 0, (WG2 && p.bias) ? 64 * 4 : 0, 0x00020000);                  // WG2: the bias
   const int pool_cnt = MODE == PSE_FWD_POOL ? 4 * ((P16 ? 1 : 2) * (p.pool_ps != nullptr) + (p.route_out != nullptr) + 8 * (p.pool_f32 != nullptr)) : 63;
 #define PS_WIN(T)                                                                                  \
     const int rb_ = WP == 64 ? 2 * wid : 4 * wid + 2 * (l31 >> 4);                                 \
@@ -436,28 +514,104 @@ k_conv3x3_ps(const PsConvArgs p) {
   }
   // maxpool2x2(lrelu(acc + bias) * scale + skip) -> pooled PS / fp32 NCHW, routing bytes.  Every load first; stores are
   // buffer stores with the validity in the offset (exactly pool_cnt per wave, counted by the next tile's first wait).
+  // the skip values, dropout scales and bias of unit (M, GP): groups 4M + 2GP and 4M + 2GP + 1 of the window's four elements
+#define PS_EPI_LOADS(M, GP)                                                                        \
+  {                                                                                                \
+    const size_t ga = (size_t)(4 * (M) + 2 * (GP)) * gstride, gb = ga + (size_t)gstride;           \
+    _Pragma("unroll") for (int n = 0; n < 4; ++n) {                                                \
+      const u32x2_t* ap = reinterpret_cast<const u32x2_t*>(p.aux + sb0 + (n >> 1) * WP + (n & 1)) + half; \
+      sk[M][GP][n][0] = ap[ga * 2];                                                                \
+      sk[M][GP][n][1] = P16 ? u32x2_t{0u, 0u} : ap[(ga + p.plane_i) * 2];                          \
+      sk[M][GP][n][2] = ap[gb * 2];                                                                \
+      sk[M][GP][n][3] = P16 ? u32x2_t{0u, 0u} : ap[(gb + p.plane_i) * 2];                          \
+    }                                                                                              \
+    _Pragma("unroll") for (int i = 0; i < 4; ++i) {                                                \
+      const int ch = 32 * (M) + 16 * (GP) + 4 * half + i;                                          \
+      scv[M][GP][0][i] = (p.scale && okw) ? p.scale[ni * 64 + ch] : 1.f;                           \
+      scv[M][GP][1][i] = (p.scale && okw) ? p.scale[ni * 64 + ch + 8] : 1.f;                       \
+      bzw[M][2 * (GP)][i] = bz[M][2 * (GP)][i];                                                    \
+      bzw[M][2 * (GP) + 1][i] = bz[M][2 * (GP) + 1][i];                                            \
+    }                                                                                              \
+  }
+  // WG2: the same values for ONE group (4M + 2GP + AB) -- 24 registers -- requested one group ahead of their use; the
+  // dropout scale comes through a buffer descriptor (empty without scales: reads 0, replaced by 1) so that the whole
+  // epilogue stays one branch-free block, and the bias is read here instead of living in 32 registers
+#define PS_EPI_LOADS_G(M, GP, AB)                                                                  \
+  {                                                                                                \
+    const int g_ = (4 * (M) + 2 * (GP) + (AB)) * gstride * 16;                                     \
+    _Pragma("unroll") for (int n = 0; n < 4; ++n) {   /* buffer loads: one offset register instead of address pairs */ \
+      const int n_ = ((n >> 1) * WP + (n & 1)) * 16;                                               \
+      sk[M][GP][n][2 * (AB)] = __builtin_amdgcn_raw_buffer_load_b64(ars, skoff, g_ + n_, 0);       \
+      sk[M][GP][n][2 * (AB) + 1] = P16 ? u32x2_t{0u, 0u} : __builtin_amdgcn_raw_buffer_load_b64(ars, skoff, g_ + p.plane_i * 16 + n_, 0); \
+    }                                                                                              \
+    _Pragma("unroll") for (int i = 0; i < 4; ++i) {                                                \
+      const int ch = 32 * (M) + 16 * (GP) + 8 * (AB) + i;                                          \
+      const unsigned sv_ = __builtin_amdgcn_raw_buffer_load_b32(srs, scoff, ch * 4, 0);            \
+      scv[M][GP][AB][i] = __uint_as_float((sv_ & scm) | (0x3f800000u & ~scm));   /* 1.f without scales / window */ \
+      bzw[M][2 * (GP) + (AB)][i] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(brs, (unsigned)halfe * 16u, ch * 4, 0)); \
+    }                                                                                              \
+  }
+  // the outputs of unit (M, GP), one piece per output: this lane's own 8 channels 32M + 16GP + 8ab + 4half + i as fp32,
+  // the half exchange (lanes 0-31 keep group 2GP: channels 0-3 own, 4-7 from the upper half; lanes 32-63 group 2GP + 1),
+  // the pooled PS unit and the routing bytes
+#define PS_EPI_ST_F32(M, GP)                                                                       \
+  {                                                                                                \
+    const unsigned off = okw ? (unsigned)(((ni * 64 + 32 * (M) + 16 * (GP) + 4 * halfe) * p.Hp + yp) * p.Wpf + xg) * 4u : 0x80000000u;\
+    _Pragma("unroll") for (int jj = 0; jj < 8; ++jj)                                               \
+      __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, pvs[M][GP][jj >> 2][jj & 3]), frs, off,\
+                                            (8 * (jj >> 2) + (jj & 3)) * p.Hp * p.Wpf * 4, 0);     \
+  }
+#define PS_EPI_XCHG(M, GP)                                                                         \
+  {                                                                                                \
+    _Pragma("unroll") for (int i = 0; i < 4; ++i) {                                                \
+      auto r_ = __builtin_amdgcn_permlane32_swap(__float_as_uint(pvs[M][GP][0][i]), __float_as_uint(pvs[M][GP][1][i]), false, false);\
+      const unsigned r0_ = r_[0], r1_ = r_[1];   /* (a bit_cast applied to a vector ELEMENT is miscompiled: copy first) */\
+      pvs[M][GP][0][i] = __uint_as_float(r0_); pvs[M][GP][1][i] = __uint_as_float(r1_);            \
+    }                                                                                              \
+    { auto r_ = __builtin_amdgcn_permlane32_swap(rts[M][GP][0], rts[M][GP][1], false, false); rts[M][GP][0] = r_[0]; rts[M][GP][1] = r_[1]; }\
+  }
+#define PS_EPI_ST_PS(M, GP)                                                                        \
+  {                                                                                                \
+    const int G = 4 * (M) + 2 * (GP) + halfe;                                                       \
+    unsigned ha[2], la[2], hb[2], lb2[2];                                                          \
+    if (P16) { ps_hi4(pvs[M][GP][0], ha); ps_hi4(pvs[M][GP][1], hb); }                             \
+    else { ps_split4(pvs[M][GP][0], ha, la); ps_split4(pvs[M][GP][1], hb, lb2); }                  \
+    const unsigned off = okw ? (unsigned)(nn * p.img_p + (G * p.HPp + yp) * p.WPp + xp + 1) * 16u : 0x80000000u;\
+    __builtin_amdgcn_raw_buffer_store_b128(u32x4{ha[0], ha[1], hb[0], hb[1]}, prs, off, 0, 0);     \
+    if (!P16) __builtin_amdgcn_raw_buffer_store_b128(u32x4{la[0], la[1], lb2[0], lb2[1]}, prs, off, p.plane_p * 16, 0);\
+  }
+#define PS_EPI_ST_RT(M, GP)                                                                        \
+  {                                                                                                \
+    const int G = 4 * (M) + 2 * (GP) + halfe;                                                       \
+    const unsigned off = okw ? (unsigned)(((nn * 8 + G) * p.Hp + yp) * p.Wp + xp) * 8u : 0x80000000u;\
+    __builtin_amdgcn_raw_buffer_store_b64(u32x2_t{rts[M][GP][0], rts[M][GP][1]}, rrs, off, 0, 0);  \
+  }
 #define PS_EPI_FWD_POOL(ACC, T)                                                                    \
   if (!(PS_DBG & 1)) {                                                                             \
+    /* WG2: the lane-derived values of the epilogue are re-made per tile from the lane number (two VALU), */\
+    /* or hipcc keeps a dozen of them in registers across the MFMA loop and spills them                               */\
+    const int l31o_ = l31, halfo_ = half;                                                          \
+    {                                                                                              \
+    int l31 = l31o_, halfe = halfo_;                                                               \
+    if (WG2) {                                                                                     \
+      const int ln_ = ps_lane_now();                                                               \
+      l31 = ln_ & 31; halfe = ln_ >> 5;                                                            \
+    }                                                                                              \
     PS_WIN(T)                                                                                      \
     const int sb0 = okw ? nn * p.img_i + y * WP + 2 * xp + 1 : 0;                                  \
     u32x2_t sk[2][2][4][4];                                                                        \
-    float scv[2][2][2][4];                                                                         \
-    _Pragma("unroll") for (int m = 0; m < 2; ++m)                                                  \
-      _Pragma("unroll") for (int gp = 0; gp < 2; ++gp) {                                           \
-        const size_t ga = (size_t)(4 * m + 2 * gp) * gstride, gb = ga + (size_t)gstride;           \
-        _Pragma("unroll") for (int n = 0; n < 4; ++n) {                                            \
-          const u32x2_t* ap = reinterpret_cast<const u32x2_t*>(p.aux + sb0 + (n >> 1) * WP + (n & 1)) + half; \
-          sk[m][gp][n][0] = ap[ga * 2];                                                            \
-          sk[m][gp][n][1] = P16 ? u32x2_t{0u, 0u} : ap[(ga + p.plane_i) * 2];                      \
-          sk[m][gp][n][2] = ap[gb * 2];                                                            \
-          sk[m][gp][n][3] = P16 ? u32x2_t{0u, 0u} : ap[(gb + p.plane_i) * 2];                      \
-        }                                                                                          \
-        _Pragma("unroll") for (int i = 0; i < 4; ++i) {                                            \
-          const int ch = 32 * m + 16 * gp + 4 * half + i;                                          \
-          scv[m][gp][0][i] = (p.scale && okw) ? p.scale[ni * 64 + ch] : 1.f;                       \
-          scv[m][gp][1][i] = (p.scale && okw) ? p.scale[ni * 64 + ch + 8] : 1.f;                   \
-        }                                                                                          \
-      }                                                                                            \
+    float scv[2][2][2][4], bzw[2][4][4];                                                           \
+    const unsigned scoff = okw ? (unsigned)(ni * 64 + 4 * halfe) * 4u : 0x80000000u;                \
+    const unsigned skoff = (unsigned)sb0 * 16u + (unsigned)halfe * 8u;                              \
+    unsigned scm = (p.scale && okw) ? 0xffffffffu : 0u;                                            \
+    ps_opaque(scm);   /* a bit mask, not a select: hipcc turns `cond ? load : 1.f` into a branch round the load, and */ \
+                      /* every branch splits the block the group-by-group order of the loads is pinned in            */ \
+    if (!WG2) {   /* the whole register file: every load of the tile first */                      \
+      _Pragma("unroll") for (int m = 0; m < 2; ++m)                                                \
+        _Pragma("unroll") for (int gp = 0; gp < 2; ++gp) PS_EPI_LOADS(m, gp)                       \
+    } else {      /* half the register file: one group's loads at a time, one group ahead */       \
+      PS_EPI_LOADS_G(0, 0, 0)                                                                      \
+    }                                                                                              \
     /* values first, then ONE section per output whose branch is uniform for the whole kernel: the number of stores */ \
     /* between the DMA and the next wait is pool_cnt on every path (tools/audit_vmcnt.py)                            */ \
     float pvs[2][2][2][4];                                                                         \
@@ -465,7 +619,12 @@ k_conv3x3_ps(const PsConvArgs p) {
     _Pragma("unroll") for (int m = 0; m < 2; ++m)                                                  \
       _Pragma("unroll") for (int gp = 0; gp < 2; ++gp) {                                           \
         unsigned rt[2] = {0u, 0u};                                                                 \
-        _Pragma("unroll") for (int ab = 0; ab < 2; ++ab)                                           \
+        _Pragma("unroll") for (int ab = 0; ab < 2; ++ab) {                                         \
+          if (WG2) {                                                                               \
+            const int s1_ = 4 * m + 2 * gp + ab + 1;                                               \
+            __builtin_amdgcn_sched_barrier(0);                                                     \
+            if (s1_ < 8) PS_EPI_LOADS_G((s1_ >> 2) & 1, (s1_ >> 1) & 1, s1_ & 1)                   \
+          }                                                                                        \
           _Pragma("unroll") for (int i = 0; i < 4; ++i) {                                          \
             float mx = -INFINITY;                                                                  \
             int arg = 0;                                                                           \
@@ -473,7 +632,7 @@ k_conv3x3_ps(const PsConvArgs p) {
             _Pragma("unroll") for (int n = 0; n < 4; ++n) {                                        \
               float z;                                                                             \
               ps_acc_read(ACC[m][n], 8 * gp + 4 * ab + i, z);                                      \
-              const float w_ = z + bz[m][2 * gp + ab][i];                                          \
+              const float w_ = z + bzw[m][2 * gp + ab][i];                                         \
               z = fmaxf(w_, w_ * p.slope);                                                         \
               bits |= (z > 0.f ? 1u : 0u) << n;                                                    \
               const float u_ = z * scv[m][gp][ab][i] + ps_join(sk[m][gp][n][2 * ab][i >> 1], sk[m][gp][n][2 * ab + 1][i >> 1], i & 1); \
@@ -481,47 +640,33 @@ k_conv3x3_ps(const PsConvArgs p) {
             }                                                                                      \
             pvs[m][gp][ab][i] = mx;                                                                \
             rt[ab] |= (bits | ((unsigned)arg << 4)) << (8 * i);                                    \
+            if (WG2) __builtin_amdgcn_sched_barrier(0);   /* one channel's four chains at a time: interleaving all sixteen costs registers and buys nothing at 4 cycles per VALU */ \
           }                                                                                        \
+        }                                                                                          \
         rts[m][gp][0] = rt[0]; rts[m][gp][1] = rt[1];                                              \
+        if (WG2) {   /* the unit's outputs leave at once: eight values and two routing words live instead of all 40 */\
+          if (p.pool_f32) PS_EPI_ST_F32(m, gp)                                                     \
+          PS_EPI_XCHG(m, gp)                                                                       \
+          if (p.pool_ps) PS_EPI_ST_PS(m, gp)                                                       \
+          if (p.route_out) PS_EPI_ST_RT(m, gp)                                                     \
+        }                                                                                          \
       }                                                                                            \
-    if (p.pool_f32) {   /* this lane's own 8 channels: 32m + 16gp + 8ab + 4half + i */              \
-      _Pragma("unroll") for (int m = 0; m < 2; ++m)                                                \
-        _Pragma("unroll") for (int gp = 0; gp < 2; ++gp) {                                         \
-          const unsigned off = okw ? (unsigned)(((ni * 64 + 32 * m + 16 * gp + 4 * half) * p.Hp + yp) * p.Wpf + xg) * 4u : 0x80000000u; \
-          _Pragma("unroll") for (int jj = 0; jj < 8; ++jj)                                         \
-            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, pvs[m][gp][jj >> 2][jj & 3]), frs, off, \
-                                                  (8 * (jj >> 2) + (jj & 3)) * p.Hp * p.Wpf * 4, 0); \
-        }                                                                                          \
-    }                                                                                              \
-    /* half exchange: lanes 0-31 keep group 2gp (channels 0-3 own, 4-7 from the upper half), lanes 32-63 group 2gp+1 */ \
-    _Pragma("unroll") for (int m = 0; m < 2; ++m)                                                  \
-      _Pragma("unroll") for (int gp = 0; gp < 2; ++gp) {                                           \
-        _Pragma("unroll") for (int i = 0; i < 4; ++i) {                                            \
-          auto r_ = __builtin_amdgcn_permlane32_swap(__float_as_uint(pvs[m][gp][0][i]), __float_as_uint(pvs[m][gp][1][i]), false, false); \
-          const unsigned r0_ = r_[0], r1_ = r_[1];   /* (a bit_cast applied to a vector ELEMENT is miscompiled: copy first) */ \
-          pvs[m][gp][0][i] = __uint_as_float(r0_); pvs[m][gp][1][i] = __uint_as_float(r1_);        \
-        }                                                                                          \
-        { auto r_ = __builtin_amdgcn_permlane32_swap(rts[m][gp][0], rts[m][gp][1], false, false); rts[m][gp][0] = r_[0]; rts[m][gp][1] = r_[1]; } \
+    if (!WG2) {                                                                                    \
+      if (p.pool_f32) {                                                                            \
+        _Pragma("unroll") for (int m = 0; m < 2; ++m)                                              \
+          _Pragma("unroll") for (int gp = 0; gp < 2; ++gp) PS_EPI_ST_F32(m, gp)                    \
       }                                                                                            \
-    if (p.pool_ps) {                                                                               \
       _Pragma("unroll") for (int m = 0; m < 2; ++m)                                                \
-        _Pragma("unroll") for (int gp = 0; gp < 2; ++gp) {                                         \
-          const int G = 4 * m + 2 * gp + half;                                                     \
-          unsigned ha[2], la[2], hb[2], lb2[2];                                                    \
-          if (P16) { ps_hi4(pvs[m][gp][0], ha); ps_hi4(pvs[m][gp][1], hb); }                       \
-          else { ps_split4(pvs[m][gp][0], ha, la); ps_split4(pvs[m][gp][1], hb, lb2); }            \
-          const unsigned off = okw ? (unsigned)(nn * p.img_p + (G * p.HPp + yp) * p.WPp + xp + 1) * 16u : 0x80000000u; \
-          __builtin_amdgcn_raw_buffer_store_b128(u32x4{ha[0], ha[1], hb[0], hb[1]}, prs, off, 0, 0); \
-          if (!P16) __builtin_amdgcn_raw_buffer_store_b128(u32x4{la[0], la[1], lb2[0], lb2[1]}, prs, off, p.plane_p * 16, 0); \
-        }                                                                                          \
+        _Pragma("unroll") for (int gp = 0; gp < 2; ++gp) PS_EPI_XCHG(m, gp)                        \
+      if (p.pool_ps) {                                                                             \
+        _Pragma("unroll") for (int m = 0; m < 2; ++m)                                              \
+          _Pragma("unroll") for (int gp = 0; gp < 2; ++gp) PS_EPI_ST_PS(m, gp)                     \
+      }                                                                                            \
+      if (p.route_out) {                                                                           \
+        _Pragma("unroll") for (int m = 0; m < 2; ++m)                                              \
+          _Pragma("unroll") for (int gp = 0; gp < 2; ++gp) PS_EPI_ST_RT(m, gp)                     \
+      }                                                                                            \
     }                                                                                              \
-    if (p.route_out) {                                                                             \
-      _Pragma("unroll") for (int m = 0; m < 2; ++m)                                                \
-        _Pragma("unroll") for (int gp = 0; gp < 2; ++gp) {                                         \
-          const int G = 4 * m + 2 * gp + half;                                                     \
-          const unsigned off = okw ? (unsigned)(((nn * 8 + G) * p.Hp + yp) * p.Wp + xp) * 8u : 0x80000000u; \
-          __builtin_amdgcn_raw_buffer_store_b64(u32x2_t{rts[m][gp][0], rts[m][gp][1]}, rrs, off, 0, 0); \
-        }                                                                                          \
     }                                                                                              \
   } else {                                                                                         \
     _Pragma("unroll") for (int m = 0; m < 2; ++m)                                                  \
@@ -612,10 +757,39 @@ k_conv3x3_ps(const PsConvArgs p) {
     }                                                                                              \
   }
 
+  // WG2: one tile into ACC through the ONE buffer.  Chunk 0 was requested before the previous tile's epilogue (only its
+  // `young` stores are younger); chunks 1.. are requested once every wave has left the chunk before them, and the next
+  // tile's chunk 0 once every wave has left the last one -- those waits run under the partner workgroup's MFMAs.
+#define PS_TILE2(ACC)                                                                              \
+  {                                                                                                \
+    PS_OPEN()                                                                                      \
+    PS_BODY2(ACC, 1)                                                                               \
+    for (int c = 1; c < p.nch; ++c) {                                                              \
+      __builtin_amdgcn_s_barrier();                                                                \
+      { const int lane = ps_lane_now(); PS_ROWOFF(tile) }   /* re-made per chunk from a fresh lane number: ten registers (and the row indices behind them) that need not live through the body */\
+      PS_DMA(c, 0)                                                                                 \
+      __builtin_amdgcn_sched_barrier(0);                                                           \
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                                             \
+      __builtin_amdgcn_s_barrier();                                                                \
+      PS_BODY2(ACC, 0)                                                                             \
+    }                                                                                              \
+    __builtin_amdgcn_s_barrier();                                                                  \
+    if (tile + tstep < tend) {                                                                     \
+      { const int lane = ps_lane_now(); PS_ROWOFF(tile + tstep) }                                  \
+      PS_DMA(0, 0)                                                                                 \
+    }                                                                                              \
+    __builtin_amdgcn_sched_barrier(0);                                                             \
+    etile = tile;                                                                                  \
+    PS_EPILOGUE(ACC)                                                                               \
+    young = (PS_DBG & 1) ? 0 : pool_cnt;                                                           \
+  }
+
   int etile = tile;                                      // the tile whose epilogue PS_EPILOGUE runs (woven: the loop has moved on)
   PS_ROWOFF(tile)
   PS_DMA(0, 0)
-  if (WOVEN) {
+  if constexpr (WG2) {
+    for (; tile < tend; tile += tstep) PS_TILE2(accA)
+  } else if (WOVEN) {
     for (;;) {
       PS_TILE(accA, accB)
       tile += tstep;
@@ -627,10 +801,20 @@ k_conv3x3_ps(const PsConvArgs p) {
   } else {
     for (; tile < tend; tile += tstep) PS_TILE(accA, accA)
   }
+#undef PS_TILE2
 #undef PS_TILE
 #undef PS_EPILOGUE
 #undef PS_EPI_ADDPOOL
 #undef PS_EPI_FWD_POOL
+#undef PS_EPI_ST_RT
+#undef PS_EPI_ST_PS
+#undef PS_EPI_XCHG
+#undef PS_EPI_ST_F32
+#undef PS_EPI_LOADS_G
+#undef PS_EPI_LOADS
+#undef PS_BODY2
+#undef PS_FRAG_B
+#undef PS_FRAG_A
 #undef PS_POOLPREF
 #undef PS_WIN
 #undef PS_WAITN
@@ -653,18 +837,18 @@ k_conv3x3_ps(const PsConvArgs p) {
 #define PS_CAT_(a, b) a##b
 #define PS_CAT(a, b) PS_CAT_(a, b)
 #define PS_TU_NAME PS_CAT(fdet_ps_launch_, PS_TU)
-template <int MODE, int WP, bool P16>
+template <int MODE, int WP, bool P16, bool WG2 = false>
 int launch_ps(const PsConvArgs& p, size_t lds, int grid, hipStream_t st) {
   static bool attr_set = false;
-  constexpr int lds_max = 2 * (2 * PSA + 4 * 648) * 16;  // the 64-slot geometry
+  constexpr int lds_max = (WG2 ? 1 : 2) * (2 * PSA + 4 * 648) * 16;  // the 64-slot geometry
   if (!attr_set) {
-    if ((int)lds > lds_max || hipFuncSetAttribute((const void*)k_conv3x3_ps<MODE, WP, P16>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max) != hipSuccess) {
+    if ((int)lds > lds_max || hipFuncSetAttribute((const void*)k_conv3x3_ps<MODE, WP, P16, WG2>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max) != hipSuccess) {
       (void)hipGetLastError();
       return fail(FDET_ELAUNCH, "conv3x3_ps: cannot reserve %zu bytes of LDS", lds);
     }
     attr_set = true;
   }
-  hipLaunchKernelGGL((k_conv3x3_ps<MODE, WP, P16>), dim3(grid), dim3(256), lds, st, p);
+  hipLaunchKernelGGL((k_conv3x3_ps<MODE, WP, P16, WG2>), dim3(grid), dim3(256), lds, st, p);
   return check_launch("fdet_conv3x3_ps");
 }
 
@@ -672,9 +856,15 @@ int launch_ps(const PsConvArgs& p, size_t lds, int grid, hipStream_t st) {
 #define PS_DECL_LAUNCH(N) extern "C" int fdet_ps_launch_##N(const void* args, size_t lds, int grid, void* stream);
 PS_DECL_LAUNCH(0) PS_DECL_LAUNCH(1) PS_DECL_LAUNCH(2) PS_DECL_LAUNCH(3) PS_DECL_LAUNCH(4) PS_DECL_LAUNCH(5) PS_DECL_LAUNCH(6) PS_DECL_LAUNCH(7)
 PS_DECL_LAUNCH(8) PS_DECL_LAUNCH(9) PS_DECL_LAUNCH(10) PS_DECL_LAUNCH(11) PS_DECL_LAUNCH(12) PS_DECL_LAUNCH(13) PS_DECL_LAUNCH(14) PS_DECL_LAUNCH(15)
+PS_DECL_LAUNCH(wg2_4) PS_DECL_LAUNCH(wg2_5)              // the two-workgroups-per-CU form of TUs 4 and 5 (bf16x3 FWD_POOL), same objects
 #if PS_TU >= 0
 extern "C" int PS_TU_NAME(const void* args, size_t lds, int grid, void* stream) {
   return launch_ps<(PS_TU & 7) / 2, (PS_TU & 1) ? 64 : 32, (PS_TU >= 8)>(*reinterpret_cast<const PsConvArgs*>(args), lds, grid, (hipStream_t)stream);
+}
+#endif
+#if PS_TU == 4 || PS_TU == 5
+extern "C" int PS_CAT(fdet_ps_launch_wg2_, PS_TU)(const void* args, size_t lds, int grid, void* stream) {
+  return launch_ps<PSE_FWD_POOL, (PS_TU & 1) ? 64 : 32, false, true>(*reinterpret_cast<const PsConvArgs*>(args), lds, grid, (hipStream_t)stream);
 }
 #endif
 namespace {
@@ -684,6 +874,9 @@ const ps_launch_fn PS_LAUNCHERS[16] = {fdet_ps_launch_0, fdet_ps_launch_1, fdet_
                                        fdet_ps_launch_4, fdet_ps_launch_5, fdet_ps_launch_6, fdet_ps_launch_7,
                                        fdet_ps_launch_8, fdet_ps_launch_9, fdet_ps_launch_10, fdet_ps_launch_11,
                                        fdet_ps_launch_12, fdet_ps_launch_13, fdet_ps_launch_14, fdet_ps_launch_15};
+// defaults of the two-workgroups-per-CU pooled forward per row width, decided by the A/B of both forms on one box
+// (DESIGN.md 2.2f): both widths gained (60x60 -12 %, 30x30 -16 % kernel time)
+constexpr bool PS_WG2_DEFAULT_64 = true, PS_WG2_DEFAULT_32 = true;
 struct PsPoolIO {
   const float* scale = nullptr; void* pool_ps = nullptr; float* pool_f32 = nullptr; unsigned char* route_out = nullptr;
   const float* dout = nullptr; const unsigned char* route_in = nullptr; float* dx_f32 = nullptr;
@@ -751,9 +944,18 @@ int run_ps(int mode, const void* x, const void* wpk, const float* bias, const vo
   p.plane_i = gi.plane; p.img_i = gi.img; p.plane_o = go.plane; p.img_o = go.img;
   p.magic_hp = magic_of(gi.HP);
   p.slope = slope;
-  const size_t lds = (size_t)2 * (2 * PSA + 4 * PT) * 16;
-  const int grid = std::min(p.ntiles, num_cus());
+  size_t lds = (size_t)2 * (2 * PSA + 4 * PT) * 16;
+  int grid = std::min(p.ntiles, num_cus());
   const bool w64 = gi.WP == 64;
+  // bf16x3 pooled forward: two workgroups per CU with one chunk buffer each (WG2 in the kernel's header).
+  // FDET_PS_POOL_WG2 = 0 / 1 forces the present / the new form; unset = the per-WP default the A/B measurement chose.
+  static const int wg2_env = [] { const char* e = getenv("FDET_PS_POOL_WG2"); return (e && (e[0] == '0' || e[0] == '1') && !e[1]) ? e[0] - '0' : -1; }();
+  bool wg2 = mode == PSE_FWD_POOL && !p16 && (wg2_env >= 0 ? wg2_env == 1 : (w64 ? PS_WG2_DEFAULT_64 : PS_WG2_DEFAULT_32));
+  if (wg2 && 2 * (lds / 2) > (size_t)160 * 1024) wg2 = false;   // two workgroups must fit the CU's LDS
+  if (wg2) {
+    lds /= 2;
+    grid = std::min(p.ntiles, 2 * num_cus());
+  }
   switch (mode) {
     case PSE_FWD_FULL:
       FDET_REQUIRE(bias, "conv3x3_ps_fwd: bias is required");
@@ -768,6 +970,7 @@ int run_ps(int mode, const void* x, const void* wpk, const float* bias, const vo
       FDET_REQUIRE(io.dout && io.route_in && io.dx_f32, "conv3x3_ps_dgrad_unpool: dout, route and dx are required");
       break;
   }
+  if (wg2) return (w64 ? fdet_ps_launch_wg2_5 : fdet_ps_launch_wg2_4)(&p, lds, grid, (void*)st);
   return PS_LAUNCHERS[(p16 ? 8 : 0) + 2 * mode + (w64 ? 1 : 0)](&p, lds, grid, (void*)st);
 }
 #endif  // PS_TU == -1
