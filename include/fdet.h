@@ -1146,6 +1146,35 @@ int fdet_q8_dequantize(const int8_t* q, float scale, float* x, int N, int C, int
 int fdet_q8_conv3x3(const int8_t* x, const int8_t* wpk, const int32_t* bias, const float* mul, const int8_t* skip,
                     float skip_mul, int8_t* y, int N, int C, int H, int W, int pool, float slope, void* stream);
 
+/* The un-pooled tail of the trunk in one launch: nblocks (1..16) residual blocks of 64 channels on maps of at most 16 x 16.
+ *     for k = 0 .. nblocks - 1:   a = conv(h; wpk1[k], b1[k], mul1[k])
+ *                                 h = conv(a; wpk2[k], b2[k], mul2[k], skip = h, skip_mul[k])
+ * with conv the un-pooled fdet_q8_conv3x3 above, element for element: the result equals nblocks pairs of fdet_q8_conv3x3
+ * calls byte for byte.  A workgroup keeps one image's two planes and two layers' packed weights in LDS for the whole chain.
+ *   x          Q8 [N][H+2][W+2][64] with its halo of zeros; no output may alias it
+ *   h_*        HOST arrays (nblocks entries) of DEVICE pointers / floats; they travel to the kernel by value, nothing is
+ *              copied to the device, so the call can be captured in a HIP graph
+ *   h_out      HOST array of DEVICE Q8 tensors, block k's output where h_out[k] != NULL (real pixels only); the array
+ *              itself may be NULL
+ *   out_f32    optional fp32 [N,64,H,W] = float(q of the last block) * out_scale, bit for bit fdet_q8_dequantize
+ * At least one of h_out[nblocks - 1] and out_f32 is given; every device pointer is 16-byte aligned.
+ * fdet_q8_chain_supported: 1 for C == 64 and 1 <= H, W <= 16 (launches nothing). */
+int fdet_q8_chain_supported(int C, int H, int W);
+int fdet_q8_chain(const int8_t* x, const int8_t* const* h_wpk1, const int32_t* const* h_b1, const float* const* h_mul1,
+                  const int8_t* const* h_wpk2, const int32_t* const* h_b2, const float* const* h_mul2,
+                  const float* h_skip_mul, int8_t* const* h_out, float* out_f32, float out_scale, int nblocks, int N, int C,
+                  int H, int W, float slope, void* stream);
+
+/* The PoolResnet stem on the uint8 frames (fdet_stem_fwd_ps_u8's kernel and shapes: F = 64, 3 channels, k10 s8 p2,
+ * W % 4 == 0, W <= 512) with the quantiser in its epilogue: q (Q8 [N][Ho+2][Wo+2][64], 16-byte aligned) receives
+ * clamp(rintf(t), -127, 127), NaN -> 0, of t = (acc + bias) * (1.0f / scale) -- the bytes of fdet_u8_to_f32_norm ->
+ * fdet_stem_fwd_bf16x3 -> fdet_q8_quantize(scale).  Real pixels only: the halo is untouched.  Large batches run as
+ * consecutive launches over image chunks.  fdet_stem_fwd_q8_ok: the entry point accepts N images of this shape (launches
+ * nothing). */
+int fdet_stem_fwd_q8_u8(const unsigned char* frames, const float* w, const float* bias, float scale, int8_t* q,
+                        int N, int Cin, int F, int H, int W, int k, int stride, int pad, void* stream);
+int fdet_stem_fwd_q8_ok(int N, int Cin, int F, int H, int W, int k, int stride, int pad);
+
 #ifdef __cplusplus
 }
 #endif

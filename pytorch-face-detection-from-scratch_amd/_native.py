@@ -191,6 +191,10 @@ SIGNATURES = {
     "fdet_q8_quantize": (_I, [_P, _F, _P, _I, _I, _I, _I, _P]),
     "fdet_q8_dequantize": (_I, [_P, _F, _P, _I, _I, _I, _I, _P]),
     "fdet_q8_conv3x3": (_I, [_P, _P, _P, _P, _P, _F, _P, _I, _I, _I, _I, _I, _F, _P]),
+    "fdet_q8_chain_supported": (_I, [_I, _I, _I]),
+    "fdet_q8_chain": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _F, _I, _I, _I, _I, _I, _F, _P]),
+    "fdet_stem_fwd_q8_u8": (_I, [_P, _P, _P, _F, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "fdet_stem_fwd_q8_ok": (_I, [_I, _I, _I, _I, _I, _I, _I, _I]),
 }
 
 

@@ -217,6 +217,166 @@ __global__ __launch_bounds__(256) void k_q8_conv3x3(const signed char* __restric
 
 inline bool q8_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// The un-pooled tail of the trunk in ONE launch: nblocks residual blocks (2 * nblocks convs of 64 channels) on maps of at
+// most 16 x 16.  A workgroup of four waves owns one image for the whole chain and keeps in LDS
+//     two weight buffers  [tap][co][64] of one layer each, 36,864 bytes: layer L computes from buffer L & 1 while the
+//                         threads hold layer L + 1 in registers (nine 16-byte loads each) and store it into the other
+//                         buffer behind the layer's MFMAs,
+//     two haloed planes   h and a, (H+2)(W+2) x 64 bytes each (at most 20,736): h is a copy of the image with its halo of
+//                         zeros, a is zero-filled once; only real pixels are written, so the halo stays the padding,
+//     biases, multipliers of every layer (16 KB), read from memory once per workgroup: inside the layer loop the only global
+//                         loads are the next layer's weights, and nothing waits for them before the layer's MFMAs are done.
+// The first conv of a block reads h and writes a; the second reads a and overwrites h in place -- a lane reads its own skip
+// dword before it writes that dword, and no other lane touches it -- so one barrier per conv is all the ordering there is.
+// A wave computes the 64 output channels of 4 rows x 16 columns exactly as k_q8_conv3x3 does (same fragments, same
+// epilogue, operands from LDS): at most four row groups, one per wave.
+constexpr int Q8C_MAXB = 16;                        // blocks per launch
+constexpr int Q8C_MAXHW = 16;                       // one MFMA column tile per map row
+constexpr int Q8C_WBYTES = 9 * 64 * 64;             // one layer's packed weights
+constexpr int Q8C_PLANE = (Q8C_MAXHW + 2) * (Q8C_MAXHW + 2) * 64;
+constexpr int Q8C_PARAMS = 2 * Q8C_MAXB * 64 * 4;                // one layer-major array of biases, one of multipliers
+constexpr int Q8C_LDS = 2 * Q8C_WBYTES + 2 * Q8C_PLANE + 2 * Q8C_PARAMS;          // 131,584
+
+struct Q8ChainArgs {
+  const signed char* x;
+  const signed char* w[2 * Q8C_MAXB];              // per conv, in execution order
+  const int* bias[2 * Q8C_MAXB];
+  const float* mul[2 * Q8C_MAXB];
+  signed char* out[Q8C_MAXB];                       // per block: Q8 output, or nullptr
+  float skip_mul[Q8C_MAXB];
+  float* out_f32;
+  float out_scale, slope;
+  int nlayers, N, H, W;
+};
+
+__host__ __device__ inline bool q8_chain_shape_ok(int C, int H, int W) {
+  return C == 64 && H >= 1 && W >= 1 && H <= Q8C_MAXHW && W <= Q8C_MAXHW;
+}
+
+__global__ __launch_bounds__(256) void k_q8_chain(const Q8ChainArgs a) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char q8_lds[];
+  const int tid = threadIdx.x;
+  const int lane = tid & 63, wave = tid >> 6;
+  const int lp = lane & 15, lk = lane >> 4;
+  const int H = a.H, W = a.W, HP = H + 2, WP = W + 2;
+  const int plane = HP * WP * 64;                   // bytes; a multiple of 64
+  unsigned char* const ph = q8_lds + 2 * Q8C_WBYTES;
+  unsigned char* const pa = ph + Q8C_PLANE;
+  const int row_groups = (H + Q8_ROWS - 1) / Q8_ROWS;           // <= 4: one per wave
+  const int pxc = min(lp, W - 1);
+  const int y0 = wave * Q8_ROWS;
+  const bool live = wave < row_groups;
+  const bool px_ok = lp < W;
+  int* const lbias = reinterpret_cast<int*>(pa + Q8C_PLANE);                  // [layer][64]
+  float* const lmul = reinterpret_cast<float*>(pa + Q8C_PLANE + Q8C_PARAMS);  // [layer][64]
+  for (int i = tid; i < plane / 16; i += 256) reinterpret_cast<q8_v4i*>(pa)[i] = q8_v4i{0, 0, 0, 0};
+  for (int i = tid; i < a.nlayers * 16; i += 256) {
+    reinterpret_cast<q8_v4i*>(lbias)[i] = reinterpret_cast<const q8_v4i*>(a.bias[i >> 4])[i & 15];
+    reinterpret_cast<q8_v4f*>(lmul)[i] = reinterpret_cast<const q8_v4f*>(a.mul[i >> 4])[i & 15];
+  }
+  for (int n = blockIdx.x; n < a.N; n += gridDim.x) {
+    // layer 0's weights and the image.  Buffer 0 and h were last read two barriers ago (the last layer of the previous
+    // image is odd: it reads buffer 1 and the a plane, and touches h only in its own dwords)
+    {
+      q8_v4i v[9];
+#pragma unroll
+      for (int k = 0; k < 9; ++k) v[k] = reinterpret_cast<const q8_v4i*>(a.w[0])[k * 256 + tid];
+      const q8_v4i* src = reinterpret_cast<const q8_v4i*>(a.x + (size_t)n * plane);
+      for (int i = tid; i < plane / 16; i += 256) reinterpret_cast<q8_v4i*>(ph)[i] = src[i];
+#pragma unroll
+      for (int k = 0; k < 9; ++k) reinterpret_cast<q8_v4i*>(q8_lds)[k * 256 + tid] = v[k];
+    }
+    __syncthreads();
+    for (int L = 0; L < a.nlayers; ++L) {
+      const bool second = L & 1;
+      const bool more = L + 1 < a.nlayers;
+      q8_v4i nw[9];
+      if (more) {
+        const q8_v4i* wn = reinterpret_cast<const q8_v4i*>(a.w[L + 1]);
+#pragma unroll
+        for (int k = 0; k < 9; ++k) nw[k] = wn[k * 256 + tid];
+      }
+      if (live) {
+        const unsigned char* src = second ? pa : ph;
+        const unsigned char* wl = q8_lds + (L & 1) * Q8C_WBYTES + lp * 64 + lk * 16;
+        const int* bias = lbias + L * 64;
+        const float* mul = lmul + L * 64;
+        q8_v4i acc[Q8_ROWS][4];
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+          const q8_v4i b = *reinterpret_cast<const q8_v4i*>(bias + 16 * t + 4 * lk);
+#pragma unroll
+          for (int j = 0; j < Q8_ROWS; ++j) acc[j][t] = b;
+        }
+        // padded rows y0 .. y0 + 5 at columns px .. px + 2; rows past H + 1 belong to rows below the map only (clamped, never
+        // stored), columns past W to lanes that store nothing
+        q8_v4i b[Q8_ROWS + 2][3];
+#pragma unroll
+        for (int r = 0; r < Q8_ROWS + 2; ++r) {
+          const unsigned char* xr = src + (min(y0 + r, H + 1) * WP + pxc) * 64 + lk * 16;
+#pragma unroll
+          for (int kx = 0; kx < 3; ++kx) b[r][kx] = *reinterpret_cast<const q8_v4i*>(xr + kx * 64);
+        }
+#pragma unroll
+        for (int tap = 0; tap < 9; ++tap) {
+          const int ky = tap / 3, kx = tap - 3 * (tap / 3);
+          q8_v4i af[4];
+#pragma unroll
+          for (int t = 0; t < 4; ++t) af[t] = *reinterpret_cast<const q8_v4i*>(wl + tap * 4096 + t * 1024);
+#pragma unroll
+          for (int j = 0; j < Q8_ROWS; ++j)
+#pragma unroll
+            for (int t = 0; t < 4; ++t) acc[j][t] = __builtin_amdgcn_mfma_i32_16x16x64_i8(af[t], b[j + ky][kx], acc[j][t], 0, 0, 0);
+        }
+        // epilogue of k_q8_conv3x3, into the other plane (first conv) or over the skip dword (second conv)
+        const int blk = L >> 1;
+        const float skip_mul = a.skip_mul[blk];
+        signed char* const gout = second ? a.out[blk] : nullptr;
+        float* const fout = L + 1 == a.nlayers ? a.out_f32 : nullptr;
+        unsigned char* dst = second ? ph : pa;
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+          const int co = 16 * t + 4 * lk;
+          const q8_v4f m = *reinterpret_cast<const q8_v4f*>(mul + co);
+#pragma unroll
+          for (int j = 0; j < Q8_ROWS; ++j) {
+            const int yy = y0 + j;
+            const int off = ((min(yy, H - 1) + 1) * WP + pxc + 1) * 64 + co;
+            int sk = 0;
+            if (second) sk = *reinterpret_cast<const int*>(ph + off);
+            int q[4];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+              float v = (float)acc[j][t][r] * m[r];
+              v = v >= 0.0f ? v : v * a.slope;
+              if (second) v = v + (float)q8_byte(sk, r) * skip_mul;
+              q[r] = q8_round(v);
+            }
+            if (px_ok && yy < H) {
+              const int pk = q8_pack4(q[0], q[1], q[2], q[3]);
+              *reinterpret_cast<int*>(dst + off) = pk;
+              if (gout != nullptr) *reinterpret_cast<int*>(gout + (size_t)n * plane + off) = pk;
+              if (fout != nullptr) {
+                float* d = fout + (((size_t)n * 64 + co) * H + yy) * W + lp;
+#pragma unroll
+                for (int r = 0; r < 4; ++r) d[(size_t)r * H * W] = (float)q[r] * a.out_scale;
+              }
+            }
+          }
+        }
+      }
+      if (more) {
+        q8_v4i* wd = reinterpret_cast<q8_v4i*>(q8_lds + ((L + 1) & 1) * Q8C_WBYTES);
+#pragma unroll
+        for (int k = 0; k < 9; ++k) wd[k * 256 + tid] = nw[k];
+      }
+      __syncthreads();
+    }
+  }
+}
+
+
 }  // namespace
 
 extern "C" int fdet_q8_supported(int C, int H, int W) { return q8_shape_ok(C, H, W) ? 1 : 0; }
@@ -286,4 +446,46 @@ extern "C" int fdet_q8_conv3x3(const int8_t* x, const int8_t* wpk, const int32_t
     hipLaunchKernelGGL(k_q8_conv3x3<false>, grid, dim3(256), lds, (hipStream_t)stream, xs, ws, bias, mul, ss, skip_mul, ys, g, tiles_x,
                        row_groups, (int)items, slope);
   return check_launch("fdet_q8_conv3x3");
+}
+
+extern "C" int fdet_q8_chain_supported(int C, int H, int W) { return q8_chain_shape_ok(C, H, W) ? 1 : 0; }
+
+extern "C" int fdet_q8_chain(const int8_t* x, const int8_t* const* h_wpk1, const int32_t* const* h_b1, const float* const* h_mul1,
+                             const int8_t* const* h_wpk2, const int32_t* const* h_b2, const float* const* h_mul2,
+                             const float* h_skip_mul, int8_t* const* h_out, float* out_f32, float out_scale, int nblocks, int N,
+                             int C, int H, int W, float slope, void* stream) {
+  FDET_REQUIRE(q8_chain_shape_ok(C, H, W) && N >= 1 && q8_bytes(N, C, H, W) > 0,
+               "q8_chain: unsupported shape N=%d C=%d H=%d W=%d (C == 64, 1 <= H, W <= %d)", N, C, H, W, Q8C_MAXHW);
+  FDET_REQUIRE(nblocks >= 1 && nblocks <= Q8C_MAXB, "q8_chain: nblocks must be 1..%d, got %d", Q8C_MAXB, nblocks);
+  FDET_REQUIRE(x && h_wpk1 && h_b1 && h_mul1 && h_wpk2 && h_b2 && h_mul2 && h_skip_mul, "q8_chain: null argument");
+  FDET_REQUIRE((h_out && h_out[nblocks - 1]) || out_f32, "q8_chain: the last block needs an output (h_out[nblocks - 1] or out_f32)");
+  FDET_REQUIRE(out_f32 == nullptr || (out_scale > 0.0f && out_scale <= 3.0e38f), "q8_chain: out_scale must be positive and finite");
+  Q8ChainArgs a{};
+  a.x = reinterpret_cast<const signed char*>(x);
+  bool ok = q8_aligned16(x) && q8_aligned16(out_f32);
+  for (int k = 0; k < nblocks; ++k) {
+    FDET_REQUIRE(h_wpk1[k] && h_b1[k] && h_mul1[k] && h_wpk2[k] && h_b2[k] && h_mul2[k], "q8_chain: null tensor in block %d", k);
+    a.w[2 * k] = reinterpret_cast<const signed char*>(h_wpk1[k]);
+    a.w[2 * k + 1] = reinterpret_cast<const signed char*>(h_wpk2[k]);
+    a.bias[2 * k] = h_b1[k];
+    a.bias[2 * k + 1] = h_b2[k];
+    a.mul[2 * k] = h_mul1[k];
+    a.mul[2 * k + 1] = h_mul2[k];
+    a.skip_mul[k] = h_skip_mul[k];
+    a.out[k] = h_out ? reinterpret_cast<signed char*>(h_out[k]) : nullptr;
+    FDET_REQUIRE(a.out[k] == nullptr || a.out[k] != a.x, "q8_chain: an output may not alias x");
+    ok = ok && q8_aligned16(h_wpk1[k]) && q8_aligned16(h_wpk2[k]) && q8_aligned16(h_b1[k]) && q8_aligned16(h_b2[k]) &&
+         q8_aligned16(h_mul1[k]) && q8_aligned16(h_mul2[k]) && q8_aligned16(a.out[k]);
+  }
+  FDET_REQUIRE(ok, "q8_chain: every tensor must be 16-byte aligned");
+  a.out_f32 = out_f32;
+  a.out_scale = out_scale;
+  a.slope = slope;
+  a.nlayers = 2 * nblocks;
+  a.N = N; a.H = H; a.W = W;
+  const int rc = set_lds_attr((const void*)k_q8_chain, Q8C_LDS, "fdet_q8_chain");
+  if (rc != FDET_OK) return rc;
+  const int grid = N < num_cus() ? N : num_cus();      // one workgroup per CU (LDS), one image at a time
+  hipLaunchKernelGGL(k_q8_chain, dim3((unsigned)grid), dim3(256), Q8C_LDS, (hipStream_t)stream, a);
+  return check_launch("fdet_q8_chain");
 }

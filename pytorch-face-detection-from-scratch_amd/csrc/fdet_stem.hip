@@ -23,6 +23,9 @@ int stem_x3_fwd(const float* x, const float* w, const float* bias, float* y, int
 int stem_x3_fwd_ps(const void* x, const float* w, const float* bias, void* y_ps, int N, int F, int H, int W, hipStream_t st, bool p16, bool u8 = false);
 int stem_x3_wgrad(const float* x, const float* dy, float* dW, float* db, float* ws, int N, int F, int H, int W, hipStream_t st, bool p16);
 bool stem_x3_fwd_ps_ok(int N, int F, int H, int W);
+int stem_x3_fwd_q8(const unsigned char* frames, const float* w, const float* bias, float q_inv, signed char* q, int N, int F, int H,
+                   int W, hipStream_t st);
+bool stem_x3_fwd_q8_ok(int N, int F, int H, int W);
 bool stem_x3_wgrad_pipe_ok(int N, int F, int H, int W);
 size_t stem_x3_wgrad_ws_floats(int N, int F, int H, int W);
 // fdet_stem_k3.hip: the Resnet stem (k3 s2 p1) on the matrix cores / with a PS (column-strip) output
@@ -469,6 +472,25 @@ extern "C" int fdet_stem_fwd_ps_u8(const unsigned char* frames, const float* w, 
                Cin, k, stride, pad, W);
   FDET_REQUIRE(stem_fwd_ps_plan_ok(N, Cin, F, H, W, k, stride, pad, true), "stem_fwd_ps_u8: no PS stem plan for N=%d %dx%d", N, H, W);
   return stem_x3_fwd_ps(frames, w, bias, y_ps, N, F, H, W, (hipStream_t)stream, precision16 != 0, true);
+}
+
+// Int8 inference: the same uint8-frame stem with its output quantised in the epilogue and written in the int8 trunk's layout
+// (fdet.h "Int8 inference").  The bytes equal fdet_u8_to_f32_norm -> fdet_stem_fwd_bf16x3 -> fdet_q8_quantize(scale).
+extern "C" int fdet_stem_fwd_q8_ok(int N, int Cin, int F, int H, int W, int k, int stride, int pad) {
+  return F == 64 && N > 0 && stem_mfma_ok(Cin, F, H, W, k, stride, pad) && stem_fwd_ps_plan_ok(N, Cin, F, H, W, k, stride, pad, true) &&
+         stem_x3_fwd_q8_ok(N, F, H, W);
+}
+
+extern "C" int fdet_stem_fwd_q8_u8(const unsigned char* frames, const float* w, const float* bias, float scale, int8_t* q, int N,
+                                   int Cin, int F, int H, int W, int k, int stride, int pad, void* stream) {
+  stem_clear_route();
+  FDET_REQUIRE(frames && w && bias && q && N > 0 && F == 64, "stem_fwd_q8_u8: bad arguments (F must be 64)");
+  FDET_REQUIRE(scale > 0.0f && scale <= 3.0e38f, "stem_fwd_q8_u8: scale must be positive and finite");
+  FDET_REQUIRE(stem_mfma_ok(Cin, F, H, W, k, stride, pad) && ((uintptr_t)frames % 4) == 0 && ((uintptr_t)q % 16) == 0,
+               "stem_fwd_q8_u8: only the PoolResnet stem (3ch k10 s8 p2, W%%4==0, W<=512) on 4-byte aligned frames and a 16-byte aligned output; got Cin=%d k=%d s=%d p=%d W=%d",
+               Cin, k, stride, pad, W);
+  FDET_REQUIRE(fdet_stem_fwd_q8_ok(N, Cin, F, H, W, k, stride, pad), "stem_fwd_q8_u8: no Q8 stem plan for N=%d %dx%d", N, H, W);
+  return stem_x3_fwd_q8(frames, w, bias, 1.0f / scale, reinterpret_cast<signed char*>(q), N, F, H, W, (hipStream_t)stream);
 }
 
 extern "C" int fdet_stem_wgrad_bf16x3(const float* x, const float* dy, float* dW, float* db, void* ws, size_t ws_bytes,

@@ -33,6 +33,9 @@ struct StemX3Args {
   int N, F, H, W, Ho, Wo, nrows;
   // PS output (fdet_ps.h) of the pipelined kernel: y is then the image-0 pointer of a PS tensor (F == 64)
   int ps_hp, ps_wp, ps_plane, ps_img;
+  // Q8 output of the pipelined kernel: y is an int8 [N][Ho+2][Wo+2][64] tensor (fdet.h "Int8 inference"), ps_hp / ps_wp its
+  // padded extent, ps_img its image size in 16-byte units, q_inv = 1.0f / scale
+  float q_inv;
 };
 
 __global__ void __launch_bounds__(256, 1)
@@ -192,18 +195,28 @@ __device__ __forceinline__ unsigned sx_hi_pair(float f0, float f1) {
   return __builtin_bit_cast(unsigned, h);
 }
 
+// fdet_q8_quantize's rounding of one product: clamp(rintf(t), -127, 127), a NaN product -> 0
+__device__ __forceinline__ int sx_q8_round(float t) {
+  return t == t ? (int)fminf(fmaxf(rintf(t), -127.0f), 127.0f) : 0;
+}
+
 // P16 (precision16, PS output only): one MFMA pass on bf16(x) x bf16(w); the lo halves are neither computed nor staged and
 // only the hi plane of the output is written.
 // U8 (inference, PS output only): the input is the uint8 frame itself -- `x / 255` (models/PoolResnet.py:95) happens in the
 // staging job through a 256-entry table of (bf16 hi | bf16 lo) pairs of p / 255 in LDS, i.e. the values the fp32 path splits
 // out of fdet_u8_to_f32_norm's output, bit for bit; a slot loads one dword (4 pixels) instead of a float4, and the fp32 image
 // (2.76 MB per frame written and read back) never exists.
-template <bool PSO, bool P16 = false, bool U8 = false>
+// Q8 (int8 inference, with PSO and U8, not P16): the epilogue quantises the fp32 value acc + bias that the fp32-output form
+// stores -- q = clamp(rintf(v * q_inv), -127, 127), NaN -> 0, as fdet_q8_quantize -- and writes the int8 trunk's layout
+// [N][Ho+2][Wo+2][64], real pixels only: after one v_permlane32_swap a lane holds the 8 consecutive channels of one group of
+// its pixel as two dwords, one 8-byte store per group pair.
+template <bool PSO, bool P16 = false, bool U8 = false, bool Q8 = false>
 __global__ void __launch_bounds__(256, 1)
 k_stem_fwd_x3_pipe(const StemX3Args a) {
   static_assert(PSO || !P16, "precision16 stem: PS output only");
   static_assert(PSO || !U8, "uint8 stem: PS output only");
-  constexpr int NST = PSO ? (P16 ? 2 : 4) : 16;        // output stores per row (they sit in the memory queue of the counted waits)
+  static_assert(!Q8 || (PSO && U8 && !P16), "Q8 stem: the uint8-frame bf16x3 form only");
+  constexpr int NST = Q8 ? 2 : PSO ? (P16 ? 2 : 4) : 16;   // output stores per row (they sit in the memory queue of the counted waits)
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int TILE = NROW * RL * 2;                   // bf16 elements per tile: hi rows, then lo rows
   __bf16* const base = reinterpret_cast<__bf16*>(smem);
@@ -252,7 +265,14 @@ k_stem_fwd_x3_pipe(const StemX3Args a) {
     const int ci = irow_ / KS, ky = irow_ - ci * KS;                                            \
     const int iy = (ROY) * ST - PD + ky;                                                        \
     const bool ok = lane_ok & ((ROY) >= 0) & (iy >= 0) & (iy < a.H);                           \
-    const unsigned off = ((unsigned)(((RN) * CIN + ci) * a.H + iy) * a.W + j4 * 4) * (U8 ? 1u : 4u); \
+    unsigned off = ((unsigned)(((RN) * CIN + ci) * a.H + iy) * a.W + j4 * 4) * (U8 ? 1u : 4u); \
+    if constexpr (Q8) {                                                                         \
+      /* the same offset as a multiply and a separate add: fused into a 64-bit multiply-add, its addend pair's unused high */ \
+      /* register was one that an in-flight load of the other set writes (tools/audit_asm_loads.py reports the read)     */ \
+      off = (unsigned)(((RN) * CIN + ci) * a.H + iy) * a.W;                                     \
+      asm volatile("" : "+v"(off));                                                             \
+      off += j4 * 4;                                                                            \
+    }                                                                                           \
     if constexpr (U8) sx_aload1<S == 0>(q##S[SL], ok ? off : 0x80000000u, rx);                  \
     else sx_aload<S == 0>(p##S[SL], ok ? off : 0x80000000u, rx);                                \
   }
@@ -334,7 +354,24 @@ k_stem_fwd_x3_pipe(const StemX3Args a) {
       if constexpr (rr >= 4 && rr - 4 < NSLOT) SXP_LOAD1(S, rr - 4, n3_, oy3_)                  \
       __builtin_amdgcn_sched_barrier(0);                                                        \
     });                                                                                         \
-    if constexpr (PSO) {                                                                        \
+    if constexpr (Q8) {                                                                         \
+      /* lane = position, registers = channels 32m + 8g + 4half + i: dword A = channels 16gp + 4half + i, dword B = those */ \
+      /* + 8; the swap gives half 0 (A, A of half 1) and half 1 (B of half 0, B): channels 8G .. 8G + 7 of the pixel    */ \
+      _Pragma("unroll") for (int gp = 0; gp < 2; ++gp) {                                        \
+        unsigned da = 0u, db = 0u;                                                              \
+        _Pragma("unroll") for (int i = 0; i < 4; ++i) {                                         \
+          const float ta = (acc[8 * gp + i] + sbias[m * 32 + 16 * gp + 4 * half + i]) * a.q_inv; \
+          const float tb = (acc[8 * gp + 4 + i] + sbias[m * 32 + 16 * gp + 8 + 4 * half + i]) * a.q_inv; \
+          da |= (unsigned)(sx_q8_round(ta) & 255) << (8 * i);                                   \
+          db |= (unsigned)(sx_q8_round(tb) & 255) << (8 * i);                                   \
+        }                                                                                       \
+        auto r1 = __builtin_amdgcn_permlane32_swap(da, db, false, false);                       \
+        const int G = 4 * m + 2 * gp + half;                                                    \
+        const unsigned off = (ox < a.Wo && row < last) ? (unsigned)((n * a.ps_hp + oy + 1) * a.ps_wp + ox + 1) * 64u + 8u * G : 0x80000000u; \
+        typedef unsigned sx_u32x2 __attribute__((ext_vector_type(2)));                          \
+        __builtin_amdgcn_raw_buffer_store_b64(sx_u32x2{r1[0], r1[1]}, ry, off, 0, 0);           \
+      }                                                                                         \
+    } else if constexpr (PSO) {                                                                 \
       /* PS output: lane = position, registers = channels 32m + 8g + 4half + i; a v_permlane32_swap pair leaves a */ \
       /* lane with the 8 channels of one unit (as fdet_conv3x3_ps.hip): two 16-byte stores per group pair          */ \
       _Pragma("unroll") for (int gp = 0; gp < 2; ++gp) {                                        \
@@ -903,6 +940,37 @@ int stem_x3_fwd_ps(const void* xin, const float* w, const float* bias, void* y_p
     else if (p16) hipLaunchKernelGGL((k_stem_fwd_x3_pipe<true, true>), dim3(nblk, 1), dim3(256), ldsb, st, a);
     else hipLaunchKernelGGL((k_stem_fwd_x3_pipe<true, false>), dim3(nblk, 1), dim3(256), ldsb, st, a);
     if (int rc = check_launch("fdet_stem_fwd_ps")) return rc;
+  }
+  return 0;
+}
+
+// Int8 inference: the uint8-frame stem with the quantised output (k_stem_fwd_x3_pipe<.., Q8>).  q: int8 [N][Ho+2][Wo+2][64];
+// chunks as stem_x3_fwd_ps (the tensor is under 2^31 bytes, so its 32-bit offsets hold whatever the chunk)
+bool stem_x3_fwd_q8_ok(int N, int F, int H, int W) {
+  if (!stem_x3_fwd_ps_ok(N, F, H, W)) return false;
+  const int Ho = (H + 4 - 10) / 8 + 1, Wo = (W + 4 - 10) / 8 + 1;
+  return (unsigned long long)N * (Ho + 2) * (Wo + 2) * 64 < (1ull << 31);
+}
+
+int stem_x3_fwd_q8(const unsigned char* frames, const float* w, const float* bias, float q_inv, signed char* q, int N, int F, int H,
+                   int W, hipStream_t st) {
+  if (!stem_x3_fwd_q8_ok(N, F, H, W)) return fail(FDET_EINVAL, "stem_fwd_q8: unsupported shape (F=%d, %dx%d, N=%d)", F, H, W, N);
+  const int Ho = (H + 4 - 10) / 8 + 1, Wo = (W + 4 - 10) / 8 + 1;
+  const int img = (Ho + 2) * (Wo + 2) * 4;                 // 16-byte units per output image
+  const int chunk = stem_x3_chunk(F, H, W, img);
+  const size_t ldsb = (size_t)NROW * RL * 2 * 2 * 2 + 256 + 1024;      // tiles, bias, the uint8 table
+  { if (int rc_ = set_lds_attr((const void*)k_stem_fwd_x3_pipe<true, false, true, true>, ldsb, __func__)) return rc_; }
+  for (int n0 = 0; n0 < N; n0 += chunk) {
+    StemX3Args a{};
+    a.x = reinterpret_cast<const float*>(frames + (size_t)n0 * CIN * H * W);
+    a.w = w; a.bias = bias; a.y = reinterpret_cast<float*>(q + (size_t)n0 * img * 16);
+    a.N = std::min(chunk, N - n0); a.F = F; a.H = H; a.W = W;
+    a.Ho = Ho; a.Wo = Wo; a.nrows = a.N * Ho;
+    a.ps_hp = Ho + 2; a.ps_wp = Wo + 2; a.ps_img = img; a.q_inv = q_inv;
+    const int nblk = a.nrows < 256 ? a.nrows : 256;
+    stem_note_route(STEM_X3_PIPE, STEM_PASS_FWD, false, true, false, nblk, a.nrows);
+    hipLaunchKernelGGL((k_stem_fwd_x3_pipe<true, false, true, true>), dim3(nblk, 1), dim3(256), ldsb, st, a);
+    if (int rc = check_launch("fdet_stem_fwd_q8_u8")) return rc;
   }
   return 0;
 }

@@ -1489,3 +1489,84 @@ def q8_conv3x3(x: Q8Tensor, wpk: torch.Tensor, bias: torch.Tensor, mul: torch.Te
     check(lib().fdet_q8_conv3x3(x.data, ptr(wpk, I8), ptr(bias, torch.int32), ptr(mul), skip.data if skip is not None else None,
                                 float(skip_mul), y.data, Nn, C, H, W, int(bool(pool)), float(slope), stream()), "fdet_q8_conv3x3")
     return y
+
+
+def q8_chain_supported(C: int, H: int, W: int) -> bool:
+    """fdet_q8_chain runs maps of this shape: 64 channels, 1 <= H, W <= 16."""
+    return bool(lib().fdet_q8_chain_supported(int(C), int(H), int(W)))
+
+
+Q8_CHAIN_MAX_BLOCKS = 16
+
+
+class Q8ChainWeights:
+    """The host pointer arrays of fdet_q8_chain, built once: convs1 / convs2 = per block (wpk, bias, mul) of its first and
+    second conv (device tensors, kept alive here), skip_muls = per block the skip multiplier."""
+
+    def __init__(self, convs1: Sequence, convs2: Sequence, skip_muls: Sequence[float], C: int = 64):
+        import ctypes
+        nb = len(skip_muls)
+        if not (1 <= nb <= Q8_CHAIN_MAX_BLOCKS) or len(convs1) != nb or len(convs2) != nb:
+            raise ValueError(f"q8_chain: 1..{Q8_CHAIN_MAX_BLOCKS} blocks with two convs each, got {len(convs1)}, {len(convs2)}, {nb}")
+        for wpk, bias, mul in list(convs1) + list(convs2):
+            if wpk.numel() != 9 * C * C:
+                raise ValueError("q8_chain: packed weight size does not match the channel count")
+            _chk4(bias, (C,), "bias")
+            _chk4(mul, (C,), "mul")
+        self.C, self.nblocks = int(C), nb
+        self.tensors = (list(convs1), list(convs2))
+        self.arrays = tuple(_ptr_array([c[i] for c in cs], dt) for cs in (convs1, convs2)
+                            for i, dt in ((0, I8), (1, torch.int32), (2, F32)))
+        self.skip_mul = (ctypes.c_float * nb)(*[float(v) for v in skip_muls])
+
+
+def q8_chain(x: Q8Tensor, weights: Q8ChainWeights, outs: Optional[Sequence[Optional[Q8Tensor]]] = None,
+             out_f32: Optional[torch.Tensor] = None, out_scale: float = 1.0, slope: float = 0.2) -> None:
+    """The blocks of `weights` on x in one launch (fdet_q8_chain).  outs: per block a Q8Tensor of x's shape or None;
+    out_f32: fp32 (N,C,H,W) = float(last block) * out_scale.  One of outs[-1] and out_f32 is needed."""
+    if not isinstance(x, Q8Tensor):
+        raise ValueError("q8_chain: x must be a Q8Tensor")
+    if not isinstance(weights, Q8ChainWeights):
+        raise ValueError("q8_chain: weights must be a Q8ChainWeights")
+    Nn, C, H, W = x.shape
+    nb = weights.nblocks
+    if C != weights.C:
+        raise ValueError(f"q8_chain: the weights are for {weights.C} channels, x has {C}")
+    h_out = None
+    if outs is not None:
+        if len(outs) != nb:
+            raise ValueError(f"q8_chain: outs needs {nb} entries (None where a block's output is not wanted)")
+        import ctypes
+        for t in outs:
+            if t is not None:
+                _q8_same(t, x.shape, "q8_chain: out")
+        h_out = (ctypes.c_void_p * nb)(*[None if t is None else t.data for t in outs])
+    if out_f32 is not None:
+        _chk4(out_f32, x.shape, "q8_chain: out_f32")
+    if out_f32 is None and (outs is None or outs[-1] is None):
+        raise ValueError("q8_chain: the last block needs an output (outs[-1] or out_f32)")
+    w1, b1, m1, w2, b2, m2 = weights.arrays
+    check(lib().fdet_q8_chain(x.data, w1, b1, m1, w2, b2, m2, weights.skip_mul, h_out, ptr(out_f32), float(out_scale), nb,
+                              Nn, C, H, W, float(slope), stream()), "fdet_q8_chain")
+
+
+def stem_fwd_q8_ok(N_, cin, F_, H, W, k, stride, pad) -> bool:
+    """fdet_stem_fwd_q8_u8 accepts N images of this shape (fdet_stem_fwd_q8_ok)."""
+    return bool(lib().fdet_stem_fwd_q8_ok(int(N_), int(cin), int(F_), int(H), int(W), int(k), int(stride), int(pad)))
+
+
+def stem_fwd_q8_u8(frames: torch.Tensor, w: torch.Tensor, bias: torch.Tensor, scale: float, out: Q8Tensor, k: int = 10,
+                   stride: int = 8, pad: int = 2) -> Q8Tensor:
+    """uint8 frames (N,3,H,W) -> the stem's output quantised with `scale`, in `out` (real pixels only): the bytes of
+    u8_to_f32_norm -> stem_fwd(x3=True) -> q8_quantize."""
+    if frames.dim() != 4 or frames.dtype != torch.uint8:
+        raise ValueError("stem_fwd_q8_u8: expected uint8 frames (N,3,H,W)")
+    Nn, cin, H, W = frames.shape
+    F_ = w.shape[0]
+    _chk4(w, (F_, cin, k, k), "w")
+    _chk4(bias, (F_,), "bias")
+    Ho, Wo = (H + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1
+    _q8_same(out, (Nn, F_, Ho, Wo), "stem_fwd_q8_u8: out")
+    check(lib().fdet_stem_fwd_q8_u8(ptr(frames, torch.uint8), ptr(w), ptr(bias), float(scale), out.data, Nn, cin, F_, H, W, k,
+                                    stride, pad, stream()), "fdet_stem_fwd_q8_u8")
+    return out

@@ -5,12 +5,14 @@
     rows, counts = m8.reduce_bounding_boxes.forward_batch(m8.forward_frames(frames))
 
 The residual trunk (every 3x3 conv, both LeakyReLUs, the skip add and the 2x2 max-pool) runs on the integer matrix cores
-(fdet_q8_conv3x3); the stem and the head keep their float kernels.  The reference has no quantised path (its deployment
-tools are pruner.py and the ONNX / TorchScript exports); the arithmetic is this project's own contract, restated in numpy by
-tests/q8_cpu_ref.py, and the kernels equal that restatement bit for bit.
+(fdet_q8_conv3x3; the un-pooled blocks at the end as one fdet_q8_chain launch); the head keeps its float kernel, and the
+stem reads uint8 frames and writes the quantised layout itself (fdet_stem_fwd_q8_u8) where it takes the shape.  The
+reference has no quantised path (its deployment tools are pruner.py and the ONNX / TorchScript exports); the arithmetic is
+this project's own contract, restated in numpy by tests/q8_cpu_ref.py, and the kernels equal that restatement bit for bit.
 """
 from __future__ import annotations
 
+import os
 from typing import Iterable, List, Optional, Sequence
 
 import numpy as np
@@ -22,6 +24,12 @@ from ._native import FdetError
 F32 = torch.float32
 NPF = np.float32
 METHODS = ("absmax", "percentile", "explicit")
+
+# Defaults of the two int8 paths that replace several launches by one (FDET_Q8_CHAIN / FDET_Q8_STEM = "auto"): on only where
+# tools/q8_throughput.py measured the new path faster than the launches it replaces by more than the run-to-run spread
+# (profiles/r15_q8_chain.json); "1" forces a path wherever its kernel takes the shape, "0" the launches.
+CHAIN_MEASURED_FASTER = True
+STEM_Q8_MEASURED_FASTER = True
 
 
 # ---------------------------------------------------------------------------------------------------------- scales
@@ -187,8 +195,10 @@ class _Q8Conv:
 # ---------------------------------------------------------------------------------------------------------- the model
 class Int8PoolResnet:
     """A trained PoolResnet with its residual trunk in int8: existing stem -> quantise -> 2 x blocks int8 convs ->
-    dequantise -> existing head.  Inference only; weights and scales are those at construction.  It offers what the rest of
-    the package asks of a model (TiledDetector, DetectionEvaluator, GraphedPredict, render / tracking / chips)."""
+    dequantise -> existing head; or, where switched on (FDET_Q8_STEM / FDET_Q8_CHAIN, `counters`), the quantising stem on
+    the uint8 frames and the un-pooled tail of the trunk as one launch that also dequantises -- the same bytes.  Inference
+    only; weights and scales are those at construction.  It offers what the rest of the package asks of a model
+    (TiledDetector, DetectionEvaluator, GraphedPredict, render / tracking / chips)."""
 
     training = False
 
@@ -233,6 +243,20 @@ class Int8PoolResnet:
         self.head_b = model.out.bias.detach().to(F32).contiguous().clone()
         g = self.geo
         self._stem_x3 = hp.x3_supported(F_, F_) and hp.stem_x3_supported(g.in_ch, g.W, g.stem_k, g.stem_s, g.stem_p)
+        # the maximal run of un-pooled blocks at the end of the trunk: one fdet_q8_chain launch where the kernel takes the map
+        # (64 channels, at most 16 x 16, 1..16 blocks); its host pointer arrays are built here, once
+        self.chain = os.environ.get("FDET_Q8_CHAIN", "auto")          # "0" launch by launch, "1" the chain wherever it runs, else measured
+        self.stem_q8 = os.environ.get("FDET_Q8_STEM", "auto")         # "0" float stem + quantise, "1" the quantising stem wherever it runs
+        self.counters = {"chain": 0, "layers": 0, "stem_q8": 0, "stem_f32": 0}
+        first = nb
+        while first > 0 and self.lv[first - 1][1] != 2:
+            first -= 1
+        self._chain_first, self._chain_w = nb, None
+        if first < nb and nb - first <= hp.Q8_CHAIN_MAX_BLOCKS and hp.q8_chain_supported(F_, self.lv[first][0], self.lv[first][0]):
+            tail = self.blocks[first:]
+            self._chain_first = first
+            self._chain_w = hp.Q8ChainWeights([(c1.wpk, c1.bias, c1.mul) for c1, _, _ in tail],
+                                              [(c2.wpk, c2.bias, c2.mul) for _, c2, _ in tail], [sm for _, _, sm in tail], F_)
         self._ws = None
         self._pool = {}                                    # (N,C,H,W) -> free Q8Tensors; kept for the life of the model
         self.timer = None                                  # a convstack.KernelTimer: per-kernel times (tools/q8_throughput.py)
@@ -259,7 +283,21 @@ class Int8PoolResnet:
         return _NOSPAN if self.timer is None else self.timer.span(f"{kind}@{h}x{h}", flops, nbytes)
 
     # ------------------------------------------------------------------ forward
-    def _forward_f32(self, x: torch.Tensor, trace: Optional[dict] = None) -> torch.Tensor:
+    def chain_on(self) -> bool:
+        """The un-pooled tail runs as one fdet_q8_chain launch."""
+        if self._chain_w is None or self.chain == "0":
+            return False
+        return self.chain == "1" or CHAIN_MEASURED_FASTER
+
+    def stem_q8_on(self, N: int) -> bool:
+        """uint8 frames at the model resolution go through the quantising stem (fdet_stem_fwd_q8_u8)."""
+        g = self.geo
+        if self.stem_q8 == "0" or not (self.stem_q8 == "1" or STEM_Q8_MEASURED_FASTER):
+            return False
+        return hp.stem_fwd_q8_ok(N, g.in_ch, self.filters, g.H, g.W, g.stem_k, g.stem_s, g.stem_p)
+
+    def _stem_f32(self, x: torch.Tensor, trace: Optional[dict] = None) -> hp.Q8Tensor:
+        """fp32 images in [0,1] -> float stem -> quantise."""
         g, F_ = self.geo, self.filters
         if not x.is_cuda:
             raise FdetError("Int8PoolResnet runs on the GPU only (no CPU fallback): move the input to cuda")
@@ -275,13 +313,34 @@ class Int8PoolResnet:
         hf = torch.empty(N, F_, h0, h0, dtype=F32, device=dev)
         with self._t("stem_fwd", h0):
             hp.stem_fwd(x, self.stem_w, self.stem_b, hf, self._ws, g.stem_k, g.stem_s, g.stem_p, x3=self._stem_x3)
-        s_h = self.qparams.s_h
         h = self._take(N, h0, h0)
         with self._t("q8_quantize", h0, 0.0, 5.0 * hf.numel()):
-            hp.q8_quantize(hf, float(s_h[0]), out=h)
+            hp.q8_quantize(hf, float(self.qparams.s_h[0]), out=h)
+        self.counters["stem_f32"] += 1
         if trace is not None:
-            trace["stem"], trace["blocks"] = hf, []
-        for k, (hk, pool) in enumerate(self.lv):
+            trace["stem"] = hf
+        return h
+
+    def _stem_u8(self, frames: torch.Tensor) -> hp.Q8Tensor:
+        """uint8 frames at the model resolution -> the quantising stem: no fp32 image, no fp32 stem output."""
+        g = self.geo
+        N, h0 = frames.shape[0], self.h0
+        h = self._take(N, h0, h0)
+        with self._t("stem_fwd_q8", h0, 0.0, float(frames.numel()) + N * self.filters * h0 * h0):
+            hp.stem_fwd_q8_u8(frames, self.stem_w, self.stem_b, float(self.qparams.s_h[0]), h, g.stem_k, g.stem_s, g.stem_p)
+        self.counters["stem_q8"] += 1
+        return h
+
+    def _trunk(self, h: hp.Q8Tensor, trace: Optional[dict] = None) -> torch.Tensor:
+        """The quantised stem output (taken from the pool; given back here) -> the (N,5,S,S) maps."""
+        g, F_, dev = self.geo, self.filters, self.device
+        N = h.shape[0]
+        s_h = self.qparams.s_h
+        if trace is not None:
+            trace["blocks"] = []
+        chain = self.chain_on()
+        nlayer = self._chain_first if chain else len(self.lv)
+        for k, (hk, pool) in enumerate(self.lv[:nlayer]):
             c1, c2, skip_mul = self.blocks[k]
             flops = 2.0 * N * F_ * F_ * 9 * hk * hk
             a = self._take(N, hk, hk)
@@ -297,8 +356,19 @@ class Int8PoolResnet:
                 trace["blocks"].append(h.nchw())
         hl = h.shape[2]
         hd = torch.empty(N, F_, hl, hl, dtype=F32, device=dev)
-        with self._t("q8_dequantize", hl, 0.0, 5.0 * hd.numel()):
-            hp.q8_dequantize(h, float(s_h[-1]), out=hd)
+        if chain:
+            nb = self._chain_w.nblocks
+            outs = [self._take(N, hl, hl) for _ in range(nb)] if trace is not None else None
+            with self._t("q8_chain", hl, 2.0 * nb * 2.0 * N * F_ * F_ * 9 * hl * hl, 5.0 * hd.numel()):
+                hp.q8_chain(h, self._chain_w, outs=outs, out_f32=hd, out_scale=float(s_h[-1]), slope=self.slope)
+            for t in outs or ():
+                trace["blocks"].append(t.nchw())
+                self._give(t)
+            self.counters["chain"] += 1
+        else:
+            with self._t("q8_dequantize", hl, 0.0, 5.0 * hd.numel()):
+                hp.q8_dequantize(h, float(s_h[-1]), out=hd)
+            self.counters["layers"] += 1
         self._give(h)
         y = torch.empty(N, 5, g.S, g.S, dtype=F32, device=dev)
         with self._t("head_fwd", hl):
@@ -307,9 +377,20 @@ class Int8PoolResnet:
             trace["y"] = y
         return y
 
+    def _forward_f32(self, x: torch.Tensor, trace: Optional[dict] = None) -> torch.Tensor:
+        return self._trunk(self._stem_f32(x, trace), trace)
+
     @torch.no_grad()
     def forward_frames(self, x: torch.Tensor) -> torch.Tensor:
-        """frames (uint8 or float, any size) -> the (N,5,S,S) maps, as BaseModel.forward_frames."""
+        """frames (uint8 or float, any size) -> the (N,5,S,S) maps, as BaseModel.forward_frames.  uint8 frames on the GPU
+        that are already at the model resolution go to the quantising stem as they are (where it is switched on and takes
+        the shape): no `/ 255` pass, no fp32 stem output, no quantise launch, the same bytes."""
+        g = self.geo
+        if x.dim() == 3:
+            x = x.unsqueeze(0)
+        if (x.is_cuda and x.dtype == torch.uint8 and x.dim() == 4 and tuple(x.shape[1:]) == (g.in_ch, g.H, g.W)
+                and self.stem_q8_on(x.shape[0])):
+            return self._trunk(self._stem_u8(x.contiguous()))
         return self._forward_f32(self._preprocess(x))
 
     @torch.no_grad()

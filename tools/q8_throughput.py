@@ -1,22 +1,29 @@
 """Inference throughput of the int8 post-training-quantised PoolResnet beside the two float modes.
 
-    python tools/q8_throughput.py [--images 256] [--launches 100] [--calls 10] [--out profiles/r13_q8.json]
+    python tools/q8_throughput.py [--images 256] [--launches 100] [--calls 10] [--out profiles/r15_q8_chain.json]
 
 Workload: the inference leg's -- --images uint8 480x480 frames on the device (the three stored frames of
 tests/golden/g6_trained_small.npz, repeated) through the medium PoolResnet (64 filters, the trained weights of
 tests/golden/g16_trained_medium.npz) to boxes: `reduce_bounding_boxes.forward_batch(model.forward_frames(frames))`.
-Three models in ONE process, every one warmed up, alternated sample by sample; a sample is --calls back-to-back calls between
-two device events (about 10 ms of work), reported per call; median / min / max and the 5th / 95th percentile over --launches
-samples (about a second of timed work per mode):
+Six models in ONE process, every one warmed up, alternated sample by sample; a sample is --calls back-to-back calls between
+two device events, reported per call; median / min / max, the 5th / 95th percentile and their distance (`spread_ms`) over
+--launches samples:
 
-  bf16x3        the default engine (three bf16 MFMA passes)
-  precision16   engine.set_precision("bf16") (one bf16 pass)
-  int8          quantize.Int8PoolResnet, calibrated (abs-max) on the first 16 frames
+  bf16x3            the default engine (three bf16 MFMA passes)
+  precision16       engine.set_precision("bf16") (one bf16 pass)
+  int8-layers       quantize.Int8PoolResnet, calibrated (abs-max) on the first 16 frames, FDET_Q8_CHAIN=0 FDET_Q8_STEM=0: the
+                    float stem, a quantise launch, twenty conv launches, a dequantise launch (the baseline of the two below)
+  int8-chain        the sixteen 15x15 convs and the dequantise as one fdet_q8_chain launch
+  int8-chain+stem   and the quantising stem on the uint8 frames (fdet_stem_fwd_q8_u8)
+  int8              the model as constructed with no switch set (the measured defaults)
 
 Then, in a second phase with a KernelTimer attached (device events around every kernel class, so launch gaps inside a class
-count as its time), the per-kernel times of the int8 path and of precision16, and from them the 20-conv trunk alone in both
-modes.  `int8_trunk_floor_share` is the trunk's MACs (119 GMAC at 256 images) over the dense int8 MFMA peak (2 x the 2.5 PF
-bf16 peak = 2.5e15 MAC/s) over the measured trunk time.  Prints one JSON line and, with --out, writes it.
+count as its time), the per-kernel times of the three int8 modes and of precision16, and from them per class: the 15x15 tail
+(sixteen launches plus dequantise against the chain), the stem (stem plus quantise against the quantising stem; the `/ 255`
+pass that the float stem needs before it is counted in the end-to-end times only) and the 20-conv trunk.  `*_floor_share` is
+a class's MACs over the dense int8 MFMA peak (2 x the 2.5 PF bf16 peak = 2.5e15 MAC/s) over its measured time.  `faster` says
+for each new path whether it beat what it replaces by more than the larger of the two spreads: the rule of its default
+(quantize.CHAIN_MEASURED_FASTER / STEM_Q8_MEASURED_FASTER).  Prints one JSON line and, with --out, writes it.
 """
 import argparse
 import json
@@ -61,17 +68,29 @@ def main(argv=None):
             m.engine.set_precision("bf16")
         return m
     m32, m16 = build(False), build(True)
-    m8 = Int8PoolResnet(m32, calibrate(m32, [frames[:16]]))
-    models = {"bf16x3": m32, "precision16": m16, "int8": m8}
+    qp = calibrate(m32, [frames[:16]])
+
+    def build8(chain, stem):
+        m = Int8PoolResnet(m32, qp)
+        if chain is not None:
+            m.chain, m.stem_q8 = chain, stem                  # (the switches FDET_Q8_CHAIN / FDET_Q8_STEM set at construction)
+        return m
+    int8 = {"int8-layers": build8("0", "0"), "int8-chain": build8("1", "0"), "int8-chain+stem": build8("1", "1"),
+            "int8": build8(None, None)}
+    models = {"bf16x3": m32, "precision16": m16, **int8}
 
     def run(m):
         with torch.no_grad():
             return m.reduce_bounding_boxes.forward_batch(m.forward_frames(frames))
-    boxes = {}
+    boxes, maps = {}, {}
     for k, m in models.items():
         for _ in range(args.warmup):
             rows, counts = run(m)
         boxes[k] = int(counts.sum())
+        if k in int8:
+            with torch.no_grad():
+                maps[k] = m.forward_frames(frames)
+    identical = all(torch.equal(v, maps["int8-layers"]) for v in maps.values())
     torch.cuda.synchronize()
     ms = {k: [] for k in models}
     for _ in range(args.launches):
@@ -86,8 +105,9 @@ def main(argv=None):
 
     def stats(v):
         a = np.sort(np.asarray(v))
+        p05, p95 = float(np.percentile(a, 5)), float(np.percentile(a, 95))
         return {"median_ms": round(float(np.median(a)), 4), "min_ms": round(float(a[0]), 4), "max_ms": round(float(a[-1]), 4),
-                "p05_ms": round(float(np.percentile(a, 5)), 4), "p95_ms": round(float(np.percentile(a, 95)), 4)}
+                "p05_ms": round(p05, 4), "p95_ms": round(p95, 4), "spread_ms": round(p95 - p05, 4)}
 
     # per-kernel times (a phase of its own: the events slow the host side down a little)
     def kernel_times(m, holder):
@@ -98,23 +118,42 @@ def main(argv=None):
         holder.timer = None
         return {name: {"launches_per_call": cnt // args.kernel_runs, "ms_per_call": round(total / args.kernel_runs, 4)}
                 for name, (cnt, total, _, _) in sorted(s.items())}
-    k8 = kernel_times(m8, m8)
+    k8 = {k: kernel_times(m, m) for k, m in int8.items() if k != "int8"}
     k16 = kernel_times(m16, m16.engine)
-    trunk8 = sum(v["ms_per_call"] for k, v in k8.items() if k.startswith("q8_conv3x3"))
+
+    def cls(ks, names):
+        return round(sum(v["ms_per_call"] for k, v in ks.items() if k.split("@")[0] in names), 4)
+    at15 = {k: {n_: v for n_, v in ks.items() if n_.endswith("@15x15")} for k, ks in k8.items()}
+    tail = {"int8-layers": cls(at15["int8-layers"], ("q8_conv3x3", "q8_conv3x3_skip", "q8_dequantize")),
+            "int8-chain": cls(at15["int8-chain"], ("q8_chain",)), "int8-chain+stem": cls(at15["int8-chain+stem"], ("q8_chain",))}
+    stem = {"int8-layers": cls(k8["int8-layers"], ("stem_fwd", "q8_quantize")), "int8-chain": cls(k8["int8-chain"], ("stem_fwd", "q8_quantize")),
+            "int8-chain+stem": cls(k8["int8-chain+stem"], ("stem_fwd_q8",)), "precision16": cls(k16, ("stem_fwd",))}
+    trunk8 = {k: cls(ks, ("q8_conv3x3", "q8_conv3x3_skip", "q8_conv3x3_pool", "q8_chain", "q8_dequantize")) for k, ks in k8.items()}
     trunk16 = sum(v["ms_per_call"] for k, v in k16.items() if k.startswith(("conv3x3_fwd", "chain_fwd")))
     # (blocks 0 and 1 are pooled: 2 convs at 60x60, 2 at 30x30; then 8 blocks = 16 convs at 15x15)
+    tail_macs = float(n) * 64 * 64 * 9 * 16 * 15 * 15
     trunk_macs = float(n) * 64 * 64 * 9 * (2 * 60 * 60 + 2 * 30 * 30 + 16 * 15 * 15)
-    floor_ms = trunk_macs / INT8_PEAK_MACS * 1e3
+    floor_ms, tail_floor_ms = trunk_macs / INT8_PEAK_MACS * 1e3, tail_macs / INT8_PEAK_MACS * 1e3
     e2e = {k: stats(v) for k, v in ms.items()}
+
+    def faster(new, old):
+        gain = e2e[old]["median_ms"] - e2e[new]["median_ms"]
+        spread = max(e2e[old]["spread_ms"], e2e[new]["spread_ms"])
+        return {"gain_ms": round(gain, 4), "spread_ms": spread, "faster": bool(gain > spread)}
     res = {"tool": "q8_throughput", "device_name": torch.cuda.get_device_name(0), "images": n, "launches": args.launches,
            "calls_per_sample": args.calls, "end_to_end": e2e, "images_per_s": {k: round(n / (v["median_ms"] * 1e-3), 1) for k, v in e2e.items()},
-           "boxes": boxes,
-           "int8_over_precision16": round(e2e["precision16"]["median_ms"] / e2e["int8"]["median_ms"], 3),
-           "int8_over_bf16x3": round(e2e["bf16x3"]["median_ms"] / e2e["int8"]["median_ms"], 3),
+           "boxes": boxes, "int8_maps_identical": identical,
+           "counters": {k: dict(m.counters) for k, m in int8.items()},
+           "faster": {"chain": faster("int8-chain", "int8-layers"), "stem": faster("int8-chain+stem", "int8-chain")},
+           "over_precision16": {k: round(e2e["precision16"]["median_ms"] / e2e[k]["median_ms"], 3) for k in int8},
+           "over_bf16x3": {k: round(e2e["bf16x3"]["median_ms"] / e2e[k]["median_ms"], 3) for k in int8},
            "int8_kernels": k8, "precision16_kernels": k16,
-           "trunk_20_convs_ms": {"int8": round(trunk8, 4), "precision16": round(trunk16, 4)},
+           "tail_15x15_ms": tail, "stem_ms": stem,
+           "trunk_20_convs_ms": {**trunk8, "precision16": round(trunk16, 4)},
+           "tail_gmac": round(tail_macs / 1e9, 2), "int8_tail_floor_ms": round(tail_floor_ms, 4),
+           "int8_tail_floor_share": {k: round(tail_floor_ms / v, 4) if v > 0 else None for k, v in tail.items()},
            "trunk_gmac": round(trunk_macs / 1e9, 2), "int8_trunk_floor_ms": round(floor_ms, 4),
-           "int8_trunk_floor_share": round(floor_ms / trunk8, 4) if trunk8 > 0 else None}
+           "int8_trunk_floor_share": {k: round(floor_ms / v, 4) if v > 0 else None for k, v in trunk8.items()}}
     line = json.dumps(res)
     print(line)
     if args.out:
