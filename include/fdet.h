@@ -1101,6 +1101,86 @@ int fdet_jpeg_reconstruct(const int16_t* coef, size_t coef_count, const fdet_jpe
                           int n_images, uint8_t* workspace, size_t workspace_bytes, uint8_t* bank, size_t bank_bytes,
                           void* stream);
 
+/* ---- baseline JPEG encode out of the device image bank (csrc/fdet_jpeg_enc.hip) ------------
+ * The mirror image of the decoder, with the entropy coder on the device as well: only the compressed scan crosses to the
+ * host.  For an RGB image, quality 1..100 and subsampling 4:4:4 | 4:2:2 | 4:2:0 the file (header + byte-stuffed scan + EOI)
+ * equals, byte for byte, what PIL's Image.save(f, "JPEG", quality=q, subsampling=s) writes with libjpeg-turbo at its
+ * defaults (no optimize, no progressive, no restart markers, no EXIF / ICC / DPI).  The reference writes its annotated
+ * images with cv2.imwrite on the host (detect_images.py); tests/jpeg_enc_cpu_ref.py restates every rule below in numpy.
+ *
+ * Two phases, so that every buffer is sized exactly before anything is written into it:
+ *   plan   colour conversion, edge padding, downsampling, forward DCT, quantisation -> int16 coefficients; the exact bit
+ *          length of every block; a per-image exclusive scan -> every block's bit offset and every image's total
+ *   emit   (after the host has read the totals and sized the scan buffer) every block writes its bits at its offset
+ * Byte stuffing (FF -> FF 00) is left to the host, which does it while it assembles the file.
+ *
+ * Blocks are numbered in scan order per image: MCU by MCU, row-major; inside an MCU the hs * vs luma blocks row-major, then
+ * Cb, then Cr.  An image has mcus_x * mcus_y * (hs * vs + 2) blocks, the dummy blocks the MCU grid adds included. */
+#define FDET_JPEG_SUB_444 0        /* luma 1x1: PIL subsampling=0 */
+#define FDET_JPEG_SUB_422 1        /* luma 2x1: PIL subsampling=1 */
+#define FDET_JPEG_SUB_420 2        /* luma 2x2: PIL subsampling=2 */
+#define FDET_JPEG_ENC_MAX_BLOCK_BITS (11 + 16 + 63 * (16 + 10)) /* DC code + bits, 63 x (AC code + bits): no block is longer */
+#define FDET_JPEG_ENC_MAX_BLOCKS (1 << 20)  /* per image: its bit total stays below 2^31 */
+#define FDET_JPEG_ENC_HEADER_BYTES 623      /* SOI .. SOS of every file this encoder writes */
+
+/* HOST only, no HIP call, no mutable global.  out[0..63] luminance, out[64..127] chrominance table of `quality` (1..100) in
+ * natural (row-major) order: clamp((base * scale + 50) / 100, 1, 255) of the Annex K tables with scale = 5000 / quality
+ * below 50 and 200 - 2 * quality from 50 on. */
+int fdet_jpeg_quant_tables(int quality, uint16_t* out);
+
+/* HOST only.  SOI, APP0 (JFIF 1.01, density 1x1), DQT 0, DQT 1 (zigzag order), SOF0, DHT DC0 AC0 DC1 AC1 (the Annex K
+ * typical tables), SOS: everything in front of the scan, FDET_JPEG_ENC_HEADER_BYTES bytes.  *n receives that count;
+ * FDET_EWORKSPACE (and *n set) when capacity is smaller.  width, height 1..65535. */
+int fdet_jpeg_write_header(int width, int height, int quality, int subsampling, uint8_t* out, size_t capacity, size_t* n);
+
+/* One image of an encode call. */
+typedef struct fdet_jpeg_enc_desc {
+  int64_t bank_offset;             /* byte offset of pixel (0,0) in the bank, any alignment; height * width * 3 bytes */
+  int64_t block_base;              /* the image's first block in the workspace's arrays; images follow each other densely,
+                                      in call order: block_base[0] = 0, block_base[i + 1] = block_base[i] + n_blocks[i] */
+  int64_t scan_offset;             /* emit only: first byte of the image's stream in the scan buffer (multiple of 4) */
+  int32_t width, height;
+  int32_t mcus_x, mcus_y;          /* ceil(width / (8 hs)), ceil(height / (8 vs)) */
+  int32_t n_blocks;                /* mcus_x * mcus_y * (hs * vs + 2) <= FDET_JPEG_ENC_MAX_BLOCKS */
+  int32_t reserved;
+} fdet_jpeg_enc_desc;              /* 48 bytes */
+
+/* Workspace of a plan over total_blocks blocks of n_images images, in bytes; 0 for a bad count.  Layout, B = total_blocks:
+ *   int16  coef[B][64]   quantised coefficients in ZIGZAG order        at byte 0
+ *   uint32 bits[B]       bit length of the block's code                at byte 128 B
+ *   uint32 start[B]      bit offset of the block in its image's stream at byte 132 B
+ *   uint32 total[n]      bits of image i's stream, before padding      at byte 136 B */
+size_t fdet_jpeg_enc_ws_bytes(int64_t total_blocks, int n_images);
+
+/* Phase 1, three kernels on `stream`; bank is read only.  Per block of 8x8 samples:
+ *   colour   Y  = ( 19595 R + 38470 G +  7471 B + 32768) >> 16
+ *            Cb = (-11059 R - 21709 G + 32768 B + (128 << 16) + 32767) >> 16
+ *            Cr = ( 32768 R - 27439 G -  5329 B + (128 << 16) + 32767) >> 16
+ *   padding  a sample column past the image reads the last column; a row past it the last row, except that a 4:2:0
+ *            chroma row past ceil(height / 2) - 1 repeats THAT downsampled row (libjpeg pads after downsampling)
+ *   chroma   4:2:0 (a + b + c + d + 1 + (x & 1)) >> 2, 4:2:2 (a + b + (x & 1)) >> 1, x the output column
+ *   FDCT     libjpeg's jpeg_fdct_islow on sample - 128 (13-bit constants, 2 pass-1 bits, rows then columns)
+ *   quantise sign(x) * ((|x| + (d >> 1)) / d), d = 8 * q[k]
+ *   dummy    a luma block outside ceil(width / 8) x ceil(height / 8): all AC zero, DC that of the nearest preceding real block
+ *            of its MCU
+ *   bits     Annex K typical Huffman tables; the DC difference against the previous block of the component in scan order
+ * descs (DEVICE) / h_descs (HOST copy, validated before anything is enqueued): a size outside 1..65535, an MCU grid that is
+ * not the size's, a block_base that does not continue the previous image, an image outside bank_bytes, a workspace smaller
+ * than fdet_jpeg_enc_ws_bytes, a quality outside 1..100 or n_images outside 1..65535 return FDET_EINVAL / FDET_EWORKSPACE. */
+int fdet_jpeg_enc_plan(const uint8_t* bank, size_t bank_bytes, const fdet_jpeg_enc_desc* descs,
+                       const fdet_jpeg_enc_desc* h_descs, int n_images, int quality, int subsampling, uint8_t* workspace,
+                       size_t workspace_bytes, void* stream);
+
+/* Phase 2, one kernel on `stream`.  h_totals: HOST copy of the workspace's total[n] after the plan has finished.  scan
+ * (DEVICE, 4-byte aligned, scan_bytes): the caller has ZERO-FILLED it on `stream`; image i's stream takes the
+ * ceil(total[i] / 8) bytes from scan_offset[i], most significant bit first, the last byte padded with 1-bits, NOT byte-stuffed.
+ * A block stores the whole 32-bit words it owns and ORs (atomically) the partial words it shares with its neighbours.
+ * Validated on the host before the launch: every total within n_blocks * FDET_JPEG_ENC_MAX_BLOCK_BITS, every scan_offset a
+ * multiple of 4, the streams (each rounded up to 4 bytes) inside scan_bytes and not overlapping (ascending offsets). */
+int fdet_jpeg_enc_emit(const fdet_jpeg_enc_desc* descs, const fdet_jpeg_enc_desc* h_descs, const uint32_t* h_totals,
+                       int n_images, int subsampling, const uint8_t* workspace, size_t workspace_bytes, uint8_t* scan,
+                       size_t scan_bytes, void* stream);
+
 /* ---------------------------------------------------------------------------------------
  * Int8 inference: the PoolResnet residual trunk post-training-quantised, on the integer matrix cores
  * (v_mfma_i32_16x16x64_i8).  Inference only.  The reference has no such path (it ships pruner.py and ONNX / TorchScript

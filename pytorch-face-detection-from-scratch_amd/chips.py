@@ -182,13 +182,27 @@ class BestShots:
         chips = self.chips.reshape(self.n_seq * self.capacity, -1)[sel].cpu().numpy()
         return rec, chips.reshape(-1, self.size, self.size, 3)
 
-    def save(self, directory, fmt: str = "png") -> list:
-        """Write every non-empty entry to directory/seq<s>_track<id>.<fmt>; -> the paths."""
+    def save(self, directory, fmt: str = "png", encoder: str = "pil", quality: int = 75) -> list:
+        """Write every non-empty entry to directory/seq<s>_track<id>.<fmt>; -> the paths.  encoder="device" with a JPEG `fmt`:
+        the entries are encoded on the device (`render.save_images(encoder="device")`), the same files."""
+        if encoder == "device" and fmt.lower() in ("jpg", "jpeg"):
+            from .render import save_images
+            snap = self.snapshot()
+            s_idx, k_idx = np.nonzero(snap["id"])
+            os.makedirs(os.fspath(directory), exist_ok=True)
+            paths = [os.path.join(os.fspath(directory), f"seq{int(s)}_track{int(snap['id'][s, k])}.{fmt}") for s, k in zip(s_idx, k_idx)]
+            if paths:
+                table = np.zeros(len(paths), dtype=IMAGE_DTYPE)
+                table["offset"] = (s_idx * self.capacity + k_idx).astype(np.int64) * (self.size * self.size * 3)
+                table["h"] = table["w"] = self.size
+                save_images(DeviceImageBank(self.chips.reshape(-1), table), paths, encoder="device", quality=quality)
+            return paths
         from PIL import Image
         rec, chips = self.gallery()
         os.makedirs(os.fspath(directory), exist_ok=True)
+        settings = {} if int(quality) == 75 or fmt.lower() not in ("jpg", "jpeg") else {"quality": int(quality)}
         paths = []
         for r, c in zip(rec, chips):
             paths.append(os.path.join(os.fspath(directory), f"seq{int(r['seq'])}_track{int(r['id'])}.{fmt}"))
-            Image.fromarray(c).save(paths[-1])
+            Image.fromarray(c).save(paths[-1], **settings)
         return paths

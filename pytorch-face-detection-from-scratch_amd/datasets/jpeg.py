@@ -8,6 +8,12 @@ buffer.  The result is byte-identical to `bank_from_files` with PIL (libjpeg-tur
 
     bank = DeviceJpegDecoder("cuda").decode_files(paths)
 
+The other direction is `DeviceJpegEncoder` (csrc/fdet_jpeg_enc.hip): colour conversion, downsampling, forward
+DCT, quantisation AND the Huffman coding run on the device, so that only the compressed scan crosses to the host, which adds
+the header, stuffs the FF bytes and writes the file -- byte for byte what PIL's `Image.save(..., "JPEG")` writes.
+
+    files = DeviceJpegEncoder("cuda", quality=75, subsampling="4:2:0").encode(bank)      # List[bytes]
+
 A file outside the supported subset (progressive, CMYK, ... : `hotpath.JPEG_UNSUPPORTED`) or that is no JPEG at all (png,
 bmp) is decoded with PIL and copied into its slot; `decoder.fallbacks` lists those indices.  A corrupt or truncated JPEG
 raises `FdetError` naming the file.
@@ -189,3 +195,178 @@ class DeviceJpegDecoder:
                 self.chunks += 1
         finally:
             stream.synchronize()                             # nothing of this call is in flight when its buffers go
+
+
+class DeviceJpegEncoder:
+    """encode / encode_to_files: the images of a DeviceImageBank -> baseline JPEG files equal to PIL's
+    `Image.fromarray(a).save(f, "JPEG", quality=quality, subsampling=subsampling)` byte for byte (libjpeg-turbo at its defaults:
+    standard Huffman tables, no restart markers, JFIF header only).  Two launches per chunk of images: the plan (coefficients
+    and every block's exact bit length and offset; its per-image bit totals come back with one copy and one synchronise and
+    size the scan buffer) and the emit.  A chunk's plan workspace stays within `chunk_bytes` (an image larger than that is a
+    chunk of its own); the scans reach the host through one of two pinned staging buffers, each guarded by an event, so that
+    the host assembles the files of one chunk while the device works on the next."""
+
+    def __init__(self, device, quality: int = 75, subsampling: str = "4:2:0", chunk_bytes: int = 256 << 20):
+        self.device = torch.device(device)
+        self.quality = int(quality)
+        if not 1 <= self.quality <= 100:
+            raise ValueError(f"DeviceJpegEncoder: quality={quality} outside 1..100")
+        if subsampling not in hp.JPEG_SUBSAMPLINGS:
+            raise ValueError(f"DeviceJpegEncoder: subsampling must be one of {sorted(hp.JPEG_SUBSAMPLINGS)}, got {subsampling!r}")
+        self.subsampling = subsampling
+        self.sub = hp.JPEG_SUBSAMPLINGS[subsampling]
+        self.chunk_bytes = max(1, int(chunk_bytes))
+        self.chunks = 0                                      # plan / emit launch pairs of the last call
+        self.scan_bytes = 0                                  # compressed bytes the last call copied to the host
+
+    # -- geometry ------------------------------------------------------------------------------------------------------
+    def _descs(self, bank: DeviceImageBank, idx: np.ndarray) -> np.ndarray:
+        hs, vs = (1, 1) if self.sub == 0 else (2, 1) if self.sub == 1 else (2, 2)
+        t = bank.table[idx]
+        d = np.zeros(len(idx), dtype=hp.JPEG_ENC_DESC_DTYPE)
+        d["bank_offset"], d["width"], d["height"] = t["offset"], t["w"], t["h"]
+        d["mcus_x"] = (t["w"].astype(np.int64) + 8 * hs - 1) // (8 * hs)
+        d["mcus_y"] = (t["h"].astype(np.int64) + 8 * vs - 1) // (8 * vs)
+        nb = d["mcus_x"].astype(np.int64) * d["mcus_y"] * (hs * vs + 2)
+        if nb.size and int(nb.max()) > hp.JPEG_ENC_MAX_BLOCKS:
+            k = int(nb.argmax())
+            raise FdetError(f"DeviceJpegEncoder: image {int(idx[k])} ({int(t['w'][k])}x{int(t['h'][k])}) has {int(nb[k])} blocks, "
+                            f"more than the {hp.JPEG_ENC_MAX_BLOCKS} one image may have")
+        d["n_blocks"] = nb
+        return d
+
+    def _chunks(self, descs: np.ndarray):
+        """-> [(first, last)) ranges of `descs`, each within chunk_bytes of plan workspace and the launch's image limit."""
+        out, first, fill = [], 0, 0
+        for k in range(len(descs)):
+            need = int(descs["n_blocks"][k]) * 136 + 4
+            if k > first and (fill + need > self.chunk_bytes or k - first >= MAX_IMAGES_PER_LAUNCH):
+                out.append((first, k))
+                first, fill = k, 0
+            fill += need
+        if len(descs) > first:
+            out.append((first, len(descs)))
+        return out
+
+    def _index(self, bank: DeviceImageBank, indices) -> np.ndarray:
+        a, b = bank.device, self.device                      # "cuda" names the current device: equal to any "cuda:k" here
+        if a.type != b.type or (a.index is not None and b.index is not None and a.index != b.index):
+            raise FdetError(f"DeviceJpegEncoder: the bank lives on {bank.device}, the encoder on {self.device}")
+        idx = np.arange(len(bank)) if indices is None else np.asarray(list(indices), dtype=np.int64).reshape(-1)
+        if idx.size and (idx.min() < 0 or idx.max() >= len(bank)):
+            raise IndexError(f"DeviceJpegEncoder: indices outside the bank of {len(bank)} images")
+        return idx
+
+    def _plan_chunk(self, bank: DeviceImageBank, descs: np.ndarray):
+        """Phase 1 of one chunk (descs: its records, block_base filled here) -> (d_descs, workspace, totals uint32 (n,))."""
+        dev = bank.device
+        n = len(descs)
+        nb = descs["n_blocks"].astype(np.int64)
+        descs["block_base"] = np.cumsum(nb) - nb
+        B = int(nb.sum())
+        workspace = torch.empty(hp.jpeg_enc_ws_bytes(B, n), dtype=torch.uint8, device=dev)
+        h = torch.from_numpy(descs.view(np.uint8)).pin_memory()
+        d_descs = h.to(dev, non_blocking=True)
+        hp.jpeg_enc_plan(bank.data, d_descs, descs, self.quality, self.sub, workspace)
+        h_totals = torch.empty(n * 4, dtype=torch.uint8).pin_memory()
+        h_totals.copy_(workspace[136 * B:136 * B + 4 * n], non_blocking=True)
+        torch.cuda.current_stream(dev).synchronize()         # the one synchronise of a chunk: its totals size the scan buffer
+        return d_descs, workspace, h_totals.numpy().view(np.uint32).copy()
+
+    # -- public --------------------------------------------------------------------------------------------------------
+    def plan_arrays(self, bank: DeviceImageBank, indices=None):
+        """The plan phase alone, for inspection -> per image (coef int16 (n_blocks, 64) in zigzag order, blocks in scan
+        order; bits uint32 (n_blocks,); start uint32 (n_blocks,); total bits)."""
+        idx = self._index(bank, indices)
+        descs = self._descs(bank, idx)
+        out = []
+        with torch.cuda.device(bank.device):
+            for first, last in self._chunks(descs):
+                part = descs[first:last].copy()
+                _d, ws, totals = self._plan_chunk(bank, part)
+                B = int(part["n_blocks"].sum())
+                host = ws.cpu().numpy()
+                coef = host[:128 * B].view(np.int16).reshape(B, 64)
+                bits = host[128 * B:132 * B].view(np.uint32)
+                start = host[132 * B:136 * B].view(np.uint32)
+                for k in range(len(part)):
+                    a, b = int(part["block_base"][k]), int(part["block_base"][k]) + int(part["n_blocks"][k])
+                    out.append((coef[a:b].copy(), bits[a:b].copy(), start[a:b].copy(), int(totals[k])))
+        return out
+
+    def encode(self, bank: DeviceImageBank, indices=None) -> List[bytes]:
+        """-> one complete JPEG file per image of `indices` (all of the bank when None), in that order."""
+        idx = self._index(bank, indices)
+        self.chunks, self.scan_bytes = 0, 0
+        if idx.size == 0:
+            return []
+        dev = bank.device
+        descs = self._descs(bank, idx)
+        headers = {}
+        out: List[bytes] = []
+
+        def assemble(job):
+            part, nbytes, staged, ev, _hold = job
+            ev.synchronize()                                 # the scans of this chunk are in its staging buffer
+            host = staged.numpy()
+            for k in range(len(part)):
+                w, h = int(part["width"][k]), int(part["height"][k])
+                if (w, h) not in headers:
+                    headers[(w, h)] = hp.jpeg_write_header(w, h, self.quality, self.sub)
+                o = int(part["scan_offset"][k])
+                out.append(headers[(w, h)] + host[o:o + int(nbytes[k])].tobytes().replace(b"\xff", b"\xff\x00") + b"\xff\xd9")
+
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream(dev)
+            stage = [None, None]                             # pinned staging, grown on demand
+            pending = None                                   # the chunk whose files the host has still to assemble
+            try:
+                for c, (first, last) in enumerate(self._chunks(descs)):
+                    part = descs[first:last].copy()
+                    d_descs, workspace, totals = self._plan_chunk(bank, part)
+                    limit = part["n_blocks"].astype(np.int64) * hp.JPEG_ENC_MAX_BLOCK_BITS
+                    if (totals < 1).any() or (totals.astype(np.int64) > limit).any():
+                        raise FdetError("DeviceJpegEncoder: the plan returned a bit total outside what its blocks can take")
+                    nbytes = (totals.astype(np.int64) + 7) // 8
+                    spans = (nbytes + 3) // 4 * 4            # every image's stream starts on a 4-byte boundary
+                    part["scan_offset"] = np.cumsum(spans) - spans
+                    size = int(spans.sum())
+                    scan = torch.empty(size, dtype=torch.uint8, device=dev)
+                    scan.zero_()                             # a memset on the stream: the emit ORs into shared words
+                    h = torch.from_numpy(part.view(np.uint8)).pin_memory()
+                    d_descs2 = h.to(dev, non_blocking=True)
+                    hp.jpeg_enc_emit(d_descs2, part, totals, self.sub, workspace, scan)
+                    s = c % 2
+                    if stage[s] is None or stage[s].numel() < size:
+                        stage[s] = torch.empty(size, dtype=torch.uint8).pin_memory()
+                    stage[s][:size].copy_(scan, non_blocking=True)
+                    ev = torch.cuda.Event()
+                    ev.record(stream)
+                    self.chunks += 1
+                    self.scan_bytes += int(nbytes.sum())
+                    if pending is not None:                  # assembled while the device emits and copies this chunk
+                        assemble(pending)
+                    pending = (part, nbytes, stage[s], ev, (h, d_descs, d_descs2))     # the descriptors live as long as the launch
+                if pending is not None:
+                    assemble(pending)
+            finally:
+                stream.synchronize()                         # nothing of this call is in flight when its buffers go
+        return out
+
+    def encode_to_files(self, bank: DeviceImageBank, paths: Sequence, threads: int = 16, indices=None) -> None:
+        """encode(bank, indices), file i written to paths[i] on at most 16 threads.  Parent directories are created."""
+        import os
+        paths = [os.fspath(p) for p in paths]
+        idx = self._index(bank, indices)
+        if len(paths) != len(idx):
+            raise ValueError(f"encode_to_files: {len(paths)} paths for {len(idx)} images")
+        for d in sorted({os.path.dirname(p) for p in paths}):
+            if d:
+                os.makedirs(d, exist_ok=True)
+        files = self.encode(bank, idx)
+
+        def write(job):
+            with open(job[1], "wb") as f:
+                f.write(job[0])
+        with ThreadPoolExecutor(max_workers=max(1, min(MAX_WORKERS, int(threads), len(paths) or 1))) as ex:
+            list(ex.map(write, zip(files, paths)))

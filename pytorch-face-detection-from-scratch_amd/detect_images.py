@@ -3,7 +3,8 @@
     python -m fdet_amd.detect_images --checkpoint CKPT --images DIR --out FILE [--model poolresnet --filters 128]
         [--tile 480 --overlap 0.25 --no-whole --edge-margin 0 --probability-threshold P --iou-threshold T --precision 16]
         [--flip --vote --min-votes N] [--draw DIR [--anonymize pixelate] [--blocks N] [--draw-format png|jpg] [--no-outline]]
-        [--chips DIR [--chip-size N] [--chip-margin F]] [--int8 [--calib DIR] [--calib-images N]]
+        [--chips DIR [--chip-size N] [--chip-margin F] [--chip-format png|jpg]] [--device-jpeg-encode] [--jpeg-quality Q]
+        [--int8 [--calib DIR] [--calib-images N]]
 
 The images under DIR (searched recursively: .jpg .jpeg .png .bmp) are decoded with PIL into a device image bank
 (`bank_from_files`; `--device-jpeg`: baseline JPEGs are reconstructed on the device instead, with the same bytes), `tiling.TiledDetector` runs the model on overlapping windows of each image (and on the whole image
@@ -18,7 +19,10 @@ fewer than N detections agree on.
 rendered on the device, chunk by chunk, from the bank the detector just read.
 `--chips DIR` also writes every detected face as a `--chip-size` x `--chip-size` crop (112) around its box widened by
 `--chip-margin` of its longer side (0.25), cut on the device (`chips.extract_chips`), to
-`DIR/<path relative to --images without its suffix>_<row>.png`.
+`DIR/<path relative to --images without its suffix>_<row>.png` (`--chip-format jpg`: `.jpg`).
+Where `--draw-format` or `--chip-format` is jpg, `--jpeg-quality Q` (75) sets the quality and `--device-jpeg-encode` has the
+files encoded on the device (`datasets/jpeg.py DeviceJpegEncoder`) instead of by PIL: the same bytes, but only
+the compressed scans are copied to the host.
 `--int8` (poolresnet) runs the residual trunk post-training-quantised on the integer matrix cores (`quantize.py`, DESIGN.md
 5j): the activation scales are calibrated first, with the float model, on the first `--calib-images` images (32) under
 `--calib DIR` (default: the input images), each resized whole to the model resolution.
@@ -129,11 +133,13 @@ def add_chip_arguments(ap, flag, what) -> None:
     ap.add_argument(flag, dest="chips_dir", default=None, metavar="DIR", help=what)
     ap.add_argument("--chip-size", type=int, default=None, help=f"with {flag}: side of a chip in pixels, 8..256 (112)")
     ap.add_argument("--chip-margin", type=float, default=None, help=f"with {flag}: margin as a share of the box's longer side, 0..1 (0.25)")
+    ap.add_argument("--chip-format", choices=("png", "jpg"), default=None, help=f"with {flag}: the files' format (png)")
 
 
 def check_chip_arguments(ap, args, flag) -> None:
     if args.chips_dir is None:
-        for name, given in (("--chip-size", args.chip_size is not None), ("--chip-margin", args.chip_margin is not None)):
+        for name, given in (("--chip-size", args.chip_size is not None), ("--chip-margin", args.chip_margin is not None),
+                            ("--chip-format", args.chip_format is not None)):
             if given:
                 ap.error(f"{name} needs {flag}")
     if args.chip_size is not None and not 8 <= args.chip_size <= 256:
@@ -142,6 +148,28 @@ def check_chip_arguments(ap, args, flag) -> None:
         ap.error("--chip-margin must be in 0..1")
     args.chip_size = 112 if args.chip_size is None else args.chip_size
     args.chip_margin = 0.25 if args.chip_margin is None else args.chip_margin
+
+
+def add_jpeg_encode_arguments(ap) -> None:
+    """How the JPEG files of --draw-format jpg / --chip-format jpg are written (shared with track_frames)."""
+    ap.add_argument("--device-jpeg-encode", action="store_true",
+                    help="write JPEG files with the device encoder (datasets/jpeg.py) instead of PIL; same bytes")
+    ap.add_argument("--jpeg-quality", type=int, default=None, help="quality of the JPEG files written, 1..100 (75)")
+
+
+def check_jpeg_encode_arguments(ap, args) -> None:
+    if args.draw_format != "jpg" and args.chip_format != "jpg":
+        for flag, given in (("--device-jpeg-encode", args.device_jpeg_encode), ("--jpeg-quality", args.jpeg_quality is not None)):
+            if given:
+                ap.error(f"{flag} needs --draw-format jpg or --chip-format jpg")
+    if args.jpeg_quality is not None and not 1 <= args.jpeg_quality <= 100:
+        ap.error("--jpeg-quality must be in 1..100")
+
+
+def jpeg_encode_options(args) -> dict:
+    """`render.save_images`' encoder options out of the parsed arguments."""
+    quality = getattr(args, "jpeg_quality", None)
+    return {"encoder": "device" if getattr(args, "device_jpeg_encode", False) else "pil", "quality": 75 if quality is None else quality}
 
 
 def main(argv=None):
@@ -160,10 +188,12 @@ def main(argv=None):
     ap.add_argument("--min-votes", type=int, default=1, help="with --vote: leave out boxes with fewer members than this")
     add_draw_arguments(ap)
     add_chip_arguments(ap, "--chips", "also write every detected face as a square crop under DIR")
+    add_jpeg_encode_arguments(ap)
     add_int8_arguments(ap)
     args = ap.parse_args(argv)
     check_int8_arguments(ap, args)
     check_draw_arguments(ap, args)
+    check_jpeg_encode_arguments(ap, args)
     check_chip_arguments(ap, args, "--chips")
     if args.min_votes < 1:
         ap.error("--min-votes must be >= 1")
@@ -227,14 +257,16 @@ def run(args):
             drawn = render_detections(bank, rows, counts, outline=not args.no_outline, anonymize=args.anonymize,
                                       blocks=8 if args.blocks is None else args.blocks)
             save_images(drawn, [(Path(args.draw) / os.path.relpath(p, root)).with_suffix("." + (args.draw_format or "png"))
-                                for p in chunk])
+                                for p in chunk], **jpeg_encode_options(args))
         if getattr(args, "chips_dir", None) is not None:
             from .chips import extract_chips
             from .render import save_images
             cs = extract_chips(bank, rows, counts, size=args.chip_size, margin=args.chip_margin)
             stems = [(Path(args.chips_dir) / os.path.relpath(p, root)).with_suffix("") for p in chunk]
             if len(cs):
-                save_images(cs.as_bank(), [f"{stems[i]}_{j}.png" for i in range(len(chunk)) for j in range(int(cs.offset[i + 1] - cs.offset[i]))])
+                ext = getattr(args, "chip_format", None) or "png"
+                save_images(cs.as_bank(), [f"{stems[i]}_{j}.{ext}" for i in range(len(chunk)) for j in range(int(cs.offset[i + 1] - cs.offset[i]))],
+                            **jpeg_encode_options(args))
         kmax = max(int(counts.max()), 1)
         all_rows.append(rows[:, :kmax].cpu())
         all_counts.append(counts.cpu())

@@ -594,6 +594,83 @@ def jpeg_reconstruct(coef: torch.Tensor, d_descs: torch.Tensor, h_descs, workspa
 
 
 # ------------------------------------------------------------------------------------------
+# Baseline JPEG encode (csrc/fdet_jpeg_enc.hip; datasets/jpeg.py DeviceJpegEncoder drives these)
+# ------------------------------------------------------------------------------------------
+JPEG_SUBSAMPLINGS = {"4:4:4": 0, "4:2:2": 1, "4:2:0": 2}     # FDET_JPEG_SUB_*: PIL's numbering
+JPEG_ENC_MAX_BLOCK_BITS = 11 + 16 + 63 * (16 + 10)
+JPEG_ENC_MAX_BLOCKS = 1 << 20
+JPEG_ENC_HEADER_BYTES = 623
+
+
+def _jpeg_enc_dtype():
+    import numpy as np
+    d = np.dtype([("bank_offset", "<i8"), ("block_base", "<i8"), ("scan_offset", "<i8"), ("width", "<i4"), ("height", "<i4"),
+                  ("mcus_x", "<i4"), ("mcus_y", "<i4"), ("n_blocks", "<i4"), ("reserved", "<i4")], align=True)   # fdet_jpeg_enc_desc
+    assert d.itemsize == 48
+    return d
+
+
+JPEG_ENC_DESC_DTYPE = _jpeg_enc_dtype()
+
+
+def jpeg_quant_tables(quality: int):
+    """fdet_jpeg_quant_tables (host only) -> uint16 (2, 64): luminance and chrominance table of `quality`, natural order."""
+    import numpy as np
+    out = np.zeros((2, 64), dtype=np.uint16)
+    check(lib().fdet_jpeg_quant_tables(int(quality), out.ctypes.data), "fdet_jpeg_quant_tables")
+    return out
+
+
+def jpeg_write_header(width: int, height: int, quality: int, subsampling: int) -> bytes:
+    """fdet_jpeg_write_header (host only, thread-safe) -> the bytes of a file in front of its scan (SOI .. SOS)."""
+    import ctypes
+    buf = ctypes.create_string_buffer(JPEG_ENC_HEADER_BYTES)
+    n = ctypes.c_size_t(0)
+    check(lib().fdet_jpeg_write_header(int(width), int(height), int(quality), int(subsampling), buf, JPEG_ENC_HEADER_BYTES,
+                                       ctypes.byref(n)), "fdet_jpeg_write_header")
+    return buf.raw[:n.value]
+
+
+def jpeg_enc_ws_bytes(total_blocks: int, n_images: int) -> int:
+    n = int(lib().fdet_jpeg_enc_ws_bytes(int(total_blocks), int(n_images)))
+    if n == 0:
+        raise N.FdetError(f"fdet_jpeg_enc_ws_bytes: no plan over {total_blocks} blocks of {n_images} images")
+    return n
+
+
+def _jpeg_enc_descs(who: str, d_descs: torch.Tensor, h_descs) -> None:
+    import numpy as np
+    if not isinstance(h_descs, np.ndarray) or h_descs.dtype != JPEG_ENC_DESC_DTYPE or h_descs.ndim != 1 or not h_descs.flags.c_contiguous:
+        raise ValueError(f"{who}: h_descs must be a contiguous (n,) record array of JPEG_ENC_DESC_DTYPE")
+    if d_descs.numel() != len(h_descs) * JPEG_ENC_DESC_DTYPE.itemsize:
+        raise ValueError(f"{who}: device and host copies of the descriptors differ in size")
+
+
+def jpeg_enc_plan(bank_data: torch.Tensor, d_descs: torch.Tensor, h_descs, quality: int, subsampling: int,
+                  workspace: torch.Tensor) -> None:
+    """fdet_jpeg_enc_plan: the images the descriptors name -> coefficients, block bit lengths, bit offsets and per-image bit
+    totals in `workspace` (layout: include/fdet.h), on the current stream.  Bad descriptors raise before anything runs."""
+    _jpeg_enc_descs("jpeg_enc_plan", d_descs, h_descs)
+    U8 = torch.uint8
+    check(lib().fdet_jpeg_enc_plan(ptr(bank_data, U8), bank_data.numel(), ptr(d_descs, U8), h_descs.ctypes.data, len(h_descs),
+                                   int(quality), int(subsampling), ptr(workspace, U8), workspace.numel(), stream()),
+          "fdet_jpeg_enc_plan")
+
+
+def jpeg_enc_emit(d_descs: torch.Tensor, h_descs, h_totals, subsampling: int, workspace: torch.Tensor, scan: torch.Tensor) -> None:
+    """fdet_jpeg_enc_emit: the planned blocks' bits -> `scan` (device uint8, zero-filled by the caller on the current stream),
+    image i at h_descs[i]["scan_offset"].  h_totals: the plan's per-image bit totals, read back by the caller (uint32 (n,))."""
+    import numpy as np
+    _jpeg_enc_descs("jpeg_enc_emit", d_descs, h_descs)
+    if not isinstance(h_totals, np.ndarray) or h_totals.dtype != np.uint32 or h_totals.shape != (len(h_descs),) or not h_totals.flags.c_contiguous:
+        raise ValueError("jpeg_enc_emit: h_totals must be a contiguous (n,) uint32 array")
+    U8 = torch.uint8
+    check(lib().fdet_jpeg_enc_emit(ptr(d_descs, U8), h_descs.ctypes.data, h_totals.ctypes.data, len(h_descs), int(subsampling),
+                                   ptr(workspace, U8), workspace.numel(), ptr(scan, U8), scan.numel(), stream()),
+          "fdet_jpeg_enc_emit")
+
+
+# ------------------------------------------------------------------------------------------
 # SSD detection math (datasets/WIDERFace/dataset_ssd.py, losses/SSDLoss.py, datasets/utils.py:8-92)
 # ------------------------------------------------------------------------------------------
 SSD_PATCH_SIZES = (60, 30, 15, 7)

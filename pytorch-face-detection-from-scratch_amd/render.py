@@ -65,20 +65,44 @@ def render_detections(bank: DeviceImageBank, rows: torch.Tensor, counts: torch.T
     return out
 
 
-def save_images(bank: DeviceImageBank, paths: Sequence, threads: int = 16) -> None:
+ENCODERS = ("pil", "device")
+JPEG_SUFFIXES = (".jpg", ".jpeg")
+
+
+def save_images(bank: DeviceImageBank, paths: Sequence, threads: int = 16, encoder: str = "pil", quality: int = 75,
+                subsampling: str = "4:2:0") -> None:
     """Write image i of `bank` to paths[i] with PIL, PNG or JPEG by the suffix, on at most 16 threads.  Parent directories
-    are created."""
-    from PIL import Image
+    are created.  encoder="device": the paths with a .jpg / .jpeg suffix are encoded on the device (datasets/jpeg.py
+    DeviceJpegEncoder: only the compressed scans cross to the host) with `quality` and `subsampling`; the files are the ones
+    PIL writes with those settings, byte for byte, and the defaults are PIL's.  Every other suffix still goes to PIL, and
+    encoder="pil" hands `quality` and `subsampling` to PIL for its JPEG files when they are not the defaults."""
+    if encoder not in ENCODERS:
+        raise ValueError(f"save_images: encoder must be 'pil' or 'device', got {encoder!r}")
     paths = [os.fspath(p) for p in paths]
     if len(paths) != len(bank):
         raise ValueError(f"save_images: {len(paths)} paths for a bank of {len(bank)} images")
     for d in sorted({os.path.dirname(p) for p in paths}):
         if d:
             os.makedirs(d, exist_ok=True)
-    arrays = bank.to_arrays()
+    rest = list(range(len(paths)))
+    if encoder == "device":
+        from .datasets.jpeg import DeviceJpegEncoder
+        jpeg = [i for i in rest if os.path.splitext(paths[i])[1].lower() in JPEG_SUFFIXES]
+        rest = [i for i in rest if os.path.splitext(paths[i])[1].lower() not in JPEG_SUFFIXES]
+        if jpeg:
+            DeviceJpegEncoder(bank.device, quality, subsampling).encode_to_files(bank, [paths[i] for i in jpeg], threads, indices=jpeg)
+    if not rest:
+        return
+    from PIL import Image
+    arrays = bank.to_arrays() if len(rest) == len(paths) else bank.to_arrays(rest)
+
+    settings = {}                                            # PIL's own defaults unless the caller chose others
+    if (int(quality), subsampling) != (75, "4:2:0"):
+        settings = {"quality": int(quality), "subsampling": subsampling}
 
     def save(job):
-        Image.fromarray(job[0]).save(job[1])
+        jpeg = os.path.splitext(job[1])[1].lower() in JPEG_SUFFIXES
+        Image.fromarray(job[0]).save(job[1], **(settings if jpeg else {}))
 
-    with ThreadPoolExecutor(max_workers=max(1, min(16, int(threads), len(paths) or 1))) as ex:
-        list(ex.map(save, zip(arrays, paths)))
+    with ThreadPoolExecutor(max_workers=max(1, min(16, int(threads), len(rest)))) as ex:
+        list(ex.map(save, zip(arrays, [paths[i] for i in rest])))

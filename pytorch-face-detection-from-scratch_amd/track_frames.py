@@ -3,7 +3,8 @@
     python -m fdet_amd.track_frames --checkpoint CKPT --frames DIR --out FILE [--model poolresnet --filters 128]
         [--tiled --tile 480 --overlap 0.25] [--iou 0.3 --alpha 0.5 --max-misses 5 --min-hits 2 --emit-misses N]
         [--draw DIR [--anonymize pixelate] [--blocks N] [--draw-format png|jpg] [--no-outline]]
-        [--best-shots DIR [--chip-size N] [--chip-margin F]]
+        [--best-shots DIR [--chip-size N] [--chip-margin F] [--chip-format png|jpg]]
+        [--device-jpeg-encode] [--jpeg-quality Q]
 
 The images directly under DIR (.jpg .jpeg .png .bmp), sorted by name, are the frames of ONE sequence and must all have the
 same size.  They are detected in chunks of --max-frames: without --tiled each frame is resized whole to the network's input,
@@ -19,8 +20,9 @@ import argparse
 import os
 from pathlib import Path
 
-from .detect_images import (EXTENSIONS, add_chip_arguments, add_draw_arguments, add_model_arguments, add_tile_arguments,
-                            check_chip_arguments, check_draw_arguments)
+from .detect_images import (EXTENSIONS, add_chip_arguments, add_draw_arguments, add_jpeg_encode_arguments, add_model_arguments,
+                            add_tile_arguments, check_chip_arguments, check_draw_arguments, check_jpeg_encode_arguments,
+                            jpeg_encode_options)
 
 
 def frame_paths(root):
@@ -70,8 +72,10 @@ def main(argv=None):
     ap.add_argument("--birth-score", type=float, default=0.0)
     add_draw_arguments(ap)
     add_chip_arguments(ap, "--best-shots", "also write the sharpest crop of every track under DIR")
+    add_jpeg_encode_arguments(ap)
     args = ap.parse_args(argv)
     check_draw_arguments(ap, args)
+    check_jpeg_encode_arguments(ap, args)
     check_chip_arguments(ap, args, "--best-shots")
     if args.max_frames < 1:
         ap.error("--max-frames must be >= 1")
@@ -117,12 +121,13 @@ def run(args):
                 from .render import render_detections, save_images
                 drawn = render_detections(bank, res.rows, res.counts, outline=not args.no_outline, anonymize=args.anonymize,
                                           blocks=8 if args.blocks is None else args.blocks)
-                save_images(drawn, [(Path(args.draw) / p.name).with_suffix("." + (args.draw_format or "png")) for p in chunk])
+                save_images(drawn, [(Path(args.draw) / p.name).with_suffix("." + (args.draw_format or "png")) for p in chunk],
+                            **jpeg_encode_options(args))
             if best is not None:
                 best.update(bank, res)
             lines += write_mot(f, a + 1, res.rows.cpu().numpy(), res.counts.cpu().numpy(), res.ids.cpu().numpy())
     if best is not None:
-        shots = best.save(args.chips_dir)
+        shots = best.save(args.chips_dir, getattr(args, "chip_format", None) or "png", **jpeg_encode_options(args))
         print(f"{len(shots)} best shots -> {args.chips_dir}" + (f" ({best.overflow} detections of tracks beyond id {best.capacity} left out)"
                                                                 if best.overflow else ""))
     snap = tracker.snapshot()
