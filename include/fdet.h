@@ -1185,7 +1185,9 @@ int fdet_jpeg_enc_emit(const fdet_jpeg_enc_desc* descs, const fdet_jpeg_enc_desc
  * Int8 inference: the PoolResnet residual trunk post-training-quantised, on the integer matrix cores
  * (v_mfma_i32_16x16x64_i8).  Inference only.  The reference has no such path (it ships pruner.py and ONNX / TorchScript
  * export for deployment); the arithmetic below is this project's contract, restated in numpy by tests/q8_cpu_ref.py, and
- * the GPU results equal that restatement bit for bit.
+ * the GPU results equal that restatement bit for bit.  Resnet shares the trunk (its blocks pool while the map is larger than
+ * S) and enters it through an integer stem of its own, fdet_stem3_fwd_q8_u8 at the end of this block (restated by
+ * tests/q8_resnet_cpu_ref.py): with it the network is integer from the frame bytes to the head's input.
  *
  * Quantisation is symmetric: q = clamp(rintf(x * (1.0f / s)), -127, 127) (round half to even, NaN -> 0, -128 never
  * produced), x = float(q) * s.  Activation scales are per tensor, weight scales per output channel.
@@ -1254,6 +1256,27 @@ int fdet_q8_chain(const int8_t* x, const int8_t* const* h_wpk1, const int32_t* c
 int fdet_stem_fwd_q8_u8(const unsigned char* frames, const float* w, const float* bias, float scale, int8_t* q,
                         int N, int Cin, int F, int H, int W, int k, int stride, int pad, void* stream);
 int fdet_stem_fwd_q8_ok(int N, int Cin, int F, int H, int W, int k, int stride, int pad);
+
+/* The Resnet stem (3x3, stride 2, pad 1, 3 -> F channels) on the uint8 frames in INTEGER arithmetic, on the integer matrix
+ * cores (v_mfma_i32_16x16x32_i8): the network is integer from the frame bytes to the head's input.  The input is the frame
+ * itself, codes x_u8 in 0..255 with the fixed scale s_in = 1.0f / 255.0f, and the weights are prepared exactly as for a
+ * trunk conv, (w_q, b_q, mul) from (conv1.weight, conv1.bias, s_in, s_out):
+ *     acc = b_q[co] + sum over (ci,ky,kx) of x_u8[ci][2oy+ky-1][2ox+kx-1] * w_q[co][ci][ky][kx]    int32, exact; outside
+ *                                                                                                   the image: 0
+ *     t   = float(acc) * mul[co]                            (int -> float RNE, one fp32 multiply)
+ *     q   = clamp(rintf(t), -127, 127)                      (half to even; no LeakyReLU: the reference's stem has none)
+ *   frames  planar uint8 [N][3][H][W]
+ *   w_q     int8 [F][32], k = (ci*3+ky)*3+kx, bytes 27..31 of every row ZERO (a plain reshape and pad of [F][3][3][3];
+ *           quantize.py does it with torch)
+ *   b_q     int32 [F];  mul fp32 [F]
+ *   q       Q8 [N][Ho+2][Wo+2][F] with Ho = H / 2, Wo = W / 2: real pixels only, the halo is untouched
+ * Accepted: Cin == 3, F a multiple of 64 up to 256, H and W even, 2 <= H, W <= 4096, q under 2^31 bytes; w_q, b_q, mul and q
+ * 16-byte aligned.  (The kernel stages the rows as x - 128 for the signed MFMA and folds 128 * sum(w_q[co]) into the bias:
+ * internal, exact, the entry takes the plain contract values.)  Large batches run as consecutive launches over image chunks.
+ * fdet_stem3_fwd_q8_ok: the entry point accepts N images of this shape (launches nothing). */
+int fdet_stem3_fwd_q8_u8(const unsigned char* frames, const int8_t* w_q, const int32_t* b_q, const float* mul, int8_t* q,
+                         int N, int Cin, int F, int H, int W, void* stream);
+int fdet_stem3_fwd_q8_ok(int N, int Cin, int F, int H, int W);
 
 #ifdef __cplusplus
 }

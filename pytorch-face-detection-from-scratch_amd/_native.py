@@ -200,6 +200,8 @@ SIGNATURES = {
     "fdet_q8_chain": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _F, _I, _I, _I, _I, _I, _F, _P]),
     "fdet_stem_fwd_q8_u8": (_I, [_P, _P, _P, _F, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     "fdet_stem_fwd_q8_ok": (_I, [_I, _I, _I, _I, _I, _I, _I, _I]),
+    "fdet_stem3_fwd_q8_u8": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
+    "fdet_stem3_fwd_q8_ok": (_I, [_I, _I, _I, _I, _I]),
 }
 
 

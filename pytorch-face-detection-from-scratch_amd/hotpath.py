@@ -1647,3 +1647,37 @@ def stem_fwd_q8_u8(frames: torch.Tensor, w: torch.Tensor, bias: torch.Tensor, sc
     check(lib().fdet_stem_fwd_q8_u8(ptr(frames, torch.uint8), ptr(w), ptr(bias), float(scale), out.data, Nn, cin, F_, H, W, k,
                                     stride, pad, stream()), "fdet_stem_fwd_q8_u8")
     return out
+
+
+def stem3_fwd_q8_ok(N_, cin, F_, H, W) -> bool:
+    """fdet_stem3_fwd_q8_u8 accepts N images of this shape (fdet_stem3_fwd_q8_ok): 3 channels, F a multiple of 64 up to 256,
+    even H and W in 2..4096."""
+    return bool(lib().fdet_stem3_fwd_q8_ok(int(N_), int(cin), int(F_), int(H), int(W)))
+
+
+def q8_pack_stem_weights(w_q: torch.Tensor) -> torch.Tensor:
+    """int8 [F,3,3,3] -> the integer stem's [F][32]: k = (ci*3+ky)*3+kx, bytes 27..31 zero (one-time work, a torch reshape)."""
+    if w_q.dtype != I8 or w_q.dim() != 4 or tuple(w_q.shape[1:]) != (3, 3, 3) or w_q.shape[0] % 64:
+        raise ValueError("q8_pack_stem_weights: expected int8 weights [F,3,3,3] with F % 64 == 0")
+    out = torch.zeros(w_q.shape[0], 32, dtype=I8, device=w_q.device)
+    out[:, :27] = w_q.reshape(w_q.shape[0], 27)
+    return out.reshape(-1)
+
+
+def stem3_fwd_q8_u8(frames: torch.Tensor, wpk: torch.Tensor, bias: torch.Tensor, mul: torch.Tensor, out: Q8Tensor) -> Q8Tensor:
+    """uint8 frames (N,3,H,W) -> the 3x3 / stride 2 / pad 1 stem in integer arithmetic, requantised into `out` (real pixels
+    only): clamp(rintf(float(bias + sum x_u8 * w_q) * mul), -127, 127) on the integer matrix cores (fdet_stem3_fwd_q8_u8)."""
+    if frames.dim() != 4 or frames.dtype != torch.uint8:
+        raise ValueError("stem3_fwd_q8_u8: expected uint8 frames (N,3,H,W)")
+    Nn, cin, H, W = frames.shape
+    F_ = bias.shape[0]
+    if wpk.numel() != 32 * F_:
+        raise ValueError("stem3_fwd_q8_u8: packed weight size does not match the channel count (q8_pack_stem_weights)")
+    _chk4(bias, (F_,), "bias")
+    _chk4(mul, (F_,), "mul")
+    if H % 2 or W % 2:
+        raise ValueError(f"stem3_fwd_q8_u8: H and W must be even, got {H}x{W}")
+    _q8_same(out, (Nn, F_, H // 2, W // 2), "stem3_fwd_q8_u8: out")
+    check(lib().fdet_stem3_fwd_q8_u8(ptr(frames, torch.uint8), ptr(wpk, I8), ptr(bias, torch.int32), ptr(mul), out.data, Nn, cin,
+                                     F_, H, W, stream()), "fdet_stem3_fwd_q8_u8")
+    return out

@@ -32,3 +32,9 @@ class Resnet(BaseModel):
         if predict == 1:
             x = self.single_non_max_suppression(x[0])
         return x
+
+    def quantize(self, frames_iter, **kw):
+        """Int8 post-training quantisation for inference: calibrate the activation scales on `frames_iter` (quantize.calibrate;
+        keywords method / percentile) and return the Int8Resnet of this model."""
+        from ..quantize import quantize_model
+        return quantize_model(self, frames_iter, **kw)

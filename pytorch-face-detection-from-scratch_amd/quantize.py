@@ -1,14 +1,18 @@
-"""Int8 post-training quantisation of PoolResnet for inference (include/fdet.h "Int8 inference").
+"""Int8 post-training quantisation of PoolResnet and Resnet for inference (include/fdet.h "Int8 inference").
 
     qp = calibrate(model, frames_iter)                  # float engine over a few frames -> activation scales
     m8 = Int8PoolResnet(model, qp)                      # int8 weights, int32 biases, fp32 multipliers, once
+    m8 = Int8Resnet(model, qp)                          # (a Resnet; quantize_model picks the class)
     rows, counts = m8.reduce_bounding_boxes.forward_batch(m8.forward_frames(frames))
 
 The residual trunk (every 3x3 conv, both LeakyReLUs, the skip add and the 2x2 max-pool) runs on the integer matrix cores
 (fdet_q8_conv3x3; the un-pooled blocks at the end as one fdet_q8_chain launch); the head keeps its float kernel, and the
-stem reads uint8 frames and writes the quantised layout itself (fdet_stem_fwd_q8_u8) where it takes the shape.  The
+stem reads uint8 frames and writes the quantised layout itself (fdet_stem_fwd_q8_u8) where it takes the shape.  Resnet's
+3x3 / stride 2 stem is an integer kernel of its own (fdet_stem3_fwd_q8_u8): the uint8 frame is its quantised input (scale
+1 / 255), so that network is integer from the frame bytes to the head's input and has one arithmetic for every input.  The
 reference has no quantised path (its deployment tools are pruner.py and the ONNX / TorchScript exports); the arithmetic is
-this project's own contract, restated in numpy by tests/q8_cpu_ref.py, and the kernels equal that restatement bit for bit.
+this project's own contract, restated in numpy by tests/q8_cpu_ref.py and tests/q8_resnet_cpu_ref.py, and the kernels equal
+those restatements bit for bit.
 """
 from __future__ import annotations
 
@@ -125,14 +129,33 @@ def _check_model(model):
         raise TypeError(f"int8 inference covers PoolResnet only, got {type(model).__name__}")
 
 
+def _check_resnet(model):
+    from .models.Resnet import Resnet
+    if type(model) is not Resnet:
+        raise TypeError(f"Int8Resnet covers Resnet only, got {type(model).__name__}")
+
+
+def _check_calibratable(model):
+    from .models.PoolResnet import PoolResnet
+    from .models.Resnet import Resnet
+    if type(model) not in (PoolResnet, Resnet):
+        raise TypeError(f"int8 calibration covers Resnet and PoolResnet only, got {type(model).__name__}")
+
+
+STEM_IN_SCALE = NPF(1.0) / NPF(255.0)                   # the scale of a uint8 frame as the integer stem's input code
+
+
 @torch.no_grad()
 def calibrate(model, frames_iter: Iterable[torch.Tensor], method: str = "absmax", percentile: Optional[float] = None) -> QuantParams:
     """Run the float engine (eval arithmetic: no dropout) over the calibration frames and reduce the intermediates it keeps
     for backward to activation scales.  frames_iter yields batches of FRAMES exactly as `forward_frames` takes them: (N,3,H,W)
     with values 0..255, uint8 or float, any size -- they go through the model's own preprocessing (resize, / 255).  Images
-    that are already normalised to [0,1] are not frames: passing them would calibrate on nearly black input."""
+    that are already normalised to [0,1] are not frames: passing them would calibrate on nearly black input.
+    A PoolResnet or a Resnet.  Resnet's engine keeps maps wider than 62 columns as column strips; PsTensor.to_f32 undoes
+    the strips (fdet_ps_to_f32 plans them from the full width and reads real columns only), so what is observed is plain
+    NCHW at every level."""
     from .ps import PsTensor
-    _check_model(model)
+    _check_calibratable(model)
     if percentile is not None and method == "absmax":
         method = "percentile"
     eng = model.engine
@@ -193,31 +216,34 @@ class _Q8Conv:
 
 
 # ---------------------------------------------------------------------------------------------------------- the model
-class Int8PoolResnet:
-    """A trained PoolResnet with its residual trunk in int8: existing stem -> quantise -> 2 x blocks int8 convs ->
-    dequantise -> existing head; or, where switched on (FDET_Q8_STEM / FDET_Q8_CHAIN, `counters`), the quantising stem on
-    the uint8 frames and the un-pooled tail of the trunk as one launch that also dequantises -- the same bytes.  Inference
-    only; weights and scales are those at construction.  It offers what the rest of the package asks of a model
-    (TiledDetector, DetectionEvaluator, GraphedPredict, render / tracking / chips)."""
+class _Int8Trunk:
+    """What Int8PoolResnet and Int8Resnet share: the int8 residual trunk (2 x blocks fdet_q8_conv3x3 launches, or the
+    un-pooled tail as one fdet_q8_chain launch that also dequantises -- the same bytes), the float head, the pooled Q8
+    buffers and the model surface that the rest of the package asks for (TiledDetector, DetectionEvaluator, GraphedPredict,
+    render / tracking / chips).  A subclass supplies the way into the trunk: `_check`, `_init_stem`, `_forward_f32`
+    (float images in [0,1] at the model resolution -> maps) and `forward_frames`.  Inference only; weights and scales are
+    those at construction."""
 
     training = False
+    _check = staticmethod(_check_model)
 
     def __init__(self, model, qparams: QuantParams):
-        _check_model(model)
+        me = type(self).__name__
+        self._check(model)
         if not isinstance(qparams, QuantParams):
-            raise TypeError("Int8PoolResnet: qparams must be a QuantParams")
+            raise TypeError(f"{me}: qparams must be a QuantParams")
         nb = len(model.residual_blocks)
         if qparams.num_blocks != nb:
-            raise ValueError(f"Int8PoolResnet: the model has {nb} residual blocks, the scales are for {qparams.num_blocks}")
+            raise ValueError(f"{me}: the model has {nb} residual blocks, the scales are for {qparams.num_blocks}")
         dev = next(model.parameters()).device
         if dev.type != "cuda":
-            raise FdetError("Int8PoolResnet runs on the GPU only (no CPU fallback): move the model to cuda first")
+            raise FdetError(f"{me} runs on the GPU only (no CPU fallback): move the model to cuda first")
         self.geo = model._geometry()
         self.h0, self.lv = self.geo.levels()
         F_ = int(model.filters)
         for hk, _ in self.lv:
             if not hp.q8_supported(F_, hk, hk):
-                raise FdetError(f"Int8PoolResnet: {F_} channels at {hk}x{hk} are outside the int8 kernels' range "
+                raise FdetError(f"{me}: {F_} channels at {hk}x{hk} are outside the int8 kernels' range "
                                 "(fdet_q8_supported: a multiple of 64 up to 256)")
         self.input_shape = model.input_shape
         self.num_of_patches = model.num_of_patches
@@ -237,16 +263,12 @@ class Int8PoolResnet:
             c1 = _Q8Conv(sd[n + ".conv1.weight"], sd[n + ".conv1.bias"], s_h[k], s_a[k], dev)
             c2 = _Q8Conv(sd[n + ".conv2.weight"], sd[n + ".conv2.bias"], s_a[k], s_h[k + 1], dev)
             self.blocks.append((c1, c2, float(NPF(s_h[k]) / NPF(s_h[k + 1]))))
-        self.stem_w = model.conv1.weight.detach().to(F32).contiguous().clone()
-        self.stem_b = model.conv1.bias.detach().to(F32).contiguous().clone()
+        self._init_stem(model, sd)
         self.head_w = model.out.weight.detach().to(F32).contiguous().clone()
         self.head_b = model.out.bias.detach().to(F32).contiguous().clone()
-        g = self.geo
-        self._stem_x3 = hp.x3_supported(F_, F_) and hp.stem_x3_supported(g.in_ch, g.W, g.stem_k, g.stem_s, g.stem_p)
         # the maximal run of un-pooled blocks at the end of the trunk: one fdet_q8_chain launch where the kernel takes the map
         # (64 channels, at most 16 x 16, 1..16 blocks); its host pointer arrays are built here, once
         self.chain = os.environ.get("FDET_Q8_CHAIN", "auto")          # "0" launch by launch, "1" the chain wherever it runs, else measured
-        self.stem_q8 = os.environ.get("FDET_Q8_STEM", "auto")         # "0" float stem + quantise, "1" the quantising stem wherever it runs
         self.counters = {"chain": 0, "layers": 0, "stem_q8": 0, "stem_f32": 0}
         first = nb
         while first > 0 and self.lv[first - 1][1] != 2:
@@ -267,7 +289,7 @@ class Int8PoolResnet:
 
     def train(self, mode: bool = True):
         if mode:
-            raise FdetError("Int8PoolResnet is inference only")
+            raise FdetError(f"{type(self).__name__} is inference only")
         return self
 
     # ------------------------------------------------------------------ buffers
@@ -288,48 +310,6 @@ class Int8PoolResnet:
         if self._chain_w is None or self.chain == "0":
             return False
         return self.chain == "1" or CHAIN_MEASURED_FASTER
-
-    def stem_q8_on(self, N: int) -> bool:
-        """uint8 frames at the model resolution go through the quantising stem (fdet_stem_fwd_q8_u8)."""
-        g = self.geo
-        if self.stem_q8 == "0" or not (self.stem_q8 == "1" or STEM_Q8_MEASURED_FASTER):
-            return False
-        return hp.stem_fwd_q8_ok(N, g.in_ch, self.filters, g.H, g.W, g.stem_k, g.stem_s, g.stem_p)
-
-    def _stem_f32(self, x: torch.Tensor, trace: Optional[dict] = None) -> hp.Q8Tensor:
-        """fp32 images in [0,1] -> float stem -> quantise."""
-        g, F_ = self.geo, self.filters
-        if not x.is_cuda:
-            raise FdetError("Int8PoolResnet runs on the GPU only (no CPU fallback): move the input to cuda")
-        if x.dim() != 4 or tuple(x.shape[1:]) != (g.in_ch, g.H, g.W):
-            raise ValueError(f"expected input (N,{g.in_ch},{g.H},{g.W}), got {tuple(x.shape)}")
-        if x.dtype != F32 or not x.is_contiguous():
-            x = x.to(F32).contiguous()
-        N, dev = x.shape[0], x.device
-        nws = hp.stem_ws_bytes(N, g.in_ch, F_, g.H, g.W, g.stem_k, g.stem_s, g.stem_p)
-        if self._ws is None or self._ws.numel() * 4 < nws:
-            self._ws = torch.empty(max((nws + 3) // 4, 4), dtype=F32, device=dev)
-        h0 = self.h0
-        hf = torch.empty(N, F_, h0, h0, dtype=F32, device=dev)
-        with self._t("stem_fwd", h0):
-            hp.stem_fwd(x, self.stem_w, self.stem_b, hf, self._ws, g.stem_k, g.stem_s, g.stem_p, x3=self._stem_x3)
-        h = self._take(N, h0, h0)
-        with self._t("q8_quantize", h0, 0.0, 5.0 * hf.numel()):
-            hp.q8_quantize(hf, float(self.qparams.s_h[0]), out=h)
-        self.counters["stem_f32"] += 1
-        if trace is not None:
-            trace["stem"] = hf
-        return h
-
-    def _stem_u8(self, frames: torch.Tensor) -> hp.Q8Tensor:
-        """uint8 frames at the model resolution -> the quantising stem: no fp32 image, no fp32 stem output."""
-        g = self.geo
-        N, h0 = frames.shape[0], self.h0
-        h = self._take(N, h0, h0)
-        with self._t("stem_fwd_q8", h0, 0.0, float(frames.numel()) + N * self.filters * h0 * h0):
-            hp.stem_fwd_q8_u8(frames, self.stem_w, self.stem_b, float(self.qparams.s_h[0]), h, g.stem_k, g.stem_s, g.stem_p)
-        self.counters["stem_q8"] += 1
-        return h
 
     def _trunk(self, h: hp.Q8Tensor, trace: Optional[dict] = None) -> torch.Tensor:
         """The quantised stem output (taken from the pool; given back here) -> the (N,5,S,S) maps."""
@@ -377,32 +357,10 @@ class Int8PoolResnet:
             trace["y"] = y
         return y
 
-    def _forward_f32(self, x: torch.Tensor, trace: Optional[dict] = None) -> torch.Tensor:
-        return self._trunk(self._stem_f32(x, trace), trace)
-
-    @torch.no_grad()
-    def forward_frames(self, x: torch.Tensor) -> torch.Tensor:
-        """frames (uint8 or float, any size) -> the (N,5,S,S) maps, as BaseModel.forward_frames.  uint8 frames on the GPU
-        that are already at the model resolution go to the quantising stem as they are (where it is switched on and takes
-        the shape): no `/ 255` pass, no fp32 stem output, no quantise launch, the same bytes."""
-        g = self.geo
-        if x.dim() == 3:
-            x = x.unsqueeze(0)
-        if (x.is_cuda and x.dtype == torch.uint8 and x.dim() == 4 and tuple(x.shape[1:]) == (g.in_ch, g.H, g.W)
-                and self.stem_q8_on(x.shape[0])):
-            return self._trunk(self._stem_u8(x.contiguous()))
-        return self._forward_f32(self._preprocess(x))
-
-    @torch.no_grad()
-    def trace(self, frames: torch.Tensor) -> dict:
-        """{"stem": fp32 stem output (N,F,h0,h0), "blocks": [int8 (N,F,h,h) output of every block], "y": (N,5,S,S)}"""
-        out = {}
-        self._forward_f32(self._preprocess(frames), trace=out)
-        return out
-
     @torch.no_grad()
     def __call__(self, x: torch.Tensor, predict: torch.Tensor = torch.tensor(0)):
-        """PoolResnet.forward: float images in [0,1] at the model resolution -> maps; predict=1: frames -> boxes of image 0."""
+        """The float model's forward: float images in [0,1] at the model resolution -> maps; predict=1: frames -> boxes of
+        image 0."""
         if predict == 1:
             return self.single_non_max_suppression(self.forward_frames(x)[0])
         return self._forward_f32(x)
@@ -432,6 +390,158 @@ class Int8PoolResnet:
         return GraphedPredict(self, example)
 
 
-def quantize_model(model, frames_iter, **kw) -> Int8PoolResnet:
-    """calibrate + Int8PoolResnet (what PoolResnet.quantize does)."""
-    return Int8PoolResnet(model, calibrate(model, frames_iter, **kw))
+class Int8PoolResnet(_Int8Trunk):
+    """A trained PoolResnet with its residual trunk in int8: existing stem -> quantise -> 2 x blocks int8 convs ->
+    dequantise -> existing head; or, where switched on (FDET_Q8_STEM / FDET_Q8_CHAIN, `counters`), the quantising stem on
+    the uint8 frames and the un-pooled tail of the trunk as one launch that also dequantises -- the same bytes.  Inference
+    only; weights and scales are those at construction.  It offers what the rest of the package asks of a model
+    (TiledDetector, DetectionEvaluator, GraphedPredict, render / tracking / chips)."""
+
+    def _init_stem(self, model, sd) -> None:
+        g, F_ = self.geo, self.filters
+        self.stem_w = model.conv1.weight.detach().to(F32).contiguous().clone()
+        self.stem_b = model.conv1.bias.detach().to(F32).contiguous().clone()
+        self._stem_x3 = hp.x3_supported(F_, F_) and hp.stem_x3_supported(g.in_ch, g.W, g.stem_k, g.stem_s, g.stem_p)
+        self.stem_q8 = os.environ.get("FDET_Q8_STEM", "auto")         # "0" float stem + quantise, "1" the quantising stem wherever it runs
+
+    def stem_q8_on(self, N: int) -> bool:
+        """uint8 frames at the model resolution go through the quantising stem (fdet_stem_fwd_q8_u8)."""
+        g = self.geo
+        if self.stem_q8 == "0" or not (self.stem_q8 == "1" or STEM_Q8_MEASURED_FASTER):
+            return False
+        return hp.stem_fwd_q8_ok(N, g.in_ch, self.filters, g.H, g.W, g.stem_k, g.stem_s, g.stem_p)
+
+    def _stem_f32(self, x: torch.Tensor, trace: Optional[dict] = None) -> hp.Q8Tensor:
+        """fp32 images in [0,1] -> float stem -> quantise."""
+        g, F_ = self.geo, self.filters
+        if not x.is_cuda:
+            raise FdetError("Int8PoolResnet runs on the GPU only (no CPU fallback): move the input to cuda")
+        if x.dim() != 4 or tuple(x.shape[1:]) != (g.in_ch, g.H, g.W):
+            raise ValueError(f"expected input (N,{g.in_ch},{g.H},{g.W}), got {tuple(x.shape)}")
+        if x.dtype != F32 or not x.is_contiguous():
+            x = x.to(F32).contiguous()
+        N, dev = x.shape[0], x.device
+        nws = hp.stem_ws_bytes(N, g.in_ch, F_, g.H, g.W, g.stem_k, g.stem_s, g.stem_p)
+        if self._ws is None or self._ws.numel() * 4 < nws:
+            self._ws = torch.empty(max((nws + 3) // 4, 4), dtype=F32, device=dev)
+        h0 = self.h0
+        hf = torch.empty(N, F_, h0, h0, dtype=F32, device=dev)
+        with self._t("stem_fwd", h0):
+            hp.stem_fwd(x, self.stem_w, self.stem_b, hf, self._ws, g.stem_k, g.stem_s, g.stem_p, x3=self._stem_x3)
+        h = self._take(N, h0, h0)
+        with self._t("q8_quantize", h0, 0.0, 5.0 * hf.numel()):
+            hp.q8_quantize(hf, float(self.qparams.s_h[0]), out=h)
+        self.counters["stem_f32"] += 1
+        if trace is not None:
+            trace["stem"] = hf
+        return h
+
+    def _stem_u8(self, frames: torch.Tensor) -> hp.Q8Tensor:
+        """uint8 frames at the model resolution -> the quantising stem: no fp32 image, no fp32 stem output."""
+        g = self.geo
+        N, h0 = frames.shape[0], self.h0
+        h = self._take(N, h0, h0)
+        with self._t("stem_fwd_q8", h0, 0.0, float(frames.numel()) + N * self.filters * h0 * h0):
+            hp.stem_fwd_q8_u8(frames, self.stem_w, self.stem_b, float(self.qparams.s_h[0]), h, g.stem_k, g.stem_s, g.stem_p)
+        self.counters["stem_q8"] += 1
+        return h
+
+    def _forward_f32(self, x: torch.Tensor, trace: Optional[dict] = None) -> torch.Tensor:
+        return self._trunk(self._stem_f32(x, trace), trace)
+
+    @torch.no_grad()
+    def forward_frames(self, x: torch.Tensor) -> torch.Tensor:
+        """frames (uint8 or float, any size) -> the (N,5,S,S) maps, as BaseModel.forward_frames.  uint8 frames on the GPU
+        that are already at the model resolution go to the quantising stem as they are (where it is switched on and takes
+        the shape): no `/ 255` pass, no fp32 stem output, no quantise launch, the same bytes."""
+        g = self.geo
+        if x.dim() == 3:
+            x = x.unsqueeze(0)
+        if (x.is_cuda and x.dtype == torch.uint8 and x.dim() == 4 and tuple(x.shape[1:]) == (g.in_ch, g.H, g.W)
+                and self.stem_q8_on(x.shape[0])):
+            return self._trunk(self._stem_u8(x.contiguous()))
+        return self._forward_f32(self._preprocess(x))
+
+    @torch.no_grad()
+    def trace(self, frames: torch.Tensor) -> dict:
+        """{"stem": fp32 stem output (N,F,h0,h0), "blocks": [int8 (N,F,h,h) output of every block], "y": (N,5,S,S)}"""
+        out = {}
+        self._forward_f32(self._preprocess(frames), trace=out)
+        return out
+
+
+class Int8Resnet(_Int8Trunk):
+    """A trained Resnet (3x3 / stride 2 stem, pooling while the map is larger than S) in int8 from the frame bytes to the
+    head's input: the integer stem on the uint8 frames (fdet_stem3_fwd_q8_u8; the frame is its quantised input, scale
+    1 / 255, and s_h[0] its output scale), the shared int8 trunk, the float head.  ONE input rule and one arithmetic: uint8
+    frames on the GPU at the model resolution go to the stem as they are; everything else (other sizes, float frames, float
+    images in [0,1] through `__call__`) goes through the model's `_preprocess` and is turned into codes by
+    clamp(rint(nan_to_num(x) * 255), 0, 255) with torch ops -- for images that came from uint8 frames that recovers the
+    bytes -- and goes to the same stem.  There is no float stem here and so no second set of bytes."""
+
+    _check = staticmethod(_check_resnet)
+
+    def _init_stem(self, model, sd) -> None:
+        g, F_ = self.geo, self.filters
+        if (g.stem_k, g.stem_s, g.stem_p) != (3, 2, 1) or not hp.stem3_fwd_q8_ok(1, g.in_ch, F_, g.H, g.W):
+            raise FdetError(f"Int8Resnet: a {g.in_ch} -> {F_} channel stem on {g.H}x{g.W} frames is outside the integer stem's "
+                            "range (fdet_stem3_fwd_q8_ok: 3 channels, F a multiple of 64 up to 256, even H and W up to 4096)")
+        w_q, b_q, mul = prepare_conv(sd["conv1.weight"], sd["conv1.bias"], STEM_IN_SCALE, self.qparams.s_h[0])
+        self.stem_wpk = hp.q8_pack_stem_weights(torch.from_numpy(w_q).to(self.device))
+        self.stem_bias = torch.from_numpy(b_q).to(self.device)
+        self.stem_mul = torch.from_numpy(mul).to(self.device)
+
+    def _stem_u8(self, frames: torch.Tensor, trace: Optional[dict] = None) -> hp.Q8Tensor:
+        """uint8 codes at the model resolution -> the integer stem."""
+        g = self.geo
+        if not frames.is_cuda:
+            raise FdetError("Int8Resnet runs on the GPU only (no CPU fallback): move the input to cuda")
+        if frames.dim() != 4 or tuple(frames.shape[1:]) != (g.in_ch, g.H, g.W):
+            raise ValueError(f"expected input (N,{g.in_ch},{g.H},{g.W}), got {tuple(frames.shape)}")
+        N, h0 = frames.shape[0], self.h0
+        if not hp.stem3_fwd_q8_ok(N, g.in_ch, self.filters, g.H, g.W):
+            raise FdetError(f"Int8Resnet: {N} images of {g.H}x{g.W} pass the int8 layout's 2 GiB per tensor: use smaller batches")
+        h = self._take(N, h0, h0)
+        with self._t("stem3_fwd_q8", h0, 2.0 * N * self.filters * 27 * h0 * h0, float(frames.numel()) + N * self.filters * h0 * h0):
+            hp.stem3_fwd_q8_u8(frames.contiguous(), self.stem_wpk, self.stem_bias, self.stem_mul, h)
+        self.counters["stem_q8"] += 1
+        if trace is not None:
+            trace["stem"] = h.nchw()
+        return h
+
+    @staticmethod
+    def _codes(x: torch.Tensor) -> torch.Tensor:
+        """float images in [0,1] -> the uint8 codes of the stem's input scale 1 / 255 (torch ops; NaN -> 0)."""
+        return torch.nan_to_num(x.to(F32)).mul(255.0).round_().clamp_(0.0, 255.0).to(torch.uint8)
+
+    def _forward_f32(self, x: torch.Tensor, trace: Optional[dict] = None) -> torch.Tensor:
+        if not x.is_cuda:
+            raise FdetError("Int8Resnet runs on the GPU only (no CPU fallback): move the input to cuda")
+        return self._trunk(self._stem_u8(self._codes(x), trace), trace)
+
+    def _forward_any(self, x: torch.Tensor, trace: Optional[dict] = None) -> torch.Tensor:
+        g = self.geo
+        if x.dim() == 3:
+            x = x.unsqueeze(0)
+        if x.is_cuda and x.dtype == torch.uint8 and x.dim() == 4 and tuple(x.shape[1:]) == (g.in_ch, g.H, g.W):
+            return self._trunk(self._stem_u8(x, trace), trace)
+        return self._forward_f32(self._preprocess(x), trace)
+
+    @torch.no_grad()
+    def forward_frames(self, x: torch.Tensor) -> torch.Tensor:
+        """frames (uint8 or float, any size) -> the (N,5,S,S) maps, as BaseModel.forward_frames."""
+        return self._forward_any(x)
+
+    @torch.no_grad()
+    def trace(self, frames: torch.Tensor) -> dict:
+        """{"stem": int8 stem output (N,F,h0,h0), "blocks": [int8 (N,F,h,h) output of every block], "y": (N,5,S,S)}"""
+        out = {}
+        self._forward_any(frames, trace=out)
+        return out
+
+
+def quantize_model(model, frames_iter, **kw):
+    """calibrate + the int8 class of the model: Int8PoolResnet or Int8Resnet (what PoolResnet.quantize / Resnet.quantize do)."""
+    from .models.Resnet import Resnet
+    cls = Int8Resnet if type(model) is Resnet else Int8PoolResnet
+    return cls(model, calibrate(model, frames_iter, **kw))

@@ -1,6 +1,8 @@
-"""Inference throughput of the int8 post-training-quantised PoolResnet beside the two float modes.
+"""Inference throughput of the int8 post-training-quantised PoolResnet beside the two float modes, and with
+`--model resnet` of the int8 Resnet (see `main_resnet` below).
 
     python tools/q8_throughput.py [--images 256] [--launches 100] [--calls 10] [--out profiles/r15_q8_chain.json]
+    python tools/q8_throughput.py --model resnet [--images 32] [--out profiles/r17_q8_resnet.json]
 
 Workload: the inference leg's -- --images uint8 480x480 frames on the device (the three stored frames of
 tests/golden/g6_trained_small.npz, repeated) through the medium PoolResnet (64 filters, the trained weights of
@@ -36,15 +38,163 @@ sys.path.insert(0, ROOT)
 INT8_PEAK_MACS = 2.5e15
 
 
+def _stats(v):
+    import numpy as np
+    a = np.sort(np.asarray(v))
+    p05, p95 = float(np.percentile(a, 5)), float(np.percentile(a, 95))
+    return {"median_ms": round(float(np.median(a)), 4), "min_ms": round(float(a[0]), 4), "max_ms": round(float(a[-1]), 4),
+            "p05_ms": round(p05, 4), "p95_ms": round(p95, 4), "spread_ms": round(p95 - p05, 4)}
+
+
+def _alternate(fns, launches, calls):
+    """{name: callable} -> {name: [ms per call]}: samples alternated between the callables, `calls` back-to-back calls between
+    two device events per sample."""
+    import torch
+    ms = {k: [] for k in fns}
+    for _ in range(launches):
+        for k, fn in fns.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(calls):
+                fn()
+            e1.record()
+            e1.synchronize()
+            ms[k].append(e0.elapsed_time(e1) / calls)
+    return ms
+
+
+def main_resnet(args):
+    """`--model resnet`: --images uint8 480x480 frames (the three stored frames, repeated) through the medium Resnet (64
+    filters, ten blocks, S = 15; the trained weights of tests/golden/g22_trained_resnet_medium*.npz) to boxes, for bf16x3,
+    precision16 and quantize.Int8Resnet (calibrated, abs-max, on the first 16 frames) -- the protocol above: one process, every
+    model warmed up, alternated sample by sample, --calls back-to-back calls per sample, median and 5th / 95th percentile.  The
+    default is 32 frames, the batch the float Resnet engine is run and tested at (config 3).  Then the per-kernel-class table of
+    the int8 model and of precision16 (stem, each level, tail, head), and the integer stem on its own beside the launches it
+    stands in for -- the float 3x3 / stride 2 stem on the normalised fp32 images followed by fdet_q8_quantize at 240 x 240 (the
+    `/ 255` pass before them is not counted) -- and beside a plain device copy that moves the stem's bytes (frames read + int8
+    output written)."""
+    import numpy as np
+    import torch
+    import fdet_amd  # noqa: F401
+    from fdet_amd import hotpath as hp
+    from fdet_amd.convstack import KernelTimer
+    from fdet_amd.models.Resnet import Resnet
+    from fdet_amd.quantize import Int8Resnet, calibrate
+    if not torch.cuda.is_available():
+        raise SystemExit("q8_throughput needs a GPU")
+    gold = os.path.join(ROOT, "tests", "golden")
+    P = {}
+    for part in ("", "_b", "_c", "_d"):
+        g = np.load(os.path.join(gold, f"g22_trained_resnet_medium{part}.npz"))
+        P.update({k[len("param/"):]: torch.from_numpy(g[k]) for k in g.files if k.startswith("param/")})
+    images = torch.from_numpy(np.load(os.path.join(gold, "g6_trained_small.npz"))["images"])
+    n = args.images
+    frames = images[torch.arange(n) % images.shape[0]].contiguous().cuda()
+
+    def build(p16):
+        m = Resnet(filters=64, input_shape=(3, 480, 480), num_of_patches=15, probability_threshold=0.7, iou_threshold=0.01)
+        m.load_state_dict({k: v.clone() for k, v in P.items()})
+        m = m.cuda().eval()
+        if p16:
+            m.engine.set_precision("bf16")
+        return m
+    m32, m16 = build(False), build(True)
+    m8 = Int8Resnet(m32, calibrate(m32, [frames[:min(16, n)]]))
+    models = {"bf16x3": m32, "precision16": m16, "int8": m8}
+
+    def run(m):
+        with torch.no_grad():
+            return m.reduce_bounding_boxes.forward_batch(m.forward_frames(frames))
+    boxes = {}
+    for k, m in models.items():
+        for _ in range(args.warmup):
+            rows, counts = run(m)
+        boxes[k] = int(counts.sum())
+    torch.cuda.synchronize()
+    e2e = {k: _stats(v) for k, v in _alternate({k: (lambda m=m: run(m)) for k, m in models.items()}, args.launches, args.calls).items()}
+
+    def kernel_times(m, holder):
+        holder.timer = KernelTimer()
+        for _ in range(args.kernel_runs):
+            run(m)
+        s = holder.timer.summary()
+        holder.timer = None
+        return {name: {"launches_per_call": cnt // args.kernel_runs, "ms_per_call": round(total / args.kernel_runs, 4)}
+                for name, (cnt, total, _, _) in sorted(s.items())}
+    k8, k16 = kernel_times(m8, m8), kernel_times(m16, m16.engine)
+
+    def classes(ks):
+        out = {}
+        for name, v in ks.items():
+            kind, at = name.split("@")
+            cls_ = "stem" if kind.startswith("stem") else "head" if kind.startswith("head") else \
+                ("tail@" if at.startswith("15x") else "level@") + at
+            out[cls_] = round(out.get(cls_, 0.0) + v["ms_per_call"], 4)
+        return out
+
+    # the stem on its own: the integer stem | the float stem + quantise it stands in for | a copy of the same bytes
+    x32 = hp.u8_to_f32_norm(frames)
+    w32, b32 = m32.conv1.weight.detach().contiguous(), m32.conv1.bias.detach().contiguous()
+    hf = torch.empty(n, 64, 240, 240, dtype=torch.float32, device="cuda")
+    ws = torch.empty(max((hp.stem_ws_bytes(n, 3, 64, 480, 480, 3, 2, 1) + 3) // 4, 4), dtype=torch.float32, device="cuda")
+    x3 = hp.x3_supported(64, 64) and hp.stem_x3_supported(3, 480, 3, 2, 1)
+    q_a, q_b = hp.Q8Tensor(n, 64, 240, 240, "cuda"), hp.Q8Tensor(n, 64, 240, 240, "cuda")
+    s0 = float(m8.qparams.s_h[0])
+    stem_bytes = frames.numel() + n * 64 * 240 * 240
+    src = torch.empty(stem_bytes // 2, dtype=torch.uint8, device="cuda").fill_(7)
+    dst = torch.empty_like(src)
+
+    def float_pair():
+        hp.stem_fwd(x32, w32, b32, hf, ws, 3, 2, 1, x3=x3)
+        hp.q8_quantize(hf, s0, out=q_b)
+    stem_fns = {"stem3_fwd_q8_u8": lambda: hp.stem3_fwd_q8_u8(frames, m8.stem_wpk, m8.stem_bias, m8.stem_mul, q_a),
+                "float_stem+quantize": float_pair, "float_stem": lambda: hp.stem_fwd(x32, w32, b32, hf, ws, 3, 2, 1, x3=x3),
+                "q8_quantize": lambda: hp.q8_quantize(hf, s0, out=q_b), "device_copy_same_bytes": lambda: dst.copy_(src)}
+    for fn in stem_fns.values():
+        for _ in range(args.warmup):
+            fn()
+    torch.cuda.synchronize()
+    stem = {k: _stats(v) for k, v in _alternate(stem_fns, args.launches, args.calls).items()}
+    code_diff = (q_a.nchw()[:3].to(torch.int16) - q_b.nchw()[:3].to(torch.int16)).abs()    # integer stem against the quantised float stem
+    pair_bytes = 4 * frames.numel() + 4 * hf.numel() + 4 * hf.numel() + n * 64 * 240 * 240
+    gbs = {"stem3_fwd_q8_u8": round(stem_bytes / stem["stem3_fwd_q8_u8"]["median_ms"] / 1e6, 1),
+           "device_copy_same_bytes": round(stem_bytes / stem["device_copy_same_bytes"]["median_ms"] / 1e6, 1),
+           "float_stem+quantize": round(pair_bytes / stem["float_stem+quantize"]["median_ms"] / 1e6, 1)}
+    macs = float(n) * 64 * 64 * 9 * (2 * 240 * 240 + 2 * 120 * 120 + 2 * 60 * 60 + 2 * 30 * 30 + 12 * 15 * 15)
+    res = {"tool": "q8_throughput", "model": "resnet", "device_name": torch.cuda.get_device_name(0), "images": n,
+           "launches": args.launches, "calls_per_sample": args.calls, "end_to_end": e2e,
+           "images_per_s": {k: round(n / (v["median_ms"] * 1e-3), 1) for k, v in e2e.items()}, "boxes": boxes,
+           "counters": dict(m8.counters),
+           "over_precision16": round(e2e["precision16"]["median_ms"] / e2e["int8"]["median_ms"], 3),
+           "over_bf16x3": round(e2e["bf16x3"]["median_ms"] / e2e["int8"]["median_ms"], 3),
+           "int8_kernels": k8, "precision16_kernels": k16, "int8_classes_ms": classes(k8), "precision16_classes_ms": classes(k16),
+           "trunk_gmac": round(macs / 1e9, 2), "int8_trunk_floor_ms": round(macs / INT8_PEAK_MACS * 1e3, 4),
+           "stem_alone": stem, "stem_bytes": stem_bytes, "float_pair_bytes": pair_bytes, "stem_gb_per_s": gbs,
+           "stem_share_of_copy_rate": round(gbs["stem3_fwd_q8_u8"] / gbs["device_copy_same_bytes"], 3),
+           "stem_codes_vs_quantized_float_stem": {"max_abs_diff": int(code_diff.max()), "share_off_by_one": round(float((code_diff == 1).float().mean()), 4)}}
+    line = json.dumps(res)
+    print(line)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+    return res
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
-    ap.add_argument("--images", type=int, default=256)
+    ap.add_argument("--model", choices=("poolresnet", "resnet"), default="poolresnet")
+    ap.add_argument("--images", type=int, default=None, help="frames per call (default 256; resnet: 32)")
     ap.add_argument("--launches", type=int, default=100, help="timed samples per mode")
     ap.add_argument("--calls", type=int, default=10, help="back-to-back calls per sample")
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--kernel-runs", type=int, default=50)
     ap.add_argument("--out", default=None)
     args = ap.parse_args(argv)
+    if args.images is None:
+        args.images = 32 if args.model == "resnet" else 256
+    if args.model == "resnet":
+        return main_resnet(args)
     import numpy as np
     import torch
     import fdet_amd  # noqa: F401
