@@ -13,6 +13,7 @@ the block input; everything else is recomputed in the fused tails.
 from __future__ import annotations
 
 from dataclasses import dataclass
+from types import SimpleNamespace
 from typing import Dict, List, Optional
 
 import torch
@@ -130,6 +131,67 @@ class _PsScope(list):
         self.release()
 
 
+@dataclass(frozen=True)
+class Stage:
+    """`run` consecutive blocks from block `k` on, all at one resolution, that a pass runs as one unit."""
+    kind: str             # "ps_pool": pooled block on PS; "ps_chain" / "chain": one-launch run (PS / fp32 I/O); "block": per layer
+    k: int
+    run: int
+    hk: int
+    pool: int
+    strips: bool          # the PS maps of the level are column strips
+    out_ps: bool          # hands its output on as a PS tensor (else fp32 NCHW)
+    fused_pool: bool      # pooling inside the conv epilogues: routing bytes are saved, not c
+    wgrad: str            # weight gradients: "ps" / "batched" (one launch per level, PS / fp32 operands) or "single" (per layer)
+    closes_level: bool    # backward: the level's queued weight gradients go out and after_block fires for its blocks
+
+
+@dataclass(frozen=True)
+class PassPlan:
+    """Every route decision of one forward + backward pass (ConvStack.plan)."""
+    N: int
+    p16: bool
+    stem_ps: bool         # the stem writes the first block's PS input itself
+    stem_x3: bool         # else: the bf16x3 stem forward
+    stem_wgrad: tuple     # (x3, p16) of the stem weight gradient
+    head_fused: bool      # head + loss + their gradients in one launch, where the caller gives targets
+    stages: tuple
+
+
+class _WgradQueue:
+    """(x, dz, weight name) of one backward pass's convs awaiting their level's batched weight-gradient launch, by route."""
+
+    def __init__(self, eng, N, p16, G, dev, after_block):
+        self.eng, self.N, self.p16, self.G, self.dev, self.after_block = eng, N, p16, G, dev, after_block
+        self.items = {"ps": [], "batched": []}
+        self.blocks = []                                   # blocks whose gradients are enqueued once the level closes
+
+    def add(self, route, x, dz, name):
+        self.items[route].append((x, dz, name))
+
+    def launch(self, hk):
+        e, N, F_, G = self.eng, self.N, self.eng.geo.filters, self.G
+        for route, items in self.items.items():
+            for i0 in range(0, len(items), 16):            # weight gradients of same-resolution convs: 16 to a launch
+                grp = items[i0:i0 + 16]
+                ops = [p[0] for p in grp], [p[1] for p in grp], [G[p[2] + ".weight"] for p in grp], [G[p[2] + ".bias"] for p in grp]
+                if route == "ps":
+                    ws = e._workspace("wgrad_ps", psm.conv3x3_wgrad_ps_ws_bytes(len(grp), N, F_, hk, hk), self.dev)
+                else:
+                    ws = e._workspace("wgrad_batched", hp.conv3x3_wgrad_batched_ws_bytes(len(grp), N, F_, F_, hk, hk), self.dev)
+                with e._t("conv3x3_wgrad", N, hk, e._conv_flops(N, hk) * len(grp), e._act_bytes(N, hk, 2) * len(grp)):
+                    (psm.conv3x3_wgrad_ps_batched if route == "ps" else hp.conv3x3_wgrad_batched)(*ops, ws, p16=self.p16)
+            items.clear()
+
+    def close(self, hk):
+        """The level is done: launch what is queued, then report its blocks (data-parallel bucket launch)."""
+        self.launch(hk)
+        if self.after_block is not None:
+            for k in sorted(self.blocks):
+                self.after_block(k)
+        self.blocks.clear()
+
+
 class ConvStack:
     """Owns packed weights, workspaces and saved activations; parameters are passed in as a
     dict of GPU tensors named like the reference's state_dict."""
@@ -163,7 +225,10 @@ class ConvStack:
         # multiple of 16 channels, e.g. PoolResnet-large F=128).  The stem forward, the head, the pooled-gradient routing and
         # the fp32-I/O block chain (64 channels with FDET_PS=0) keep their fp32-grade kernels.
         self.p16 = self.x3 and want == "bf16"
-        self._cur_N = 1                                    # batch size of the pass being planned (forward() sets it)
+        self._ps_pool_N = None                             # the batch size _ps_pool was filled for
+        # runs of un-pooled blocks as one LDS-resident launch (FDET_CHAIN=0: the per-layer kernels)
+        self.chain = self.x3 and os.environ.get("FDET_CHAIN", "1") != "0"
+        self._plans: Dict[tuple, PassPlan] = {}
         # training head fused with the loss (fdet_head_loss_fused: forward + yolo_loss + their gradients in one kernel on
         # the matrix cores); FDET_HEAD_FUSED=0 keeps the separate head_fwd / yolo_loss / head_bwd launches
         self.head_fused = self.x3 and os.environ.get("FDET_HEAD_FUSED", "1") != "0"
@@ -240,53 +305,77 @@ class ConvStack:
             self._ws[name] = t
         return t
 
-    def _fused_pool(self, hk: int, N: int = 1) -> bool:
-        return self.pool_fusion and hp.pool_fusion_supported(self.geo.filters, self.geo.filters, hk, hk, N)
+    # ------------------------------------------------------------------ plan
+    def plan(self, N: int, p16: Optional[bool] = None) -> PassPlan:
+        """Every route of a pass at batch size N in precision p16 (default: the engine's): a pure function of the geometry, the
+        engine's switches, N and p16, and the only place that asks the library's routing queries.  forward() runs it and
+        saves it, backward() runs the saved one, tests read it."""
+        p16 = self.p16 if p16 is None else bool(p16)
+        key = (N, p16, self.x3, self.pool_fusion, self.ps, self.ps_strips, self.chain, self.head_fused)
+        if key not in self._plans:
+            self._plans[key] = self._derive_plan(N, p16)
+        return self._plans[key]
+
+    def _derive_plan(self, N: int, p16: bool) -> PassPlan:
+        g, F_, lv = self.geo, self.geo.filters, self.lv
+
+        def fits32(hk):       # (the batch-dependent limit of run_ps: 32-bit byte offsets of the fp32 tensors the PS kernels touch)
+            return N * F_ * hk * hk * 4 < 2 ** 31
+
+        def wgrad_ps(hk):     # the PS weight gradient has a slab plan for this batch
+            return psm.conv3x3_wgrad_ps_ws_bytes(1, N, F_, hk, hk) > 0
+
+        def route(k):         # (kind, run) of the stage that starts at block k
+            if k >= len(lv):
+                return None, 0
+            hk, pool = lv[k]
+            # a pooled block runs on pre-split activations when its even map is 30..62 columns wide, or wider and kept as
+            # column strips (csrc/fdet_ps.h; FDET_PS_STRIPS=0: the round-2 kernels for wide maps)
+            if self.ps and pool == 2 and hk % 2 == 0 and hk >= 30 and fits32(hk) and \
+                    ((self.ps_strips and psm.strips_of(hk)[0] > 1 and wgrad_ps(hk)) if hk > 62 else
+                     hp.pool_fusion_supported(F_, F_, hk, hk, N)):
+                return "ps_pool", 1
+            # consecutive un-pooled blocks that can run as one LDS-resident chain (bf16x3, 64 channels, small maps), with
+            # their per-block tensors in PS where the PS weight gradient takes them
+            run = 0
+            if self.chain and pool == 1 and hp.block_chain_supported(F_, hk, hk):
+                run = 1
+                while k + run < len(lv) and lv[k + run] == (hk, 1) and run < 16:
+                    run += 1
+            if run > 1:
+                return ("ps_chain" if self.ps and wgrad_ps(hk) and fits32(hk) else "chain"), run
+            return "block", 1
+
+        stages, k = [], 0
+        while k < len(lv):
+            hk, pool = lv[k]
+            kind, run = route(k)
+            strips = kind == "ps_pool" and hk > 62
+            # (a strip level hands its pooled output on as fp32 NCHW; the next level's converter writes its halos)
+            out_ps = kind == "ps_pool" and not strips and route(k + 1)[0] in ("ps_pool", "ps_chain")
+            fused = kind == "ps_pool" or (kind == "block" and pool == 2 and self.pool_fusion and
+                                          hp.pool_fusion_supported(F_, F_, hk, hk, N))
+            if kind == "block":
+                wgrad = "batched" if self.x3 and hp.wgrad_x3_supported(N, F_, F_, hk, hk) else "single"
+            else:
+                wgrad = "batched" if kind == "chain" else "ps"
+            # weight gradients of a run of same-resolution blocks go out in one launch, behind the level's first block
+            closes = wgrad == "single" or not stages or stages[-1].hk != hk
+            stages.append(Stage(kind, k, run, hk, pool, strips, out_ps, fused, wgrad, closes))
+            k += run
+        # the stem writes the first block's PS input itself: the PoolResnet stem (k10 s8 p2, plain layout) or the Resnet stem
+        # (k3 s2 p1, column strips included)
+        stem = (g.in_ch, g.W, g.stem_k, g.stem_s, g.stem_p)
+        stem_k3 = (g.in_ch, F_, g.H, g.W, g.stem_k, g.stem_s, g.stem_p)
+        stem_ps = bool(stages) and stages[0].kind == "ps_pool" and self.x3 and \
+            ((not stages[0].strips and hp.stem_x3_supported(*stem)) or hp.stem_k3_fwd_ps_supported(*stem_k3))
+        # the stem weight gradient: the matrix-core kernel where one exists for the stem's shape, in precision16 where the
+        # pass runs it and the PoolResnet stem's kernel has its one-pass form (48 < Wo <= 60)
+        wg_x3 = self.x3 and ((g.W % 16 == 0 and hp.stem_x3_supported(*stem)) or hp.stem_k3_wgrad_x3_supported(*stem_k3))
+        return PassPlan(N, p16, stem_ps, self.x3 and hp.stem_x3_supported(*stem), (wg_x3, p16 and wg_x3 and 48 < self.h0 <= 60),
+                        self.head_loss_fusable(), tuple(stages))
 
     # ------------------------------------------------------------------ PS buffers
-    def _ps_block(self, k: int) -> bool:
-        """Block k runs on pre-split activations: a pooled block whose even map is 30..62 columns wide, or wider and kept
-        as column strips (csrc/fdet_ps.h; FDET_PS_STRIPS=0: the round-2 kernels for wide maps)."""
-        if not self.ps or k >= len(self.lv):
-            return False
-        hk, pool = self.lv[k]
-        if pool != 2 or hk % 2 or hk < 30:
-            return False
-        # (the batch-dependent limits of run_ps: 32-bit byte offsets of the fp32 tensors the pooled modes touch)
-        if self._cur_N * self.geo.filters * hk * hk * 4 >= 2 ** 31:
-            return False
-        if hk > 62:
-            return self.ps_strips and psm.strips_of(hk)[0] > 1 and psm.conv3x3_wgrad_ps_ws_bytes(1, self._cur_N, self.geo.filters, hk, hk) > 0
-        return self._fused_pool(hk, self._cur_N)
-
-    def _stem_ps(self) -> bool:
-        """The stem writes the first block's PS input itself (for the batch size of the pass, _cur_N): the PoolResnet stem
-        (k10 s8 p2, plain layout) or the Resnet stem (k3 s2 p1, column strips included)."""
-        g = self.geo
-        return self._ps_block(0) and self.x3 and \
-            ((not self._strips(self.h0) and hp.stem_x3_supported(g.in_ch, g.W, g.stem_k, g.stem_s, g.stem_p)) or
-             hp.stem_k3_fwd_ps_supported(g.in_ch, g.filters, g.H, g.W, g.stem_k, g.stem_s, g.stem_p))
-
-    def _stem_wgrad_kind(self):
-        """(x3, p16) of the stem weight gradient: the matrix-core kernel where one exists for the stem's shape, in precision16
-        where the engine runs it and the PoolResnet stem's kernel has its one-pass form (48 < Wo <= 60)."""
-        g = self.geo
-        x3 = self.x3 and ((g.W % 16 == 0 and hp.stem_x3_supported(g.in_ch, g.W, g.stem_k, g.stem_s, g.stem_p)) or
-                          hp.stem_k3_wgrad_x3_supported(g.in_ch, g.filters, g.H, g.W, g.stem_k, g.stem_s, g.stem_p))
-        return x3, self.p16 and x3 and 48 < self.h0 <= 60
-
-    def _strips(self, hk: int) -> bool:
-        return hk > 62
-
-    def _ps_chain(self, k: int) -> bool:
-        """The chain run starting at block k keeps its per-block tensors in PS (fdet_block_chain_*_ps) and its weight
-        gradients come from the PS kernel."""
-        if not self.ps or k >= len(self.lv) or self._chain_run(k) <= 1:
-            return False
-        hk = self.lv[k][0]
-        return psm.conv3x3_wgrad_ps_ws_bytes(1, self._cur_N, self.geo.filters, hk, hk) > 0 and \
-            self._cur_N * self.geo.filters * hk * hk * 4 < 2 ** 31
-
     def _ps_take(self, scope: "_PsScope", N: int, C: int, H: int, W: int, dev) -> "psm.PsTensor":
         """A zero-haloed PS buffer from the engine's pool; it returns to the pool when `scope` (kept alive by the saved
         state of a forward pass, or released at the end of an inference call) goes away.  Producers write real elements
@@ -297,19 +386,16 @@ class ConvStack:
         scope.append((key, t))
         return t
 
-    def _chain_run(self, k: int) -> int:
-        """Number of consecutive un-pooled blocks starting at block k that can run as one
-        LDS-resident chain (bf16x3, 64 channels, small maps); 0/1 = use the per-layer kernels."""
-        import os
-        if not self.x3 or os.environ.get("FDET_CHAIN", "1") == "0":
-            return 0
-        hk, pool = self.lv[k]
-        if pool != 1 or not hp.block_chain_supported(self.geo.filters, hk, hk):
-            return 0
-        run = 1
-        while k + run < len(self.lv) and self.lv[k + run] == (hk, 1) and run < 16:
-            run += 1
-        return run
+    def _as_ps(self, t, r, hk: int) -> "psm.PsTensor":
+        """`t` as a PS tensor of the pass `r`: an fp32 NCHW map (a level handed on in fp32, or a saved tensor that a caller
+        replaced) is converted into a leased buffer."""
+        if isinstance(t, psm.PsTensor):
+            return t
+        return psm.PsTensor.from_f32(t.to(F32).contiguous(), out=self._ps_take(r.scope, r.N, self.geo.filters, hk, hk, r.dev))
+
+    @staticmethod
+    def _names(st: Stage) -> List[str]:
+        return [f"residual_blocks.{q}" for q in range(st.k, st.k + st.run)]
 
     # ------------------------------------------------------------------ forward
     def forward(self, x: torch.Tensor, P: Dict[str, torch.Tensor], masks: Optional[Dict[str, torch.Tensor]] = None,
@@ -333,128 +419,33 @@ class ConvStack:
             x = x.to(F32).contiguous()
         self._ensure_packed(P)
         N, F_, dev = x.shape[0], g.filters, x.device
-        if N != self._cur_N:
+        if N != self._ps_pool_N:
             # PS buffers are sized per batch: a pool filled for another N (a last partial batch, a validation batch) would
             # only pile up ~260 MB sets outside the caching allocator -- drop it
             self._ps_pool.clear()
-            self._cur_N = N
+            self._ps_pool_N = N
+        plan = self.plan(N, self.p16)
         ws = self._workspace("stem", hp.stem_ws_bytes(N, g.in_ch, F_, g.H, g.W, g.stem_k, g.stem_s, g.stem_p), dev)
-        # the stem writes the first block's PS input itself: the PoolResnet stem (k10 s8 p2, plain layout) or the Resnet stem
-        # (k3 s2 p1, column strips included)
-        stem_ps = self._stem_ps()
-        if u8_frames and not stem_ps:                      # (a batch too large for the pre-split path: the separate x / 255)
+        if u8_frames and not plan.stem_ps:                 # (a batch too large for the pre-split path: the separate x / 255)
             x = hp.u8_to_f32_norm(x)
-        h = torch.empty(N, F_, self.h0, self.h0, dtype=F32, device=dev) if not stem_ps else None
-        stem_flops = 2.0 * N * F_ * g.in_ch * g.stem_k * g.stem_k * self.h0 * self.h0
-        stem_bytes = 4.0 * N * (g.in_ch * g.H * g.W + F_ * self.h0 * self.h0)
         scope = _PsScope(self._ps_pool)
-        h_ps = None
-        stem_x3 = self.x3 and hp.stem_x3_supported(g.in_ch, g.W, g.stem_k, g.stem_s, g.stem_p)
-        with self._t("stem_fwd", N, self.h0, stem_flops, stem_bytes):
-            if stem_ps:
-                h, h_ps = None, self._ps_take(scope, N, F_, self.h0, self.h0, dev)
-                psm.stem_fwd_ps(x, P["conv1.weight"], P["conv1.bias"], h_ps, g.stem_k, g.stem_s, g.stem_p, p16=self.p16)
+        # r: the running state of the pass -- h / h_ps: the current activation as fp32 NCHW or PS (the other is None)
+        r = SimpleNamespace(N=N, dev=dev, p16=plan.p16, P=P, masks=masks, scope=scope, h=None, h_ps=None, blocks=[] if save else None)
+        stem_flops = 2.0 * N * F_ * g.in_ch * g.stem_k * g.stem_k * self.h0 * self.h0
+        with self._t("stem_fwd", N, self.h0, stem_flops, 4.0 * N * (g.in_ch * g.H * g.W + F_ * self.h0 * self.h0)):
+            if plan.stem_ps:
+                r.h_ps = self._ps_take(scope, N, F_, self.h0, self.h0, dev)
+                psm.stem_fwd_ps(x, P["conv1.weight"], P["conv1.bias"], r.h_ps, g.stem_k, g.stem_s, g.stem_p, p16=plan.p16)
             else:
-                hp.stem_fwd(x, P["conv1.weight"], P["conv1.bias"], h, ws, g.stem_k, g.stem_s, g.stem_p, x3=stem_x3)
-        # (the precision is stamped into the saved state: backward() runs the pass in the precision of its forward)
-        saved = {"x": x, "blocks": [], "masks": masks, "ps_scope": scope, "p16": self.p16} if save else None
-        k = -1
-        while k + 1 < len(self.lv):
-            k += 1
-            hk, pool = self.lv[k]
-            if self._ps_block(k):
-                # pooled block on pre-split activations: conv1 -> a (PS); conv2 + tail -> pooled output (PS when the next
-                # block is a PS block too, else fp32 NCHW) + channel-innermost routing bytes
-                name = f"residual_blocks.{k}"
-                sc = masks[name] if masks is not None else None
-                if h_ps is None:
-                    h_ps = psm.PsTensor.from_f32(h, out=self._ps_take(scope, N, F_, hk, hk, dev))
-                a_ps = self._ps_take(scope, N, F_, hk, hk, dev)
-                with self._t("conv3x3_fwd", N, hk, self._conv_flops(N, hk), self._act_bytes(N, hk, 2)):
-                    psm.conv3x3_ps_fwd(h_ps, self._wpk[name + ".conv1.f"], P[name + ".conv1.bias"], a_ps, self.slope, p16=self.p16)
-                    psm.halo_exchange(a_ps, p16=self.p16)      # strips: conv2 (and the weight gradient) read a's edge columns
-                # (a strip level hands its pooled output on as fp32 NCHW; the next level's converter writes its halos)
-                nxt = (self._ps_block(k + 1) or self._ps_chain(k + 1)) and not self._strips(hk)
-                out_ps = self._ps_take(scope, N, F_, hk // 2, hk // 2, dev) if nxt else None
-                out = None if nxt else torch.empty(N, F_, hk // 2, hk // 2, dtype=F32, device=dev)
-                route = psm.route8_like(N, F_, hk, hk, dev) if save else None
-                with self._t("conv3x3_fwd_pool", N, hk, self._conv_flops(N, hk), self._act_bytes(N, hk, 2 + 0.25 + (1 / 16 if save else 0))):
-                    psm.conv3x3_ps_fwd_pool(a_ps, self._wpk[name + ".conv2.f"], P[name + ".conv2.bias"], h_ps, sc, out_ps, out,
-                                            route, self.slope, p16=self.p16)
-                if save:
-                    saved["blocks"].append((h_ps, a_ps, route))
-                h, h_ps = out, out_ps
-                continue
-            run = self._chain_run(k)
-            if run > 1 and self._ps_chain(k):
-                # blocks k .. k+run-1 keep their activation on the CU: one launch (fdet_block_chain_fwd_ps); what backward
-                # needs is kept in PS (a_k, block outputs: operands of the weight gradients; c_k: hi plane = its signs)
-                names = [f"residual_blocks.{kk}" for kk in range(k, k + run)]
-                if h_ps is None:
-                    h_ps = psm.PsTensor.from_f32(h, out=self._ps_take(scope, N, F_, hk, hk, dev))
-                a_l = [self._ps_take(scope, N, F_, hk, hk, dev) for _ in names] if save else None
-                c_l = [self._ps_take(scope, N, F_, hk, hk, dev) for _ in names] if save else None
-                o_l = [self._ps_take(scope, N, F_, hk, hk, dev) for _ in names[:-1]] if save else None
-                out = torch.empty(N, F_, hk, hk, dtype=F32, device=dev)
-                with self._t("chain_fwd", N, hk, 2 * run * self._conv_flops(N, hk), self._act_bytes(N, hk, 1 + (2.5 * run if save else 1))):
-                    psm.block_chain_fwd_ps(h_ps, [self._wpk[nm + ".conv1.f"] for nm in names], [P[nm + ".conv1.bias"] for nm in names],
-                                           [self._wpk[nm + ".conv2.f"] for nm in names], [P[nm + ".conv2.bias"] for nm in names],
-                                           [masks[nm] for nm in names] if masks is not None else None, a_l, c_l, o_l, out, self.slope,
-                                           p16=self.p16)
-                if save:
-                    for i in range(run):
-                        saved["blocks"].append((h_ps if i == 0 else o_l[i - 1], a_l[i], c_l[i]))
-                h, h_ps = out, None
-                k += run - 1
-                continue
-            if run > 1:
-                # the same with fp32 NCHW tensors (fdet_block_chain_fwd_bf16x3)
-                names = [f"residual_blocks.{kk}" for kk in range(k, k + run)]
-                a_l = [torch.empty(N, F_, hk, hk, dtype=F32, device=dev) for _ in names] if save else None
-                c_l = [torch.empty(N, F_, hk, hk, dtype=F32, device=dev) for _ in names] if save else None
-                o_l = [torch.empty(N, F_, hk, hk, dtype=F32, device=dev) if (save or i == run - 1) else None
-                       for i in range(run)]
-                with self._t("chain_fwd", N, hk, 2 * run * self._conv_flops(N, hk), self._act_bytes(N, hk, 1 + (3 * run if save else 1))):
-                    hp.block_chain_fwd(h, [self._wpk[nm + ".conv1.f"] for nm in names], [P[nm + ".conv1.bias"] for nm in names],
-                                       [self._wpk[nm + ".conv2.f"] for nm in names], [P[nm + ".conv2.bias"] for nm in names],
-                                       [masks[nm] for nm in names] if masks is not None else None, a_l, c_l, o_l, self.slope)
-                if save:
-                    for i in range(run):
-                        saved["blocks"].append((h if i == 0 else o_l[i - 1], a_l[i], c_l[i]))
-                h = o_l[-1]
-                k += run - 1
-                continue
-            name = f"residual_blocks.{k}"
-            sc = masks[name] if masks is not None else None
-            a = torch.empty(N, F_, hk, hk, dtype=F32, device=dev)
-            with self._t("conv3x3_fwd", N, hk, self._conv_flops(N, hk), self._act_bytes(N, hk, 2)):
-                hp.conv3x3_fwd(h, self._wpk[name + ".conv1.f"], P[name + ".conv1.bias"], F_, y_full=a, slope=self.slope, x3=self.x3,
-                               p16=self.p16)
-            out = torch.empty(N, F_, hk // pool, hk // pool, dtype=F32, device=dev)
-            if pool == 2 and self._fused_pool(hk, N):
-                # conv2 + lrelu + dropout*skip + maxpool in one kernel; c is never written, backward gets one
-                # routing byte per pooling window instead
-                c = torch.empty(N, F_, hk // 2, hk // 2, dtype=torch.uint8, device=dev) if save else None
-                with self._t("conv3x3_fwd_pool", N, hk, self._conv_flops(N, hk), self._act_bytes(N, hk, 2 + 0.25 + (1 / 16 if save else 0))):
-                    hp.conv3x3_fwd_pool(a, self._wpk[name + ".conv2.f"], P[name + ".conv2.bias"], h, sc, out, c, self.slope,
-                                        p16=self.p16)
-            elif pool == 2:
-                c = torch.empty_like(a)
-                with self._t("conv3x3_fwd", N, hk, self._conv_flops(N, hk), self._act_bytes(N, hk, 2)):
-                    hp.conv3x3_fwd(a, self._wpk[name + ".conv2.f"], P[name + ".conv2.bias"], F_, y_full=c, slope=self.slope, x3=self.x3,
-                                   p16=self.p16)
-                with self._t("tail_fwd", N, hk, 0.0, self._act_bytes(N, hk, 2.25)):
-                    hp.block_tail_fwd(c, h, sc, out, 2)
-            else:
-                c = torch.empty_like(a) if save else None
-                with self._t("conv3x3_fwd", N, hk, self._conv_flops(N, hk), self._act_bytes(N, hk, 4 if save else 3)):
-                    hp.conv3x3_fwd(a, self._wpk[name + ".conv2.f"], P[name + ".conv2.bias"], F_, y_full=c, skip=h,
-                                   drop_scale=sc, y_out=out, slope=self.slope, x3=self.x3, p16=self.p16)
-            if save:
-                saved["blocks"].append((h, a, c))
-            h = out
+                r.h = torch.empty(N, F_, self.h0, self.h0, dtype=F32, device=dev)
+                hp.stem_fwd(x, P["conv1.weight"], P["conv1.bias"], r.h, ws, g.stem_k, g.stem_s, g.stem_p, x3=plan.stem_x3)
+        for st in plan.stages:
+            getattr(self, "_fwd_" + st.kind)(st, r)
+        # (plan and precision are stamped into the saved state: backward() runs the pass its forward ran)
+        saved = {"x": x, "blocks": r.blocks, "masks": masks, "ps_scope": scope, "p16": plan.p16, "plan": plan} if save else None
+        h = r.h
         y = torch.empty(N, 5, g.S, g.S, dtype=F32, device=dev)
-        if loss_targets is not None and save and G is not None and self.head_loss_fusable():
+        if loss_targets is not None and save and G is not None and plan.head_fused:
             if tuple(loss_targets.shape) != tuple(y.shape):
                 raise ValueError(f"loss targets {tuple(loss_targets.shape)} != head output {tuple(y.shape)}")
             tg = loss_targets if (loss_targets.dtype == F32 and loss_targets.is_contiguous()) else loss_targets.to(F32).contiguous()
@@ -482,29 +473,96 @@ class ConvStack:
             scope.release()                                # inference: every PS buffer of the pass is free again
         return y, saved
 
+    def _fwd_ps_pool(self, st: Stage, r) -> None:
+        """Pooled block on pre-split activations: conv1 -> a (PS); conv2 + tail -> pooled output (PS when the next stage
+        takes PS, else fp32 NCHW) + channel-innermost routing bytes."""
+        N, F_, hk, dev, P, save = r.N, self.geo.filters, st.hk, r.dev, r.P, r.blocks is not None
+        name = f"residual_blocks.{st.k}"
+        x_ps = r.h_ps if r.h_ps is not None else self._as_ps(r.h, r, hk)
+        a_ps = self._ps_take(r.scope, N, F_, hk, hk, dev)
+        with self._t("conv3x3_fwd", N, hk, self._conv_flops(N, hk), self._act_bytes(N, hk, 2)):
+            psm.conv3x3_ps_fwd(x_ps, self._wpk[name + ".conv1.f"], P[name + ".conv1.bias"], a_ps, self.slope, p16=r.p16)
+            psm.halo_exchange(a_ps, p16=r.p16)             # strips: conv2 (and the weight gradient) read a's edge columns
+        out_ps = self._ps_take(r.scope, N, F_, hk // 2, hk // 2, dev) if st.out_ps else None
+        out = None if st.out_ps else torch.empty(N, F_, hk // 2, hk // 2, dtype=F32, device=dev)
+        route = psm.route8_like(N, F_, hk, hk, dev) if save else None
+        with self._t("conv3x3_fwd_pool", N, hk, self._conv_flops(N, hk), self._act_bytes(N, hk, 2 + 0.25 + (1 / 16 if save else 0))):
+            psm.conv3x3_ps_fwd_pool(a_ps, self._wpk[name + ".conv2.f"], P[name + ".conv2.bias"], x_ps,
+                                    r.masks[name] if r.masks is not None else None, out_ps, out, route, self.slope, p16=r.p16)
+        if save:
+            r.blocks.append((x_ps, a_ps, route))
+        r.h, r.h_ps = out, out_ps
+
+    def _fwd_chain_args(self, st: Stage, r):
+        names = self._names(st)
+        return ([self._wpk[nm + ".conv1.f"] for nm in names], [r.P[nm + ".conv1.bias"] for nm in names],
+                [self._wpk[nm + ".conv2.f"] for nm in names], [r.P[nm + ".conv2.bias"] for nm in names],
+                [r.masks[nm] for nm in names] if r.masks is not None else None)
+
+    def _fwd_ps_chain(self, st: Stage, r) -> None:
+        """The blocks of the run keep their activation on the CU: one launch (fdet_block_chain_fwd_ps); what backward needs is
+        kept in PS (a_k, block outputs: operands of the weight gradients; c_k: hi plane = its signs)."""
+        N, F_, hk, run, dev, save = r.N, self.geo.filters, st.hk, st.run, r.dev, r.blocks is not None
+        x_ps = r.h_ps if r.h_ps is not None else self._as_ps(r.h, r, hk)
+        a_l, c_l, o_l = ([self._ps_take(r.scope, N, F_, hk, hk, dev) for _ in range(n)] if save else None for n in (run, run, run - 1))
+        out = torch.empty(N, F_, hk, hk, dtype=F32, device=dev)
+        with self._t("chain_fwd", N, hk, 2 * run * self._conv_flops(N, hk), self._act_bytes(N, hk, 1 + (2.5 * run if save else 1))):
+            psm.block_chain_fwd_ps(x_ps, *self._fwd_chain_args(st, r), a_l, c_l, o_l, out, self.slope, p16=r.p16)
+        if save:
+            r.blocks.extend((x_ps if i == 0 else o_l[i - 1], a_l[i], c_l[i]) for i in range(run))
+        r.h, r.h_ps = out, None
+
+    def _fwd_chain(self, st: Stage, r) -> None:
+        """The same with fp32 NCHW tensors (fdet_block_chain_fwd_bf16x3)."""
+        N, F_, hk, run, dev, save = r.N, self.geo.filters, st.hk, st.run, r.dev, r.blocks is not None
+        a_l, c_l = ([torch.empty(N, F_, hk, hk, dtype=F32, device=dev) for _ in range(run)] if save else None for _ in (1, 2))
+        o_l = [torch.empty(N, F_, hk, hk, dtype=F32, device=dev) if (save or i == run - 1) else None for i in range(run)]
+        with self._t("chain_fwd", N, hk, 2 * run * self._conv_flops(N, hk), self._act_bytes(N, hk, 1 + (3 * run if save else 1))):
+            hp.block_chain_fwd(r.h, *self._fwd_chain_args(st, r), a_l, c_l, o_l, self.slope)
+        if save:
+            r.blocks.extend((r.h if i == 0 else o_l[i - 1], a_l[i], c_l[i]) for i in range(run))
+        r.h = o_l[-1]
+
+    def _fwd_block(self, st: Stage, r) -> None:
+        """One block, layer by layer, on fp32 NCHW tensors: pooling fused into conv2, as a separate tail, or none."""
+        N, F_, hk, pool, dev, P, save = r.N, self.geo.filters, st.hk, st.pool, r.dev, r.P, r.blocks is not None
+        name, h, x3, p16 = f"residual_blocks.{st.k}", r.h, self.x3, r.p16
+        sc = r.masks[name] if r.masks is not None else None
+        fl, w2, b2 = self._conv_flops(N, hk), self._wpk[name + ".conv2.f"], P[name + ".conv2.bias"]
+        a = torch.empty(N, F_, hk, hk, dtype=F32, device=dev)
+        with self._t("conv3x3_fwd", N, hk, fl, self._act_bytes(N, hk, 2)):
+            hp.conv3x3_fwd(h, self._wpk[name + ".conv1.f"], P[name + ".conv1.bias"], F_, y_full=a, slope=self.slope, x3=x3, p16=p16)
+        out = torch.empty(N, F_, hk // pool, hk // pool, dtype=F32, device=dev)
+        if st.fused_pool:
+            # conv2 + lrelu + dropout*skip + maxpool in one kernel; c is never written, backward gets one
+            # routing byte per pooling window instead
+            c = torch.empty(N, F_, hk // 2, hk // 2, dtype=torch.uint8, device=dev) if save else None
+            with self._t("conv3x3_fwd_pool", N, hk, fl, self._act_bytes(N, hk, 2 + 0.25 + (1 / 16 if save else 0))):
+                hp.conv3x3_fwd_pool(a, w2, b2, h, sc, out, c, self.slope, p16=p16)
+        elif pool == 2:
+            c = torch.empty_like(a)
+            with self._t("conv3x3_fwd", N, hk, fl, self._act_bytes(N, hk, 2)):
+                hp.conv3x3_fwd(a, w2, b2, F_, y_full=c, slope=self.slope, x3=x3, p16=p16)
+            with self._t("tail_fwd", N, hk, 0.0, self._act_bytes(N, hk, 2.25)):
+                hp.block_tail_fwd(c, h, sc, out, 2)
+        else:
+            c = torch.empty_like(a) if save else None
+            with self._t("conv3x3_fwd", N, hk, fl, self._act_bytes(N, hk, 4 if save else 3)):
+                hp.conv3x3_fwd(a, w2, b2, F_, y_full=c, skip=h, drop_scale=sc, y_out=out, slope=self.slope, x3=x3, p16=p16)
+        if save:
+            r.blocks.append((h, a, c))
+        r.h = out
+
     # ------------------------------------------------------------------ backward
     def backward(self, saved, dy: torch.Tensor, P: Dict[str, torch.Tensor], G: Dict[str, torch.Tensor],
                  after_block=None) -> None:
         """dy = d loss / d y (N,5,S,S).  Writes every parameter gradient into G[name]
         (overwrites; same names/shapes as P).  `after_block(k)` is called once block k's
-        gradients have been enqueued (data-parallel bucket launch).  Runs in the precision the forward pass ran in
-        (saved["p16"]), whatever set_precision() said since."""
-        p16 = bool(saved.get("p16", self.p16))
-        if p16 and not self.x3:
-            raise ValueError("backward: the saved pass ran in precision16, which this engine cannot run")
-        keep = self.p16
-        self.p16 = p16
-        try:
-            self._backward(saved, dy, P, G, after_block)
-        finally:
-            self.p16 = keep
-
-    def _backward(self, saved, dy, P, G, after_block) -> None:
-        g = self.geo
-        F_ = g.filters
+        gradients have been enqueued (data-parallel bucket launch).  Runs the plan of the forward pass (saved["plan"]): its
+        routes and its precision, whatever set_precision() said since."""
+        g, F_, plan = self.geo, self.geo.filters, saved["plan"]
         x, masks = saved["x"], saved["masks"]
-        N, dev = x.shape[0], x.device
-        self._cur_N = N                                    # the path decisions below are those of this pass's forward
+        N, dev = plan.N, x.device
         h_last, y = saved["h_last"], saved["y"]
         if saved.get("head_dout") is not None:
             dout = saved["head_dout"]                      # the fused head already ran its backward (G["out.*"] written)
@@ -518,214 +576,134 @@ class ConvStack:
             with self._t("head_bwd", N, hl, 4.0 * N * 5 * F_ * g.head_k ** 2 * g.S ** 2, self._act_bytes(N, hl, 2)):
                 hp.head_bwd(h_last, masks["head"] if masks is not None else None, P["out.weight"], y, dy, dout,
                             G["out.weight"], G["out.bias"], ws, g.head_k, g.head_p)
-        pending = []          # (x, dz, weight name) of same-resolution convs awaiting one batched wgrad launch
-
-        def flush(hk_):
-            if not pending:
-                return
-            fl_ = self._conv_flops(N, hk_)
-            for i0 in range(0, len(pending), 16):
-                grp = pending[i0:i0 + 16]
-                wsb_ = self._workspace("wgrad_batched", hp.conv3x3_wgrad_batched_ws_bytes(len(grp), N, F_, F_, hk_, hk_), dev)
-                with self._t("conv3x3_wgrad", N, hk_, fl_ * len(grp), self._act_bytes(N, hk_, 2) * len(grp)):
-                    hp.conv3x3_wgrad_batched([p_[0] for p_ in grp], [p_[1] for p_ in grp],
-                                             [G[p_[2] + ".weight"] for p_ in grp], [G[p_[2] + ".bias"] for p_ in grp], wsb_,
-                                             p16=self.p16)
-            pending.clear()
-
-        pending_ps = []       # the same for blocks on pre-split activations: (x PS, dz PS, weight name)
-
-        def flush_ps(hk_):
-            if not pending_ps:
-                return
-            fl_ = self._conv_flops(N, hk_)
-            for i0 in range(0, len(pending_ps), 16):
-                grp = pending_ps[i0:i0 + 16]
-                wsb_ = self._workspace("wgrad_ps", psm.conv3x3_wgrad_ps_ws_bytes(len(grp), N, F_, hk_, hk_), dev)
-                with self._t("conv3x3_wgrad", N, hk_, fl_ * len(grp), self._act_bytes(N, hk_, 2) * len(grp)):
-                    psm.conv3x3_wgrad_ps_batched([p_[0] for p_ in grp], [p_[1] for p_ in grp],
-                                                 [G[p_[2] + ".weight"] for p_ in grp], [G[p_[2] + ".bias"] for p_ in grp], wsb_,
-                                                 p16=self.p16)
-            pending_ps.clear()
-
-        # runs of blocks that went through the forward chain come back through the backward chain
-        chain_start = {}
-        kk = 0
-        while kk < g.num_blocks:
-            run = self._chain_run(kk)
-            if run > 1:
-                chain_start[kk + run - 1] = kk
-                kk += run
-            else:
-                kk += 1
-        k = g.num_blocks
-        while k > 0:
-            k -= 1
-            hk, pool = self.lv[k]
-            if k in chain_start and self._ps_chain(chain_start[k]):
-                k0 = chain_start[k]
-                ks = list(range(k0, k + 1))
-                names = [f"residual_blocks.{q}" for q in ks]
-                scope = saved.get("ps_scope")
-                if scope is None:
-                    scope = saved["ps_scope"] = _PsScope(self._ps_pool)
-
-                def as_ps(t):                             # (a caller may have replaced saved tensors by fp32 NCHW ones)
-                    if isinstance(t, psm.PsTensor):
-                        return t
-                    return psm.PsTensor.from_f32(t.to(F32).contiguous(), out=self._ps_take(scope, N, F_, hk, hk, dev))
-                x_l = [as_ps(saved["blocks"][q][0]) for q in ks]
-                a_l = [as_ps(saved["blocks"][q][1]) for q in ks]
-                c_l = [as_ps(saved["blocks"][q][2]) for q in ks]
-                dz1_l = [self._ps_take(scope, N, F_, hk, hk, dev) for _ in ks]
-                dz2_l = [self._ps_take(scope, N, F_, hk, hk, dev) for _ in ks]
-                dx = torch.empty_like(dout)
-                with self._t("chain_bwd", N, hk, 2 * len(ks) * self._conv_flops(N, hk), self._act_bytes(N, hk, 2 + 3 * len(ks))):
-                    psm.block_chain_bwd_ps(dout, [self._wpk[nm + ".conv1.b"] for nm in names], [self._wpk[nm + ".conv2.b"] for nm in names],
-                                           [masks[nm] for nm in names] if masks is not None else None, a_l, c_l, dz1_l, dz2_l, dx, self.slope,
-                                           p16=self.p16)
-                for i in reversed(range(len(ks))):
-                    pending_ps.append((a_l[i], dz2_l[i], names[i] + ".conv2"))
-                    pending_ps.append((x_l[i], dz1_l[i], names[i] + ".conv1"))
-                dout = dx
-                k = k0
-                if k == 0 or self.lv[k - 1][0] != hk:
-                    flush_ps(hk)
-                    if after_block is not None:
-                        for q in range(k, g.num_blocks):
-                            if self.lv[q][0] == hk:
-                                after_block(q)
-                continue
-            if k in chain_start:
-                k0 = chain_start[k]
-                ks = list(range(k0, k + 1))
-                names = [f"residual_blocks.{q}" for q in ks]
-                dz1_l = [torch.empty_like(saved["blocks"][q][1]) for q in ks]
-                dz2_l = [torch.empty_like(saved["blocks"][q][1]) for q in ks]
-                dx = torch.empty_like(dout)
-                with self._t("chain_bwd", N, hk, 2 * len(ks) * self._conv_flops(N, hk), self._act_bytes(N, hk, 2 + 4 * len(ks))):
-                    hp.block_chain_bwd(dout, [self._wpk[nm + ".conv1.b"] for nm in names], [self._wpk[nm + ".conv2.b"] for nm in names],
-                                       [masks[nm] for nm in names] if masks is not None else None,
-                                       [saved["blocks"][q][1] for q in ks], [saved["blocks"][q][2] for q in ks],
-                                       dz1_l, dz2_l, dx, self.slope)
-                for i in reversed(range(len(ks))):
-                    q = ks[i]
-                    pending.append((saved["blocks"][q][1], dz2_l[i], names[i] + ".conv2"))
-                    pending.append((saved["blocks"][q][0], dz1_l[i], names[i] + ".conv1"))
-                dout = dx
-                k = k0
-                if k == 0 or self.lv[k - 1][0] != hk:
-                    flush(hk)
-                    if after_block is not None:
-                        for q in range(k, g.num_blocks):
-                            if self.lv[q][0] == hk:
-                                after_block(q)
-                continue
-            name = f"residual_blocks.{k}"
-            xin, a, c = saved["blocks"][k]
-            sc = masks[name] if masks is not None else None
-            if self._ps_block(k) and c is not None and c.dtype == torch.uint8 and \
-                    (isinstance(a, psm.PsTensor) or isinstance(xin, psm.PsTensor) or c.dim() == 5):
-                # pooled block on pre-split activations (a caller may have replaced saved tensors by fp32 / NCHW ones)
-                scope = saved.get("ps_scope")
-                if scope is None:
-                    scope = saved["ps_scope"] = _PsScope(self._ps_pool)
-                if not isinstance(xin, psm.PsTensor):
-                    xin = psm.PsTensor.from_f32(xin.to(F32).contiguous(), out=self._ps_take(scope, N, F_, hk, hk, dev))
-                if not isinstance(a, psm.PsTensor):
-                    a = psm.PsTensor.from_f32(a.to(F32).contiguous(), out=self._ps_take(scope, N, F_, hk, hk, dev))
-                strips = self._strips(hk)
-                if c.dim() == 4:                           # routing bytes in NCHW -> channel-innermost
-                    if strips:
-                        raise ValueError("routing bytes of a strip level are per strip (ps.route8_shape)")
-                    c = c.view(N, F_ // 8, 8, hk // 2, hk // 2).permute(0, 1, 3, 4, 2).contiguous()
-                fl = self._conv_flops(N, hk)
-
-                def wgrad_now(x_, dz_, nm_, clean=False):
-                    # strips: the weight gradient wants ZERO halo slots in dz (a halo is not a position of its strip), the
-                    # data-gradient conv behind it the neighbour columns -- so each layer's weight gradient runs right
-                    # here, between the two halo passes, instead of in the level's batched launch (clean: the producer
-                    # cleared the halo slots itself)
-                    if not clean:
-                        psm.halo_exchange(dz_, zero_only=True, p16=self.p16)
-                    pending_ps.append((x_, dz_, nm_))
-                    flush_ps(hk)
-                    psm.halo_exchange(dz_, p16=self.p16)
-                dz2 = self._ps_take(scope, N, F_, hk, hk, dev)
-                with self._t("pool_route_bwd", N, hk, 0.0, self._act_bytes(N, hk, 1 + 0.25 + 1 / 16)):
-                    psm.pool_route_bwd_ps(dout, c, sc, dz2, self.slope, p16=self.p16)
-                if strips:
-                    wgrad_now(a, dz2, name + ".conv2", clean=True)      # fdet_pool_route_bwd_ps clears dz2's halo slots
-                dz1 = self._ps_take(scope, N, F_, hk, hk, dev)
-                with self._t("conv3x3_dgrad", N, hk, fl, self._act_bytes(N, hk, 3)):
-                    psm.conv3x3_ps_dgrad_act(dz2, self._wpk[name + ".conv2.b"], a, dz1, self.slope, p16=self.p16)
-                if strips:
-                    wgrad_now(xin, dz1, name + ".conv1")
-                dx = torch.empty(N, F_, hk, hk, dtype=F32, device=dev)
-                with self._t("conv3x3_dgrad_unpool", N, hk, fl, self._act_bytes(N, hk, 2 + 0.25 + 1 / 16)):
-                    psm.conv3x3_ps_dgrad_unpool(dz1, self._wpk[name + ".conv1.b"], dout, c, dx, self.slope, p16=self.p16)
-                if not strips:
-                    pending_ps.append((a, dz2, name + ".conv2"))
-                    pending_ps.append((xin, dz1, name + ".conv1"))
-                dout = dx
-                if k == 0 or self.lv[k - 1][0] != hk or not self._ps_block(k - 1):
-                    flush_ps(hk)
-                    if after_block is not None:
-                        for kk in range(k, g.num_blocks):
-                            if self.lv[kk][0] == hk:
-                                after_block(kk)
-                continue
-            dz2 = torch.empty_like(a)
-            fused_pool = pool == 2 and c.dtype == torch.uint8      # forward kept routing bytes instead of c
-            de = torch.empty_like(a) if (pool == 2 and not fused_pool) else None
-            if fused_pool:
-                with self._t("pool_route_bwd", N, hk, 0.0, self._act_bytes(N, hk, 1 + 0.25 + 1 / 16)):
-                    hp.pool_route_bwd(dout, c, sc, dz2, self.slope)
-            else:
-                with self._t("tail_bwd", N, hk, 0.0, self._act_bytes(N, hk, 4.25 if pool == 2 else 3)):
-                    hp.block_tail_bwd(dout, c, xin, sc, dz2, de, pool, self.slope)
-            if pool == 1:
-                de = dout
-            fl = self._conv_flops(N, hk)
-            batched = self.x3 and hp.wgrad_x3_supported(N, F_, F_, hk, hk)
-            if not batched:
-                wws = self._workspace("wgrad", hp.conv3x3_wgrad_ws_bytes(N, F_, F_, hk, hk), dev)
-                with self._t("conv3x3_wgrad", N, hk, fl, self._act_bytes(N, hk, 2)):
-                    hp.conv3x3_wgrad(a, dz2, G[name + ".conv2.weight"], G[name + ".conv2.bias"], wws)
-            dz1 = torch.empty_like(a)
-            with self._t("conv3x3_dgrad", N, hk, fl, self._act_bytes(N, hk, 3)):
-                hp.conv3x3_dgrad(dz2, self._wpk[name + ".conv2.b"], F_, dz1, act=a, slope=self.slope, x3=self.x3, p16=self.p16)
-            if not batched:
-                with self._t("conv3x3_wgrad", N, hk, fl, self._act_bytes(N, hk, 2)):
-                    hp.conv3x3_wgrad(xin, dz1, G[name + ".conv1.weight"], G[name + ".conv1.bias"], wws)
-            dx = torch.empty_like(a) if batched else dz2      # batched: dz2 stays alive until the flush
-            if fused_pool:
-                with self._t("conv3x3_dgrad_unpool", N, hk, fl, self._act_bytes(N, hk, 2 + 0.25 + 1 / 16)):
-                    hp.conv3x3_dgrad_unpool(dz1, self._wpk[name + ".conv1.b"], F_, dout, c, dx, self.slope, p16=self.p16)
-            else:
-                with self._t("conv3x3_dgrad", N, hk, fl, self._act_bytes(N, hk, 3)):
-                    hp.conv3x3_dgrad(dz1, self._wpk[name + ".conv1.b"], F_, dx, add=de, slope=self.slope, x3=self.x3, p16=self.p16)
-            dout = dx
-            if batched:
-                pending.append((a, dz2, name + ".conv2"))
-                pending.append((xin, dz1, name + ".conv1"))
-                # weight gradients of a run of same-resolution blocks go out in one launch
-                if k == 0 or self.lv[k - 1][0] != hk:
-                    flush(hk)
-                    if after_block is not None:
-                        for kk in range(k, g.num_blocks):
-                            if self.lv[kk][0] == hk:
-                                after_block(kk)
-            elif after_block is not None:
-                after_block(k)
+        if saved.get("ps_scope") is None:
+            saved["ps_scope"] = _PsScope(self._ps_pool)
+        r = SimpleNamespace(N=N, dev=dev, p16=plan.p16, P=P, G=G, masks=masks, scope=saved["ps_scope"], blocks=saved["blocks"],
+                            dout=dout, wq=_WgradQueue(self, N, plan.p16, G, dev, after_block))
+        for st in reversed(plan.stages):
+            getattr(self, "_bwd_" + st.kind)(st, r)
+            r.wq.blocks.extend(range(st.k, st.k + st.run))
+            if st.closes_level:
+                r.wq.close(st.hk)
         ws = self._workspace("stem", hp.stem_ws_bytes(N, g.in_ch, F_, g.H, g.W, g.stem_k, g.stem_s, g.stem_p), dev)
         stem_flops = 2.0 * N * F_ * g.in_ch * g.stem_k * g.stem_k * self.h0 * self.h0
         with self._t("stem_wgrad", N, self.h0, stem_flops, 4.0 * N * (g.in_ch * g.H * g.W + F_ * self.h0 * self.h0)):
-            stem_x3, stem_p16 = self._stem_wgrad_kind()
-            hp.stem_wgrad(x, dout, G["conv1.weight"], G["conv1.bias"], ws, g.stem_k, g.stem_s, g.stem_p, x3=stem_x3, p16=stem_p16)
-        if saved.get("ps_scope") is not None:
-            saved["ps_scope"].release()                    # the saved PS activations / gradients are dead: back to the pool
-            saved["blocks"] = []
+            hp.stem_wgrad(x, r.dout, G["conv1.weight"], G["conv1.bias"], ws, g.stem_k, g.stem_s, g.stem_p,
+                          x3=plan.stem_wgrad[0], p16=plan.stem_wgrad[1])
+        saved["ps_scope"].release()                        # the saved PS activations / gradients are dead: back to the pool
+        saved["blocks"] = []
+
+    def _bwd_ps_chain(self, st: Stage, r) -> None:
+        """The run comes back through the backward chain (fdet_block_chain_bwd_ps)."""
+        N, F_, hk, run, names = r.N, self.geo.filters, st.hk, st.run, self._names(st)
+        x_l, a_l, c_l = ([self._as_ps(r.blocks[q][j], r, hk) for q in range(st.k, st.k + run)] for j in range(3))
+        dz1_l = [self._ps_take(r.scope, N, F_, hk, hk, r.dev) for _ in names]
+        dz2_l = [self._ps_take(r.scope, N, F_, hk, hk, r.dev) for _ in names]
+        dx = torch.empty_like(r.dout)
+        with self._t("chain_bwd", N, hk, 2 * run * self._conv_flops(N, hk), self._act_bytes(N, hk, 2 + 3 * run)):
+            psm.block_chain_bwd_ps(r.dout, [self._wpk[nm + ".conv1.b"] for nm in names], [self._wpk[nm + ".conv2.b"] for nm in names],
+                                   [r.masks[nm] for nm in names] if r.masks is not None else None, a_l, c_l, dz1_l, dz2_l, dx,
+                                   self.slope, p16=r.p16)
+        for i in reversed(range(run)):
+            r.wq.add("ps", a_l[i], dz2_l[i], names[i] + ".conv2")
+            r.wq.add("ps", x_l[i], dz1_l[i], names[i] + ".conv1")
+        r.dout = dx
+
+    def _bwd_chain(self, st: Stage, r) -> None:
+        """The same with fp32 NCHW tensors (fdet_block_chain_bwd_bf16x3)."""
+        N, hk, run, names = r.N, st.hk, st.run, self._names(st)
+        x_l, a_l, c_l = ([r.blocks[q][j] for q in range(st.k, st.k + run)] for j in range(3))
+        dz1_l = [torch.empty_like(a) for a in a_l]
+        dz2_l = [torch.empty_like(a) for a in a_l]
+        dx = torch.empty_like(r.dout)
+        with self._t("chain_bwd", N, hk, 2 * run * self._conv_flops(N, hk), self._act_bytes(N, hk, 2 + 4 * run)):
+            hp.block_chain_bwd(r.dout, [self._wpk[nm + ".conv1.b"] for nm in names], [self._wpk[nm + ".conv2.b"] for nm in names],
+                               [r.masks[nm] for nm in names] if r.masks is not None else None, a_l, c_l, dz1_l, dz2_l, dx, self.slope)
+        for i in reversed(range(run)):
+            r.wq.add("batched", a_l[i], dz2_l[i], names[i] + ".conv2")
+            r.wq.add("batched", x_l[i], dz1_l[i], names[i] + ".conv1")
+        r.dout = dx
+
+    def _bwd_ps_pool(self, st: Stage, r) -> None:
+        """Pooled block on pre-split activations (a caller may have replaced saved tensors by fp32 / NCHW ones)."""
+        N, F_, hk, dev, p16, dout = r.N, self.geo.filters, st.hk, r.dev, r.p16, r.dout
+        name = f"residual_blocks.{st.k}"
+        sc = r.masks[name] if r.masks is not None else None
+        xin, a, c = r.blocks[st.k]
+        xin, a = self._as_ps(xin, r, hk), self._as_ps(a, r, hk)
+        if c.dim() == 4:                                   # routing bytes in NCHW -> channel-innermost
+            if st.strips:
+                raise ValueError("routing bytes of a strip level are per strip (ps.route8_shape)")
+            c = c.view(N, F_ // 8, 8, hk // 2, hk // 2).permute(0, 1, 3, 4, 2).contiguous()
+        fl = self._conv_flops(N, hk)
+
+        def wgrad(x_, dz_, nm_, clean=False):
+            # strips: the weight gradient wants ZERO halo slots in dz (a halo is not a position of its strip), the
+            # data-gradient conv behind it the neighbour columns -- so each layer's weight gradient runs right
+            # here, between the two halo passes, instead of in the level's batched launch (clean: the producer
+            # cleared the halo slots itself)
+            if st.strips and not clean:
+                psm.halo_exchange(dz_, zero_only=True, p16=p16)
+            r.wq.add("ps", x_, dz_, nm_)
+            if st.strips:
+                r.wq.launch(hk)
+                psm.halo_exchange(dz_, p16=p16)
+        dz2 = self._ps_take(r.scope, N, F_, hk, hk, dev)
+        with self._t("pool_route_bwd", N, hk, 0.0, self._act_bytes(N, hk, 1 + 0.25 + 1 / 16)):
+            psm.pool_route_bwd_ps(dout, c, sc, dz2, self.slope, p16=p16)
+        if st.strips:
+            wgrad(a, dz2, name + ".conv2", clean=True)     # fdet_pool_route_bwd_ps clears dz2's halo slots
+        dz1 = self._ps_take(r.scope, N, F_, hk, hk, dev)
+        with self._t("conv3x3_dgrad", N, hk, fl, self._act_bytes(N, hk, 3)):
+            psm.conv3x3_ps_dgrad_act(dz2, self._wpk[name + ".conv2.b"], a, dz1, self.slope, p16=p16)
+        if st.strips:
+            wgrad(xin, dz1, name + ".conv1")
+        dx = torch.empty(N, F_, hk, hk, dtype=F32, device=dev)
+        with self._t("conv3x3_dgrad_unpool", N, hk, fl, self._act_bytes(N, hk, 2 + 0.25 + 1 / 16)):
+            psm.conv3x3_ps_dgrad_unpool(dz1, self._wpk[name + ".conv1.b"], dout, c, dx, self.slope, p16=p16)
+        if not st.strips:
+            wgrad(a, dz2, name + ".conv2")
+            wgrad(xin, dz1, name + ".conv1")
+        r.dout = dx
+
+    def _bwd_block(self, st: Stage, r) -> None:
+        """One block, layer by layer, on fp32 NCHW tensors."""
+        N, F_, hk, pool, p16, G, dout = r.N, self.geo.filters, st.hk, st.pool, r.p16, r.G, r.dout
+        name, x3, batched = f"residual_blocks.{st.k}", self.x3, st.wgrad == "batched"
+        sc = r.masks[name] if r.masks is not None else None
+        xin, a, c = r.blocks[st.k]
+        dz2 = torch.empty_like(a)
+        de = torch.empty_like(a) if (pool == 2 and not st.fused_pool) else None
+        if st.fused_pool:                                  # forward kept routing bytes instead of c
+            with self._t("pool_route_bwd", N, hk, 0.0, self._act_bytes(N, hk, 1 + 0.25 + 1 / 16)):
+                hp.pool_route_bwd(dout, c, sc, dz2, self.slope)
+        else:
+            with self._t("tail_bwd", N, hk, 0.0, self._act_bytes(N, hk, 4.25 if pool == 2 else 3)):
+                hp.block_tail_bwd(dout, c, xin, sc, dz2, de, pool, self.slope)
+        if pool == 1:
+            de = dout
+        fl = self._conv_flops(N, hk)
+        if not batched:
+            wws = self._workspace("wgrad", hp.conv3x3_wgrad_ws_bytes(N, F_, F_, hk, hk), r.dev)
+            with self._t("conv3x3_wgrad", N, hk, fl, self._act_bytes(N, hk, 2)):
+                hp.conv3x3_wgrad(a, dz2, G[name + ".conv2.weight"], G[name + ".conv2.bias"], wws)
+        dz1 = torch.empty_like(a)
+        with self._t("conv3x3_dgrad", N, hk, fl, self._act_bytes(N, hk, 3)):
+            hp.conv3x3_dgrad(dz2, self._wpk[name + ".conv2.b"], F_, dz1, act=a, slope=self.slope, x3=x3, p16=p16)
+        if not batched:
+            with self._t("conv3x3_wgrad", N, hk, fl, self._act_bytes(N, hk, 2)):
+                hp.conv3x3_wgrad(xin, dz1, G[name + ".conv1.weight"], G[name + ".conv1.bias"], wws)
+        dx = torch.empty_like(a) if batched else dz2       # batched: dz2 stays alive until the level's launch
+        if st.fused_pool:
+            with self._t("conv3x3_dgrad_unpool", N, hk, fl, self._act_bytes(N, hk, 2 + 0.25 + 1 / 16)):
+                hp.conv3x3_dgrad_unpool(dz1, self._wpk[name + ".conv1.b"], F_, dout, c, dx, self.slope, p16=p16)
+        else:
+            with self._t("conv3x3_dgrad", N, hk, fl, self._act_bytes(N, hk, 3)):
+                hp.conv3x3_dgrad(dz1, self._wpk[name + ".conv1.b"], F_, dx, add=de, slope=self.slope, x3=x3, p16=p16)
+        if batched:
+            r.wq.add("batched", a, dz2, name + ".conv2")
+            r.wq.add("batched", xin, dz1, name + ".conv1")
+        r.dout = dx
 
 
 def param_names(num_blocks: int) -> List[str]:

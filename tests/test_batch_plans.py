@@ -1,6 +1,6 @@
 """Batch-size-dependent kernel choices of the engines against the library's own plan checks (CPU only).
 
-The engines pick kernels per batch (ConvStack._cur_N feeds _ps_block, _ps_chain, the stem decisions and the PS weight
+The engines pick kernels per batch (ConvStack.plan(N): the PS blocks and chains, the stem decisions and the PS weight
 gradient's workspace plan), and the C entry points refuse shapes whose 32-bit offsets a batch would overflow.  For every
 deployed geometry and a sweep of batch sizes around each switch, every stage the engine routes a training step (and the
 uint8 frame path) to must be accepted by the side-effect-free query of that entry point -- the same check function the entry
@@ -23,45 +23,39 @@ def _around(*ts):
 
 
 def conv_stack_stages(eng, N):
-    """[(stage, accepted)] of one training step (forward + backward) at batch N, walked as ConvStack.forward / _backward
-    walk it, through the engine's own decisions."""
-    eng._cur_N = N
+    """[(stage, accepted)] of one training step (forward + backward) at batch N: every stage of the engine's plan of the pass
+    against the side-effect-free query of the entry points it is routed to."""
+    plan = eng.plan(N)
     g = eng.geo
     F_ = g.filters
     out = []
-    if eng._stem_ps():
-        out.append(("stem_fwd_ps", hp.stem_fwd_ps_ok(N, g.in_ch, F_, g.H, g.W, g.stem_k, g.stem_s, g.stem_p, p16=eng.p16)))
+    if plan.stem_ps:
+        out.append(("stem_fwd_ps", hp.stem_fwd_ps_ok(N, g.in_ch, F_, g.H, g.W, g.stem_k, g.stem_s, g.stem_p, p16=plan.p16)))
         if eng.u8_frames_ok():
-            out.append(("stem_fwd_ps_u8", hp.stem_fwd_ps_ok(N, g.in_ch, F_, g.H, g.W, g.stem_k, g.stem_s, g.stem_p, p16=eng.p16,
+            out.append(("stem_fwd_ps_u8", hp.stem_fwd_ps_ok(N, g.in_ch, F_, g.H, g.W, g.stem_k, g.stem_s, g.stem_p, p16=plan.p16,
                                                             u8=True)))
-    k = 0
-    while k < len(eng.lv):
-        hk, pool = eng.lv[k]
-        if eng._ps_block(k):
-            nxt = (eng._ps_block(k + 1) or eng._ps_chain(k + 1)) and not eng._strips(hk)
+    for st in plan.stages:
+        k, hk, run = st.k, st.hk, st.run
+        if st.kind == "ps_pool":
             out.append((f"block{k}@{hk} conv_ps", psm.conv3x3_ps_ok(N, F_, F_, hk, hk, 0)))
-            out.append((f"block{k}@{hk} conv_ps_pool", psm.conv3x3_ps_ok(N, F_, F_, hk, hk, 2 if nxt else 1)))
+            out.append((f"block{k}@{hk} conv_ps_pool", psm.conv3x3_ps_ok(N, F_, F_, hk, hk, 2 if st.out_ps else 1)))
             out.append((f"block{k}@{hk} wgrad_ps", psm.conv3x3_wgrad_ps_ws_bytes(1, N, F_, hk, hk) > 0))
-            k += 1
-            continue
-        run = eng._chain_run(k)
-        if run > 1:
-            ps = eng._ps_chain(k)
+        elif st.kind in ("ps_chain", "chain"):
+            ps = st.kind == "ps_chain"
+            assert st.wgrad == ("ps" if ps else "batched")
             out.append((f"chain{k}@{hk} ps={ps}", hp.block_chain_ok(N, F_, hk, hk, ps)))
             if ps:
                 out.append((f"chain{k}@{hk} wgrad_ps", psm.conv3x3_wgrad_ps_ws_bytes(min(16, 2 * run), N, F_, hk, hk) > 0))
             else:
                 out.append((f"chain{k}@{hk} wgrad_batched", hp.conv3x3_wgrad_batched_ws_bytes(min(16, 2 * run), N, F_, F_, hk, hk) > 0))
-            k += run
-            continue
-        if pool == 2 and eng._fused_pool(hk, N):
-            out.append((f"block{k}@{hk} fwd_pool", hp.pool_fusion_supported(F_, F_, hk, hk, N)))
-        if eng.x3 and hp.wgrad_x3_supported(N, F_, F_, hk, hk):
-            out.append((f"block{k}@{hk} wgrad_batched", hp.conv3x3_wgrad_batched_ws_bytes(2, N, F_, F_, hk, hk) > 0))
         else:
-            out.append((f"block{k}@{hk} wgrad", hp.conv3x3_wgrad_ws_bytes(N, F_, F_, hk, hk) > 0))
-        k += 1
-    x3, p16 = eng._stem_wgrad_kind()
+            if st.fused_pool:
+                out.append((f"block{k}@{hk} fwd_pool", hp.pool_fusion_supported(F_, F_, hk, hk, N)))
+            if st.wgrad == "batched":
+                out.append((f"block{k}@{hk} wgrad_batched", hp.conv3x3_wgrad_batched_ws_bytes(2, N, F_, F_, hk, hk) > 0))
+            else:
+                out.append((f"block{k}@{hk} wgrad", hp.conv3x3_wgrad_ws_bytes(N, F_, F_, hk, hk) > 0))
+    x3, p16 = plan.stem_wgrad
     if x3:
         out.append((f"stem_wgrad p16={p16}", hp.stem_wgrad_x3_ok(N, g.in_ch, F_, g.H, g.W, g.stem_k, g.stem_s, g.stem_p, p16=p16)))
     out.append(("stem_ws", hp.stem_ws_bytes(N, g.in_ch, F_, g.H, g.W, g.stem_k, g.stem_s, g.stem_p) > 0))
@@ -99,12 +93,12 @@ def test_switches_sit_where_the_gpu_tests_expect_them():
     """tests/test_gpu_batch_sizes.py puts a batch and its halves on the two sides of these switches."""
     e = PoolResnet(64, (3, 480, 480), 10).engine
     for N, want in ((1200, True), (2330, True), (2331, False), (2400, False)):
-        e._cur_N = N
-        assert e._ps_block(0) == want and e._stem_ps() == want, N
+        p = e.plan(N)
+        assert (p.stages[0].kind == "ps_pool") == want and p.stem_ps == want, N
     r = Resnet(64, (3, 640, 640), 20).engine
     for N, want in ((42, True), (81, True), (82, False), (84, False)):
-        r._cur_N = N
-        assert r._ps_block(0) == want and r._ps_block(1), N
+        p = r.plan(N)
+        assert (p.stages[0].kind == "ps_pool") == want and p.stages[1].kind == "ps_pool", N
 
 
 @pytest.mark.parametrize("N", sorted(set(SWEEP) | {776, 777, 800, 1165, 1166, 2330, 2331}))
@@ -113,8 +107,7 @@ def test_precision16_keeps_its_one_pass_stem_weight_gradient_at_every_batch(N):
     for F_ in (64, 128):
         eng = PoolResnet(F_, (3, 480, 480), 10).engine
         eng.set_precision("bf16")
-        eng._cur_N = N
-        assert eng._stem_wgrad_kind() == (True, True), (F_, N)
+        assert eng.plan(N).stem_wgrad == (True, True), (F_, N)
         assert hp.stem_wgrad_x3_ok(N, 3, F_, 480, 480, 10, 8, 2, p16=True), (F_, N)
 
 

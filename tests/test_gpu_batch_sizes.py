@@ -1,8 +1,8 @@
 """Training and inference at small, odd, deployed and switch-crossing batch sizes.
 
-The engines pick their kernels per batch (ConvStack._stem_ps / _ps_block / _ps_chain, the PS weight gradient's slab plan, the
-32-bit offset limits of the C plans).  Small and odd batches are compared with the oracle; batches on the far side of a
-switch are compared with their halves (which sit on the near side): forward and loss bit-exact where both run the same
+The engines pick their kernels per batch (ConvStack.plan(N): the stem, PS block and PS chain routes; the PS weight gradient's
+slab plan; the 32-bit offset limits of the C plans).  Small and odd batches are compared with the oracle; batches on the
+far side of a switch are compared with their halves (which sit on the near side): forward and loss bit-exact where both run the same
 kernels, else within 1e-4.  Gradients add up to 1e-4 of each tensor's scale where both sides run the same kernels.  Where
 they do not (fp32-I/O vs pre-split activations, which keep 16 significant bits), the gradient is a discontinuous function
 of the activations (pool routing, LeakyReLU kinks), so the two sides are compared with test_gpu_model's bounds for one step
@@ -246,8 +246,7 @@ def test_poolresnet64_batch800_stem_runs_in_chunks(prec):
     eng = model.engine
     assert B // 2 <= _stem_launch_images() < B
     for n in (B, B // 2):
-        eng._cur_N = n
-        assert eng._stem_ps() and eng._stem_wgrad_kind() == (True, prec == "bf16"), n
+        assert eng.plan(n).stem_ps and eng.plan(n).stem_wgrad == (True, prec == "bf16"), n
     x, y, masks = _inputs(spec, B, 480, 10, seed=102)
     model.train()
     full = _to_cpu(_step(model, x, y, masks))
@@ -283,10 +282,8 @@ def test_resnet64_640_batch84_level320_leaves_ps():
     _need(40)
     spec, P, model = _yolo_model("resnet", 64, 640, 20, 10, seed=121)
     eng = model.engine
-    eng._cur_N = B
-    assert not eng._ps_block(0) and eng._ps_block(1)
-    eng._cur_N = B // 2
-    assert eng._ps_block(0) and eng._ps_block(1)
+    assert [st.kind == "ps_pool" for st in eng.plan(B).stages[:2]] == [False, True]
+    assert [st.kind == "ps_pool" for st in eng.plan(B // 2).stages[:2]] == [True, True]
     x, y, masks = _inputs(spec, B, 640, 20, seed=122)
     model.train()
     full = _to_cpu(_step(model, x, y, masks))
@@ -303,10 +300,9 @@ def test_poolresnet64_batch2400_level60_leaves_ps():
     _need(120)
     spec, P, model = _yolo_model("poolresnet", 64, 480, 10, 10, seed=131)
     eng = model.engine
-    eng._cur_N = B
-    assert not eng._ps_block(0) and not eng._stem_ps() and eng._ps_block(1)
-    eng._cur_N = B // 2
-    assert eng._ps_block(0) and eng._stem_ps()
+    full, half = eng.plan(B), eng.plan(B // 2)
+    assert full.stages[0].kind != "ps_pool" and not full.stem_ps and full.stages[1].kind == "ps_pool"
+    assert half.stages[0].kind == "ps_pool" and half.stem_ps
     x, y, masks = _inputs(spec, B, 480, 10, seed=132)
     model.train()
     full = _to_cpu(_step(model, x, y, masks))
@@ -328,8 +324,7 @@ def test_poolresnet128_batch1166_staged_wgrad60(prec):
     assert (B // 2) * 128 * 60 * 60 < 2 ** 29 <= B * 128 * 60 * 60
     from fdet_amd import hotpath as hp
     for n in (B, B // 2):
-        eng._cur_N = n
-        assert hp.wgrad_x3_supported(n, 128, 128, 60, 60) and eng._stem_wgrad_kind() == (True, prec == "bf16"), n
+        assert hp.wgrad_x3_supported(n, 128, 128, 60, 60) and eng.plan(n).stem_wgrad == (True, prec == "bf16"), n
     x, y, masks = _inputs(spec, B, 480, 10, seed=142)
     model.train()
     full = _to_cpu(_step(model, x, y, masks))

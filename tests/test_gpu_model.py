@@ -359,7 +359,7 @@ def test_reference_f64_train_step_through_the_pre_split_kernels(fd, golden):
         assert float(sd[n].double().sum()) == s, n          # same seed -> the reference constructor's parameters
     model = model.cuda().train()
     eng = model.engine
-    assert eng.x3 and eng.ps and eng._ps_block(0) and eng._ps_block(1) and eng._ps_chain(2)
+    assert eng.x3 and eng.ps and [(st.kind, st.k) for st in eng.plan(2).stages] == [("ps_pool", 0), ("ps_pool", 1), ("ps_chain", 2)]
     mm = ModelMeta(model=model, lr=1e-4)
     mm.configure_optimizers()
     x_u8 = _redraw_u8(2, 480, int(g["x_seed"]), g["x_sum"])
