@@ -1187,7 +1187,8 @@ int fdet_jpeg_enc_emit(const fdet_jpeg_enc_desc* descs, const fdet_jpeg_enc_desc
  * export for deployment); the arithmetic below is this project's contract, restated in numpy by tests/q8_cpu_ref.py, and
  * the GPU results equal that restatement bit for bit.  Resnet shares the trunk (its blocks pool while the map is larger than
  * S) and enters it through an integer stem of its own, fdet_stem3_fwd_q8_u8 at the end of this block (restated by
- * tests/q8_resnet_cpu_ref.py): with it the network is integer from the frame bytes to the head's input.
+ * tests/q8_resnet_cpu_ref.py): with it the network is integer from the frame bytes to the head's input.  PoolResnet has the
+ * same kind of stem as an option, fdet_stem10_fwd_q8_u8 (restated by tests/q8_pool_stem_cpu_ref.py).
  *
  * Quantisation is symmetric: q = clamp(rintf(x * (1.0f / s)), -127, 127) (round half to even, NaN -> 0, -128 never
  * produced), x = float(q) * s.  Activation scales are per tensor, weight scales per output channel.
@@ -1277,6 +1278,28 @@ int fdet_stem_fwd_q8_ok(int N, int Cin, int F, int H, int W, int k, int stride, 
 int fdet_stem3_fwd_q8_u8(const unsigned char* frames, const int8_t* w_q, const int32_t* b_q, const float* mul, int8_t* q,
                          int N, int Cin, int F, int H, int W, void* stream);
 int fdet_stem3_fwd_q8_ok(int N, int Cin, int F, int H, int W);
+
+/* The PoolResnet stem (10x10, stride 8, pad 2, 3 -> F channels) on the uint8 frames in the same INTEGER arithmetic, on
+ * v_mfma_i32_16x16x64_i8 (restated by tests/q8_pool_stem_cpu_ref.py).  The input is the frame itself at the fixed scale
+ * s_in = 1.0f / 255.0f, (w_q, b_q, mul) are prepared exactly as for a trunk conv from (conv1.weight, conv1.bias, s_in, s_out):
+ *     acc = b_q[co] + sum over (ci,ky,kx) of x_u8[ci][8oy+ky-2][8ox+kx-2] * w_q[co][ci][ky][kx]    int32, exact; outside
+ *                                                                                                   the image: 0
+ *     t   = float(acc) * mul[co]                            (int -> float RNE, one fp32 multiply)
+ *     q   = clamp(rintf(t), -127, 127)                      (half to even; no LeakyReLU: the reference's stem has none)
+ *   frames  planar uint8 [N][3][H][W]
+ *   w_q     int8 [F][32][16]: row kr = ci*10+ky (rows 30 and 31 ZERO), slot kx (slots 10..15 ZERO) -- 512 bytes per output
+ *           channel, a plain permutation of [F][3][10][10] plus zero padding (hotpath.q8_pack_stem10_weights does it with torch)
+ *   b_q     int32 [F];  mul fp32 [F]
+ *   q       Q8 [N][Ho+2][Wo+2][F] with Ho = (H - 6) / 8 + 1, Wo = (W - 6) / 8 + 1 (integer division): real pixels only, the
+ *           halo is untouched, nothing is written past the tensor
+ * Accepted: Cin == 3, F a multiple of 64 up to 256, 6 <= H, W <= 4096 (no alignment requirement on W: rows are read as
+ * bytes where W % 4 != 0 or the frame pointer is not 4-byte aligned), q under 2^31 bytes; w_q, b_q, mul and q 16-byte
+ * aligned.  (The kernel stages the rows as x - 128 for the signed MFMA and folds 128 * sum(w_q[co]) into the bias: internal,
+ * exact, the entry takes the plain contract values.)  Large batches run as consecutive launches over image chunks.
+ * fdet_stem10_fwd_q8_ok: the entry point accepts N images of this shape (launches nothing). */
+int fdet_stem10_fwd_q8_u8(const unsigned char* frames, const int8_t* w_q, const int32_t* b_q, const float* mul, int8_t* q,
+                          int N, int Cin, int F, int H, int W, void* stream);
+int fdet_stem10_fwd_q8_ok(int N, int Cin, int F, int H, int W);
 
 #ifdef __cplusplus
 }

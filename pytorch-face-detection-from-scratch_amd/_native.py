@@ -202,6 +202,8 @@ SIGNATURES = {
     "fdet_stem_fwd_q8_ok": (_I, [_I, _I, _I, _I, _I, _I, _I, _I]),
     "fdet_stem3_fwd_q8_u8": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "fdet_stem3_fwd_q8_ok": (_I, [_I, _I, _I, _I, _I]),
+    "fdet_stem10_fwd_q8_u8": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
+    "fdet_stem10_fwd_q8_ok": (_I, [_I, _I, _I, _I, _I]),
 }
 
 

@@ -4,7 +4,7 @@
         [--tile 480 --overlap 0.25 --no-whole --edge-margin 0 --probability-threshold P --iou-threshold T --precision 16]
         [--flip --vote --min-votes N] [--draw DIR [--anonymize pixelate] [--blocks N] [--draw-format png|jpg] [--no-outline]]
         [--chips DIR [--chip-size N] [--chip-margin F] [--chip-format png|jpg]] [--device-jpeg-encode] [--jpeg-quality Q]
-        [--int8 [--calib DIR] [--calib-images N]]
+        [--int8 [--calib DIR] [--calib-images N] [--int8-stem {float,integer}]]
 
 The images under DIR (searched recursively: .jpg .jpeg .png .bmp) are decoded with PIL into a device image bank
 (`bank_from_files`; `--device-jpeg`: baseline JPEGs are reconstructed on the device instead, with the same bytes), `tiling.TiledDetector` runs the model on overlapping windows of each image (and on the whole image
@@ -25,7 +25,8 @@ files encoded on the device (`datasets/jpeg.py DeviceJpegEncoder`)
 the compressed scans are copied to the host.
 `--int8` (poolresnet) runs the residual trunk post-training-quantised on the integer matrix cores (`quantize.py`, DESIGN.md
 5j): the activation scales are calibrated first, with the float model, on the first `--calib-images` images (32) under
-`--calib DIR` (default: the input images), each resized whole to the model resolution.
+`--calib DIR` (default: the input images), each resized whole to the model resolution.  `--int8-stem integer` gives the
+int8 model the integer uint8-frame stem; the default, `float`, keeps the float stem and its bytes.
 """
 import argparse
 import os
@@ -64,13 +65,17 @@ def add_int8_arguments(ap) -> None:
     ap.add_argument("--int8", action="store_true", help="poolresnet: run the residual trunk in int8 (post-training quantisation)")
     ap.add_argument("--calib", default=None, metavar="DIR", help="with --int8: calibration images (default: the first input images)")
     ap.add_argument("--calib-images", type=int, default=None, help="with --int8: number of calibration images (32)")
+    ap.add_argument("--int8-stem", choices=("float", "integer"), default=None,
+                    help="with --int8: the stem of the int8 model, float (default) or the integer uint8-frame kernel")
 
 
 def check_int8_arguments(ap, args) -> None:
     if not args.int8:
-        for flag, given in (("--calib", args.calib is not None), ("--calib-images", args.calib_images is not None)):
+        for flag, given in (("--calib", args.calib is not None), ("--calib-images", args.calib_images is not None),
+                            ("--int8-stem", args.int8_stem is not None)):
             if given:
                 ap.error(f"{flag} needs --int8")
+        args.int8_stem = "float"
         return
     if args.precision == 16:
         ap.error("--int8 and --precision 16 are two arithmetic modes of the same convolutions: choose one")
@@ -79,6 +84,7 @@ def check_int8_arguments(ap, args) -> None:
     if args.calib_images is not None and args.calib_images < 1:
         ap.error("--calib-images must be >= 1")
     args.calib_images = 32 if args.calib_images is None else args.calib_images
+    args.int8_stem = "float" if args.int8_stem is None else args.int8_stem
 
 
 def image_paths(root):
@@ -98,7 +104,7 @@ def quantize_loaded_model(model, args, default_bank=None, decoder="pil"):
         bank = bank_from_files(paths, "cuda", decoder=decoder)
     qp = calibrate(model, bank_frames(bank, model.input_shape[1:], args.calib_images))
     print(f"int8: calibrated on {qp.images_seen} images ({qp.method})")
-    return Int8PoolResnet(model, qp)
+    return Int8PoolResnet(model, qp, stem=getattr(args, "int8_stem", None) or "float")
 
 
 def add_tile_arguments(ap) -> None:

@@ -1681,3 +1681,38 @@ def stem3_fwd_q8_u8(frames: torch.Tensor, wpk: torch.Tensor, bias: torch.Tensor,
     check(lib().fdet_stem3_fwd_q8_u8(ptr(frames, torch.uint8), ptr(wpk, I8), ptr(bias, torch.int32), ptr(mul), out.data, Nn, cin,
                                      F_, H, W, stream()), "fdet_stem3_fwd_q8_u8")
     return out
+
+
+def stem10_fwd_q8_ok(N_, cin, F_, H, W) -> bool:
+    """fdet_stem10_fwd_q8_u8 accepts N images of this shape (fdet_stem10_fwd_q8_ok): 3 channels, F a multiple of 64 up to
+    256, H and W in 6..4096, the output under 2 GiB."""
+    return bool(lib().fdet_stem10_fwd_q8_ok(int(N_), int(cin), int(F_), int(H), int(W)))
+
+
+def q8_pack_stem10_weights(w_q: torch.Tensor) -> torch.Tensor:
+    """int8 [F,3,10,10] -> the integer stem's [F][32][16]: row ci*10+ky (rows 30, 31 zero), slot kx (slots 10..15 zero);
+    one-time work, a torch reshape and pad."""
+    if w_q.dtype != I8 or w_q.dim() != 4 or tuple(w_q.shape[1:]) != (3, 10, 10) or w_q.shape[0] % 64:
+        raise ValueError("q8_pack_stem10_weights: expected int8 weights [F,3,10,10] with F % 64 == 0")
+    out = torch.zeros(w_q.shape[0], 32, 16, dtype=I8, device=w_q.device)
+    out[:, :30, :10] = w_q.reshape(w_q.shape[0], 30, 10)
+    return out.reshape(-1)
+
+
+def stem10_fwd_q8_u8(frames: torch.Tensor, wpk: torch.Tensor, bias: torch.Tensor, mul: torch.Tensor, out: Q8Tensor) -> Q8Tensor:
+    """uint8 frames (N,3,H,W) -> the 10x10 / stride 8 / pad 2 stem in integer arithmetic, requantised into `out` (real pixels
+    only): clamp(rintf(float(bias + sum x_u8 * w_q) * mul), -127, 127) on the integer matrix cores (fdet_stem10_fwd_q8_u8)."""
+    if frames.dim() != 4 or frames.dtype != torch.uint8:
+        raise ValueError("stem10_fwd_q8_u8: expected uint8 frames (N,3,H,W)")
+    Nn, cin, H, W = frames.shape
+    F_ = bias.shape[0]
+    if wpk.numel() != 512 * F_:
+        raise ValueError("stem10_fwd_q8_u8: packed weight size does not match the channel count (q8_pack_stem10_weights)")
+    _chk4(bias, (F_,), "bias")
+    _chk4(mul, (F_,), "mul")
+    if H < 6 or W < 6:
+        raise ValueError(f"stem10_fwd_q8_u8: H and W must be at least 6, got {H}x{W}")
+    _q8_same(out, (Nn, F_, (H - 6) // 8 + 1, (W - 6) // 8 + 1), "stem10_fwd_q8_u8: out")
+    check(lib().fdet_stem10_fwd_q8_u8(ptr(frames, torch.uint8), ptr(wpk, I8), ptr(bias, torch.int32), ptr(mul), out.data, Nn, cin,
+                                      F_, H, W, stream()), "fdet_stem10_fwd_q8_u8")
+    return out

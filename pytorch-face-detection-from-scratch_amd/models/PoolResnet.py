@@ -48,8 +48,9 @@ class PoolResnet(BaseModel):
             x = self.single_non_max_suppression(x[0])      # image 0 only, as the reference (:103-104)
         return x
 
-    def quantize(self, frames_iter, **kw):
+    def quantize(self, frames_iter, stem="float", **kw):
         """Int8 post-training quantisation for inference: calibrate the activation scales on `frames_iter` (quantize.calibrate;
-        keywords method / percentile) and return the Int8PoolResnet of this model."""
+        keywords method / percentile) and return the Int8PoolResnet of this model.  stem="integer": the integer uint8-frame
+        stem instead of the float one (opt-in: it changes the stem's bytes)."""
         from ..quantize import quantize_model
-        return quantize_model(self, frames_iter, **kw)
+        return quantize_model(self, frames_iter, stem=stem, **kw)

@@ -1,7 +1,8 @@
-"""Int8 post-training quantisation of PoolResnet and Resnet for inference (DESIGN 5j, 5l; include/fdet.h "Int8 inference").
+"""Int8 post-training quantisation of PoolResnet and Resnet for inference (DESIGN 5j, 5l, 5m; include/fdet.h "Int8 inference").
 
     qp = calibrate(model, frames_iter)                  # float engine over a few frames -> activation scales
     m8 = Int8PoolResnet(model, qp)                      # int8 weights, int32 biases, fp32 multipliers, once
+    m8 = Int8PoolResnet(model, qp, stem="integer")      # (opt-in: the integer uint8-frame stem, fdet_stem10_fwd_q8_u8)
     m8 = Int8Resnet(model, qp)                          # (a Resnet; quantize_model picks the class)
     rows, counts = m8.reduce_bounding_boxes.forward_batch(m8.forward_frames(frames))
 
@@ -11,8 +12,10 @@ stem reads uint8 frames and writes the quantised layout itself (fdet_stem_fwd_q8
 3x3 / stride 2 stem is an integer kernel of its own (fdet_stem3_fwd_q8_u8): the uint8 frame is its quantised input (scale
 1 / 255), so that network is integer from the frame bytes to the head's input and has one arithmetic for every input.  The
 reference has no quantised path (its deployment tools are pruner.py and the ONNX / TorchScript exports); the arithmetic is
-this project's own contract, restated in numpy by tests/q8_cpu_ref.py and tests/q8_resnet_cpu_ref.py, and the kernels equal
-those restatements bit for bit.
+this project's own contract, restated in numpy by tests/q8_cpu_ref.py, tests/q8_resnet_cpu_ref.py and
+tests/q8_pool_stem_cpu_ref.py, and the kernels equal those restatements bit for bit.  Int8PoolResnet(stem="integer") gives
+PoolResnet the same kind of stem (fdet_stem10_fwd_q8_u8) in place of the float one; it is opt-in because it changes the
+stem's bytes.
 """
 from __future__ import annotations
 
@@ -357,6 +360,22 @@ class _Int8Trunk:
             trace["y"] = y
         return y
 
+    # ------------------------------------------------------------------ the one-input rule of the integer stems
+    @staticmethod
+    def _codes(x: torch.Tensor) -> torch.Tensor:
+        """float images in [0,1] -> the uint8 codes of the stem's input scale 1 / 255 (torch ops; NaN -> 0)."""
+        return torch.nan_to_num(x.to(F32)).mul(255.0).round_().clamp_(0.0, 255.0).to(torch.uint8)
+
+    def _forward_any(self, x: torch.Tensor, trace: Optional[dict] = None) -> torch.Tensor:
+        """Frames of any kind through an integer stem (`_stem_u8`): uint8 frames on the GPU at the model resolution as they
+        are, everything else through `_preprocess` and `_codes`."""
+        g = self.geo
+        if x.dim() == 3:
+            x = x.unsqueeze(0)
+        if x.is_cuda and x.dtype == torch.uint8 and x.dim() == 4 and tuple(x.shape[1:]) == (g.in_ch, g.H, g.W):
+            return self._trunk(self._stem_u8(x, trace), trace)
+        return self._forward_f32(self._preprocess(x), trace)
+
     @torch.no_grad()
     def __call__(self, x: torch.Tensor, predict: torch.Tensor = torch.tensor(0)):
         """The float model's forward: float images in [0,1] at the model resolution -> maps; predict=1: frames -> boxes of
@@ -395,10 +414,35 @@ class Int8PoolResnet(_Int8Trunk):
     dequantise -> existing head; or, where switched on (FDET_Q8_STEM / FDET_Q8_CHAIN, `counters`), the quantising stem on
     the uint8 frames and the un-pooled tail of the trunk as one launch that also dequantises -- the same bytes.  Inference
     only; weights and scales are those at construction.  It offers what the rest of the package asks of a model
-    (TiledDetector, DetectionEvaluator, GraphedPredict, render / tracking / chips)."""
+    (TiledDetector, DetectionEvaluator, GraphedPredict, render / tracking / chips).
+
+    stem="float" (the default) is the path above.  stem="integer" replaces the float stem by the integer kernel
+    fdet_stem10_fwd_q8_u8: the uint8 frame is the stem's quantised input (scale 1 / 255), its weights are prepared as a trunk
+    conv's, and Int8Resnet's one-input rule holds -- uint8 frames on the GPU at the model resolution go to the kernel as they
+    are, everything else through `_preprocess` and `_codes` to the same kernel.  No float stem, no `/ 255` pass, no quantise
+    launch and no FDET_Q8_STEM lookup; the stem's bytes differ from the float stem's (by at most one code on the trained
+    archive), which is why it is opt-in.  F = 128 and 256 models are accepted (their trunk runs launch by launch)."""
+
+    STEMS = ("float", "integer")
+
+    def __init__(self, model, qparams: QuantParams, stem: str = "float"):
+        if stem not in self.STEMS:
+            raise ValueError(f"Int8PoolResnet: stem must be one of {self.STEMS}, got {stem!r}")
+        self.stem = stem
+        super().__init__(model, qparams)
 
     def _init_stem(self, model, sd) -> None:
         g, F_ = self.geo, self.filters
+        if self.stem == "integer":
+            if (g.stem_k, g.stem_s, g.stem_p) != (10, 8, 2) or not hp.stem10_fwd_q8_ok(1, g.in_ch, F_, g.H, g.W):
+                raise FdetError(f"Int8PoolResnet: a {g.in_ch} -> {F_} channel k{g.stem_k} s{g.stem_s} p{g.stem_p} stem on {g.H}x{g.W} "
+                                "frames is outside the integer stem's range (fdet_stem10_fwd_q8_ok: 3 channels, k10 s8 p2, F a "
+                                "multiple of 64 up to 256, H and W in 6..4096)")
+            w_q, b_q, mul = prepare_conv(sd["conv1.weight"], sd["conv1.bias"], STEM_IN_SCALE, self.qparams.s_h[0])
+            self.stem_wpk = hp.q8_pack_stem10_weights(torch.from_numpy(w_q).to(self.device))
+            self.stem_bias = torch.from_numpy(b_q).to(self.device)
+            self.stem_mul = torch.from_numpy(mul).to(self.device)
+            return
         self.stem_w = model.conv1.weight.detach().to(F32).contiguous().clone()
         self.stem_b = model.conv1.bias.detach().to(F32).contiguous().clone()
         self._stem_x3 = hp.x3_supported(F_, F_) and hp.stem_x3_supported(g.in_ch, g.W, g.stem_k, g.stem_s, g.stem_p)
@@ -407,6 +451,8 @@ class Int8PoolResnet(_Int8Trunk):
     def stem_q8_on(self, N: int) -> bool:
         """uint8 frames at the model resolution go through the quantising stem (fdet_stem_fwd_q8_u8)."""
         g = self.geo
+        if self.stem == "integer":                                    # (that stem has one route and no switch)
+            return False
         if self.stem_q8 == "0" or not (self.stem_q8 == "1" or STEM_Q8_MEASURED_FASTER):
             return False
         return hp.stem_fwd_q8_ok(N, g.in_ch, self.filters, g.H, g.W, g.stem_k, g.stem_s, g.stem_p)
@@ -436,8 +482,29 @@ class Int8PoolResnet(_Int8Trunk):
             trace["stem"] = hf
         return h
 
-    def _stem_u8(self, frames: torch.Tensor) -> hp.Q8Tensor:
-        """uint8 frames at the model resolution -> the quantising stem: no fp32 image, no fp32 stem output."""
+    def _stem_i8(self, frames: torch.Tensor, trace: Optional[dict] = None) -> hp.Q8Tensor:
+        """stem="integer": uint8 codes at the model resolution -> the integer stem."""
+        g = self.geo
+        if not frames.is_cuda:
+            raise FdetError("Int8PoolResnet runs on the GPU only (no CPU fallback): move the input to cuda")
+        if frames.dim() != 4 or tuple(frames.shape[1:]) != (g.in_ch, g.H, g.W):
+            raise ValueError(f"expected input (N,{g.in_ch},{g.H},{g.W}), got {tuple(frames.shape)}")
+        N, h0 = frames.shape[0], self.h0
+        if not hp.stem10_fwd_q8_ok(N, g.in_ch, self.filters, g.H, g.W):
+            raise FdetError(f"Int8PoolResnet: {N} images of {g.H}x{g.W} pass the int8 layout's 2 GiB per tensor: use smaller batches")
+        h = self._take(N, h0, h0)
+        with self._t("stem10_fwd_q8", h0, 2.0 * N * self.filters * 300 * h0 * h0, float(frames.numel()) + N * self.filters * h0 * h0):
+            hp.stem10_fwd_q8_u8(frames.contiguous(), self.stem_wpk, self.stem_bias, self.stem_mul, h)
+        self.counters["stem_q8"] += 1
+        if trace is not None:
+            trace["stem"] = h.nchw()
+        return h
+
+    def _stem_u8(self, frames: torch.Tensor, trace: Optional[dict] = None) -> hp.Q8Tensor:
+        """uint8 frames at the model resolution -> the quantising stem: no fp32 image, no fp32 stem output (stem="integer":
+        the integer stem)."""
+        if self.stem == "integer":
+            return self._stem_i8(frames, trace)
         g = self.geo
         N, h0 = frames.shape[0], self.h0
         h = self._take(N, h0, h0)
@@ -447,13 +514,20 @@ class Int8PoolResnet(_Int8Trunk):
         return h
 
     def _forward_f32(self, x: torch.Tensor, trace: Optional[dict] = None) -> torch.Tensor:
+        if self.stem == "integer":
+            if not x.is_cuda:
+                raise FdetError("Int8PoolResnet runs on the GPU only (no CPU fallback): move the input to cuda")
+            return self._trunk(self._stem_i8(self._codes(x), trace), trace)
         return self._trunk(self._stem_f32(x, trace), trace)
 
     @torch.no_grad()
     def forward_frames(self, x: torch.Tensor) -> torch.Tensor:
         """frames (uint8 or float, any size) -> the (N,5,S,S) maps, as BaseModel.forward_frames.  uint8 frames on the GPU
         that are already at the model resolution go to the quantising stem as they are (where it is switched on and takes
-        the shape): no `/ 255` pass, no fp32 stem output, no quantise launch, the same bytes."""
+        the shape): no `/ 255` pass, no fp32 stem output, no quantise launch, the same bytes.  stem="integer": every input
+        reaches the integer stem (`_forward_any`)."""
+        if self.stem == "integer":
+            return self._forward_any(x)
         g = self.geo
         if x.dim() == 3:
             x = x.unsqueeze(0)
@@ -464,9 +538,13 @@ class Int8PoolResnet(_Int8Trunk):
 
     @torch.no_grad()
     def trace(self, frames: torch.Tensor) -> dict:
-        """{"stem": fp32 stem output (N,F,h0,h0), "blocks": [int8 (N,F,h,h) output of every block], "y": (N,5,S,S)}"""
+        """{"stem": fp32 stem output (N,F,h0,h0) -- stem="integer": the int8 stem output --, "blocks": [int8 (N,F,h,h) output
+        of every block], "y": (N,5,S,S)}"""
         out = {}
-        self._forward_f32(self._preprocess(frames), trace=out)
+        if self.stem == "integer":
+            self._forward_any(frames, trace=out)
+        else:
+            self._forward_f32(self._preprocess(frames), trace=out)
         return out
 
 
@@ -509,23 +587,10 @@ class Int8Resnet(_Int8Trunk):
             trace["stem"] = h.nchw()
         return h
 
-    @staticmethod
-    def _codes(x: torch.Tensor) -> torch.Tensor:
-        """float images in [0,1] -> the uint8 codes of the stem's input scale 1 / 255 (torch ops; NaN -> 0)."""
-        return torch.nan_to_num(x.to(F32)).mul(255.0).round_().clamp_(0.0, 255.0).to(torch.uint8)
-
     def _forward_f32(self, x: torch.Tensor, trace: Optional[dict] = None) -> torch.Tensor:
         if not x.is_cuda:
             raise FdetError("Int8Resnet runs on the GPU only (no CPU fallback): move the input to cuda")
         return self._trunk(self._stem_u8(self._codes(x), trace), trace)
-
-    def _forward_any(self, x: torch.Tensor, trace: Optional[dict] = None) -> torch.Tensor:
-        g = self.geo
-        if x.dim() == 3:
-            x = x.unsqueeze(0)
-        if x.is_cuda and x.dtype == torch.uint8 and x.dim() == 4 and tuple(x.shape[1:]) == (g.in_ch, g.H, g.W):
-            return self._trunk(self._stem_u8(x, trace), trace)
-        return self._forward_f32(self._preprocess(x), trace)
 
     @torch.no_grad()
     def forward_frames(self, x: torch.Tensor) -> torch.Tensor:
@@ -540,8 +605,14 @@ class Int8Resnet(_Int8Trunk):
         return out
 
 
-def quantize_model(model, frames_iter, **kw):
-    """calibrate + the int8 class of the model: Int8PoolResnet or Int8Resnet (what PoolResnet.quantize / Resnet.quantize do)."""
+def quantize_model(model, frames_iter, stem: str = "float", **kw):
+    """calibrate + the int8 class of the model: Int8PoolResnet or Int8Resnet (what PoolResnet.quantize / Resnet.quantize do).
+    `stem` is Int8PoolResnet's ("float" or "integer"); a Resnet has the integer stem only and its call leaves `stem` alone."""
     from .models.Resnet import Resnet
-    cls = Int8Resnet if type(model) is Resnet else Int8PoolResnet
-    return cls(model, calibrate(model, frames_iter, **kw))
+    if type(model) is Resnet:
+        if stem != "float":
+            raise ValueError("quantize_model: stem= selects PoolResnet's stem; Int8Resnet has its integer stem only")
+        return Int8Resnet(model, calibrate(model, frames_iter, **kw))
+    if stem not in Int8PoolResnet.STEMS:
+        raise ValueError(f"quantize_model: stem must be one of {Int8PoolResnet.STEMS}, got {stem!r}")
+    return Int8PoolResnet(model, calibrate(model, frames_iter, **kw), stem=stem)

@@ -21,6 +21,7 @@ Images are matched to the .mat files by `<event>/<image>`; the synthetic bank's 
 `--int8` (poolresnet) adds the same evaluator numbers from the int8 post-training-quantised model (`quantize.py`, DESIGN.md
 5j) beside the float ones of the same run: the scales are calibrated with the float model on the first `--calib-images`
 images (32) under `--calib DIR` (default: the validation bank's first images).  `--json` then gains the key "int8".
+`--int8-stem integer` gives that model the integer uint8-frame stem (the default is `float`).
 """
 import argparse
 import json

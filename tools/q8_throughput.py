@@ -7,7 +7,7 @@
 Workload: the inference leg's -- --images uint8 480x480 frames on the device (the three stored frames of
 tests/golden/g6_trained_small.npz, repeated) through the medium PoolResnet (64 filters, the trained weights of
 tests/golden/g16_trained_medium.npz) to boxes: `reduce_bounding_boxes.forward_batch(model.forward_frames(frames))`.
-Six models in ONE process, every one warmed up, alternated sample by sample; a sample is --calls back-to-back calls between
+Seven models in ONE process, every one warmed up, alternated sample by sample; a sample is --calls back-to-back calls between
 two device events, reported per call; median / min / max, the 5th / 95th percentile and their distance (`spread_ms`) over
 --launches samples:
 
@@ -18,6 +18,8 @@ two device events, reported per call; median / min / max, the 5th / 95th percent
   int8-chain        the sixteen 15x15 convs and the dequantise as one fdet_q8_chain launch
   int8-chain+stem   and the quantising stem on the uint8 frames (fdet_stem_fwd_q8_u8)
   int8              the model as constructed with no switch set (the measured defaults)
+  int8-integer-stem Int8PoolResnet(stem="integer"): the integer uint8-frame stem (fdet_stem10_fwd_q8_u8) in front of the same
+                    trunk; compared with `int8` of the same run (`faster.integer_stem`)
 
 Then, in a second phase with a KernelTimer attached (device events around every kernel class, so launch gaps inside a class
 count as its time), the per-kernel times of the three int8 modes and of precision16, and from them per class: the 15x15 tail
@@ -25,7 +27,9 @@ count as its time), the per-kernel times of the three int8 modes and of precisio
 pass that the float stem needs before it is counted in the end-to-end times only) and the 20-conv trunk.  `*_floor_share` is
 a class's MACs over the dense int8 MFMA peak (2 x the 2.5 PF bf16 peak = 2.5e15 MAC/s) over its measured time.  `faster` says
 for each new path whether it beat what it replaces by more than the larger of the two spreads: the rule of its default
-(quantize.CHAIN_MEASURED_FASTER / STEM_Q8_MEASURED_FASTER).  Prints one JSON line and, with --out, writes it.
+(quantize.CHAIN_MEASURED_FASTER / STEM_Q8_MEASURED_FASTER).  `stem_alone` times the integer stem on its own beside the
+quantising float stem, the float stem + quantise pair and a plain device copy of the integer stem's bytes (frames read + int8
+output written).  Prints one JSON line and, with --out, writes it.
 """
 import argparse
 import json
@@ -227,7 +231,8 @@ def main(argv=None):
         return m
     int8 = {"int8-layers": build8("0", "0"), "int8-chain": build8("1", "0"), "int8-chain+stem": build8("1", "1"),
             "int8": build8(None, None)}
-    models = {"bf16x3": m32, "precision16": m16, **int8}
+    mi = Int8PoolResnet(m32, qp, stem="integer")
+    models = {"bf16x3": m32, "precision16": m16, **int8, "int8-integer-stem": mi}
 
     def run(m):
         with torch.no_grad():
@@ -270,6 +275,7 @@ def main(argv=None):
                 for name, (cnt, total, _, _) in sorted(s.items())}
     k8 = {k: kernel_times(m, m) for k, m in int8.items() if k != "int8"}
     k16 = kernel_times(m16, m16.engine)
+    ki = kernel_times(mi, mi)
 
     def cls(ks, names):
         return round(sum(v["ms_per_call"] for k, v in ks.items() if k.split("@")[0] in names), 4)
@@ -277,7 +283,8 @@ def main(argv=None):
     tail = {"int8-layers": cls(at15["int8-layers"], ("q8_conv3x3", "q8_conv3x3_skip", "q8_dequantize")),
             "int8-chain": cls(at15["int8-chain"], ("q8_chain",)), "int8-chain+stem": cls(at15["int8-chain+stem"], ("q8_chain",))}
     stem = {"int8-layers": cls(k8["int8-layers"], ("stem_fwd", "q8_quantize")), "int8-chain": cls(k8["int8-chain"], ("stem_fwd", "q8_quantize")),
-            "int8-chain+stem": cls(k8["int8-chain+stem"], ("stem_fwd_q8",)), "precision16": cls(k16, ("stem_fwd",))}
+            "int8-chain+stem": cls(k8["int8-chain+stem"], ("stem_fwd_q8",)), "int8-integer-stem": cls(ki, ("stem10_fwd_q8",)),
+            "precision16": cls(k16, ("stem_fwd",))}
     trunk8 = {k: cls(ks, ("q8_conv3x3", "q8_conv3x3_skip", "q8_conv3x3_pool", "q8_chain", "q8_dequantize")) for k, ks in k8.items()}
     trunk16 = sum(v["ms_per_call"] for k, v in k16.items() if k.startswith(("conv3x3_fwd", "chain_fwd")))
     # (blocks 0 and 1 are pooled: 2 convs at 60x60, 2 at 30x30; then 8 blocks = 16 convs at 15x15)
@@ -285,6 +292,34 @@ def main(argv=None):
     trunk_macs = float(n) * 64 * 64 * 9 * (2 * 60 * 60 + 2 * 30 * 30 + 16 * 15 * 15)
     floor_ms, tail_floor_ms = trunk_macs / INT8_PEAK_MACS * 1e3, tail_macs / INT8_PEAK_MACS * 1e3
     e2e = {k: stats(v) for k, v in ms.items()}
+
+    # the stem on its own: the integer stem | the quantising float stem | the float stem + quantise | a copy of the same bytes
+    from fdet_amd import hotpath as hp
+    x32 = hp.u8_to_f32_norm(frames)
+    w32, b32 = m32.conv1.weight.detach().contiguous(), m32.conv1.bias.detach().contiguous()
+    hf = torch.empty(n, 64, 60, 60, dtype=torch.float32, device="cuda")
+    ws = torch.empty(max((hp.stem_ws_bytes(n, 3, 64, 480, 480, 10, 8, 2) + 3) // 4, 4), dtype=torch.float32, device="cuda")
+    x3 = hp.x3_supported(64, 64) and hp.stem_x3_supported(3, 480, 10, 8, 2)
+    q_a, q_b, q_c = (hp.Q8Tensor(n, 64, 60, 60, "cuda") for _ in range(3))
+    s0 = float(qp.s_h[0])
+    stem_bytes = frames.numel() + n * 64 * 60 * 60
+    src = torch.empty(stem_bytes // 2, dtype=torch.uint8, device="cuda").fill_(7)
+    dst = torch.empty_like(src)
+
+    def float_pair():
+        hp.stem_fwd(x32, w32, b32, hf, ws, 10, 8, 2, x3=x3)
+        hp.q8_quantize(hf, s0, out=q_b)
+    stem_fns = {"stem10_fwd_q8_u8": lambda: hp.stem10_fwd_q8_u8(frames, mi.stem_wpk, mi.stem_bias, mi.stem_mul, q_a),
+                "float_stem+quantize": float_pair, "device_copy_same_bytes": lambda: dst.copy_(src)}
+    if hp.stem_fwd_q8_ok(n, 3, 64, 480, 480, 10, 8, 2):
+        stem_fns["stem_fwd_q8_u8"] = lambda: hp.stem_fwd_q8_u8(frames, w32, b32, s0, q_c, 10, 8, 2)
+    for fn in stem_fns.values():
+        for _ in range(args.warmup):
+            fn()
+    torch.cuda.synchronize()
+    stem_alone = {k: _stats(v) for k, v in _alternate(stem_fns, args.launches, args.calls).items()}
+    code_diff = (q_a.nchw()[:3].to(torch.int16) - q_b.nchw()[:3].to(torch.int16)).abs()    # integer stem against the quantised float stem
+    gbs = {k: round(stem_bytes / stem_alone[k]["median_ms"] / 1e6, 1) for k in ("stem10_fwd_q8_u8", "device_copy_same_bytes")}
 
     def faster(new, old):
         gain = e2e[old]["median_ms"] - e2e[new]["median_ms"]
@@ -294,10 +329,15 @@ def main(argv=None):
            "calls_per_sample": args.calls, "end_to_end": e2e, "images_per_s": {k: round(n / (v["median_ms"] * 1e-3), 1) for k, v in e2e.items()},
            "boxes": boxes, "int8_maps_identical": identical,
            "counters": {k: dict(m.counters) for k, m in int8.items()},
-           "faster": {"chain": faster("int8-chain", "int8-layers"), "stem": faster("int8-chain+stem", "int8-chain")},
-           "over_precision16": {k: round(e2e["precision16"]["median_ms"] / e2e[k]["median_ms"], 3) for k in int8},
-           "over_bf16x3": {k: round(e2e["bf16x3"]["median_ms"] / e2e[k]["median_ms"], 3) for k in int8},
-           "int8_kernels": k8, "precision16_kernels": k16,
+           "faster": {"chain": faster("int8-chain", "int8-layers"), "stem": faster("int8-chain+stem", "int8-chain"),
+                      "integer_stem": faster("int8-integer-stem", "int8")},
+           "over_precision16": {k: round(e2e["precision16"]["median_ms"] / e2e[k]["median_ms"], 3) for k in (*int8, "int8-integer-stem")},
+           "over_bf16x3": {k: round(e2e["bf16x3"]["median_ms"] / e2e[k]["median_ms"], 3) for k in (*int8, "int8-integer-stem")},
+           "int8_kernels": k8, "int8_integer_stem_kernels": ki, "integer_stem_counters": dict(mi.counters), "precision16_kernels": k16,
+           "stem_alone": stem_alone, "stem_bytes": stem_bytes, "stem_gb_per_s": gbs,
+           "stem_share_of_copy_rate": round(gbs["stem10_fwd_q8_u8"] / gbs["device_copy_same_bytes"], 3),
+           "stem_codes_vs_quantized_float_stem": {"max_abs_diff": int(code_diff.max()),
+                                                  "share_that_differ": round(float((code_diff != 0).float().mean()), 4)},
            "tail_15x15_ms": tail, "stem_ms": stem,
            "trunk_20_convs_ms": {**trunk8, "precision16": round(trunk16, 4)},
            "tail_gmac": round(tail_macs / 1e9, 2), "int8_tail_floor_ms": round(tail_floor_ms, 4),
