@@ -1301,6 +1301,56 @@ int fdet_stem10_fwd_q8_u8(const unsigned char* frames, const int8_t* w_q, const 
                           int N, int Cin, int F, int H, int W, void* stream);
 int fdet_stem10_fwd_q8_ok(int N, int Cin, int F, int H, int W);
 
+/* ---------------------------------------------------------------------------------------
+ * Int8 inference: the separable block of SeparableCNN (csrc/fdet_q8_sep.hip; restated by tests/q8_sep_cpu_ref.py, and the GPU
+ * results equal that restatement bit for bit).  The reference block (models/SeparableCNN.py, no bias anywhere) is
+ *     pw1 1x1 -> LeakyReLU -> depthwise 3x3 pad 1 -> LeakyReLU -> pw2 1x1 -> + skip -> MaxPool2d(2) iff pooled
+ * With the symmetric quantisation, the Q8 layout and the single-rounding float steps of "Int8 inference" above (int -> float
+ * is RNE, each float operation is one fp32 operation and never fused, rintf rounds half to even, the clamp is to +-127, NaN
+ * cannot arise):
+ *     acc1[co] = sum_ci h_q[ci] * w1_q[co][ci]                          int32, exact
+ *     a_q      = clamp(rintf(lrelu(float(acc1) * mul1[co])))
+ *     acc2[c]  = sum_{ky,kx} a_q[c][y+ky-1][x+kx-1] * wd_q[c][ky][kx]   int32, exact; a_q outside the image is 0
+ *     b_q      = clamp(rintf(lrelu(float(acc2) * mul2[c])))
+ *     acc3[co] = sum_c b_q[c] * w2_q[co][c]                             int32, exact
+ *     t        = float(acc3) * mul3[co] + float(h_q[co]) * skip_mul     (two multiplies, one add)
+ *     q        = clamp(rintf(t));   y = pool ? max of q over each 2x2 window : q
+ * with lrelu(t) = t >= 0 ? t : t * slope.  For block k with activation scales s_h[k] (input), s_a[k], s_b[k] (the two
+ * intermediates) and s_h[k+1] (output): mul1 = (s_w1 * s_h[k]) / s_a[k], mul2 = (s_wd * s_a[k]) / s_b[k],
+ * mul3 = (s_w2 * s_b[k]) / s_h[k+1], skip_mul = s_h[k] / s_h[k+1]; weight scales are per output channel (per channel for
+ * the depthwise filter), absmax / 127, 1 for a channel of zeros, exactly as for a trunk conv and with no bias term.
+ *   x        Q8 [N][H+2][W+2][C] with its halo of zeros
+ *   w1, w2   int8 [Cout][Cin] rows
+ *   wd       int8 [9][C], tap ky*3+kx major (a plain permutation of [C][1][3][3]; hotpath.q8_pack_sep_dw does it with torch)
+ *   mul1..3  fp32 [C]
+ *   y        Q8 [N][H+2][W+2][C], or [N][H/2+2][W/2+2][C] when pooled (even H and W): real pixels only; may not alias x
+ * Every pointer is 16-byte aligned.  One launch: a workgroup owns one image x one tile of tile_rows x tile_cols pixels.
+ * tile_rows = tile_cols = 0 lets the planner choose (fdet_q8_sepblock_plan); non-zero values force a tiling (both even when
+ * pooled; FDET_EINVAL when the tile does not fit the 160 KB of LDS) -- same bytes, for tests that put band and segment seams
+ * on small maps.
+ * fdet_q8_sepblock_supported: 1 for C in {64, 128} and 1 <= H, W <= 4096 (launches nothing).
+ * fdet_q8_sepblock_plan: the planner's tile and its LDS bytes; 1, or 0 for an unsupported shape (or odd H, W when pooled). */
+int fdet_q8_sepblock_supported(int C, int H, int W);
+int fdet_q8_sepblock_plan(int C, int H, int W, int pool, int* rows, int* cols, size_t* lds_bytes);
+int fdet_q8_sepblock(const int8_t* x, const int8_t* w1, const float* mul1, const int8_t* wd, const float* mul2, const int8_t* w2,
+                     const float* mul3, float skip_mul, int8_t* y, int N, int C, int H, int W, int pool, int tile_rows,
+                     int tile_cols, float slope, void* stream);
+
+/* nblocks (1..16) un-pooled separable blocks of 64 channels on maps of at most 16 x 16 in one launch: the result equals
+ * nblocks calls of fdet_q8_sepblock byte for byte.  A workgroup keeps one image's planes and the blocks' parameters in LDS
+ * for the whole chain.
+ *   h_*        HOST arrays (nblocks entries) of DEVICE pointers / floats, as for fdet_q8_chain: they travel to the kernel by
+ *              value, so the call can be captured in a HIP graph
+ *   h_out      HOST array of DEVICE Q8 tensors, block k's output where h_out[k] != NULL (real pixels only); may be NULL
+ *   out_f32    optional fp32 [N,64,H,W] = float(q of the last block) * out_scale, bit for bit fdet_q8_dequantize
+ * At least one of h_out[nblocks - 1] and out_f32 is given; no output may alias x; every device pointer is 16-byte aligned.
+ * fdet_q8_sepchain_supported: 1 for C == 64 and 1 <= H, W <= 16 (launches nothing). */
+int fdet_q8_sepchain_supported(int C, int H, int W);
+int fdet_q8_sepchain(const int8_t* x, const int8_t* const* h_w1, const float* const* h_mul1, const int8_t* const* h_wd,
+                     const float* const* h_mul2, const int8_t* const* h_w2, const float* const* h_mul3, const float* h_skip_mul,
+                     int8_t* const* h_out, float* out_f32, float out_scale, int nblocks, int N, int C, int H, int W, float slope,
+                     void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -204,6 +204,11 @@ SIGNATURES = {
     "fdet_stem3_fwd_q8_ok": (_I, [_I, _I, _I, _I, _I]),
     "fdet_stem10_fwd_q8_u8": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "fdet_stem10_fwd_q8_ok": (_I, [_I, _I, _I, _I, _I]),
+    "fdet_q8_sepblock_supported": (_I, [_I, _I, _I]),
+    "fdet_q8_sepblock_plan": (_I, [_I, _I, _I, _I, _P, _P, _P]),
+    "fdet_q8_sepblock": (_I, [_P, _P, _P, _P, _P, _P, _P, _F, _P, _I, _I, _I, _I, _I, _I, _I, _F, _P]),
+    "fdet_q8_sepchain_supported": (_I, [_I, _I, _I]),
+    "fdet_q8_sepchain": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _F, _I, _I, _I, _I, _I, _F, _P]),
 }
 
 

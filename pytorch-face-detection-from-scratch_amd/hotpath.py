@@ -1716,3 +1716,109 @@ def stem10_fwd_q8_u8(frames: torch.Tensor, wpk: torch.Tensor, bias: torch.Tensor
     check(lib().fdet_stem10_fwd_q8_u8(ptr(frames, torch.uint8), ptr(wpk, I8), ptr(bias, torch.int32), ptr(mul), out.data, Nn, cin,
                                       F_, H, W, stream()), "fdet_stem10_fwd_q8_u8")
     return out
+
+
+# ------------------------------------------------------------------------------------------
+# int8 inference of the separable block (csrc/fdet_q8_sep.hip; include/fdet.h "Int8 inference: the separable block")
+# ------------------------------------------------------------------------------------------
+def q8_sepblock_supported(C: int, H: int, W: int) -> bool:
+    """fdet_q8_sepblock runs maps of this shape: 64 or 128 channels, 1 <= H, W <= 4096."""
+    return bool(lib().fdet_q8_sepblock_supported(int(C), int(H), int(W)))
+
+
+def q8_sepblock_plan(C: int, H: int, W: int, pool: bool = False):
+    """(tile rows, tile columns, LDS bytes) the planner of fdet_q8_sepblock chooses, or None."""
+    import ctypes
+    r, c, l = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_size_t(0)
+    ok = lib().fdet_q8_sepblock_plan(int(C), int(H), int(W), int(bool(pool)), ctypes.byref(r), ctypes.byref(c), ctypes.byref(l))
+    return (r.value, c.value, l.value) if ok else None
+
+
+def q8_pack_sep_pw(w_q: torch.Tensor) -> torch.Tensor:
+    """int8 pointwise weights [Cout,Cin,1,1] (or [Cout,Cin]) -> the kernel's [Cout][Cin] rows."""
+    if w_q.dtype != I8 or w_q.dim() not in (2, 4) or w_q.shape[0] != w_q.shape[1] or w_q.numel() != w_q.shape[0] ** 2:
+        raise ValueError("q8_pack_sep_pw: expected int8 weights [C,C,1,1]")
+    return w_q.reshape(w_q.shape[0], w_q.shape[0]).contiguous().reshape(-1)
+
+
+def q8_pack_sep_dw(w_q: torch.Tensor) -> torch.Tensor:
+    """int8 depthwise weights [C,1,3,3] -> the kernel's [9 taps ky*3+kx][C]."""
+    if w_q.dtype != I8 or w_q.dim() != 4 or tuple(w_q.shape[1:]) != (1, 3, 3):
+        raise ValueError("q8_pack_sep_dw: expected int8 weights [C,1,3,3]")
+    return w_q.reshape(w_q.shape[0], 9).t().contiguous().reshape(-1)
+
+
+def _q8_sep_check(C, w1, mul1, wd, mul2, w2, mul3, name):
+    if w1.numel() != C * C or w2.numel() != C * C or wd.numel() != 9 * C:
+        raise ValueError(f"{name}: packed weight sizes do not match the channel count (q8_pack_sep_pw / q8_pack_sep_dw)")
+    for m in (mul1, mul2, mul3):
+        _chk4(m, (C,), "mul")
+
+
+def q8_sepblock(x: Q8Tensor, w1: torch.Tensor, mul1: torch.Tensor, wd: torch.Tensor, mul2: torch.Tensor, w2: torch.Tensor,
+                mul3: torch.Tensor, skip_mul: float, y: Q8Tensor, pool: bool = False, tile=(0, 0), slope: float = 0.2) -> Q8Tensor:
+    """One separable block in one launch (fdet_q8_sepblock): pw1 -> lrelu -> dw3x3 -> lrelu -> pw2 -> + x * skip_mul
+    [-> 2x2 max], requantised after each stage.  tile=(rows, columns) forces a tiling; (0, 0) is the planner's."""
+    if not isinstance(x, Q8Tensor):
+        raise ValueError("q8_sepblock: x must be a Q8Tensor")
+    Nn, C, H, W = x.shape
+    if pool and (H % 2 or W % 2):
+        raise ValueError(f"q8_sepblock: cannot 2x2-pool an odd {H}x{W} map")
+    _q8_same(y, (Nn, C, H // 2, W // 2) if pool else (Nn, C, H, W), "q8_sepblock: y")
+    _q8_sep_check(C, w1, mul1, wd, mul2, w2, mul3, "q8_sepblock")
+    check(lib().fdet_q8_sepblock(x.data, ptr(w1, I8), ptr(mul1), ptr(wd, I8), ptr(mul2), ptr(w2, I8), ptr(mul3), float(skip_mul),
+                                 y.data, Nn, C, H, W, int(bool(pool)), int(tile[0]), int(tile[1]), float(slope), stream()),
+          "fdet_q8_sepblock")
+    return y
+
+
+def q8_sepchain_supported(C: int, H: int, W: int) -> bool:
+    """fdet_q8_sepchain runs maps of this shape: 64 channels, 1 <= H, W <= 16."""
+    return bool(lib().fdet_q8_sepchain_supported(int(C), int(H), int(W)))
+
+
+class Q8SepChainWeights:
+    """The host pointer arrays of fdet_q8_sepchain, built once: blocks = per block (w1, mul1, wd, mul2, w2, mul3) (device
+    tensors, kept alive here), skip_muls = per block the skip multiplier."""
+
+    def __init__(self, blocks: Sequence, skip_muls: Sequence[float], C: int = 64):
+        import ctypes
+        nb = len(skip_muls)
+        if not (1 <= nb <= Q8_CHAIN_MAX_BLOCKS) or len(blocks) != nb:
+            raise ValueError(f"q8_sepchain: 1..{Q8_CHAIN_MAX_BLOCKS} blocks, got {len(blocks)} with {nb} skip multipliers")
+        for b in blocks:
+            _q8_sep_check(C, *b, "q8_sepchain")
+        self.C, self.nblocks = int(C), nb
+        self.tensors = [tuple(b) for b in blocks]
+        self.arrays = tuple(_ptr_array([b[i] for b in blocks], I8 if i in (0, 2, 4) else F32) for i in range(6))
+        self.skip_mul = (ctypes.c_float * nb)(*[float(v) for v in skip_muls])
+
+
+def q8_sepchain(x: Q8Tensor, weights: Q8SepChainWeights, outs: Optional[Sequence[Optional[Q8Tensor]]] = None,
+                out_f32: Optional[torch.Tensor] = None, out_scale: float = 1.0, slope: float = 0.2) -> None:
+    """The blocks of `weights` on x in one launch (fdet_q8_sepchain).  outs: per block a Q8Tensor of x's shape or None;
+    out_f32: fp32 (N,C,H,W) = float(last block) * out_scale.  One of outs[-1] and out_f32 is needed."""
+    if not isinstance(x, Q8Tensor):
+        raise ValueError("q8_sepchain: x must be a Q8Tensor")
+    if not isinstance(weights, Q8SepChainWeights):
+        raise ValueError("q8_sepchain: weights must be a Q8SepChainWeights")
+    Nn, C, H, W = x.shape
+    nb = weights.nblocks
+    if C != weights.C:
+        raise ValueError(f"q8_sepchain: the weights are for {weights.C} channels, x has {C}")
+    h_out = None
+    if outs is not None:
+        if len(outs) != nb:
+            raise ValueError(f"q8_sepchain: outs needs {nb} entries (None where a block's output is not wanted)")
+        import ctypes
+        for t in outs:
+            if t is not None:
+                _q8_same(t, x.shape, "q8_sepchain: out")
+        h_out = (ctypes.c_void_p * nb)(*[None if t is None else t.data for t in outs])
+    if out_f32 is not None:
+        _chk4(out_f32, x.shape, "q8_sepchain: out_f32")
+    if out_f32 is None and (outs is None or outs[-1] is None):
+        raise ValueError("q8_sepchain: the last block needs an output (outs[-1] or out_f32)")
+    w1, m1, wd, m2, w2, m3 = weights.arrays
+    check(lib().fdet_q8_sepchain(x.data, w1, m1, wd, m2, w2, m3, weights.skip_mul, h_out, ptr(out_f32), float(out_scale), nb,
+                                 Nn, C, H, W, float(slope), stream()), "fdet_q8_sepchain")

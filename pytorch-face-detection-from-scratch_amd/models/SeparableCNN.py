@@ -81,6 +81,12 @@ class SeparableCNN(BaseModel):
         raise hp.N.FdetError(f"SeparableCNN at {size}x{size} ends on a {h}x{h} map: no head of the model gives the 16x16 grid its "
                              "decoder assumes (480 and 512 do)")
 
+    def quantize(self, frames_iter, **kw):
+        """Int8 post-training quantisation for inference: calibrate the activation scales on `frames_iter` (quantize.calibrate;
+        keywords method / percentile) and return the Int8SeparableCNN of this model (64 or 128 filters)."""
+        from ..quantize import quantize_model
+        return quantize_model(self, frames_iter, **kw)
+
     def forward(self, x: torch.Tensor, predict: torch.Tensor = torch.tensor(0)):
         if predict == 1:
             x = self.forward_frames(x)

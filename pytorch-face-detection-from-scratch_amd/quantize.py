@@ -16,6 +16,11 @@ this project's own contract, restated in numpy by tests/q8_cpu_ref.py, tests/q8_
 tests/q8_pool_stem_cpu_ref.py, and the kernels equal those restatements bit for bit.  Int8PoolResnet(stem="integer") gives
 PoolResnet the same kind of stem (fdet_stem10_fwd_q8_u8) in place of the float one; it is opt-in because it changes the
 stem's bytes.
+
+    m8 = Int8SeparableCNN(model, qp)                    # (a SeparableCNN: qp carries s_b; quantize_model picks the class)
+
+SeparableCNN enters through that integer stem and runs every separable block as one launch of fdet_q8_sepblock
+(the un-pooled tail as one fdet_q8_sepchain launch where measured faster); tests/q8_sep_cpu_ref.py restates the block.
 """
 from __future__ import annotations
 
@@ -37,21 +42,29 @@ METHODS = ("absmax", "percentile", "explicit")
 # (profiles/r15_q8_chain.json); "1" forces a path wherever its kernel takes the shape, "0" the launches.
 CHAIN_MEASURED_FASTER = True
 STEM_Q8_MEASURED_FASTER = True
+# Int8SeparableCNN's un-pooled tail as one fdet_q8_sepchain launch (FDET_Q8_SEPCHAIN = "auto"): by the same rule, from
+# profiles/r19_q8_sep.json
+SEPCHAIN_MEASURED_FASTER = True
 
 
 # ---------------------------------------------------------------------------------------------------------- scales
 class QuantParams:
     """Activation scales of the int8 trunk, on the CPU: s_h[k] of block k's input (k = 0..nb; s_h[nb] is the head's input)
-    and s_a[k] of block k's first-conv output.  Symmetric, per tensor, float32."""
+    and s_a[k] of block k's first-conv output.  Symmetric, per tensor, float32.  A SeparableCNN has a third list, s_b[k] of
+    block k's depthwise output (s_a[k] is its first pointwise output); it is None for the 3x3 models, and files and objects
+    without it are what they were."""
 
     def __init__(self, s_h: Sequence[float], s_a: Sequence[float], method: str = "explicit", percentile: Optional[float] = None,
-                 images_seen: int = 0):
+                 images_seen: int = 0, s_b: Optional[Sequence[float]] = None):
         self.s_h = np.asarray(s_h, dtype=NPF).reshape(-1).copy()
         self.s_a = np.asarray(s_a, dtype=NPF).reshape(-1).copy()
+        self.s_b = None if s_b is None else np.asarray(s_b, dtype=NPF).reshape(-1).copy()
         if self.s_a.size < 1 or self.s_h.size != self.s_a.size + 1:
             raise ValueError(f"QuantParams: {self.s_h.size} block-input scales need {self.s_h.size - 1} first-conv scales, "
                              f"got {self.s_a.size}")
-        for name, s in (("s_h", self.s_h), ("s_a", self.s_a)):
+        if self.s_b is not None and self.s_b.size != self.s_a.size:
+            raise ValueError(f"QuantParams: {self.s_a.size} blocks need {self.s_a.size} depthwise scales, got {self.s_b.size}")
+        for name, s in (("s_h", self.s_h), ("s_a", self.s_a)) + ((("s_b", self.s_b),) if self.s_b is not None else ()):
             if not (np.all(np.isfinite(s)) and np.all(s > 0)):
                 raise ValueError(f"QuantParams: every scale in {name} must be positive and finite")
         if method not in METHODS:
@@ -65,18 +78,21 @@ class QuantParams:
         return int(self.s_a.size)
 
     def save(self, path) -> None:
+        extra = {} if self.s_b is None else {"s_b": self.s_b}
         np.savez(path, s_h=self.s_h, s_a=self.s_a, method=np.array(self.method),
                  percentile=np.array(np.nan if self.percentile is None else self.percentile, dtype=np.float64),
-                 images_seen=np.array(self.images_seen, dtype=np.int64))
+                 images_seen=np.array(self.images_seen, dtype=np.int64), **extra)
 
     @classmethod
     def load(cls, path) -> "QuantParams":
         with np.load(path, allow_pickle=False) as z:
             pct = float(z["percentile"])
-            return cls(z["s_h"], z["s_a"], str(z["method"]), None if np.isnan(pct) else pct, int(z["images_seen"]))
+            return cls(z["s_h"], z["s_a"], str(z["method"]), None if np.isnan(pct) else pct, int(z["images_seen"]),
+                       z["s_b"] if "s_b" in z.files else None)
 
     def __eq__(self, other):
         return (isinstance(other, QuantParams) and np.array_equal(self.s_h, other.s_h) and np.array_equal(self.s_a, other.s_a)
+                and (self.s_b is None) == (other.s_b is None) and (self.s_b is None or np.array_equal(self.s_b, other.s_b))
                 and (self.method, self.percentile, self.images_seen) == (other.method, other.percentile, other.images_seen))
 
     def __repr__(self):
@@ -88,7 +104,7 @@ class ActivationObserver:
     """Running range of the trunk's activations over calibration batches (torch reductions: offline work).  "absmax": the
     largest magnitude seen.  "percentile": per batch the given percentile of the magnitudes, the largest over the batches."""
 
-    def __init__(self, num_blocks: int, method: str = "absmax", percentile: Optional[float] = None):
+    def __init__(self, num_blocks: int, method: str = "absmax", percentile: Optional[float] = None, with_b: bool = False):
         if method not in ("absmax", "percentile"):
             raise ValueError("calibration method must be 'absmax' or 'percentile'")
         if method == "percentile" and not (percentile is not None and 50.0 <= float(percentile) <= 100.0):
@@ -98,6 +114,7 @@ class ActivationObserver:
         self.method, self.percentile = method, (None if percentile is None else float(percentile))
         self.h = [0.0] * (num_blocks + 1)
         self.a = [0.0] * num_blocks
+        self.b = [0.0] * num_blocks if with_b else None    # (SeparableCNN: the depthwise outputs)
         self.images = 0
 
     def _range(self, t: torch.Tensor) -> float:
@@ -107,10 +124,13 @@ class ActivationObserver:
         k = min(m.numel(), max(1, int(np.ceil(self.percentile / 100.0 * m.numel()))))
         return float(m.kthvalue(k).values)
 
-    def observe(self, h: List[torch.Tensor], a: List[torch.Tensor]) -> None:
-        """h: the nb + 1 block inputs (the last one is the head's input), a: the nb first-conv outputs, of one batch."""
-        if len(h) != len(self.h) or len(a) != len(self.a):
+    def observe(self, h: List[torch.Tensor], a: List[torch.Tensor], b: Optional[List[torch.Tensor]] = None) -> None:
+        """h: the nb + 1 block inputs (the last one is the head's input), a: the nb first-conv outputs, of one batch; b: the nb
+        depthwise outputs where the observer was made with_b."""
+        if len(h) != len(self.h) or len(a) != len(self.a) or (b is None) != (self.b is None) or (b is not None and len(b) != len(self.b)):
             raise ValueError("ActivationObserver.observe: wrong number of tensors")
+        for i, t in enumerate(b or ()):
+            self.b[i] = max(self.b[i], self._range(t))
         for i, t in enumerate(h):
             self.h[i] = max(self.h[i], self._range(t))
         for i, t in enumerate(a):
@@ -123,7 +143,8 @@ class ActivationObserver:
 
         def scale(v):                                      # an all-zero tensor quantises with scale 1
             return NPF(1.0) if v == 0.0 else NPF(v) / NPF(127.0)
-        return QuantParams([scale(v) for v in self.h], [scale(v) for v in self.a], self.method, self.percentile, self.images)
+        return QuantParams([scale(v) for v in self.h], [scale(v) for v in self.a], self.method, self.percentile, self.images,
+                           None if self.b is None else [scale(v) for v in self.b])
 
 
 def _check_model(model):
@@ -138,11 +159,18 @@ def _check_resnet(model):
         raise TypeError(f"Int8Resnet covers Resnet only, got {type(model).__name__}")
 
 
+def _check_separable(model):
+    from .models.SeparableCNN import SeparableCNN
+    if type(model) is not SeparableCNN:
+        raise TypeError(f"Int8SeparableCNN covers SeparableCNN only, got {type(model).__name__}")
+
+
 def _check_calibratable(model):
     from .models.PoolResnet import PoolResnet
     from .models.Resnet import Resnet
-    if type(model) not in (PoolResnet, Resnet):
-        raise TypeError(f"int8 calibration covers Resnet and PoolResnet only, got {type(model).__name__}")
+    from .models.SeparableCNN import SeparableCNN
+    if type(model) not in (PoolResnet, Resnet, SeparableCNN):
+        raise TypeError(f"int8 calibration covers SeparableCNN, Resnet and PoolResnet only, got {type(model).__name__}")
 
 
 STEM_IN_SCALE = NPF(1.0) / NPF(255.0)                   # the scale of a uint8 frame as the integer stem's input code
@@ -154,7 +182,7 @@ def calibrate(model, frames_iter: Iterable[torch.Tensor], method: str = "absmax"
     for backward to activation scales.  frames_iter yields batches of FRAMES exactly as `forward_frames` takes them: (N,3,H,W)
     with values 0..255, uint8 or float, any size -- they go through the model's own preprocessing (resize, / 255).  Images
     that are already normalised to [0,1] are not frames: passing them would calibrate on nearly black input.
-    A PoolResnet or a Resnet.  Resnet's engine keeps maps wider than 62 columns as column strips; PsTensor.to_f32 undoes
+    A PoolResnet, a Resnet or a SeparableCNN (whose engine keeps (x, a, b) per block: the result carries s_b).  Resnet's engine keeps maps wider than 62 columns as column strips; PsTensor.to_f32 undoes
     the strips (fdet_ps_to_f32 plans them from the full width and reads real columns only), so what is observed is plain
     NCHW at every level."""
     from .ps import PsTensor
@@ -165,7 +193,8 @@ def calibrate(model, frames_iter: Iterable[torch.Tensor], method: str = "absmax"
     if eng.p16:
         raise FdetError("calibrate: run the calibration on the bf16x3 engine, not in precision16")
     nb = len(model.residual_blocks)
-    obs = ActivationObserver(nb, method, percentile)
+    sep = model._geometry().kind == "separablecnn"
+    obs = ActivationObserver(nb, method, percentile, with_b=sep)
     dev = next(model.parameters()).device
     names, params = model.named_stack_params()
     P = {n: p.detach() for n, p in zip(names, params)}
@@ -176,8 +205,10 @@ def calibrate(model, frames_iter: Iterable[torch.Tensor], method: str = "absmax"
         x = model._preprocess(torch.as_tensor(frames).to(dev))
         _, saved = eng.forward(x, P, None, save=True)
         blocks = saved["blocks"]
-        obs.observe([f32(b[0]) for b in blocks] + [f32(saved["h_last"])], [f32(b[1]) for b in blocks])
-        saved["ps_scope"].release()
+        obs.observe([f32(b[0]) for b in blocks] + [f32(saved["h_last"])], [f32(b[1]) for b in blocks],
+                    [b[2] for b in blocks] if sep else None)
+        if not sep:
+            saved["ps_scope"].release()
     return obs.params()
 
 
@@ -225,10 +256,13 @@ class _Int8Trunk:
     buffers and the model surface that the rest of the package asks for (TiledDetector, DetectionEvaluator, GraphedPredict,
     render / tracking / chips).  A subclass supplies the way into the trunk: `_check`, `_init_stem`, `_forward_f32`
     (float images in [0,1] at the model resolution -> maps) and `forward_frames`.  Inference only; weights and scales are
-    those at construction."""
+    those at construction.  Int8SeparableCNN replaces the block as well (`_check_levels`, `_init_blocks`, `_trunk`) and keeps
+    the rest: buffers, timer, the float head (`_head`), the integer 10x10 stem (`_init_stem10`, `_stem10_u8`), the one-input
+    rule and the model surface."""
 
     training = False
     _check = staticmethod(_check_model)
+    COUNTERS = ("chain", "layers", "stem_q8", "stem_f32")
 
     def __init__(self, model, qparams: QuantParams):
         me = type(self).__name__
@@ -244,10 +278,7 @@ class _Int8Trunk:
         self.geo = model._geometry()
         self.h0, self.lv = self.geo.levels()
         F_ = int(model.filters)
-        for hk, _ in self.lv:
-            if not hp.q8_supported(F_, hk, hk):
-                raise FdetError(f"{me}: {F_} channels at {hk}x{hk} are outside the int8 kernels' range "
-                                "(fdet_q8_supported: a multiple of 64 up to 256)")
+        self._check_levels(F_)
         self.input_shape = model.input_shape
         self.num_of_patches = model.num_of_patches
         self.filters = F_
@@ -259,32 +290,47 @@ class _Int8Trunk:
         self.slope = 0.2
         self._preprocess = model._preprocess               # resize / 255 exactly as the float model
         sd = {k: v.detach().cpu().numpy() for k, v in model.state_dict().items()}
-        s_h, s_a = qparams.s_h, qparams.s_a
+        self.counters = {k: 0 for k in self.COUNTERS}
+        self._init_blocks(sd)
+        self._init_stem(model, sd)
+        self.head_w = model.out.weight.detach().to(F32).contiguous().clone()
+        self.head_b = model.out.bias.detach().to(F32).contiguous().clone()
+        self._ws = None
+        self._pool = {}                                    # (N,C,H,W) -> free Q8Tensors; kept for the life of the model
+        self.timer = None                                  # a convstack.KernelTimer: per-kernel times (tools/q8_throughput.py)
+
+    def _check_levels(self, F_: int) -> None:
+        for hk, _ in self.lv:
+            if not hp.q8_supported(F_, hk, hk):
+                raise FdetError(f"{type(self).__name__}: {F_} channels at {hk}x{hk} are outside the int8 kernels' range "
+                                "(fdet_q8_supported: a multiple of 64 up to 256)")
+
+    def _tail_first(self) -> int:
+        """Index of the first block of the maximal run of un-pooled blocks at the end of the trunk."""
+        first = len(self.lv)
+        while first > 0 and self.lv[first - 1][1] != 2:
+            first -= 1
+        return first
+
+    def _init_blocks(self, sd) -> None:
+        nb, dev, F_ = len(self.lv), self.device, self.filters
+        s_h, s_a = self.qparams.s_h, self.qparams.s_a
         self.blocks = []
         for k in range(nb):
             n = f"residual_blocks.{k}"
             c1 = _Q8Conv(sd[n + ".conv1.weight"], sd[n + ".conv1.bias"], s_h[k], s_a[k], dev)
             c2 = _Q8Conv(sd[n + ".conv2.weight"], sd[n + ".conv2.bias"], s_a[k], s_h[k + 1], dev)
             self.blocks.append((c1, c2, float(NPF(s_h[k]) / NPF(s_h[k + 1]))))
-        self._init_stem(model, sd)
-        self.head_w = model.out.weight.detach().to(F32).contiguous().clone()
-        self.head_b = model.out.bias.detach().to(F32).contiguous().clone()
         # the maximal run of un-pooled blocks at the end of the trunk: one fdet_q8_chain launch where the kernel takes the map
         # (64 channels, at most 16 x 16, 1..16 blocks); its host pointer arrays are built here, once
         self.chain = os.environ.get("FDET_Q8_CHAIN", "auto")          # "0" launch by launch, "1" the chain wherever it runs, else measured
-        self.counters = {"chain": 0, "layers": 0, "stem_q8": 0, "stem_f32": 0}
-        first = nb
-        while first > 0 and self.lv[first - 1][1] != 2:
-            first -= 1
+        first = self._tail_first()
         self._chain_first, self._chain_w = nb, None
         if first < nb and nb - first <= hp.Q8_CHAIN_MAX_BLOCKS and hp.q8_chain_supported(F_, self.lv[first][0], self.lv[first][0]):
             tail = self.blocks[first:]
             self._chain_first = first
             self._chain_w = hp.Q8ChainWeights([(c1.wpk, c1.bias, c1.mul) for c1, _, _ in tail],
                                               [(c2.wpk, c2.bias, c2.mul) for _, c2, _ in tail], [sm for _, _, sm in tail], F_)
-        self._ws = None
-        self._pool = {}                                    # (N,C,H,W) -> free Q8Tensors; kept for the life of the model
-        self.timer = None                                  # a convstack.KernelTimer: per-kernel times (tools/q8_throughput.py)
 
     # ------------------------------------------------------------------ nn.Module-shaped odds and ends
     def eval(self):
@@ -353,12 +399,50 @@ class _Int8Trunk:
                 hp.q8_dequantize(h, float(s_h[-1]), out=hd)
             self.counters["layers"] += 1
         self._give(h)
-        y = torch.empty(N, 5, g.S, g.S, dtype=F32, device=dev)
+        return self._head(hd, trace)
+
+    def _head(self, hd: torch.Tensor, trace: Optional[dict] = None) -> torch.Tensor:
+        """The float head on the dequantised last map (N,F,hl,hl) -> (N,5,S,S); S is what the head's kernel and padding leave
+        of hl (num_of_patches for PoolResnet and Resnet, whose geometry demands it)."""
+        g = self.geo
+        N, hl = hd.shape[0], hd.shape[2]
+        S = hl + 2 * g.head_p - g.head_k + 1
+        y = torch.empty(N, 5, S, S, dtype=F32, device=hd.device)
         with self._t("head_fwd", hl):
             hp.head_fwd(hd, None, self.head_w, self.head_b, y, g.head_k, g.head_p)
         if trace is not None:
             trace["y"] = y
         return y
+
+    # ------------------------------------------------------------------ the integer 10x10 / stride 8 / pad 2 stem
+    def _init_stem10(self, sd) -> None:
+        g, F_, me = self.geo, self.filters, type(self).__name__
+        if (g.stem_k, g.stem_s, g.stem_p) != (10, 8, 2) or not hp.stem10_fwd_q8_ok(1, g.in_ch, F_, g.H, g.W):
+            raise FdetError(f"{me}: a {g.in_ch} -> {F_} channel k{g.stem_k} s{g.stem_s} p{g.stem_p} stem on {g.H}x{g.W} "
+                            "frames is outside the integer stem's range (fdet_stem10_fwd_q8_ok: 3 channels, k10 s8 p2, F a "
+                            "multiple of 64 up to 256, H and W in 6..4096)")
+        w_q, b_q, mul = prepare_conv(sd["conv1.weight"], sd["conv1.bias"], STEM_IN_SCALE, self.qparams.s_h[0])
+        self.stem_wpk = hp.q8_pack_stem10_weights(torch.from_numpy(w_q).to(self.device))
+        self.stem_bias = torch.from_numpy(b_q).to(self.device)
+        self.stem_mul = torch.from_numpy(mul).to(self.device)
+
+    def _stem10_u8(self, frames: torch.Tensor, trace: Optional[dict] = None) -> hp.Q8Tensor:
+        """uint8 codes at the model resolution -> the integer stem (fdet_stem10_fwd_q8_u8)."""
+        g, me = self.geo, type(self).__name__
+        if not frames.is_cuda:
+            raise FdetError(f"{me} runs on the GPU only (no CPU fallback): move the input to cuda")
+        if frames.dim() != 4 or tuple(frames.shape[1:]) != (g.in_ch, g.H, g.W):
+            raise ValueError(f"expected input (N,{g.in_ch},{g.H},{g.W}), got {tuple(frames.shape)}")
+        N, h0 = frames.shape[0], self.h0
+        if not hp.stem10_fwd_q8_ok(N, g.in_ch, self.filters, g.H, g.W):
+            raise FdetError(f"{me}: {N} images of {g.H}x{g.W} pass the int8 layout's 2 GiB per tensor: use smaller batches")
+        h = self._take(N, h0, h0)
+        with self._t("stem10_fwd_q8", h0, 2.0 * N * self.filters * 300 * h0 * h0, float(frames.numel()) + N * self.filters * h0 * h0):
+            hp.stem10_fwd_q8_u8(frames.contiguous(), self.stem_wpk, self.stem_bias, self.stem_mul, h)
+        self.counters["stem_q8"] += 1
+        if trace is not None:
+            trace["stem"] = h.nchw()
+        return h
 
     # ------------------------------------------------------------------ the one-input rule of the integer stems
     @staticmethod
@@ -434,14 +518,7 @@ class Int8PoolResnet(_Int8Trunk):
     def _init_stem(self, model, sd) -> None:
         g, F_ = self.geo, self.filters
         if self.stem == "integer":
-            if (g.stem_k, g.stem_s, g.stem_p) != (10, 8, 2) or not hp.stem10_fwd_q8_ok(1, g.in_ch, F_, g.H, g.W):
-                raise FdetError(f"Int8PoolResnet: a {g.in_ch} -> {F_} channel k{g.stem_k} s{g.stem_s} p{g.stem_p} stem on {g.H}x{g.W} "
-                                "frames is outside the integer stem's range (fdet_stem10_fwd_q8_ok: 3 channels, k10 s8 p2, F a "
-                                "multiple of 64 up to 256, H and W in 6..4096)")
-            w_q, b_q, mul = prepare_conv(sd["conv1.weight"], sd["conv1.bias"], STEM_IN_SCALE, self.qparams.s_h[0])
-            self.stem_wpk = hp.q8_pack_stem10_weights(torch.from_numpy(w_q).to(self.device))
-            self.stem_bias = torch.from_numpy(b_q).to(self.device)
-            self.stem_mul = torch.from_numpy(mul).to(self.device)
+            self._init_stem10(sd)
             return
         self.stem_w = model.conv1.weight.detach().to(F32).contiguous().clone()
         self.stem_b = model.conv1.bias.detach().to(F32).contiguous().clone()
@@ -484,21 +561,7 @@ class Int8PoolResnet(_Int8Trunk):
 
     def _stem_i8(self, frames: torch.Tensor, trace: Optional[dict] = None) -> hp.Q8Tensor:
         """stem="integer": uint8 codes at the model resolution -> the integer stem."""
-        g = self.geo
-        if not frames.is_cuda:
-            raise FdetError("Int8PoolResnet runs on the GPU only (no CPU fallback): move the input to cuda")
-        if frames.dim() != 4 or tuple(frames.shape[1:]) != (g.in_ch, g.H, g.W):
-            raise ValueError(f"expected input (N,{g.in_ch},{g.H},{g.W}), got {tuple(frames.shape)}")
-        N, h0 = frames.shape[0], self.h0
-        if not hp.stem10_fwd_q8_ok(N, g.in_ch, self.filters, g.H, g.W):
-            raise FdetError(f"Int8PoolResnet: {N} images of {g.H}x{g.W} pass the int8 layout's 2 GiB per tensor: use smaller batches")
-        h = self._take(N, h0, h0)
-        with self._t("stem10_fwd_q8", h0, 2.0 * N * self.filters * 300 * h0 * h0, float(frames.numel()) + N * self.filters * h0 * h0):
-            hp.stem10_fwd_q8_u8(frames.contiguous(), self.stem_wpk, self.stem_bias, self.stem_mul, h)
-        self.counters["stem_q8"] += 1
-        if trace is not None:
-            trace["stem"] = h.nchw()
-        return h
+        return self._stem10_u8(frames, trace)
 
     def _stem_u8(self, frames: torch.Tensor, trace: Optional[dict] = None) -> hp.Q8Tensor:
         """uint8 frames at the model resolution -> the quantising stem: no fp32 image, no fp32 stem output (stem="integer":
@@ -605,10 +668,141 @@ class Int8Resnet(_Int8Trunk):
         return out
 
 
+def prepare_sepblock(w1, wd, w2, s_in, s_a, s_b, s_out):
+    """One separable block's integers (include/fdet.h, "Int8 inference: the separable block"): (w1_q int8 [C,C,1,1], mul1,
+    wd_q int8 [C,1,3,3], mul2, w2_q int8 [C,C,1,1], mul3, skip_mul), each conv prepared as `prepare_conv` does, without a bias."""
+    zero = np.zeros(np.asarray(w1).shape[0], NPF)
+    w1_q, _, mul1 = prepare_conv(w1, zero, s_in, s_a)
+    wd_q, _, mul2 = prepare_conv(wd, zero, s_a, s_b)
+    w2_q, _, mul3 = prepare_conv(w2, zero, s_b, s_out)
+    return w1_q, mul1, wd_q, mul2, w2_q, mul3, NPF(NPF(s_in) / NPF(s_out))
+
+
+class Int8SeparableCNN(_Int8Trunk):
+    """A SeparableCNN in int8 from the frame bytes to the head's input: the integer 10x10 stem on the uint8 frames
+    (fdet_stem10_fwd_q8_u8, PoolResnet's integer stem: conv1 is the same conv), every separable block as one launch of
+    fdet_q8_sepblock (pw1, LeakyReLU, depthwise 3x3, LeakyReLU, pw2, skip and the 2x2 max, requantised after each stage), the
+    un-pooled blocks at the end as one fdet_q8_sepchain launch where that is switched on (FDET_Q8_SEPCHAIN: "0" launch by
+    launch, "1" the chain wherever it runs, otherwise SEPCHAIN_MEASURED_FASTER) -- the same bytes --, the float head.  One
+    input rule and one arithmetic, as Int8Resnet: there is no float stem.  F = 128 models run launch by launch (the chain is
+    built for 64 channels).  `qparams` carries s_b (calibrate on a SeparableCNN gives it).  `counters`: "sepchain" chain
+    launches, "sepblocks" fdet_q8_sepblock launches, "stem_q8" stem launches.  Accuracy is pinned on seeded random models
+    only: no trained SeparableCNN archive exists."""
+
+    _check = staticmethod(_check_separable)
+    COUNTERS = ("sepchain", "sepblocks", "stem_q8")
+
+    def __init__(self, model, qparams: QuantParams):
+        if isinstance(qparams, QuantParams) and qparams.s_b is None:
+            _check_separable(model)
+            raise ValueError("Int8SeparableCNN: the scales lack s_b (the depthwise outputs): calibrate on the SeparableCNN")
+        super().__init__(model, qparams)
+
+    def _check_levels(self, F_: int) -> None:
+        for hk, _ in self.lv:
+            if not hp.q8_sepblock_supported(F_, hk, hk):
+                raise FdetError(f"Int8SeparableCNN: {F_} channels at {hk}x{hk} are outside the int8 block's range "
+                                "(fdet_q8_sepblock_supported: 64 or 128 channels, maps up to 4096 a side)")
+
+    def _init_blocks(self, sd) -> None:
+        nb, dev, F_ = len(self.lv), self.device, self.filters
+        q = self.qparams
+        self.blocks = []
+        for k in range(nb):
+            n = f"residual_blocks.{k}"
+            w1_q, mul1, wd_q, mul2, w2_q, mul3, sm = prepare_sepblock(
+                sd[n + ".pointwise_conv1.weight"], sd[n + ".depthwise_conv.weight"], sd[n + ".pointwise_conv2.weight"],
+                q.s_h[k], q.s_a[k], q.s_b[k], q.s_h[k + 1])
+
+            def t(a):
+                return torch.from_numpy(a).to(dev)
+            self.blocks.append((hp.q8_pack_sep_pw(t(w1_q)), t(mul1), hp.q8_pack_sep_dw(t(wd_q)), t(mul2), hp.q8_pack_sep_pw(t(w2_q)),
+                                t(mul3), float(sm)))
+        self.chain = os.environ.get("FDET_Q8_SEPCHAIN", "auto")
+        first = self._tail_first()
+        self._chain_first, self._chain_w = nb, None
+        if first < nb and nb - first <= hp.Q8_CHAIN_MAX_BLOCKS and hp.q8_sepchain_supported(F_, self.lv[first][0], self.lv[first][0]):
+            self._chain_first = first
+            self._chain_w = hp.Q8SepChainWeights([b[:6] for b in self.blocks[first:]], [b[6] for b in self.blocks[first:]], F_)
+
+    def _init_stem(self, model, sd) -> None:
+        self._init_stem10(sd)
+
+    def chain_on(self) -> bool:
+        """The un-pooled tail runs as one fdet_q8_sepchain launch."""
+        if self._chain_w is None or self.chain == "0":
+            return False
+        return self.chain == "1" or SEPCHAIN_MEASURED_FASTER
+
+    def _trunk(self, h: hp.Q8Tensor, trace: Optional[dict] = None) -> torch.Tensor:
+        """The quantised stem output (taken from the pool; given back here) -> the head's maps."""
+        F_, dev = self.filters, self.device
+        N = h.shape[0]
+        if trace is not None:
+            trace["blocks"] = []
+        chain = self.chain_on()
+        nlayer = self._chain_first if chain else len(self.lv)
+        for k, (hk, pool) in enumerate(self.lv[:nlayer]):
+            *w, skip_mul = self.blocks[k]
+            out = self._take(N, hk // pool, hk // pool)
+            # 2 F + 9 MACs per channel and position; compulsory bytes: x in, y out
+            with self._t("q8_sepblock_pool" if pool == 2 else "q8_sepblock", hk, 2.0 * N * F_ * (2 * F_ + 9) * hk * hk,
+                         (1.0 + 1.0 / (pool * pool)) * N * F_ * hk * hk):
+                hp.q8_sepblock(h, *w, skip_mul, out, pool=pool == 2, slope=self.slope)
+            self.counters["sepblocks"] += 1
+            self._give(h)
+            h = out
+            if trace is not None:
+                trace["blocks"].append(h.nchw())
+        hl = h.shape[2]
+        hd = torch.empty(N, F_, hl, hl, dtype=F32, device=dev)
+        s_last = float(self.qparams.s_h[-1])
+        if chain:
+            nb = self._chain_w.nblocks
+            outs = [self._take(N, hl, hl) for _ in range(nb)] if trace is not None else None
+            with self._t("q8_sepchain", hl, nb * 2.0 * N * F_ * (2 * F_ + 9) * hl * hl, 5.0 * hd.numel()):
+                hp.q8_sepchain(h, self._chain_w, outs=outs, out_f32=hd, out_scale=s_last, slope=self.slope)
+            for t in outs or ():
+                trace["blocks"].append(t.nchw())
+                self._give(t)
+            self.counters["sepchain"] += 1
+        else:
+            with self._t("q8_dequantize", hl, 0.0, 5.0 * hd.numel()):
+                hp.q8_dequantize(h, s_last, out=hd)
+        self._give(h)
+        return self._head(hd, trace)
+
+    def _stem_u8(self, frames: torch.Tensor, trace: Optional[dict] = None) -> hp.Q8Tensor:
+        return self._stem10_u8(frames, trace)
+
+    def _forward_f32(self, x: torch.Tensor, trace: Optional[dict] = None) -> torch.Tensor:
+        if not x.is_cuda:
+            raise FdetError("Int8SeparableCNN runs on the GPU only (no CPU fallback): move the input to cuda")
+        return self._trunk(self._stem_u8(self._codes(x), trace), trace)
+
+    @torch.no_grad()
+    def forward_frames(self, x: torch.Tensor) -> torch.Tensor:
+        """frames (uint8 or float, any size) -> the head's maps, as BaseModel.forward_frames."""
+        return self._forward_any(x)
+
+    @torch.no_grad()
+    def trace(self, frames: torch.Tensor) -> dict:
+        """{"stem": int8 stem output (N,F,h0,h0), "blocks": [int8 (N,F,h,h) output of every block], "y": the head's maps}"""
+        out = {}
+        self._forward_any(frames, trace=out)
+        return out
+
+
 def quantize_model(model, frames_iter, stem: str = "float", **kw):
-    """calibrate + the int8 class of the model: Int8PoolResnet or Int8Resnet (what PoolResnet.quantize / Resnet.quantize do).
-    `stem` is Int8PoolResnet's ("float" or "integer"); a Resnet has the integer stem only and its call leaves `stem` alone."""
+    """calibrate + the int8 class of the model: Int8PoolResnet, Int8Resnet or Int8SeparableCNN (what the models' `quantize`
+    do).  `stem` is Int8PoolResnet's ("float" or "integer"); a Resnet and a SeparableCNN have their integer stem only and
+    their calls leave `stem` alone."""
     from .models.Resnet import Resnet
+    from .models.SeparableCNN import SeparableCNN
+    if type(model) is SeparableCNN:
+        if stem != "float":
+            raise ValueError("quantize_model: stem= selects PoolResnet's stem; Int8SeparableCNN has its integer stem only")
+        return Int8SeparableCNN(model, calibrate(model, frames_iter, **kw))
     if type(model) is Resnet:
         if stem != "float":
             raise ValueError("quantize_model: stem= selects PoolResnet's stem; Int8Resnet has its integer stem only")

@@ -3,6 +3,7 @@
 
     python tools/q8_throughput.py [--images 256] [--launches 100] [--calls 10] [--out profiles/r15_q8_chain.json]
     python tools/q8_throughput.py --model resnet [--images 32] [--out profiles/r17_q8_resnet.json]
+    python tools/q8_throughput.py --model separablecnn [--out profiles/r19_q8_sep.json]      (`main_separablecnn`)
 
 Workload: the inference leg's -- --images uint8 480x480 frames on the device (the three stored frames of
 tests/golden/g6_trained_small.npz, repeated) through the medium PoolResnet (64 filters, the trained weights of
@@ -185,9 +186,126 @@ def main_resnet(args):
     return res
 
 
+def main_separablecnn(args):
+    """`--model separablecnn`: --images uint8 480x480 frames (seeded random bytes) through a seeded random
+    SeparableCNN(filters=64, output_padding=3) to boxes, for the float engine (bf16x3), quantize.Int8SeparableCNN with the
+    un-pooled tail as one fdet_q8_sepchain launch, launch by launch, and as constructed -- the protocol above: one process,
+    every model warmed up, alternated sample by sample, --calls back-to-back calls per sample, median and 5th / 95th
+    percentile.  `faster.sepchain` is the rule of quantize.SEPCHAIN_MEASURED_FASTER.  Then the per-kernel-class table of the
+    two int8 modes and of the float engine, and the block kernel on its own at the model's three levels: time, compulsory
+    bytes (x read + y written) per second beside a plain device copy of the same bytes, MACs over the dense int8 peak, and at
+    60x60 the planner's tile (budget: two workgroups per CU) beside a forced 20x30 tile (one workgroup per CU)."""
+    import torch
+    import fdet_amd  # noqa: F401
+    from fdet_amd import hotpath as hp
+    from fdet_amd.convstack import KernelTimer
+    from fdet_amd.models.SeparableCNN import SeparableCNN
+    from fdet_amd.quantize import Int8SeparableCNN, calibrate
+    if not torch.cuda.is_available():
+        raise SystemExit("q8_throughput needs a GPU")
+    n = args.images
+    torch.manual_seed(190)
+    m32 = SeparableCNN(filters=64, input_shape=(3, 480, 480), output_padding=3).cuda().eval()
+    frames = torch.randint(0, 256, (n, 3, 480, 480), dtype=torch.uint8, generator=torch.Generator().manual_seed(1190)).cuda()
+    qp = calibrate(m32, [frames[:min(16, n)]])
+
+    def build8(chain):
+        m = Int8SeparableCNN(m32, qp)
+        if chain is not None:
+            m.chain = chain                                    # (the switch FDET_Q8_SEPCHAIN sets at construction)
+        return m
+    int8 = {"int8-blocks": build8("0"), "int8-chain": build8("1"), "int8": build8(None)}
+    models = {"bf16x3": m32, **int8}
+
+    def run(m):
+        with torch.no_grad():
+            return m.reduce_bounding_boxes.forward_batch(m.forward_frames(frames))
+    boxes, maps = {}, {}
+    for k, m in models.items():
+        for _ in range(args.warmup):
+            rows, counts = run(m)
+        boxes[k] = int(counts.sum())
+        with torch.no_grad():
+            maps[k] = m.forward_frames(frames)
+    identical = all(torch.equal(maps[k], maps["int8-blocks"]) for k in int8)
+    dy = (maps["int8"] - maps["bf16x3"]).abs()
+    torch.cuda.synchronize()
+    e2e = {k: _stats(v) for k, v in _alternate({k: (lambda m=m: run(m)) for k, m in models.items()}, args.launches, args.calls).items()}
+
+    def kernel_times(m, holder):
+        holder.timer = KernelTimer()
+        for _ in range(args.kernel_runs):
+            run(m)
+        s = holder.timer.summary()
+        holder.timer = None
+        return {name: {"launches_per_call": cnt // args.kernel_runs, "ms_per_call": round(total / args.kernel_runs, 4)}
+                for name, (cnt, total, _, _) in sorted(s.items())}
+    k8 = {k: kernel_times(m, m) for k, m in int8.items() if k != "int8"}
+    k32 = kernel_times(m32, m32.engine)
+
+    def classes(ks):
+        out = {}
+        for name, v in ks.items():
+            kind, at = name.split("@")
+            cls_ = "stem" if kind.startswith("stem") else "head" if kind.startswith("head") else \
+                ("tail@" if at.startswith("15x") else "level@") + at
+            out[cls_] = round(out.get(cls_, 0.0) + v["ms_per_call"], 4)
+        return out
+
+    # the block kernel on its own
+    mb = int8["int8-blocks"]
+    alone, fns, info = {}, {}, {}
+    for k, (h, pool, tile) in {"60x60_pool": (60, True, (0, 0)), "60x60_pool_tile20x30": (60, True, (20, 30)), "30x30_pool": (30, True, (0, 0)),
+                               "15x15": (15, False, (0, 0))}.items():
+        blk = {60: 0, 30: 1, 15: 2}[h]
+        x, y = hp.Q8Tensor(n, 64, h, h, "cuda"), hp.Q8Tensor(n, 64, h // (2 if pool else 1), h // (2 if pool else 1), "cuda")
+        x.storage.random_(-127, 128)
+        *w, sm = mb.blocks[blk]
+        fns[k] = lambda x=x, y=y, w=w, sm=sm, pool=pool, tile=tile: hp.q8_sepblock(x, *w, sm, y, pool=pool, tile=tile)
+        nbytes = n * 64 * h * h * (1.25 if pool else 2.0)
+        cp = torch.empty(int(nbytes) // 2, dtype=torch.uint8, device="cuda").fill_(7)
+        cd = torch.empty_like(cp)
+        fns["copy_" + k] = lambda cp=cp, cd=cd: cd.copy_(cp)
+        plan = hp.q8_sepblock_plan(64, h, h, pool)
+        info[k] = {"bytes": int(nbytes), "macs": float(n) * 64 * (2 * 64 + 9) * h * h,
+                   "tile": list(tile) if tile[0] else list(plan[:2]), "lds_bytes": plan[2] if not tile[0] else None}
+    for fn in fns.values():
+        for _ in range(args.warmup):
+            fn()
+    torch.cuda.synchronize()
+    st = {k: _stats(v) for k, v in _alternate(fns, args.launches, args.calls).items()}
+    for k, v in info.items():
+        ms, cms = st[k]["median_ms"], st["copy_" + k]["median_ms"]
+        alone[k] = {**v, **st[k], "gb_per_s": round(v["bytes"] / ms / 1e6, 1), "copy_same_bytes_ms": cms,
+                    "copy_gb_per_s": round(v["bytes"] / cms / 1e6, 1), "share_of_copy_rate": round(cms / ms, 3),
+                    "int8_peak_share": round(v["macs"] / INT8_PEAK_MACS * 1e3 / ms, 4)}
+
+    def faster(new, old):
+        gain = e2e[old]["median_ms"] - e2e[new]["median_ms"]
+        spread = max(e2e[old]["spread_ms"], e2e[new]["spread_ms"])
+        return {"gain_ms": round(gain, 4), "spread_ms": spread, "faster": bool(gain > spread)}
+    from fdet_amd import quantize as Q
+    res = {"tool": "q8_throughput", "model": "separablecnn", "device_name": torch.cuda.get_device_name(0), "images": n,
+           "launches": args.launches, "calls_per_sample": args.calls, "end_to_end": e2e,
+           "images_per_s": {k: round(n / (v["median_ms"] * 1e-3), 1) for k, v in e2e.items()}, "boxes": boxes,
+           "int8_maps_identical": identical, "counters": {k: dict(m.counters) for k, m in int8.items()},
+           "faster": {"sepchain": faster("int8-chain", "int8-blocks")}, "sepchain_default": bool(Q.SEPCHAIN_MEASURED_FASTER),
+           "over_bf16x3": {k: round(e2e["bf16x3"]["median_ms"] / e2e[k]["median_ms"], 3) for k in int8},
+           "dy_vs_float_engine": {"max": round(float(dy.max()), 6), "mean": round(float(dy.mean()), 6)},
+           "int8_kernels": k8, "float_kernels": k32, "int8_classes_ms": {k: classes(v) for k, v in k8.items()},
+           "float_classes_ms": classes(k32), "float_counters": dict(m32.engine.counters), "block_alone": alone}
+    line = json.dumps(res)
+    print(line)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+    return res
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
-    ap.add_argument("--model", choices=("poolresnet", "resnet"), default="poolresnet")
+    ap.add_argument("--model", choices=("poolresnet", "resnet", "separablecnn"), default="poolresnet")
     ap.add_argument("--images", type=int, default=None, help="frames per call (default 256; resnet: 32)")
     ap.add_argument("--launches", type=int, default=100, help="timed samples per mode")
     ap.add_argument("--calls", type=int, default=10, help="back-to-back calls per sample")
@@ -199,6 +317,8 @@ def main(argv=None):
         args.images = 32 if args.model == "resnet" else 256
     if args.model == "resnet":
         return main_resnet(args)
+    if args.model == "separablecnn":
+        return main_separablecnn(args)
     import numpy as np
     import torch
     import fdet_amd  # noqa: F401
