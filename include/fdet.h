@@ -1351,6 +1351,72 @@ int fdet_q8_sepchain(const int8_t* x, const int8_t* const* h_w1, const float* co
                      int8_t* const* h_out, float* out_f32, float out_scale, int nblocks, int N, int C, int H, int W, float slope,
                      void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Int8 inference: mixed widths -- the SSD detector (csrc/fdet_q8_ssd.hip; restated by tests/q8_ssd_cpu_ref.py, and the GPU
+ * results equal that restatement bit for bit).  SSD(filters = 16) has 16, 32, 64, 128 and 256 channels, blocks whose width
+ * changes (each with a 1x1 skip conv), a floor pool 15 -> 7, four Linear(C,5) heads and a 16-filter stem: none of it fits
+ * the entries above, which keep their shapes and refusals.  Quantisation, the Q8 layout, the preparation of (w_q, b_q, mul)
+ * and the single-rounding float steps are those of "Int8 inference" above; accumulation is exact int32 (Cin <= 256:
+ * |acc| < 2^26 + |b_q|).
+ *
+ * Here a Q8 tensor has C any multiple of 16 up to 256 (fdet_q8x_supported / fdet_q8x_act_bytes; the old helpers keep their
+ * answers).
+ *
+ * Packed weights ("Q8X"): flatten K tap-major, channel-minor, k = tap * Cin + ci (tap = ky*3+kx; a 1x1 conv has the one tap
+ * and k = ci), zero-pad K to a multiple of 64, lay out as int8 [K/64][Cout][64] -- a plain permutation of [Cout][Cin][3][3]
+ * plus zero bytes (hotpath.q8x_pack_weights does it with torch).  For Cin a multiple of 64 this is the packed order of
+ * fdet_q8_conv3x3.
+ * ------------------------------------------------------------------------------------- */
+
+/* 1 when Q8 tensors of this shape exist for the entries below: C a multiple of 16 up to 256, 1 <= H, W <= 4096. */
+int fdet_q8x_supported(int C, int H, int W);
+
+/* Bytes of such a tensor, N * (H+2) * (W+2) * C; 0 for an unsupported shape or 2^31 bytes and more. */
+size_t fdet_q8x_act_bytes(int N, int C, int H, int W);
+
+/* 3x3 convolution, pad 1, Cin -> Cout channels, with the epilogue of fdet_q8_conv3x3 element for element:
+ *     acc = bias[co] + sum x_q * w_q                       int32, exact
+ *     t   = float(acc) * mul[co]
+ *     t   = t >= 0 ? t : t * slope
+ *     t   = t + float(skip_q) * skip_mul                   (skip != NULL only; skip has Cout channels)
+ *     q   = clamp(rintf(t), -127, 127)
+ *     y   = pool ? max of q over each 2x2 window : q
+ * The pool is a FLOOR pool: y is H/2 x W/2 by integer division, and an odd last row or column takes part in no window
+ * (15 -> 7); for even maps it is the pool of fdet_q8_conv3x3.
+ *   x [N,Cin,H,W] Q8; skip [N,Cout,H,W] Q8 or NULL; wpk Q8X packed weights; bias [Cout] int32; mul [Cout] fp32;
+ *   y Q8 [N,Cout,H,W] or [N,Cout,H/2,W/2], real pixels only, not aliasing x or skip.
+ * Accepted: Cin and Cout multiples of 16 up to 256, 1 <= H, W <= 4096 (at least 2 x 2 when pooled), every tensor under 2^31
+ * bytes and 16-byte aligned.  A block computes 16, 32 or 64 output channels (no channel is computed and thrown away).
+ * fdet_q8x_conv3x3_ok: the entry accepts this shape (launches nothing). */
+int fdet_q8x_conv3x3_ok(int N, int Cin, int Cout, int H, int W, int pool);
+int fdet_q8x_conv3x3(const int8_t* x, const int8_t* wpk, const int32_t* bias, const float* mul, const int8_t* skip,
+                     float skip_mul, int8_t* y, int N, int Cin, int Cout, int H, int W, int pool, float slope, void* stream);
+
+/* The 1x1 skip conv of a block whose width changes, Cin -> Cout, identity activation:
+ *     q = clamp(rintf(float(bias[co] + sum_ci x_q[ci] * w_q[co][ci]) * mul[co]), -127, 127)
+ * written as a Q8 tensor of Cout channels (real pixels only; y may not alias x).  wpk: Q8X packed [Cout][Cin][1][1].  Same
+ * acceptance as fdet_q8x_conv3x3 without pool.  fdet_q8x_pointwise_ok launches nothing. */
+int fdet_q8x_pointwise_ok(int N, int Cin, int Cout, int H, int W);
+int fdet_q8x_pointwise(const int8_t* x, const int8_t* wpk, const int32_t* bias, const float* mul, int8_t* y, int N, int Cin, int Cout,
+                       int H, int W, void* stream);
+
+/* Linear(C,5) at every position of a Q8 map:
+ *     z[n][o][y][x] = float(b_q[o] + sum_c h_q[c] * w_q[o][c]) * m[o]         (int -> float RNE, one fp32 multiply)
+ * with m = s_w * s_in (one fp32 multiply on the host) and b_q = rint(b / (s_w * s_in)).  z is fp32 [N,5,H,W], what
+ * fdet_ssd_head_pack_fwd takes (CP = 5): sigmoid and priors stay the float kernel.
+ *   x Q8 [N,C,H,W]; w_q int8 [5][C] rows; b_q int32 [5]; m fp32 [5]; every pointer 16-byte aligned.
+ * fdet_q8x_head_ok launches nothing. */
+int fdet_q8x_head_ok(int N, int C, int H, int W);
+int fdet_q8x_head_f32(const int8_t* x, const int8_t* w_q, const int32_t* b_q, const float* m, float* z, int N, int C, int H, int W,
+                      void* stream);
+
+/* fdet_stem3_fwd_q8_u8's contract, unchanged, for F a multiple of 16 up to 256 (the SSD stem has 16 filters): uint8 frames
+ * as codes of scale 1 / 255, 27 taps, t = float(acc) * mul[co], no LeakyReLU, Q8 output of H/2 x W/2, w_q int8 [F][32].  For
+ * F % 64 == 0 it is the existing entry.  fdet_stem3_fwd_q8x_ok launches nothing. */
+int fdet_stem3_fwd_q8x_ok(int N, int Cin, int F, int H, int W);
+int fdet_stem3_fwd_q8x_u8(const unsigned char* frames, const int8_t* w_q, const int32_t* b_q, const float* mul, int8_t* q,
+                          int N, int Cin, int F, int H, int W, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

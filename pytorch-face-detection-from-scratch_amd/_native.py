@@ -209,6 +209,16 @@ SIGNATURES = {
     "fdet_q8_sepblock": (_I, [_P, _P, _P, _P, _P, _P, _P, _F, _P, _I, _I, _I, _I, _I, _I, _I, _F, _P]),
     "fdet_q8_sepchain_supported": (_I, [_I, _I, _I]),
     "fdet_q8_sepchain": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _F, _I, _I, _I, _I, _I, _F, _P]),
+    "fdet_q8x_supported": (_I, [_I, _I, _I]),
+    "fdet_q8x_act_bytes": (_SZ, [_I, _I, _I, _I]),
+    "fdet_q8x_conv3x3_ok": (_I, [_I, _I, _I, _I, _I, _I]),
+    "fdet_q8x_conv3x3": (_I, [_P, _P, _P, _P, _P, _F, _P, _I, _I, _I, _I, _I, _I, _F, _P]),
+    "fdet_q8x_pointwise_ok": (_I, [_I, _I, _I, _I, _I]),
+    "fdet_q8x_pointwise": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
+    "fdet_q8x_head_ok": (_I, [_I, _I, _I, _I]),
+    "fdet_q8x_head_f32": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
+    "fdet_stem3_fwd_q8x_ok": (_I, [_I, _I, _I, _I, _I]),
+    "fdet_stem3_fwd_q8x_u8": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
 }
 
 

@@ -19,6 +19,7 @@
 // contract's.  Both operands take tap k from the same byte of the same lane group, so the sum does not depend on how the
 // instruction orders k inside a fragment; the one-hot tests (tests/test_gpu_q8_resnet.py) check taps, lanes and channels.
 #include "fdet_common.h"
+#include "fdet_stem3_q8.h"
 
 namespace {
 using namespace fdet;
@@ -26,25 +27,10 @@ using namespace fdet;
 typedef int s3_v4i __attribute__((ext_vector_type(4)));
 typedef float s3_v4f __attribute__((ext_vector_type(4)));
 
-constexpr int S3_ROWS = 4;                          // output rows per workgroup: one per wave
-constexpr int S3_SEG = 256;                         // output columns per workgroup: 16 MFMA column tiles
-constexpr int S3_IN_ROWS = 2 * S3_ROWS + 1;         // input rows under S3_ROWS output rows
-constexpr int S3_RS = 2 * S3_SEG + 16;              // bytes of one staged input row: image columns 2 ox0 - 4 .. 2 ox0 + 2 SEG + 11
-constexpr int S3_LDS = 3 * S3_IN_ROWS * S3_RS;      // 14,256 bytes
+// (geometry, row staging, tap offsets and the B gather: fdet_stem3_q8.h, shared with k_stem3_q8x of fdet_q8_ssd.hip)
 constexpr int S3_MAX_HW = 4096;
 constexpr int S3_MAX_F = 256;
-constexpr long long S3_MAX_ITEMS = 1ll << 20;       // workgroups per launch (larger batches: consecutive launches)
-
-struct Stem3Args {
-  const unsigned char* frames;
-  const signed char* w;                              // [F][32]
-  const int* bias;
-  const float* mul;
-  signed char* q;
-  int N, F, H, W, Ho, Wo;
-  int segs, row_groups;
-  int dwords;                                        // 1: W % 4 == 0 and a 4-byte aligned frame pointer, rows are read as dwords
-};
+typedef s3::Args Stem3Args;
 
 __host__ __device__ inline bool s3_shape_ok(int Cin, int F, int H, int W) {
   return Cin == 3 && F >= 64 && F <= S3_MAX_F && (F & 63) == 0 && H >= 2 && W >= 2 && H <= S3_MAX_HW && W <= S3_MAX_HW &&
@@ -71,35 +57,10 @@ __device__ __forceinline__ int s3_pack4(int a, int b, int c, int d) {
 // blockIdx.y * 64 .. + 63.  It stages the 9 input rows x 3 channels under its rows once; wave j then walks the column tiles of
 // output row j.  LDS row (ci, iy) holds input row 2 oy0 - 1 + iy of channel ci; its byte i is image column 2 ox0 - 4 + i.
 __global__ __launch_bounds__(256) void k_stem3_q8(const Stem3Args a) {
-  __shared__ __attribute__((aligned(16))) unsigned char rows[S3_LDS];
-  const int item = blockIdx.x;
-  const int per_img = a.segs * a.row_groups;
-  const int n = item / per_img;
-  const int rem = item - n * per_img;
-  const int rg = rem / a.segs;
-  const int ox0 = (rem - rg * a.segs) * S3_SEG;
-  const int oy0 = rg * S3_ROWS;
-  const int ntiles = (min(S3_SEG, a.Wo - ox0) + 15) >> 4;
-  const int nd = ((32 * ntiles + 3) >> 2) + 1;              // dwords of a staged row that the tiles read (bytes 3 .. 32 ntiles + 3)
-  const int c0 = 2 * ox0 - 4;                               // image column of byte 0 (a multiple of 4)
-  const int y0 = 2 * oy0 - 1;
-  for (int u = threadIdx.x; u < 3 * S3_IN_ROWS * nd; u += 256) {
-    const int lr = u / nd, d = u - lr * nd;
-    const int ci = lr / S3_IN_ROWS, iy = lr - ci * S3_IN_ROWS;
-    const int y = y0 + iy, c = c0 + 4 * d;
-    unsigned v = 0;                                         // outside the image: code 0
-    if (y >= 0 && y < a.H && c + 3 >= 0 && c < a.W) {
-      const unsigned char* src = a.frames + ((size_t)(n * 3 + ci) * a.H + y) * a.W;
-      if (a.dwords) {                                       // c and W are multiples of 4: the dword is inside the row as a whole
-        v = *reinterpret_cast<const unsigned*>(src + c);
-      } else {
-#pragma unroll
-        for (int b = 0; b < 4; ++b)
-          if (c + b >= 0 && c + b < a.W) v |= (unsigned)src[c + b] << (8 * b);
-      }
-    }
-    *reinterpret_cast<unsigned*>(rows + lr * S3_RS + 4 * d) = v ^ 0x80808080u;          // x - 128 as a signed byte
-  }
+  __shared__ __attribute__((aligned(16))) unsigned char rows[s3::LDS];
+  const s3::Item it = s3::item_of(a, blockIdx.x);
+  const int n = it.n, ox0 = it.ox0, oy0 = it.oy0, ntiles = it.ntiles;
+  s3::stage_rows(a, it, rows);
   const int lane = threadIdx.x & 63, j = threadIdx.x >> 6;
   const int lp = lane & 15, lk = lane >> 4;
   const int co0 = blockIdx.y * 64;
@@ -126,26 +87,14 @@ __global__ __launch_bounds__(256) void k_stem3_q8(const Stem3Args a) {
       cst[t][r] = (unsigned)bv[r] + 128u * (unsigned)ws[r];
     }
   }
-  // B: tap k = 8 lk + e -> LDS row (ci, 2 j + ky), byte 2 (ox - ox0) + kx + 3; taps 27..31 read tap 26 again (weight zero)
   int off[8];
-#pragma unroll
-  for (int e = 0; e < 8; ++e) {
-    const int k = min(8 * lk + e, 26);
-    const int ci = k / 9, ky = (k - 9 * ci) / 3, kx = k - 9 * ci - 3 * ky;
-    off[e] = (ci * S3_IN_ROWS + 2 * j + ky) * S3_RS + kx + 3 + 2 * lp;
-  }
+  s3::tap_offsets(off, lk, lp, j);
   __syncthreads();
   const int oy = oy0 + j;
   if (oy >= a.Ho) return;                                   // (after the only barrier)
   signed char* qrow = a.q + ((size_t)(n * (a.Ho + 2) + oy + 1) * (a.Wo + 2) + ox0 + 1) * a.F + co0 + 16 * lk;
   for (int tile = 0; tile < ntiles; ++tile) {
-    unsigned lo = 0, hi = 0;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      lo |= (unsigned)rows[off[e] + 32 * tile] << (8 * e);
-      hi |= (unsigned)rows[off[e + 4] + 32 * tile] << (8 * e);
-    }
-    const long b = (long)(((unsigned long)hi << 32) | lo);
+    const long b = s3::gather(rows, off, tile);
     int o[4];
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
@@ -178,25 +127,7 @@ extern "C" int fdet_stem3_fwd_q8_u8(const unsigned char* frames, const int8_t* w
                "output under 2^31 bytes)", N, Cin, F, H, W, S3_MAX_F, S3_MAX_HW);
   FDET_REQUIRE(s3_aligned16(w_q) && s3_aligned16(b_q) && s3_aligned16(mul) && s3_aligned16(q),
                "stem3_fwd_q8: w_q, b_q, mul and q must be 16-byte aligned");
-  const int Ho = H / 2, Wo = W / 2;
-  const int segs = (Wo + S3_SEG - 1) / S3_SEG, row_groups = (Ho + S3_ROWS - 1) / S3_ROWS;
-  const long long per_img = (long long)segs * row_groups;
-  const int chunk = (int)std::max(1ll, S3_MAX_ITEMS / per_img);
-  for (int n0 = 0; n0 < N; n0 += chunk) {
-    Stem3Args a{};
-    a.frames = frames + (size_t)n0 * 3 * H * W;
-    a.w = reinterpret_cast<const signed char*>(w_q);
-    a.bias = b_q;
-    a.mul = mul;
-    a.q = reinterpret_cast<signed char*>(q) + (size_t)n0 * (Ho + 2) * (Wo + 2) * F;
-    a.N = std::min(chunk, N - n0); a.F = F; a.H = H; a.W = W; a.Ho = Ho; a.Wo = Wo;
-    a.segs = segs; a.row_groups = row_groups;
-    a.dwords = (W & 3) == 0 && (reinterpret_cast<uintptr_t>(a.frames) & 3) == 0;
-    const dim3 grid((unsigned)(a.N * per_img), (unsigned)(F / 64));
-    hipLaunchKernelGGL(k_stem3_q8, grid, dim3(256), 0, (hipStream_t)stream, a);
-    if (int rc = check_launch("fdet_stem3_fwd_q8_u8")) return rc;
-  }
-  return FDET_OK;
+  return s3::launch(k_stem3_q8, F / 64, frames, w_q, b_q, mul, q, N, F, H, W, (hipStream_t)stream, "fdet_stem3_fwd_q8_u8");
 }
 
 namespace {

@@ -1822,3 +1822,127 @@ def q8_sepchain(x: Q8Tensor, weights: Q8SepChainWeights, outs: Optional[Sequence
     w1, m1, wd, m2, w2, m3 = weights.arrays
     check(lib().fdet_q8_sepchain(x.data, w1, m1, wd, m2, w2, m3, weights.skip_mul, h_out, ptr(out_f32), float(out_scale), nb,
                                  Nn, C, H, W, float(slope), stream()), "fdet_q8_sepchain")
+
+
+# ------------------------------------------------------------------------------------------
+# int8 inference, mixed widths: the SSD detector (csrc/fdet_q8_ssd.hip; include/fdet.h "Int8 inference: mixed widths")
+# ------------------------------------------------------------------------------------------
+def q8x_supported(C: int, H: int, W: int) -> bool:
+    """Q8 tensors of this shape exist for the q8x entries: C a multiple of 16 up to 256, 1 <= H, W <= 4096."""
+    return bool(lib().fdet_q8x_supported(int(C), int(H), int(W)))
+
+
+def q8x_act_bytes(Nn: int, C: int, H: int, W: int) -> int:
+    return int(lib().fdet_q8x_act_bytes(int(Nn), int(C), int(H), int(W)))
+
+
+class Q8XTensor(Q8Tensor):
+    """A Q8Tensor whose channel count is any multiple of 16 up to 256 (fdet_q8x_act_bytes): the same layout, zero-filled
+    when it is made."""
+
+    def __init__(self, Nn: int, C: int, H: int, W: int, device):
+        nbytes = q8x_act_bytes(Nn, C, H, W)
+        if nbytes == 0:
+            raise N.FdetError(f"Q8XTensor: unsupported shape ({Nn},{C},{H},{W}) (C % 16 == 0, C <= 256, under 2 GiB)")
+        self.storage = torch.zeros(nbytes, dtype=I8, device=device)
+        self.shape = (int(Nn), int(C), int(H), int(W))
+
+    def reshape_(self, Nn: int, C: int, H: int, W: int):
+        raise N.FdetError("Q8XTensor: make a new tensor for another shape")
+
+
+def q8x_pack_weights(w_q: torch.Tensor) -> torch.Tensor:
+    """int8 [Cout,Cin,kh,kw] (3x3 or 1x1) -> [K/64][Cout][64] with k = tap * Cin + ci, K zero-padded to a multiple of 64 (one-time
+    work: a torch permutation and zero bytes)."""
+    if w_q.dtype != I8 or w_q.dim() != 4 or tuple(w_q.shape[2:]) not in ((3, 3), (1, 1)) or w_q.shape[0] % 16 or w_q.shape[1] % 16:
+        raise ValueError("q8x_pack_weights: expected int8 weights [Cout,Cin,3,3] or [Cout,Cin,1,1] with Cout and Cin multiples of 16")
+    co, ci = w_q.shape[:2]
+    K = ci * w_q.shape[2] * w_q.shape[3]
+    KP = (K + 63) // 64 * 64
+    flat = torch.zeros(co, KP, dtype=I8, device=w_q.device)
+    flat[:, :K] = w_q.permute(0, 2, 3, 1).reshape(co, K)
+    return flat.reshape(co, KP // 64, 64).permute(1, 0, 2).contiguous().reshape(-1)
+
+
+def _q8x_weights_ok(wpk, bias, mul, cin, cout, taps, name):
+    if wpk.numel() != (taps * cin + 63) // 64 * 64 * cout:
+        raise ValueError(f"{name}: packed weight size does not match the channel counts (q8x_pack_weights)")
+    _chk4(bias, (cout,), "bias")
+    _chk4(mul, (cout,), "mul")
+
+
+def q8x_conv3x3(x: Q8Tensor, wpk: torch.Tensor, bias: torch.Tensor, mul: torch.Tensor, y: Q8Tensor, skip: Optional[Q8Tensor] = None,
+                skip_mul: float = 0.0, pool: bool = False, slope: float = 0.2) -> Q8Tensor:
+    """y = requantise(LeakyReLU((bias + conv3x3(x)) * mul) [+ skip * skip_mul]) [2x2 floor-max-pooled], Cin -> Cout
+    (fdet_q8x_conv3x3); Cout is y's channel count."""
+    if not isinstance(x, Q8Tensor) or not isinstance(y, Q8Tensor):
+        raise ValueError("q8x_conv3x3: x and y must be Q8 tensors")
+    Nn, Cin, H, W = x.shape
+    Cout = y.shape[1]
+    _q8_same(y, (Nn, Cout, H // 2, W // 2) if pool else (Nn, Cout, H, W), "q8x_conv3x3: y")
+    if skip is not None:
+        _q8_same(skip, (Nn, Cout, H, W), "q8x_conv3x3: skip")
+    _q8x_weights_ok(wpk, bias, mul, Cin, Cout, 9, "q8x_conv3x3")
+    check(lib().fdet_q8x_conv3x3(x.data, ptr(wpk, I8), ptr(bias, torch.int32), ptr(mul), skip.data if skip is not None else None,
+                                 float(skip_mul), y.data, Nn, Cin, Cout, H, W, int(bool(pool)), float(slope), stream()),
+          "fdet_q8x_conv3x3")
+    return y
+
+
+def q8x_pointwise(x: Q8Tensor, wpk: torch.Tensor, bias: torch.Tensor, mul: torch.Tensor, y: Q8Tensor) -> Q8Tensor:
+    """y = requantise((bias + conv1x1(x)) * mul), Cin -> Cout, identity activation (fdet_q8x_pointwise)."""
+    if not isinstance(x, Q8Tensor) or not isinstance(y, Q8Tensor):
+        raise ValueError("q8x_pointwise: x and y must be Q8 tensors")
+    Nn, Cin, H, W = x.shape
+    Cout = y.shape[1]
+    _q8_same(y, (Nn, Cout, H, W), "q8x_pointwise: y")
+    _q8x_weights_ok(wpk, bias, mul, Cin, Cout, 1, "q8x_pointwise")
+    check(lib().fdet_q8x_pointwise(x.data, ptr(wpk, I8), ptr(bias, torch.int32), ptr(mul), y.data, Nn, Cin, Cout, H, W, stream()),
+          "fdet_q8x_pointwise")
+    return y
+
+
+def q8x_head_f32(x: Q8Tensor, w_q: torch.Tensor, b_q: torch.Tensor, m: torch.Tensor, z: torch.Tensor) -> torch.Tensor:
+    """z (N,5,H,W) fp32 = float(b_q + sum_c x[c] * w_q[o][c]) * m[o] at every position (fdet_q8x_head_f32)."""
+    if not isinstance(x, Q8Tensor):
+        raise ValueError("q8x_head_f32: x must be a Q8 tensor")
+    Nn, C, H, W = x.shape
+    _chk4(w_q, (5, C), "w_q")
+    _chk4(b_q, (5,), "b_q")
+    _chk4(m, (5,), "m")
+    _chk4(z, (Nn, 5, H, W), "z")
+    check(lib().fdet_q8x_head_f32(x.data, ptr(w_q, I8), ptr(b_q, torch.int32), ptr(m), ptr(z), Nn, C, H, W, stream()),
+          "fdet_q8x_head_f32")
+    return z
+
+
+def stem3_fwd_q8x_ok(N_, cin, F_, H, W) -> bool:
+    """fdet_stem3_fwd_q8x_u8 accepts N images of this shape: 3 channels, F a multiple of 16 up to 256, even H and W up to 4096."""
+    return bool(lib().fdet_stem3_fwd_q8x_ok(int(N_), int(cin), int(F_), int(H), int(W)))
+
+
+def q8x_pack_stem_weights(w_q: torch.Tensor) -> torch.Tensor:
+    """int8 [F,3,3,3] -> the integer stem's [F][32] (q8_pack_stem_weights for F a multiple of 16)."""
+    if w_q.dtype != I8 or w_q.dim() != 4 or tuple(w_q.shape[1:]) != (3, 3, 3) or w_q.shape[0] % 16:
+        raise ValueError("q8x_pack_stem_weights: expected int8 weights [F,3,3,3] with F % 16 == 0")
+    out = torch.zeros(w_q.shape[0], 32, dtype=I8, device=w_q.device)
+    out[:, :27] = w_q.reshape(w_q.shape[0], 27)
+    return out.reshape(-1)
+
+
+def stem3_fwd_q8x_u8(frames: torch.Tensor, wpk: torch.Tensor, bias: torch.Tensor, mul: torch.Tensor, out: Q8Tensor) -> Q8Tensor:
+    """stem3_fwd_q8_u8 for F a multiple of 16 (fdet_stem3_fwd_q8x_u8)."""
+    if frames.dim() != 4 or frames.dtype != torch.uint8:
+        raise ValueError("stem3_fwd_q8x_u8: expected uint8 frames (N,3,H,W)")
+    Nn, cin, H, W = frames.shape
+    F_ = bias.shape[0]
+    if wpk.numel() != 32 * F_:
+        raise ValueError("stem3_fwd_q8x_u8: packed weight size does not match the channel count (q8x_pack_stem_weights)")
+    _chk4(bias, (F_,), "bias")
+    _chk4(mul, (F_,), "mul")
+    if H % 2 or W % 2:
+        raise ValueError(f"stem3_fwd_q8x_u8: H and W must be even, got {H}x{W}")
+    _q8_same(out, (Nn, F_, H // 2, W // 2), "stem3_fwd_q8x_u8: out")
+    check(lib().fdet_stem3_fwd_q8x_u8(ptr(frames, torch.uint8), ptr(wpk, I8), ptr(bias, torch.int32), ptr(mul), out.data, Nn, cin,
+                                      F_, H, W, stream()), "fdet_stem3_fwd_q8x_u8")
+    return out

@@ -92,6 +92,12 @@ class SSD(nn.Module):
         from ..torchscript import to_torchscript
         return to_torchscript(self, file_path)
 
+    def quantize(self, frames_iter, **kw):
+        """Post-training int8 inference model (quantize.Int8SSD): calibrate on `frames_iter` (frames as forward(x, predict=1)
+        takes them), then the integer stem, trunk and heads.  filters=16 at 480x480 only."""
+        from ..quantize import quantize_ssd
+        return quantize_ssd(self, frames_iter, **kw)
+
     def forward(self, x: torch.Tensor, predict: torch.Tensor = torch.tensor(0)):
         if predict == 1:
             if x.dim() == 3:

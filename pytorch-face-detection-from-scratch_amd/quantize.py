@@ -21,6 +21,12 @@ stem's bytes.
 
 SeparableCNN enters through that integer stem and runs every separable block as one launch of fdet_q8_sepblock
 (the un-pooled tail as one fdet_q8_sepchain launch where measured faster); tests/q8_sep_cpu_ref.py restates the block.
+
+    m8 = Int8SSD(model, calibrate_ssd(model, frames_iter))                  # (an SSD(filters=16); SSD.quantize does both)
+
+SSD has its own scales (SSDQuantParams), calibration (calibrate_ssd) and kernels (csrc/fdet_q8_ssd.hip: the
+Cin -> Cout conv with a floor pool, the 1x1 skip conv, the Linear(C,5) head, the 16-filter stem); tests/q8_ssd_cpu_ref.py
+restates them.  `calibrate`, `QuantParams` and `quantize_model` are what they were and refuse an SSD.
 """
 from __future__ import annotations
 
@@ -791,6 +797,366 @@ class Int8SeparableCNN(_Int8Trunk):
         out = {}
         self._forward_any(frames, trace=out)
         return out
+
+
+# ---------------------------------------------------------------------------------------------------------- SSD
+SSD_QPARAMS_VERSION = 1
+
+
+class SSDQuantParams:
+    """Activation scales of the int8 SSD, on the CPU: s_h[k] of block k's input (k = 0..nb; s_h[nb] is the last
+    head's input), s_a[k] of block k's first-conv output, and s_k[j] of the 1x1 skip conv's output of the j-th block whose
+    width changes (in block order).  Symmetric, per tensor, float32.  Its own class and its own versioned file (its arrays carry
+    their own names, so neither class reads the other's file): QuantParams and its files are what they were."""
+
+    def __init__(self, s_h: Sequence[float], s_a: Sequence[float], s_k: Sequence[float], method: str = "explicit",
+                 percentile: Optional[float] = None, images_seen: int = 0):
+        self.s_h = np.asarray(s_h, dtype=NPF).reshape(-1).copy()
+        self.s_a = np.asarray(s_a, dtype=NPF).reshape(-1).copy()
+        self.s_k = np.asarray(s_k, dtype=NPF).reshape(-1).copy()
+        if self.s_a.size < 1 or self.s_h.size != self.s_a.size + 1:
+            raise ValueError(f"SSDQuantParams: {self.s_h.size} block-input scales need {self.s_h.size - 1} first-conv scales, "
+                             f"got {self.s_a.size}")
+        if self.s_k.size > self.s_a.size:
+            raise ValueError(f"SSDQuantParams: {self.s_k.size} skip-conv scales for {self.s_a.size} blocks")
+        for name, s in (("s_h", self.s_h), ("s_a", self.s_a), ("s_k", self.s_k)):
+            if not (np.all(np.isfinite(s)) and np.all(s > 0)):
+                raise ValueError(f"SSDQuantParams: every scale in {name} must be positive and finite")
+        if method not in METHODS:
+            raise ValueError(f"SSDQuantParams: method must be one of {METHODS}")
+        self.method = method
+        self.percentile = None if percentile is None else float(percentile)
+        self.images_seen = int(images_seen)
+
+    @property
+    def num_blocks(self) -> int:
+        return int(self.s_a.size)
+
+    def save(self, path) -> None:
+        np.savez(path, kind=np.array("ssd"), version=np.array(SSD_QPARAMS_VERSION, dtype=np.int64), ssd_s_h=self.s_h,
+                 ssd_s_a=self.s_a, ssd_s_k=self.s_k, method=np.array(self.method),
+                 percentile=np.array(np.nan if self.percentile is None else self.percentile, dtype=np.float64),
+                 images_seen=np.array(self.images_seen, dtype=np.int64))
+
+    @classmethod
+    def load(cls, path) -> "SSDQuantParams":
+        with np.load(path, allow_pickle=False) as z:
+            if "kind" not in z.files or str(z["kind"]) != "ssd":
+                raise ValueError("SSDQuantParams.load: not an SSD scale file")
+            if int(z["version"]) != SSD_QPARAMS_VERSION:
+                raise ValueError(f"SSDQuantParams.load: file version {int(z['version'])}, this code reads {SSD_QPARAMS_VERSION}")
+            pct = float(z["percentile"])
+            return cls(z["ssd_s_h"], z["ssd_s_a"], z["ssd_s_k"], str(z["method"]), None if np.isnan(pct) else pct, int(z["images_seen"]))
+
+    def __eq__(self, other):
+        return (isinstance(other, SSDQuantParams) and np.array_equal(self.s_h, other.s_h) and np.array_equal(self.s_a, other.s_a)
+                and np.array_equal(self.s_k, other.s_k)
+                and (self.method, self.percentile, self.images_seen) == (other.method, other.percentile, other.images_seen))
+
+    def __repr__(self):
+        return (f"SSDQuantParams(blocks={self.num_blocks}, skips={self.s_k.size}, method={self.method!r}, "
+                f"percentile={self.percentile}, images_seen={self.images_seen})")
+
+
+def _check_ssd(model, me: str):
+    from .models.SSD import SSD
+    if type(model) is not SSD:
+        raise TypeError(f"{me} covers SSD only, got {type(model).__name__}")
+
+
+def _ssd_preprocess(model, x: torch.Tensor) -> torch.Tensor:
+    """Frames -> float images in [0,1] at the model resolution: the preprocessing of SSD.forward(x, predict=1)."""
+    if x.dim() == 3:
+        x = x.unsqueeze(0)
+    size = tuple(model.input_shape[1:])
+    return hp.resize_bilinear_norm(x, size) if tuple(x.shape[-2:]) != size or x.dtype == torch.uint8 else x.float() / 255.0
+
+
+@torch.no_grad()
+def calibrate_ssd(model, frames_iter: Iterable[torch.Tensor], method: str = "absmax",
+                  percentile: Optional[float] = None) -> SSDQuantParams:
+    """`calibrate` for an SSD: the float bf16x3 engine (eval arithmetic) over frames as `forward_frames` takes them, its saved
+    block inputs, skip-conv outputs, first-conv outputs and head inputs reduced to scales by ActivationObserver's range rule."""
+    _check_ssd(model, "calibrate_ssd")
+    if percentile is not None and method == "absmax":
+        method = "percentile"
+    eng = model.engine
+    if eng.p16:
+        raise FdetError("calibrate_ssd: run the calibration on the bf16x3 engine, not in precision16")
+    specs = eng.specs
+    nb = len(specs)
+    obs = ActivationObserver(nb, method, percentile)
+    wide = [k for k, s in enumerate(specs) if s[1] != s[2]]
+    k_range = [0.0] * len(wide)
+    dev = next(model.parameters()).device
+    names, params = model.named_stack_params()
+    P = {n: p.detach() for n, p in zip(names, params)}
+    nheads = len(model.patch_sizes)
+    for frames in frames_iter:
+        x = _ssd_preprocess(model, torch.as_tensor(frames).to(dev))
+        _, saved = eng.forward(x, P, None, save=True)
+        blocks = saved["blocks"]
+        obs.observe([b[0] for b in blocks] + [saved["heads"][nheads - 1]], [b[2] for b in blocks])
+        for j, k in enumerate(wide):
+            k_range[j] = max(k_range[j], obs._range(blocks[k][1]))
+        for i in range(nheads - 1):                        # (heads 0..2 read the inputs of the blocks after them: the same tensors)
+            k_in = nb - (nheads - 1) + i
+            obs.h[k_in] = max(obs.h[k_in], obs._range(saved["heads"][i]))
+    q = obs.params()
+    return SSDQuantParams(q.s_h, q.s_a, [NPF(1.0) if v == 0.0 else NPF(v) / NPF(127.0) for v in k_range], q.method, q.percentile,
+                          q.images_seen)
+
+
+def prepare_head(w: np.ndarray, b: np.ndarray, s_in):
+    """One Linear(C,5) head's integers: (w_q int8 [5,C], b_q int32 [5], m float32 [5]) with s_w[o] = absmax(w[o]) / 127 (1 for
+    a row of zeros), b_q = rint(b / (s_w * s_in)) in float64 and m = s_w * s_in, one float32 multiply."""
+    w = np.asarray(w, dtype=NPF)
+    w_q, b_q, _ = prepare_conv(w.reshape(w.shape[0], -1, 1, 1), b, s_in, NPF(1.0))
+    a = np.abs(w).max(axis=1).astype(NPF)
+    s_w = np.where(a == 0, NPF(1.0), a / NPF(127.0)).astype(NPF)
+    return w_q.reshape(w.shape), b_q, (s_w * NPF(s_in)).astype(NPF)
+
+
+class _Q8XConv:
+    def __init__(self, w, b, s_in, s_out, dev):
+        w_q, b_q, mul = prepare_conv(w, b, s_in, s_out)
+        self.wpk = hp.q8x_pack_weights(torch.from_numpy(w_q).to(dev))
+        self.bias = torch.from_numpy(b_q).to(dev)
+        self.mul = torch.from_numpy(mul).to(dev)
+
+
+class Int8SSD:
+    """An SSD(filters=16) at 480x480 in int8 from the frame bytes to the heads' outputs: the integer stem on the
+    uint8 frames (fdet_stem3_fwd_q8x_u8), thirteen residual blocks on the integer matrix cores (fdet_q8x_conv3x3 with the
+    skip add and the floor pool in its epilogue; fdet_q8x_pointwise for the 1x1 skip conv of the blocks whose width changes),
+    the four Linear(C,5) heads as integer dot products (fdet_q8x_head_f32), and the float sigmoid-and-priors kernel
+    (fdet_ssd_head_pack_fwd).  One input rule, as Int8Resnet: uint8 frames on the GPU at the model resolution go to the stem
+    as they are; everything else goes through the model's preprocessing and `_codes` to the same stem.
+
+    Inference only, GPU only, eval arithmetic; weights and scales are those at construction.  The Q8 buffers of a batch size
+    are made (zero-filled) on the first call with it and the (N,4774,5) output is preallocated: a later call with the same N
+    allocates nothing, runs on one stream without a host synchronisation and can be captured in a HIP graph.  The returned
+    tensor is that buffer: the next call with the same N overwrites it.  Accuracy on trained weights is unpinned (no trained
+    SSD archive exists); the tests pin the arithmetic and the quantisation error of a seeded model."""
+
+    training = False
+    COUNTERS = ("stem_q8", "convs", "pointwise", "heads")
+
+    def __init__(self, model, qparams: SSDQuantParams):
+        _check_ssd(model, "Int8SSD")
+        if not isinstance(qparams, SSDQuantParams):
+            raise TypeError("Int8SSD: qparams must be an SSDQuantParams")
+        if int(model.filters) != 16 or tuple(model.input_shape) != (3, 480, 480):
+            raise ValueError(f"Int8SSD: filters=16 at 480x480 only, got filters={model.filters} at {tuple(model.input_shape)}: a "
+                             "wider model exceeds the 256 channels of the int8 kernels")
+        from .ssdstack import PATCH_SIZES, block_specs
+        self.specs = block_specs(16)
+        nb = len(self.specs)
+        self.wide = [k for k, s in enumerate(self.specs) if s[1] != s[2]]
+        if qparams.num_blocks != nb or qparams.s_k.size != len(self.wide):
+            raise ValueError(f"Int8SSD: the model has {nb} blocks, {len(self.wide)} of them with a skip conv; the scales are for "
+                             f"{qparams.num_blocks} and {qparams.s_k.size}")
+        dev = next(model.parameters()).device
+        if dev.type != "cuda":
+            raise FdetError("Int8SSD runs on the GPU only (no CPU fallback): move the model to cuda first")
+        self.input_shape = model.input_shape
+        self.patch_sizes = tuple(model.patch_sizes)
+        self.filters = 16
+        self.size = 480
+        self.probability_threshold = model.probability_threshold
+        self.iou_threshold = model.iou_threshold
+        self.reduce_bounding_boxes = model.reduce_bounding_boxes
+        self.qparams = qparams
+        self.device = dev
+        self.slope = 0.2
+        self.starts = [0]
+        for ps in PATCH_SIZES:
+            self.starts.append(self.starts[-1] + ps * ps)
+        self.P = self.starts[-1]
+        self.counters = {k: 0 for k in self.COUNTERS}
+        self.timer = None                                  # a convstack.KernelTimer: per-kernel times (tools/q8_throughput.py)
+        sd = {k: v.detach().cpu().numpy() for k, v in model.state_dict().items()}
+        s_h, s_a, s_k = qparams.s_h, qparams.s_a, qparams.s_k
+        w_q, b_q, mul = prepare_conv(sd["input_normalizer.weight"], sd["input_normalizer.bias"], STEM_IN_SCALE, s_h[0])
+        self.stem_wpk = hp.q8x_pack_stem_weights(torch.from_numpy(w_q).to(dev))
+        self.stem_bias = torch.from_numpy(b_q).to(dev)
+        self.stem_mul = torch.from_numpy(mul).to(dev)
+        self.blocks, self.heads = [], {}
+        for k, (name, ci, co, pool, head) in enumerate(self.specs):
+            c1 = _Q8XConv(sd[name + ".conv1.weight"], sd[name + ".conv1.bias"], s_h[k], s_a[k], dev)
+            c2 = _Q8XConv(sd[name + ".conv2.weight"], sd[name + ".conv2.bias"], s_a[k], s_h[k + 1], dev)
+            if ci != co:
+                sk = s_k[self.wide.index(k)]
+                cs = _Q8XConv(sd[name + ".pointwise_conv_skip.weight"], sd[name + ".pointwise_conv_skip.bias"], s_h[k], sk, dev)
+                skip_mul = float(NPF(sk) / NPF(s_h[k + 1]))
+            else:
+                cs, skip_mul = None, float(NPF(s_h[k]) / NPF(s_h[k + 1]))
+            self.blocks.append((c1, c2, cs, skip_mul))
+            if head >= 0:
+                hn = f"extracting_layers.{head}.0"
+                hw, hb, hm = prepare_head(sd[hn + ".weight"], sd[hn + ".bias"], s_h[k + 1])
+                self.heads[k] = (head, torch.from_numpy(hw).to(dev).contiguous(), torch.from_numpy(hb).to(dev),
+                                 torch.from_numpy(hm).to(dev))
+        self._model_preprocess = lambda x: _ssd_preprocess(model, x)
+        self._plans = {}                                   # N -> the buffers of one pass; kept for the life of the model
+
+    # ------------------------------------------------------------------ nn.Module-shaped odds and ends
+    def eval(self):
+        return self
+
+    def train(self, mode: bool = True):
+        if mode:
+            raise FdetError("Int8SSD is inference only")
+        return self
+
+    _codes = staticmethod(_Int8Trunk._codes)
+
+    def _preprocess(self, x: torch.Tensor) -> torch.Tensor:
+        return self._model_preprocess(x)
+
+    def _t(self, kind, h, ci, co, flops=0.0, nbytes=0.0):
+        from .convstack import _NOSPAN
+        return _NOSPAN if self.timer is None else self.timer.span(f"{kind}@{h}x{h}:{ci}->{co}", flops, nbytes)
+
+    # ------------------------------------------------------------------ buffers
+    def _plan(self, N: int) -> dict:
+        """The buffers of a pass over N images, made once: per block its input, first-conv output, skip-conv output (or None)
+        and output.  Buffers of one shape are shared where their lives do not overlap."""
+        plan = self._plans.get(N)
+        if plan is not None:
+            return plan
+        if not hp.stem3_fwd_q8x_ok(N, 3, 16, self.size, self.size) or not hp.q8x_act_bytes(N, 32, 240, 240):
+            raise FdetError(f"Int8SSD: {N} images pass the int8 layout's 2 GiB per tensor: use smaller batches")
+        dev, free = self.device, {}
+
+        def take(C, H):
+            lst = free.setdefault((C, H), [])
+            return lst.pop() if lst else hp.Q8XTensor(N, C, H, H, dev)
+
+        def give(t):
+            free.setdefault((t.shape[1], t.shape[2]), []).append(t)
+        h = take(16, self.size // 2)
+        steps = []
+        for name, ci, co, pool, head in self.specs:
+            hk = h.shape[2]
+            sk = take(co, hk) if ci != co else None
+            a = take(co, hk)
+            out = take(co, hk // 2 if pool else hk)
+            steps.append((h, a, sk, out))
+            give(h)
+            give(a)
+            if sk is not None:
+                give(sk)
+            h = out
+        z = [torch.empty(N, 5, ps, ps, dtype=F32, device=dev) for ps in self.patch_sizes]
+        y = torch.empty(N, self.P, 5, dtype=F32, device=dev)
+        plan = {"steps": steps, "z": z, "y": y}
+        self._plans[N] = plan
+        return plan
+
+    # ------------------------------------------------------------------ forward
+    def _forward_u8(self, frames: torch.Tensor, trace: Optional[dict] = None) -> torch.Tensor:
+        """uint8 codes (N,3,480,480) on the GPU -> the (N,4774,5) rows."""
+        if not frames.is_cuda:
+            raise FdetError("Int8SSD runs on the GPU only (no CPU fallback): move the input to cuda")
+        if frames.dim() != 4 or tuple(frames.shape[1:]) != (3, self.size, self.size) or frames.dtype != torch.uint8:
+            raise ValueError(f"expected uint8 input (N,3,{self.size},{self.size}), got {frames.dtype} {tuple(frames.shape)}")
+        N = frames.shape[0]
+        plan = self._plan(N)
+        steps, y = plan["steps"], plan["y"]
+        h0 = steps[0][0]
+        with self._t("stem3_fwd_q8x", 240, 3, 16, 2.0 * N * 16 * 27 * 240 * 240, float(frames.numel()) + N * 16 * 240 * 240):
+            hp.stem3_fwd_q8x_u8(frames.contiguous(), self.stem_wpk, self.stem_bias, self.stem_mul, h0)
+        self.counters["stem_q8"] += 1
+        if trace is not None:
+            trace["stem"] = h0.nchw()
+            trace["blocks"], trace["z"] = [], []
+        for k, ((name, ci, co, pool, head), (h, a, sk, out), (c1, c2, cs, skip_mul)) in enumerate(zip(self.specs, steps, self.blocks)):
+            hk = h.shape[2]
+            px = float(N * hk * hk)
+            if cs is not None:
+                with self._t("q8x_pointwise", hk, ci, co, 2.0 * px * ci * co, px * (ci + co)):
+                    hp.q8x_pointwise(h, cs.wpk, cs.bias, cs.mul, sk)
+                self.counters["pointwise"] += 1
+            with self._t("q8x_conv3x3", hk, ci, co, 2.0 * px * 9 * ci * co, px * (ci + co)):
+                hp.q8x_conv3x3(h, c1.wpk, c1.bias, c1.mul, a, slope=self.slope)
+            with self._t("q8x_conv3x3_pool" if pool else "q8x_conv3x3_skip", hk, co, co, 2.0 * px * 9 * co * co,
+                         px * co * (2.0 + (0.25 if pool else 1.0))):
+                hp.q8x_conv3x3(a, c2.wpk, c2.bias, c2.mul, out, skip=sk if cs is not None else h, skip_mul=skip_mul, pool=bool(pool),
+                               slope=self.slope)
+            self.counters["convs"] += 2
+            if trace is not None:
+                trace["blocks"].append(out.nchw())
+            if head >= 0:
+                _, hw, hb, hm = self.heads[k]
+                z = plan["z"][head]
+                ho = out.shape[2]
+                with self._t("q8x_head", ho, co, 5, 2.0 * N * ho * ho * co * 5, float(N * ho * ho * (co + 40))):
+                    hp.q8x_head_f32(out, hw, hb, hm, z)
+                    hp.ssd_head_pack_fwd(z, self.patch_sizes[head], self.starts[head], y)
+                self.counters["heads"] += 1
+                if trace is not None:
+                    trace["z"].append(z.clone())
+        if trace is not None:
+            trace["y"] = y
+        return y
+
+    def _forward_f32(self, x: torch.Tensor, trace: Optional[dict] = None) -> torch.Tensor:
+        """float images in [0,1] at the model resolution -> codes -> the integer stem."""
+        if not x.is_cuda:
+            raise FdetError("Int8SSD runs on the GPU only (no CPU fallback): move the input to cuda")
+        if x.dim() == 3:
+            x = x.unsqueeze(0)
+        return self._forward_u8(self._codes(x), trace)
+
+    def _forward_any(self, x: torch.Tensor, trace: Optional[dict] = None) -> torch.Tensor:
+        if x.dim() == 3:
+            x = x.unsqueeze(0)
+        if x.is_cuda and x.dtype == torch.uint8 and x.dim() == 4 and tuple(x.shape[1:]) == (3, self.size, self.size):
+            return self._forward_u8(x, trace)
+        if not x.is_cuda:
+            raise FdetError("Int8SSD runs on the GPU only (no CPU fallback): move the input to cuda")
+        return self._forward_f32(self._preprocess(x), trace)
+
+    @torch.no_grad()
+    def forward_frames(self, x: torch.Tensor) -> torch.Tensor:
+        """frames (uint8 or float, values 0..255, any size) -> the (N,4774,5) rows [score, x, y, w, h] of SSD.forward."""
+        return self._forward_any(x)
+
+    @torch.no_grad()
+    def __call__(self, x: torch.Tensor, predict: torch.Tensor = torch.tensor(0)):
+        """SSD.forward: float images in [0,1] at the model resolution -> rows; predict=1: frames -> boxes per image."""
+        if predict == 1:
+            return self.non_max_suppression(self.forward_frames(x))
+        return self._forward_f32(x)
+
+    forward = __call__
+
+    @torch.no_grad()
+    def trace(self, frames: torch.Tensor) -> dict:
+        """{"stem": int8 (N,16,240,240), "blocks": [int8 output of every block], "z": [fp32 (N,5,ps,ps) of every head before
+        sigmoid and priors], "y": (N,4774,5)}"""
+        out = {}
+        self._forward_any(frames, trace=out)
+        return out
+
+    def non_max_suppression(self, x):
+        from .models.BaseModel import split_rows
+        if len(x.shape) == 3:
+            return split_rows(*self.reduce_bounding_boxes.forward_batch(x))
+        return self.reduce_bounding_boxes(x)
+
+    def single_non_max_suppression(self, x):
+        return self.reduce_bounding_boxes(x)
+
+
+def quantize_ssd(model, frames_iter, **kw) -> Int8SSD:
+    """calibrate_ssd + Int8SSD (what SSD.quantize does)."""
+    _check_ssd(model, "quantize_ssd")
+    if int(model.filters) != 16 or tuple(model.input_shape) != (3, 480, 480):
+        raise ValueError(f"Int8SSD: filters=16 at 480x480 only, got filters={model.filters} at {tuple(model.input_shape)}: a wider "
+                         "model exceeds the 256 channels of the int8 kernels")
+    return Int8SSD(model, calibrate_ssd(model, frames_iter, **kw))
 
 
 def quantize_model(model, frames_iter, stem: str = "float", **kw):

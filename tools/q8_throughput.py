@@ -4,6 +4,7 @@
     python tools/q8_throughput.py [--images 256] [--launches 100] [--calls 10] [--out profiles/r15_q8_chain.json]
     python tools/q8_throughput.py --model resnet [--images 32] [--out profiles/r17_q8_resnet.json]
     python tools/q8_throughput.py --model separablecnn [--out profiles/r19_q8_sep.json]      (`main_separablecnn`)
+    python tools/q8_throughput.py --model ssd [--images 64] [--out profiles/r20_q8_ssd.json]  (`main_ssd`)
 
 Workload: the inference leg's -- --images uint8 480x480 frames on the device (the three stored frames of
 tests/golden/g6_trained_small.npz, repeated) through the medium PoolResnet (64 filters, the trained weights of
@@ -303,18 +304,129 @@ def main_separablecnn(args):
     return res
 
 
+def main_ssd(args):
+    """`--model ssd`: uint8 480x480 frames (seeded smooth random images) through a seeded random SSD(filters=16) to boxes, for
+    the float engine (bf16x3), precision16 and quantize.Int8SSD (calibrated, abs-max, on the first 16 frames) -- the protocol
+    above: one process, every model warmed up, alternated sample by sample, --calls back-to-back calls per sample, median and
+    5th / 95th percentile -- at --images frames (default 64) and at 24, the recipe's batch.  The float models take the frames
+    as TiledDetector hands them over (resize_bilinear_norm, then the stack); the int8 model takes the bytes.  `faster` is the
+    rule of the other int8 models: int8 against precision16 by more than the larger of the two spreads.  `frames_to_rows` times
+    the same calls without the reducer.  The model is untrained (no trained SSD archive exists) and scores every prior near
+    0.5, so at the default threshold of 0.5 the reducer would sort and suppress all 4774 priors of every image and hide the
+    network; --threshold (default 0.9) is the reducer's threshold of the three models, at which it keeps what a trained
+    detector's would, a few candidates at the most.  Then the per-kernel
+    table of the int8 model and of precision16 at --images frames, with each int8 class's MACs over the dense int8 peak."""
+    import torch
+    import torch.nn.functional as F
+    import fdet_amd  # noqa: F401
+    from fdet_amd import hotpath as hp
+    from fdet_amd.convstack import KernelTimer
+    from fdet_amd.models.SSD import SSD
+    from fdet_amd.quantize import Int8SSD, calibrate_ssd
+    if not torch.cuda.is_available():
+        raise SystemExit("q8_throughput needs a GPU")
+
+    def build(p16):
+        torch.manual_seed(200)
+        m = SSD(16, (3, 480, 480), probability_threshold=args.threshold).cuda().eval()
+        if p16:
+            m.engine.set_precision("bf16")
+        return m
+    m32, m16 = build(False), build(True)
+    batches = [args.images] + ([24] if args.images != 24 else [])
+    nmax = max(batches)
+    low = torch.rand(nmax, 3, 30, 30, generator=torch.Generator().manual_seed(1200))
+    all_frames = F.interpolate(low, size=(480, 480), mode="bilinear", align_corners=False).mul(255.0).round().clamp(0, 255).to(torch.uint8).cuda()
+    m8 = Int8SSD(m32, calibrate_ssd(m32, [all_frames[:min(16, nmax)]]))
+    models = {"bf16x3": m32, "precision16": m16, "int8": m8}
+
+    def rows_of(m, frames):
+        with torch.no_grad():
+            return m.forward_frames(frames) if hasattr(m, "forward_frames") else m(hp.resize_bilinear_norm(frames, (480, 480)))
+
+    def run(m, frames):
+        with torch.no_grad():
+            return m.reduce_bounding_boxes.forward_batch(rows_of(m, frames))
+    per_batch = {}
+    for n in batches:
+        frames = all_frames[:n].contiguous()
+        boxes, ys = {}, {}
+        for k, m in models.items():
+            for _ in range(args.warmup):
+                rows, counts = run(m, frames)
+            boxes[k] = int(counts.sum())
+            ys[k] = rows_of(m, frames).clone()
+        torch.cuda.synchronize()
+        fns = {k: (lambda m=m: run(m, frames)) for k, m in models.items()}
+        fns.update({k + ":rows": (lambda m=m: rows_of(m, frames)) for k, m in models.items()})
+        st = {k: _stats(v) for k, v in _alternate(fns, args.launches, args.calls).items()}
+        e2e = {k: v for k, v in st.items() if not k.endswith(":rows")}
+        net = {k[:-5]: v for k, v in st.items() if k.endswith(":rows")}
+
+        def faster(t):
+            gain = t["precision16"]["median_ms"] - t["int8"]["median_ms"]
+            spread = max(t["precision16"]["spread_ms"], t["int8"]["spread_ms"])
+            return {"gain_ms": round(gain, 4), "spread_ms": spread, "faster": bool(gain > spread)}
+        ds = (ys["int8"][..., 0] - ys["bf16x3"][..., 0]).abs()
+        per_batch[str(n)] = {"end_to_end": e2e, "frames_to_rows": net,
+                             "images_per_s": {k: round(n / (v["median_ms"] * 1e-3), 1) for k, v in e2e.items()},
+                             "boxes": boxes, "over_precision16": round(e2e["precision16"]["median_ms"] / e2e["int8"]["median_ms"], 3),
+                             "over_bf16x3": round(e2e["bf16x3"]["median_ms"] / e2e["int8"]["median_ms"], 3),
+                             "rows_over_precision16": round(net["precision16"]["median_ms"] / net["int8"]["median_ms"], 3),
+                             "rows_over_bf16x3": round(net["bf16x3"]["median_ms"] / net["int8"]["median_ms"], 3),
+                             "faster_than_precision16": faster(e2e), "rows_faster_than_precision16": faster(net),
+                             "dscore_vs_float_engine": {"max": round(float(ds.max()), 6), "mean": round(float(ds.mean()), 6)}}
+    n = args.images
+    frames = all_frames[:n].contiguous()
+
+    def kernel_times(m, holder):
+        holder.timer = KernelTimer()
+        for _ in range(args.kernel_runs):
+            run(m, frames)
+        s = holder.timer.summary()
+        holder.timer = None
+        return {name: {"launches_per_call": cnt // args.kernel_runs, "ms_per_call": round(total / args.kernel_runs, 4)}
+                for name, (cnt, total, _, _) in sorted(s.items())}
+    k8, k16 = kernel_times(m8, m8), kernel_times(m16, m16.engine)
+    # MACs of an int8 conv class over the dense int8 peak, from the class name "kind@HxH:ci->co"
+    share = {}
+    for name, v in k8.items():
+        kind, rest = name.split("@")
+        at, io = rest.split(":")
+        h = int(at.split("x")[0])
+        ci, co = (int(t) for t in io.split("->"))
+        taps = 9 if kind.startswith(("q8x_conv3x3", "stem")) else 1        # (the stem: 9 taps x 3 input channels)
+        macs = float(n) * h * h * taps * ci * co * v["launches_per_call"]
+        share[name] = {"gmac": round(macs / 1e9, 3), "int8_peak_share": round(macs / INT8_PEAK_MACS * 1e3 / v["ms_per_call"], 4) if v["ms_per_call"] > 0 else None}
+    res = {"tool": "q8_throughput", "model": "ssd", "device_name": torch.cuda.get_device_name(0), "images": n, "batches": batches,
+           "probability_threshold": args.threshold, "launches": args.launches, "calls_per_sample": args.calls, "by_batch": per_batch, "counters": dict(m8.counters),
+           "int8_kernels": k8, "precision16_kernels": k16, "int8_kernel_macs": share,
+           "int8_sum_ms": round(sum(v["ms_per_call"] for v in k8.values()), 4),
+           "precision16_sum_ms": round(sum(v["ms_per_call"] for v in k16.values()), 4)}
+    line = json.dumps(res)
+    print(line)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+    return res
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
-    ap.add_argument("--model", choices=("poolresnet", "resnet", "separablecnn"), default="poolresnet")
-    ap.add_argument("--images", type=int, default=None, help="frames per call (default 256; resnet: 32)")
+    ap.add_argument("--model", choices=("poolresnet", "resnet", "separablecnn", "ssd"), default="poolresnet")
+    ap.add_argument("--images", type=int, default=None, help="frames per call (default 256; resnet: 32; ssd: 64)")
     ap.add_argument("--launches", type=int, default=100, help="timed samples per mode")
     ap.add_argument("--calls", type=int, default=10, help="back-to-back calls per sample")
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--kernel-runs", type=int, default=50)
+    ap.add_argument("--threshold", type=float, default=0.9, help="ssd: the reducer's probability threshold (see main_ssd)")
     ap.add_argument("--out", default=None)
     args = ap.parse_args(argv)
     if args.images is None:
-        args.images = 32 if args.model == "resnet" else 256
+        args.images = 32 if args.model == "resnet" else 64 if args.model == "ssd" else 256
+    if args.model == "ssd":
+        return main_ssd(args)
     if args.model == "resnet":
         return main_resnet(args)
     if args.model == "separablecnn":
