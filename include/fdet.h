@@ -1181,6 +1181,128 @@ int fdet_jpeg_enc_emit(const fdet_jpeg_enc_desc* descs, const fdet_jpeg_enc_desc
                        int n_images, int subsampling, const uint8_t* workspace, size_t workspace_bytes, uint8_t* scan,
                        size_t scan_bytes, void* stream);
 
+/* ---- Huffman decoding of baseline JPEG scans on the device (csrc/fdet_jpeg.hip prepare, csrc/fdet_jpeg_huff.hip kernels,
+ * DESIGN.md 5p) ----
+ * The entropy decoder of the section above moved to the device: the host only unstuffs the scan and builds the decode
+ * tables (fdet_jpeg_scan_prepare, O(file bytes)); the device finds the symbol boundaries by self-synchronisation
+ * (fdet_jpeg_huffman_sync) and writes the coefficient planes (fdet_jpeg_huffman_emit).  The planes are BYTE FOR BYTE what
+ * fdet_jpeg_entropy_decode writes for every stream that function accepts; a stream it refuses sets the image's flag word,
+ * and the caller decodes that image on the host, so that the error is the host decoder's.  tests/jpeg_huff_cpu_ref.py
+ * restates every rule below in Python.
+ *
+ * Segments.  A segment is one restart interval, or the whole scan without DRI.  Its unstuffed bytes (FF 00 -> FF; fill FFs
+ * in front of a marker dropped; the run ends at any marker or at the end of the file) start at a multiple of 16 bytes of the
+ * scan buffer and are zero-padded to the next multiple of 16.
+ *
+ * Subsequences and states.  Every segment is cut into subsequences of sub_bits bits (a multiple of 32, >= 64): segment s
+ * has max(1, ceil(8 * byte_len / sub_bits)) of them and one thread owns one.  The decoder's state at a subsequence
+ * boundary is off | blk << 8 | z << 16: `off` (0..31) the bits between the boundary and the start of the first symbol
+ * behind it (a symbol is a Huffman code plus its extra bits, at most 32 bits), `blk` the block index within the MCU, `z`
+ * the zigzag index of the next coefficient (0: a DC symbol is next).  FDET_JPEG_HUFF_END stands for "the bits ran out".
+ * Per subsequence g the state buffer holds three 8-byte words: [3g] its exit state, [3g+1] the blocks it completed, [3g+2]
+ * 1 + the entry state it was last decoded from (0: never; the caller zero-fills the buffer before the first pass, which
+ * also makes every exit state the guess (0, 0, 0)).  Subsequence 0 of a segment enters with (0, 0, 0).
+ *
+ * One parse step (the same in sync and emit), at bit p of a segment of B = 8 * byte_len bits, bits behind B reading as 0:
+ *   code   the component's DC table when z = 0, else its AC table: the 9-bit lookahead, then maxcode / valoffset / vals
+ *          for lengths 1..16 (build_huff's canonical form).  No length matches, or the value index is outside the table:
+ *          event NOCODE, p += 1, nothing else changes.  The code is longer than B - p: the subsequence ends in END.
+ *   DC     s = symbol; s > 16: event DCCAT, s = 0.  code + s bits > B - p: END.  The difference (receive-extend of the s
+ *          bits) goes to natural position 0 of the block; z = 1.
+ *   AC     r = symbol >> 4, s = symbol & 15.  s != 0: k = z + r; k > 63: event RUN, the block closes, only the code is
+ *          consumed; else code + s > B - p: END; else the value goes to kNatural[k], z = k + 1 and the block closes at 64.
+ *          s = 0, r = 15: z += 16, the block closes at z > 63 (no event, as in the host decoder).  s = 0, r < 15: the
+ *          block closes.  Closing a block: count + 1, blk = (blk + 1) mod blocks-per-MCU, z = 0.
+ * A thread parses the symbols that START inside its subsequence (p < min((k + 1) * sub_bits, B)); its exit state is
+ * (p - (k + 1) * sub_bits, blk, z) when p reached the boundary and END otherwise.  An entry of END gives exit END, count 0.
+ * No step stops at an event and no state carries one, which is what lets wrong guesses re-synchronise within a few
+ * subsequences.
+ *
+ * Trailing bits.  The emit parse stops at the segment's block count.  Behind the image's last segment anything may follow,
+ * as for the host decoder.  Behind any other segment the host decoder refills its 64-bit window ONCE and expects the
+ * restart marker where that leaves it: with p the bit behind the segment's last block it accepts exactly when B - p <= 64
+ * (its window holds floor((p + 64) / 8) bytes after any refill).  The thread that closes the segment's last block sets
+ * FDET_JPEG_HUFF_TRAILING when B - p > 64, so that such a stream is the host decoder's to refuse.
+ *
+ * Every loop is bounded by the bits of one subsequence, every table index is masked or range-checked, every bit position
+ * is checked against the segment's length and every store against the segment's block count and the plane's range; no
+ * thread waits for another.  Neither entry point synchronises or allocates. */
+#define FDET_JPEG_HUFF_HOST 1            /* fdet_jpeg_scan_prepare: a valid header, but decode this image on the host */
+#define FDET_JPEG_HUFF_END 0x80000000u   /* the state "the bits ran out" */
+#define FDET_JPEG_HUFF_NOCODE 1u         /* flag bits of an image: no matching code */
+#define FDET_JPEG_HUFF_RUN 2u            /* a coefficient run past 63 */
+#define FDET_JPEG_HUFF_DCCAT 4u          /* a DC category above 16 */
+#define FDET_JPEG_HUFF_EXHAUSTED 8u      /* a segment's bits ended before its block count */
+#define FDET_JPEG_HUFF_TRAILING 16u      /* more than 64 bits behind the blocks of a segment that is not the image's last */
+
+typedef struct fdet_jpeg_huff_table {    /* build_huff's canonical form as a POD */
+  uint8_t look_nbits[512], look_sym[512];/* 9-bit lookahead: code length (0: longer than 9 bits) and symbol */
+  int32_t maxcode[18], valoffset[18];    /* per length 1..16: largest code (-1: none), value index - code */
+  uint8_t vals[256];
+  int32_t nvals, reserved;
+} fdet_jpeg_huff_table;                  /* 1432 bytes */
+
+typedef struct fdet_jpeg_huff_tables {
+  fdet_jpeg_huff_table dc[3], ac[3];     /* per COMPONENT (the scan header's selectors resolved) */
+} fdet_jpeg_huff_tables;                 /* 8592 bytes */
+
+typedef struct fdet_jpeg_huff_segment {
+  int64_t byte_offset;                   /* first unstuffed byte in the scan buffer, a multiple of 16 (prepare: relative to
+                                            scan_out; the caller adds the image's base) */
+  int32_t byte_len;                      /* unstuffed bytes, < 2^27 */
+  int32_t first_mcu, mcu_count;          /* raster MCU index of the segment's first MCU; its MCUs */
+  int32_t image;                         /* index into `images` (the caller fills this and the two below) */
+  int32_t sub_first, sub_count;          /* its subsequences in the state buffer: max(1, ceil(8 * byte_len / sub_bits)) */
+} fdet_jpeg_huff_segment;                /* 32 bytes */
+
+typedef struct fdet_jpeg_huff_image {
+  int64_t coef_offset[3];                /* as fdet_jpeg_desc: first int16 of component c's plane, a multiple of 8 */
+  int32_t ncomp, hs, vs;                 /* luma sampling (chroma 1x1), 1x1 for ncomp = 1: fdet_jpeg_reconstruct's set */
+  int32_t mcus_x, mcus_y;
+  int32_t seg_first, seg_count;          /* its segments: consecutive, covering MCU 0 .. mcus_x * mcus_y - 1 in order */
+  int32_t sub_first, sub_count;          /* its subsequences: those of its segments, consecutive */
+  int32_t wg_first;                      /* its first workgroup of 256 subsequences: the sum of ceil(sub_count / 256) over the
+                                            images before it (a workgroup finds its image by a search over these) */
+  int32_t reserved[2];
+} fdet_jpeg_huff_image;                  /* 72 bytes */
+
+/* HOST, thread-safe, no HIP call.  Parses the headers as fdet_jpeg_info does (the same FDET_JPEG_UNSUPPORTED /
+ * FDET_JPEG_ECORRUPT for what that refuses), fills `tables` and unstuffs the scan into segments (byte_offset, byte_len,
+ * first_mcu, mcu_count; the other fields 0).  *scan_bytes receives the bytes used at scan_out (a multiple of 16), *n_segs
+ * the segments.  FDET_JPEG_HUFF_HOST: out of the ordinary, decode on the host -- RSTn out of sequence, a marker other than
+ * the expected RSTn or the end of the file before the last segment, a segment of 2^27 bytes or more.  FDET_EWORKSPACE: a
+ * capacity is too small (align16(n) + 16 * ceil(mcus / interval) bytes and ceil(mcus / interval) segments always do).  No
+ * read past bytes + n, no write past the capacities. */
+int fdet_jpeg_scan_prepare(const uint8_t* bytes, size_t n, uint8_t* scan_out, size_t scan_capacity, size_t* scan_bytes,
+                           fdet_jpeg_huff_segment* segs, int seg_capacity, int* n_segs, fdet_jpeg_huff_tables* tables);
+
+/* ONE synchronisation pass on `stream`: thread k of a segment reads the exit state of k - 1 ((0, 0, 0) for k = 0); if it
+ * equals the entry k was last decoded from it does nothing, else it parses its subsequence without writing coefficients,
+ * stores exit state, block count and entry, and stores 1 to changed[image].  The caller zero-fills `changed` (DEVICE,
+ * n_images words) before a pass and repeats passes until one leaves it all zero: that state is the unique fixed point,
+ * every entry state the sequential decoder's.  Correct states advance at least one subsequence per pass, so the largest
+ * sub_count of a segment (+ 1 pass to see nothing change) is enough.  scan / tables / images / segs / state are DEVICE
+ * memory, h_images / h_segs the HOST copies everything is validated on before the launch: sub_bits not a multiple of 32
+ * or below 64, a segment outside scan_bytes, misaligned offsets, sub counts that do not follow from byte_len, ranges that
+ * are not consecutive or leave n_subs, a wg_first that is not that sum, geometry outside the supported set return FDET_EINVAL and nothing is written. */
+int fdet_jpeg_huffman_sync(const uint8_t* scan, size_t scan_bytes, const fdet_jpeg_huff_tables* tables,
+                           const fdet_jpeg_huff_image* images, const fdet_jpeg_huff_image* h_images, int n_images,
+                           const fdet_jpeg_huff_segment* segs, const fdet_jpeg_huff_segment* h_segs, int n_segs,
+                           int sub_bits, uint64_t* state, size_t n_subs, uint32_t* changed, void* stream);
+
+/* After the passes converged, on `stream`: (1) an exclusive scan of the block counts per segment -> first_block (DEVICE,
+ * n_subs words of workspace); a segment whose counts sum to less than its blocks sets FDET_JPEG_HUFF_EXHAUSTED; (2)
+ * hipMemsetAsync of the coef_count int16 at `coef`; (3) every thread parses its subsequence again from its entry state and
+ * stores each coefficient at coef_offset[c] + ((my * vs_c + v) * blocks_w[c] + mx * hs_c + h) * 64 + kNatural[z], the DC
+ * position holding the DIFFERENCE, stopping at the segment's block count; events OR into flags[image] (DEVICE, n_images
+ * words, zero-filled by the caller); (4) a prefix sum per (segment, component) over the blocks in scan order turns the
+ * differences into DC values modulo 2^16.  Validation as in fdet_jpeg_huffman_sync, plus every plane inside coef_count. */
+int fdet_jpeg_huffman_emit(const uint8_t* scan, size_t scan_bytes, const fdet_jpeg_huff_tables* tables,
+                           const fdet_jpeg_huff_image* images, const fdet_jpeg_huff_image* h_images, int n_images,
+                           const fdet_jpeg_huff_segment* segs, const fdet_jpeg_huff_segment* h_segs, int n_segs,
+                           int sub_bits, const uint64_t* state, size_t n_subs, uint32_t* first_block, int16_t* coef,
+                           size_t coef_count, uint32_t* flags, void* stream);
+
 /* ---------------------------------------------------------------------------------------
  * Int8 inference: the PoolResnet residual trunk post-training-quantised, on the integer matrix cores
  * (v_mfma_i32_16x16x64_i8).  Inference only.  The reference has no such path (it ships pruner.py and ONNX / TorchScript

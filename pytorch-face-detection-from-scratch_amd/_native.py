@@ -186,6 +186,9 @@ SIGNATURES = {
     "fdet_jpeg_info": (_I, [_P, _SZ, _P]),
     "fdet_jpeg_entropy_decode": (_I, [_P, _SZ, _P, _SZ]),
     "fdet_jpeg_reconstruct": (_I, [_P, _SZ, _P, _P, _I, _P, _SZ, _P, _SZ, _P]),
+    "fdet_jpeg_scan_prepare": (_I, [_P, _SZ, _P, _SZ, _P, _P, _I, _P, _P]),
+    "fdet_jpeg_huffman_sync": (_I, [_P, _SZ, _P, _P, _P, _I, _P, _P, _I, _I, _P, _SZ, _P, _P]),
+    "fdet_jpeg_huffman_emit": (_I, [_P, _SZ, _P, _P, _P, _I, _P, _P, _I, _I, _P, _SZ, _P, _P, _SZ, _P, _P]),
     "fdet_jpeg_quant_tables": (_I, [_I, _P]),
     "fdet_jpeg_write_header": (_I, [_I, _I, _I, _I, _P, _SZ, _P]),
     "fdet_jpeg_enc_ws_bytes": (_SZ, [_c.c_int64, _I]),

@@ -3,6 +3,8 @@
 //   host    fdet_jpeg_info            marker parsing (SOF0/SOF1, DQT, DHT, DRI, SOS, APP0/APP14), the supported-subset decision
 //           fdet_jpeg_entropy_decode  Huffman decoding with DC prediction, byte stuffing and restart markers -> quantised
 //                                     int16 coefficients in natural order, one [blocks_h][blocks_w][64] plane per component
+//           fdet_jpeg_scan_prepare    instead of the line above when the device Huffman-decodes (fdet_jpeg_huff.hip): the decode
+//                                     tables as a POD and the scan unstuffed into one byte run per restart interval
 //   device  fdet_jpeg_reconstruct     k_jpeg_idct: dequantise + libjpeg's accurate-integer 8x8 inverse DCT -> uint8 sample planes
 //                                     k_jpeg_rgb:  "fancy" chroma upsampling + YCbCr -> RGB + crop -> HWC uint8 in the bank
 //
@@ -382,6 +384,81 @@ extern "C" int fdet_jpeg_entropy_decode(const uint8_t* bytes, size_t n, int16_t*
       if (P.restart_interval) --to_go;
     }
   }
+  return FDET_OK;
+}
+
+// The host half of the device Huffman decoder (fdet_jpeg_huff.hip): the same headers and tables, and one walk
+// over the entropy-coded bytes with BitReader::fill's rules that unstuffs them into one run per restart interval.
+extern "C" int fdet_jpeg_scan_prepare(const uint8_t* bytes, size_t n, uint8_t* scan_out, size_t scan_capacity,
+                                      size_t* scan_bytes, fdet_jpeg_huff_segment* segs, int seg_capacity, int* n_segs,
+                                      fdet_jpeg_huff_tables* tables) {
+  FDET_REQUIRE(bytes && scan_out && scan_bytes && segs && n_segs && tables && n > 0 && seg_capacity > 0,
+               "jpeg_scan_prepare: null pointer or empty buffer");
+  Parsed P;
+  if (int rc = parse_headers(bytes, n, P)) return rc;
+  memset(tables, 0, sizeof(*tables));
+  for (int c = 0; c < P.ncomp; ++c) {
+    for (int k = 0; k < 2; ++k) {
+      HuffTab T;
+      if (int rc = build_huff(k ? P.ac[P.ta[c]] : P.dc[P.td[c]], T)) return rc;
+      fdet_jpeg_huff_table& D = k ? tables->ac[c] : tables->dc[c];
+      memcpy(D.look_nbits, T.look_nbits, sizeof(D.look_nbits));
+      memcpy(D.look_sym, T.look_sym, sizeof(D.look_sym));
+      memcpy(D.maxcode, T.maxcode, sizeof(D.maxcode));
+      memcpy(D.valoffset, T.valoffset, sizeof(D.valoffset));
+      memcpy(D.vals, T.vals, (size_t)T.nvals);
+      D.nvals = T.nvals;
+    }
+  }
+  const int64_t mcus = (int64_t)P.mcus_x * P.mcus_y;
+  const int64_t interval = P.restart_interval ? P.restart_interval : mcus;
+  const int64_t expect = (mcus + interval - 1) / interval;
+  if (expect > (int64_t)seg_capacity)
+    return fail(FDET_EWORKSPACE, "jpeg_scan_prepare: the scan has %lld segments, the buffer holds %d", (long long)expect,
+                seg_capacity);
+  size_t pos = P.scan_pos, at = 0;
+  for (int64_t s = 0; s < expect; ++s) {
+    const size_t start = at;
+    for (;;) {                                           // BitReader::fill, byte by byte
+      if (pos >= n) break;
+      const uint8_t c = bytes[pos];
+      if (c == 0xFF) {
+        if (pos + 1 >= n || bytes[pos + 1] != 0x00) break;
+        pos += 2;
+      } else {
+        pos += 1;
+      }
+      if (at >= scan_capacity)
+        return fail(FDET_EWORKSPACE, "jpeg_scan_prepare: the unstuffed scan does not fit in %zu bytes", scan_capacity);
+      scan_out[at++] = c;
+    }
+    const size_t len = at - start;
+    if (len >= ((size_t)1 << 27)) return FDET_JPEG_HUFF_HOST;
+    const size_t padded = (at + 15) & ~(size_t)15;
+    if (padded > scan_capacity)
+      return fail(FDET_EWORKSPACE, "jpeg_scan_prepare: the unstuffed scan does not fit in %zu bytes", scan_capacity);
+    memset(scan_out + at, 0, padded - at);
+    at = padded;
+    memset(&segs[s], 0, sizeof(segs[s]));
+    segs[s].byte_offset = (int64_t)start;
+    segs[s].byte_len = (int32_t)len;
+    segs[s].first_mcu = (int32_t)(s * interval);
+    segs[s].mcu_count = (int32_t)(mcus - s * interval < interval ? mcus - s * interval : interval);
+    if (s + 1 < expect) {                                // the host decoder's restart rule, nothing more lenient
+      size_t p = pos;
+      if (p >= n || bytes[p] != 0xFF) return FDET_JPEG_HUFF_HOST;
+      while (p < n && bytes[p] == 0xFF) ++p;
+      if (p >= n || bytes[p] != 0xD0 + (int)(s & 7)) return FDET_JPEG_HUFF_HOST;
+      pos = p + 1;
+    }
+  }
+  {                                                      // more segments than the MCUs need: out of the ordinary
+    size_t p = pos;
+    while (p < n && bytes[p] == 0xFF) ++p;
+    if (p > pos && p < n && bytes[p] >= 0xD0 && bytes[p] <= 0xD7) return FDET_JPEG_HUFF_HOST;
+  }
+  *scan_bytes = at;
+  *n_segs = (int)expect;
   return FDET_OK;
 }
 

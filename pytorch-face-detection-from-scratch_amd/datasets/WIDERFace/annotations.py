@@ -59,16 +59,21 @@ def _decode(path) -> np.ndarray:
         return np.ascontiguousarray(np.asarray(im.convert("RGB"), dtype=np.uint8))
 
 
-def bank_from_files(paths: Sequence, device, workers: int = 16, decoder: str = "pil"):
+def bank_from_files(paths: Sequence, device, workers: int = 16, decoder: str = "pil", huffman: str = "host"):
     """Decode `paths` on at most 16 threads into a DeviceImageBank on `device` (RGB, HWC uint8).  A once-per-run cost: the
     bank stays resident.  decoder="pil" decodes on the host with PIL; decoder="device" Huffman-decodes on the host and
-    reconstructs on the device (datasets/jpeg.py DeviceJpegDecoder; files outside its JPEG subset still go through PIL).
-    Both give the same bank, byte for byte."""
+    reconstructs on the device (datasets/jpeg.py DeviceJpegDecoder; files outside its JPEG subset still go through PIL);
+    with huffman="device" the Huffman decoding runs on the device too and only the file bytes cross to it.  All give the
+    same bank, byte for byte."""
     if decoder not in ("pil", "device"):
         raise ValueError(f"decoder must be 'pil' or 'device', got {decoder!r}")
+    if huffman not in ("host", "device"):
+        raise ValueError(f"huffman must be 'host' or 'device', got {huffman!r}")
+    if huffman == "device" and decoder != "device":
+        raise ValueError("huffman='device' needs decoder='device'")
     if decoder == "device":
         from ..jpeg import DeviceJpegDecoder
-        return DeviceJpegDecoder(device, workers=workers).decode_files(paths)
+        return DeviceJpegDecoder(device, workers=workers, huffman=huffman).decode_files(paths)
     from ..augment import DeviceImageBank
     workers = max(1, min(16, int(workers), len(paths) or 1))
     with ThreadPoolExecutor(max_workers=workers) as ex:

@@ -8,6 +8,13 @@ buffer.  The result is byte-identical to `bank_from_files` with PIL (libjpeg-tur
 
     bank = DeviceJpegDecoder("cuda").decode_files(paths)
 
+With `huffman="device"` (csrc/fdet_jpeg_huff.hip) the Huffman decoding runs on the device as well: the worker
+threads only unstuff the scans and build the decode tables (`fdet_jpeg_scan_prepare`), the file bytes cross to the device,
+self-synchronising passes find the symbol boundaries and an emit launch writes the same int16 planes there.  An image the
+device path cannot vouch for is decoded by the host path after all (`decoder.huffman_fallbacks`); the bank is the same.
+
+    bank = DeviceJpegDecoder("cuda", huffman="device").decode_files(paths)
+
 The other direction is `DeviceJpegEncoder` (csrc/fdet_jpeg_enc.hip): colour conversion, downsampling, forward
 DCT, quantisation AND the Huffman coding run on the device, so that only the compressed scan crosses to the host, which adds
 the header, stuffs the FF bytes and writes the file -- byte for byte what PIL's `Image.save(..., "JPEG")` writes.
@@ -21,6 +28,7 @@ raises `FdetError` naming the file.
 from __future__ import annotations
 
 import io
+import time
 from concurrent.futures import ThreadPoolExecutor
 from typing import List, Optional, Sequence
 
@@ -33,6 +41,8 @@ from .augment import IMAGE_DTYPE, DeviceImageBank
 
 MAX_WORKERS = 16
 MAX_IMAGES_PER_LAUNCH = 65535                                # fdet_jpeg_reconstruct's grid limit
+DEFAULT_SUB_BITS = 1024                                      # huffman="device": bits per subsequence
+SYNC_ROUND = 4                                               # sync passes enqueued between two looks at `changed`
 
 
 def _align(v: int, a: int) -> int:
@@ -41,14 +51,34 @@ def _align(v: int, a: int) -> int:
 
 class DeviceJpegDecoder:
     """decode_bytes / decode_files -> DeviceImageBank.  `workers` host threads (at most 16) entropy-decode into one of two
-    pinned staging buffers of at most `chunk_bytes` of coefficients while the previous chunk copies and reconstructs."""
+    pinned staging buffers of at most `chunk_bytes` of coefficients while the previous chunk copies and reconstructs.
+    huffman="device": the threads run fdet_jpeg_scan_prepare instead and the device decodes the scans, in subsequences of
+    `sub_bits` bits (a multiple of 32, at least 64) and at most `max_sync_passes` synchronisation passes per chunk (None: as
+    many as the longest segment can need); `huffman_fallbacks` lists the images the host decoded after all, `sync_passes`
+    the passes enqueued."""
 
-    def __init__(self, device, workers: int = 16, chunk_bytes: int = 256 << 20):
+    def __init__(self, device, workers: int = 16, chunk_bytes: int = 256 << 20, huffman: str = "host",
+                 sub_bits: int = DEFAULT_SUB_BITS, max_sync_passes: Optional[int] = None):
+        if huffman not in ("host", "device"):
+            raise ValueError(f"DeviceJpegDecoder: huffman must be 'host' or 'device', got {huffman!r}")
+        sub_bits = int(sub_bits)
+        if sub_bits < 64 or sub_bits % 32:
+            raise ValueError(f"DeviceJpegDecoder: sub_bits={sub_bits} must be a multiple of 32 and at least 64")
+        if max_sync_passes is not None and int(max_sync_passes) < 1:
+            raise ValueError(f"DeviceJpegDecoder: max_sync_passes={max_sync_passes} must be at least 1")
         self.device = torch.device(device)
         self.workers = max(1, min(MAX_WORKERS, int(workers)))
         self.chunk_bytes = max(128, int(chunk_bytes))
+        self.huffman = huffman
+        self.sub_bits = sub_bits
+        self.max_sync_passes = None if max_sync_passes is None else int(max_sync_passes)
         self.fallbacks: List[int] = []
         self.chunks = 0                                      # reconstruct launches of the last call
+        self.huffman_fallbacks: List[int] = []               # huffman="device": images the host Huffman-decoded after all
+        self.sync_passes = 0                                 # synchronisation passes enqueued by the last call
+        self.scan_bytes = 0                                  # bytes of scans, tables and descriptors the last call copied across
+        self.timings = None                                  # a dict to fill with per-stage seconds (tools/jpeg_throughput.py)
+        self._bufs = {}
 
     # -- host stages ---------------------------------------------------------------------------------------------------
     @staticmethod
@@ -154,6 +184,7 @@ class DeviceJpegDecoder:
     def _decode_into(self, pool, blobs, names, probed, table, data) -> None:
         dev = self.device
         stream = torch.cuda.current_stream(dev)
+        self.huffman_fallbacks, self.sync_passes, self.scan_bytes = [], 0, 0
         for i, (info, arr) in enumerate(probed):             # the files another decoder took
             if info is None:
                 self.fallbacks.append(i)
@@ -163,6 +194,8 @@ class DeviceJpegDecoder:
         if not chunks:
             return
         plans = [self._describe(ch, table) for ch in chunks]
+        if self.huffman == "device":
+            return self._decode_chunks_device_huffman(pool, blobs, names, chunks, plans, data)
         cap = max(p[2] for p in plans)
         ws_cap = max(p[3] for p in plans)
         n_stage = min(2, len(chunks))
@@ -193,6 +226,192 @@ class DeviceJpegDecoder:
                 ev.record(stream)
                 busy[s], hold[s] = ev, (h_descs, d_descs)
                 self.chunks += 1
+        finally:
+            stream.synchronize()                             # nothing of this call is in flight when its buffers go
+
+
+    # -- huffman="device" ---------------------------------------------------------------------------------------------
+    def _buf(self, key, numel, dtype, pinned=False):
+        """A grow-only buffer kept across calls -> its first `numel` elements."""
+        t = self._bufs.get(key)
+        if t is None or t.numel() < numel:
+            cap = max(int(numel), 16)
+            t = torch.empty(cap, dtype=dtype).pin_memory() if pinned else torch.empty(cap, dtype=dtype, device=self.device)
+            self._bufs[key] = t
+        return t[:numel]
+
+    def _clock(self, key, t0):
+        if self.timings is not None:
+            self.timings[key] = self.timings.get(key, 0.0) + time.perf_counter() - t0
+
+    def huffman_stage(self, pool, blobs, names, chunk, descs):
+        """fdet_jpeg_scan_prepare of one chunk on the worker threads into pinned staging, the subsequence layout, and the
+        asynchronous copies -> (d_scan, d_tables, d_images, images, d_segs, segs, subsequences, positions prepare sent to
+        the host): the arguments of hotpath.jpeg_huffman_sync / jpeg_huffman_emit."""
+        dev = self.device
+        stream = torch.cuda.current_stream(dev)
+        n = len(chunk)
+        t0 = time.perf_counter()
+        images = np.zeros(n, dtype=hp.JPEG_HUFF_IMAGE_DTYPE)
+        nsegs = np.zeros(n, dtype=np.int64)
+        for k, (i, info) in enumerate(chunk):
+            mcus = int(info["mcus_x"]) * int(info["mcus_y"])
+            nsegs[k] = -(-mcus // (int(info["restart_interval"]) or mcus))
+            im = images[k]
+            im["coef_offset"], im["ncomp"] = descs[k]["coef_offset"], info["ncomp"]
+            im["hs"], im["vs"], im["mcus_x"], im["mcus_y"] = info["hs"][0], info["vs"][0], info["mcus_x"], info["mcus_y"]
+        caps = np.array([_align(len(blobs[i]), 16) for i, _ in chunk], dtype=np.int64) + 16 * nsegs
+        base = np.cumsum(caps) - caps
+        images["seg_count"] = nsegs
+        images["seg_first"] = np.cumsum(nsegs) - nsegs
+        S = int(nsegs.sum())
+        h_scan = self._buf("h_scan", int(caps.sum()), torch.uint8, pinned=True)
+        h_segs_t = self._buf("h_segs", S * hp.JPEG_HUFF_SEG_DTYPE.itemsize, torch.uint8, pinned=True)
+        h_tab = self._buf("h_tables", n * hp.JPEG_HUFF_TABLES_DTYPE.itemsize, torch.uint8, pinned=True)
+        segs = h_segs_t.numpy().view(hp.JPEG_HUFF_SEG_DTYPE)
+        p_scan, p_segs, p_tab = h_scan.data_ptr(), h_segs_t.data_ptr(), h_tab.data_ptr()
+
+        def work(k):
+            i = chunk[k][0]
+            rc, used, got, msg = hp.jpeg_scan_prepare(blobs[i], p_scan + int(base[k]), int(caps[k]),
+                                                      p_segs + int(images["seg_first"][k]) * hp.JPEG_HUFF_SEG_DTYPE.itemsize,
+                                                      int(nsegs[k]),
+                                                      p_tab + k * hp.JPEG_HUFF_TABLES_DTYPE.itemsize)
+            return k, rc, got, msg
+        host = set()
+        for k, rc, got, msg in pool.map(work, range(n)):
+            a = int(images["seg_first"][k])
+            if rc == hp.JPEG_HUFF_HOST or (rc == 0 and got != int(nsegs[k])):
+                # an empty scan over all the MCUs: valid for the kernels, flagged EXHAUSTED by the emit, decoded below
+                host.add(k)
+                segs[a:a + int(nsegs[k])] = 0
+                segs["mcu_count"][a:a + int(nsegs[k])] = 0
+                images["seg_count"][k] = 1
+                segs["mcu_count"][a] = int(images["mcus_x"][k]) * int(images["mcus_y"][k])
+            elif rc != 0:
+                raise FdetError(f"{names[chunk[k][0]]}: {msg} (code {rc})")
+            segs["byte_offset"][a:a + int(nsegs[k])] += int(base[k])
+            segs["image"][a:a + int(nsegs[k])] = k
+        if host:                                             # their unused segment records leave the array
+            keep = segs["mcu_count"] > 0
+            segs = np.ascontiguousarray(segs[keep])
+            images["seg_first"] = np.cumsum(images["seg_count"]) - images["seg_count"]
+        n_subs = hp.jpeg_huff_layout(images, segs, self.sub_bits)
+        if host:                                             # the compacted records, back into the pinned buffer
+            h_segs_t = h_segs_t[:segs.nbytes]
+            h_segs_t.numpy()[:] = segs.view(np.uint8)
+            segs = h_segs_t.numpy().view(hp.JPEG_HUFF_SEG_DTYPE)
+        self._clock("prepare", t0)
+        t0 = time.perf_counter()
+        h_images_t = self._buf("h_images", images.nbytes, torch.uint8, pinned=True)
+        h_images_t.numpy()[:] = images.view(np.uint8)
+        d_scan = self._buf("d_scan", h_scan.numel(), torch.uint8)
+        d_segs = self._buf("d_segs", h_segs_t.numel(), torch.uint8)
+        d_tab = self._buf("d_tables", h_tab.numel(), torch.uint8)
+        d_images = self._buf("d_images", h_images_t.numel(), torch.uint8)
+        for d, h in ((d_scan, h_scan), (d_segs, h_segs_t), (d_tab, h_tab), (d_images, h_images_t)):
+            d.copy_(h, non_blocking=True)
+        self.scan_bytes += h_scan.numel() + h_segs_t.numel() + h_tab.numel() + h_images_t.numel()
+        if self.timings is not None:
+            stream.synchronize()
+            self._clock("copy", t0)
+        return d_scan, d_tab, d_images, images, d_segs, segs, n_subs, host
+
+    def huffman_chunk(self, pool, blobs, names, chunk, descs, coef_count: int, d_coef: torch.Tensor):
+        """The scans of one chunk (chunk: [(index, info)], descs: its fdet_jpeg_desc records) -> coefficient planes in
+        d_coef[:coef_count] on the current stream.  -> the positions within the chunk whose planes the host has still to
+        decode (prepare said so, the emit parse flagged them, or they were still changing at the pass cap)."""
+        stream = torch.cuda.current_stream(self.device)
+        n = len(chunk)
+        d_scan, d_tab, d_images, images, d_segs, segs, n_subs, host = self.huffman_stage(pool, blobs, names, chunk, descs)
+        state = self._buf("state", 3 * n_subs, torch.int64)
+        first_block = self._buf("first_block", n_subs, torch.int32)
+        words = self._buf("words", (SYNC_ROUND + 1) * n, torch.int32)       # `changed` of a round's passes, then the flags
+        h_words = self._buf("h_words", (SYNC_ROUND + 1) * n, torch.int32, pinned=True)
+        state.zero_()
+        # sync passes in rounds: one small copy and one synchronise per round
+        t0 = time.perf_counter()
+        cap = self.max_sync_passes if self.max_sync_passes is not None else int(segs["sub_count"].max()) + 1
+        done, quiet = 0, np.zeros(n, dtype=bool)
+        while done < cap and not quiet.all():
+            r = min(SYNC_ROUND, cap - done)
+            words[:r * n].zero_()
+            for j in range(r):
+                hp.jpeg_huffman_sync(d_scan, d_tab, d_images, images, d_segs, segs, self.sub_bits, state, words[j * n:(j + 1) * n])
+            h_words[:r * n].copy_(words[:r * n], non_blocking=True)
+            stream.synchronize()
+            done += r
+            quiet = (h_words[:r * n].numpy().reshape(r, n) == 0).any(axis=0)   # a pass that changed nothing: the fixed point
+        self.sync_passes += done
+        self._clock("sync", t0)
+        t0 = time.perf_counter()
+        flags = words[SYNC_ROUND * n:]
+        flags.zero_()
+        hp.jpeg_huffman_emit(d_scan, d_tab, d_images, images, d_segs, segs, self.sub_bits, state, first_block, d_coef[:coef_count],
+                             flags)
+        h_flags = h_words[SYNC_ROUND * n:]
+        h_flags.copy_(flags, non_blocking=True)
+        stream.synchronize()
+        self._clock("emit", t0)
+        bad = (h_flags.numpy() != 0) | ~quiet
+        for k in host:
+            bad[k] = True
+        return [int(k) for k in np.nonzero(bad)[0]]
+
+    def coefficient_planes(self, blobs: Sequence[bytes]):
+        """The device Huffman decoder alone, for inspection: files of the supported subset, as ONE chunk -> (per image the
+        int16 tensor fdet_jpeg_entropy_decode would fill, [positions whose planes the host would still have to decode])."""
+        n = len(blobs)
+        probed = []
+        for i, b in enumerate(blobs):
+            rc, info, msg = hp.jpeg_info(b)
+            if rc != 0:
+                raise FdetError(f"image {i}: {msg} (code {rc})")
+            probed.append((i, info))
+        descs, spans, used, _ws = self._describe(probed, np.zeros(n, dtype=IMAGE_DTYPE))
+        self.sync_passes, self.scan_bytes = 0, 0
+        with torch.cuda.device(self.device):
+            d_coef = torch.full((used,), 0x5555, dtype=torch.int16, device=self.device)
+            pool = ThreadPoolExecutor(max_workers=max(1, min(self.workers, n)))
+            try:
+                todo = self.huffman_chunk(pool, blobs, [f"image {i}" for i in range(n)], probed, descs, used, d_coef)
+            finally:
+                pool.shutdown(wait=True)
+                torch.cuda.current_stream(self.device).synchronize()
+        return [d_coef[a:a + c] for a, c in spans], todo
+
+    def _decode_chunks_device_huffman(self, pool, blobs, names, chunks, plans, data) -> None:
+        dev = self.device
+        stream = torch.cuda.current_stream(dev)
+        cap = max(p[2] for p in plans)
+        ws_cap = max(p[3] for p in plans)
+        d_coef = self._buf("d_coef", cap, torch.int16)
+        workspace = self._buf("workspace", max(ws_cap, 8), torch.uint8)
+        try:
+            for chunk, (descs, spans, used, _ws) in zip(chunks, plans):
+                todo = self.huffman_chunk(pool, blobs, names, chunk, descs, used, d_coef)
+                if todo:                                     # the host path of huffman="host", image by image, into the same planes
+                    need = max(spans[k][1] for k in todo)
+                    for k in todo:
+                        stream.synchronize()                 # the copy out of the staging buffer has finished
+                        stage = self._buf("h_coef", need, torch.int16, pinned=True)
+                        i = chunk[k][0]
+                        start, count = spans[k]
+                        rc, msg = hp.jpeg_entropy_decode(blobs[i], stage.data_ptr(), count)
+                        if rc != 0:
+                            raise FdetError(f"{names[i]}: {msg} (code {rc})")
+                        d_coef[start:start + count].copy_(stage[:count], non_blocking=True)
+                        self.huffman_fallbacks.append(i)
+                t0 = time.perf_counter()
+                h_descs = self._buf("h_descs", descs.nbytes, torch.uint8, pinned=True)
+                h_descs.numpy()[:] = descs.view(np.uint8)
+                d_descs = self._buf("d_descs", descs.nbytes, torch.uint8)
+                d_descs.copy_(h_descs, non_blocking=True)
+                hp.jpeg_reconstruct(d_coef[:used], d_descs, descs, workspace, data)
+                self.chunks += 1
+                if self.timings is not None:
+                    stream.synchronize()
+                    self._clock("reconstruct", t0)
         finally:
             stream.synchronize()                             # nothing of this call is in flight when its buffers go
 

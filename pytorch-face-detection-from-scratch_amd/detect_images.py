@@ -92,7 +92,7 @@ def image_paths(root):
     return sorted(p for p in root.rglob("*") if p.suffix.lower() in EXTENSIONS)
 
 
-def quantize_loaded_model(model, args, default_bank=None, decoder="pil"):
+def quantize_loaded_model(model, args, default_bank=None, decoder="pil", huffman="host"):
     """--int8: calibrate `model` on the images under --calib (or on `default_bank`) and return its Int8PoolResnet."""
     from .quantize import Int8PoolResnet, bank_frames, calibrate
     bank = default_bank
@@ -101,7 +101,7 @@ def quantize_loaded_model(model, args, default_bank=None, decoder="pil"):
         paths = image_paths(args.calib)[:args.calib_images]
         if not paths:
             raise SystemExit(f"no image under {args.calib}")
-        bank = bank_from_files(paths, "cuda", decoder=decoder)
+        bank = bank_from_files(paths, "cuda", decoder=decoder, huffman=huffman)
     qp = calibrate(model, bank_frames(bank, model.input_shape[1:], args.calib_images))
     print(f"int8: calibrated on {qp.images_seen} images ({qp.method})")
     return Int8PoolResnet(model, qp, stem=getattr(args, "int8_stem", None) or "float")
@@ -189,6 +189,8 @@ def main(argv=None):
     ap.add_argument("--batch-images", type=int, default=64, help="source images per detect() call")
     ap.add_argument("--device-jpeg", action="store_true",
                     help="decode baseline JPEGs with the device decoder (datasets/jpeg.py) instead of PIL; same bytes")
+    ap.add_argument("--device-jpeg-huffman", action="store_true",
+                    help="--device-jpeg: Huffman-decode on the device too, so that only the file bytes cross to it")
     ap.add_argument("--flip", action="store_true", help="every window a second time, mirrored left to right")
     ap.add_argument("--vote", action="store_true", help="box voting: a kept box is the score-weighted mean of its cluster")
     ap.add_argument("--min-votes", type=int, default=1, help="with --vote: leave out boxes with fewer members than this")
@@ -201,6 +203,8 @@ def main(argv=None):
     check_draw_arguments(ap, args)
     check_jpeg_encode_arguments(ap, args)
     check_chip_arguments(ap, args, "--chips")
+    if args.device_jpeg_huffman and not args.device_jpeg:
+        ap.error("--device-jpeg-huffman needs --device-jpeg")
     if args.min_votes < 1:
         ap.error("--min-votes must be >= 1")
     if args.min_votes > 1 and not args.vote:
@@ -247,16 +251,17 @@ def run(args):
     paths = image_paths(root)
     if not paths:
         raise SystemExit(f"no image under {root}")
+    huffman = "device" if getattr(args, "device_jpeg_huffman", False) else "host"
     if getattr(args, "int8", False):
         decoder = "device" if args.device_jpeg else "pil"
-        first = None if args.calib is not None else bank_from_files(paths[:args.calib_images], "cuda", decoder=decoder)
-        model = quantize_loaded_model(model, args, first, decoder)
+        first = None if args.calib is not None else bank_from_files(paths[:args.calib_images], "cuda", decoder=decoder, huffman=huffman)
+        model = quantize_loaded_model(model, args, first, decoder, huffman)
     det = TiledDetector(model, tile_sizes=tuple(args.tile), overlap=args.overlap, include_whole=not args.no_whole,
                         edge_margin=args.edge_margin, flip=args.flip, vote=args.vote, min_votes=args.min_votes)
     names, all_rows, all_counts = [], [], []
     for a in range(0, len(paths), args.batch_images):
         chunk = paths[a:a + args.batch_images]
-        bank = bank_from_files(chunk, "cuda", decoder="device" if args.device_jpeg else "pil")
+        bank = bank_from_files(chunk, "cuda", decoder="device" if args.device_jpeg else "pil", huffman=huffman)
         rows, counts = det.detect(bank, range(len(bank)))
         if args.draw is not None:
             from .render import render_detections, save_images

@@ -594,6 +594,127 @@ def jpeg_reconstruct(coef: torch.Tensor, d_descs: torch.Tensor, h_descs, workspa
 
 
 # ------------------------------------------------------------------------------------------
+# Huffman decoding of JPEG scans on the device (csrc/fdet_jpeg_huff.hip; datasets/jpeg.py huffman="device" drives these)
+# ------------------------------------------------------------------------------------------
+JPEG_HUFF_HOST = 1                                           # FDET_JPEG_HUFF_* of include/fdet.h
+JPEG_HUFF_END = 0x80000000
+JPEG_HUFF_NOCODE, JPEG_HUFF_RUN, JPEG_HUFF_DCCAT, JPEG_HUFF_EXHAUSTED, JPEG_HUFF_TRAILING = 1, 2, 4, 8, 16
+
+
+def _jpeg_huff_dtypes():
+    import numpy as np
+    table = np.dtype([("look_nbits", "u1", (512,)), ("look_sym", "u1", (512,)), ("maxcode", "<i4", (18,)),
+                      ("valoffset", "<i4", (18,)), ("vals", "u1", (256,)), ("nvals", "<i4"), ("reserved", "<i4")], align=True)
+    tables = np.dtype([("dc", table, (3,)), ("ac", table, (3,))], align=True)                                # fdet_jpeg_huff_tables
+    seg = np.dtype([("byte_offset", "<i8"), ("byte_len", "<i4"), ("first_mcu", "<i4"), ("mcu_count", "<i4"), ("image", "<i4"),
+                    ("sub_first", "<i4"), ("sub_count", "<i4")], align=True)                                 # fdet_jpeg_huff_segment
+    image = np.dtype([("coef_offset", "<i8", (3,)), ("ncomp", "<i4"), ("hs", "<i4"), ("vs", "<i4"), ("mcus_x", "<i4"),
+                      ("mcus_y", "<i4"), ("seg_first", "<i4"), ("seg_count", "<i4"), ("sub_first", "<i4"), ("sub_count", "<i4"),
+                      ("wg_first", "<i4"), ("reserved", "<i4", (2,))], align=True)                                                # fdet_jpeg_huff_image
+    assert table.itemsize == 1432 and tables.itemsize == 8592 and seg.itemsize == 32 and image.itemsize == 72
+    return tables, seg, image
+
+
+JPEG_HUFF_TABLES_DTYPE, JPEG_HUFF_SEG_DTYPE, JPEG_HUFF_IMAGE_DTYPE = _jpeg_huff_dtypes()
+
+
+def jpeg_scan_prepare(data: bytes, scan_ptr: int, scan_capacity: int, segs_ptr: int, seg_capacity: int, tables_ptr: int):
+    """fdet_jpeg_scan_prepare (host only, thread-safe; ctypes releases the GIL): the file `data` -> its unstuffed segments
+    at host address `scan_ptr`, `seg_capacity` fdet_jpeg_huff_segment records at `segs_ptr` and one fdet_jpeg_huff_tables at
+    `tables_ptr`.  -> (rc, scan bytes used, segments, message); rc JPEG_HUFF_HOST: decode this image on the host."""
+    import ctypes
+    L = lib()
+    used, nseg = ctypes.c_size_t(0), ctypes.c_int(0)
+    rc = L.fdet_jpeg_scan_prepare(data, len(data), scan_ptr, scan_capacity, ctypes.addressof(used), segs_ptr, seg_capacity,
+                                  ctypes.addressof(nseg), tables_ptr)
+    if rc == 0:
+        return 0, int(used.value), int(nseg.value), ""
+    return rc, 0, 0, ("decode on the host" if rc == JPEG_HUFF_HOST else L.fdet_last_error().decode(errors="replace"))
+
+
+def jpeg_scan_prepare_arrays(data: bytes, seg_capacity=None, scan_capacity=None):
+    """jpeg_scan_prepare into fresh numpy arrays -> (rc, scan uint8 (used,), segments (n,) of JPEG_HUFF_SEG_DTYPE, tables
+    (1,) of JPEG_HUFF_TABLES_DTYPE, message).  The capacities default to what always suffices."""
+    import numpy as np
+    rc, info, msg = jpeg_info(data)
+    if rc != 0:
+        return rc, None, None, None, msg
+    mcus = int(info["mcus_x"]) * int(info["mcus_y"])
+    ri = int(info["restart_interval"]) or mcus
+    nseg = -(-mcus // ri) if seg_capacity is None else int(seg_capacity)
+    cap = (len(data) + 15) // 16 * 16 + 16 * nseg if scan_capacity is None else int(scan_capacity)
+    scan = np.zeros(max(cap, 1), np.uint8)
+    segs = np.zeros(max(nseg, 1), JPEG_HUFF_SEG_DTYPE)
+    tables = np.zeros(1, JPEG_HUFF_TABLES_DTYPE)
+    rc, used, n, msg = jpeg_scan_prepare(data, scan.ctypes.data, cap, segs.ctypes.data, nseg, tables.ctypes.data)
+    if rc != 0:
+        return rc, None, None, None, msg
+    return 0, scan[:used], segs[:n], tables, ""
+
+
+def jpeg_huff_layout(images, segs, sub_bits: int) -> int:
+    """Fill the subsequence ranges (segments: sub_first, sub_count; images: sub_first, sub_count, wg_first) that follow from
+    the segments' byte_len and `sub_bits`, in place.  `images` must already hold seg_first / seg_count.  -> subsequences."""
+    import numpy as np
+    bits = segs["byte_len"].astype(np.int64) * 8
+    cnt = np.maximum(1, -(-bits // int(sub_bits)))
+    first = np.cumsum(cnt) - cnt
+    total = int(cnt.sum())
+    if total > 0x7fffffff:
+        raise N.FdetError(f"jpeg_huff_layout: {total} subsequences are more than one launch takes")
+    segs["sub_count"], segs["sub_first"] = cnt, first
+    ends = np.concatenate([first, [total]])
+    images["sub_first"] = ends[images["seg_first"]]
+    images["sub_count"] = ends[images["seg_first"] + images["seg_count"]] - images["sub_first"]
+    wgs = -(-images["sub_count"].astype(np.int64) // 256)
+    images["wg_first"] = np.cumsum(wgs) - wgs
+    return total
+
+
+def _jpeg_huff_args(who, scan, d_tables, d_images, h_images, d_segs, h_segs, state):
+    import numpy as np
+    for name, h, dt, d in (("h_images", h_images, JPEG_HUFF_IMAGE_DTYPE, d_images), ("h_segs", h_segs, JPEG_HUFF_SEG_DTYPE, d_segs)):
+        if not isinstance(h, np.ndarray) or h.dtype != dt or h.ndim != 1 or not h.flags.c_contiguous:
+            raise ValueError(f"{who}: {name} must be a contiguous (n,) record array of its dtype")
+        if d.numel() != len(h) * dt.itemsize:
+            raise ValueError(f"{who}: device and host copies of {name} differ in size")
+    if d_tables.numel() != len(h_images) * JPEG_HUFF_TABLES_DTYPE.itemsize:
+        raise ValueError(f"{who}: one fdet_jpeg_huff_tables per image is expected")
+    if state.numel() % 3:
+        raise ValueError(f"{who}: state holds three words per subsequence")
+
+
+def jpeg_huffman_sync(scan: torch.Tensor, d_tables: torch.Tensor, d_images: torch.Tensor, h_images, d_segs: torch.Tensor, h_segs,
+                      sub_bits: int, state: torch.Tensor, changed: torch.Tensor) -> None:
+    """fdet_jpeg_huffman_sync: ONE synchronisation pass on the current stream.  scan / d_tables / d_images / d_segs device
+    uint8, state device int64 (3 words per subsequence, zero-filled before the first pass), changed device int32 (one word
+    per image, zero-filled by the caller).  Bad descriptors raise before anything runs."""
+    _jpeg_huff_args("jpeg_huffman_sync", scan, d_tables, d_images, h_images, d_segs, h_segs, state)
+    if changed.numel() < len(h_images):
+        raise ValueError("jpeg_huffman_sync: one `changed` word per image is expected")
+    U8 = torch.uint8
+    check(lib().fdet_jpeg_huffman_sync(ptr(scan, U8), scan.numel(), ptr(d_tables, U8), ptr(d_images, U8), h_images.ctypes.data,
+                                       len(h_images), ptr(d_segs, U8), h_segs.ctypes.data, len(h_segs), int(sub_bits),
+                                       ptr(state, torch.int64), state.numel() // 3, ptr(changed, I32), stream()),
+          "fdet_jpeg_huffman_sync")
+
+
+def jpeg_huffman_emit(scan: torch.Tensor, d_tables: torch.Tensor, d_images: torch.Tensor, h_images, d_segs: torch.Tensor, h_segs,
+                      sub_bits: int, state: torch.Tensor, first_block: torch.Tensor, coef: torch.Tensor, flags: torch.Tensor) -> None:
+    """fdet_jpeg_huffman_emit on the current stream: converged states -> the int16 coefficient planes of `coef` (zeroed here),
+    byte for byte fdet_jpeg_entropy_decode's; flags device int32, one word per image, zero-filled by the caller."""
+    _jpeg_huff_args("jpeg_huffman_emit", scan, d_tables, d_images, h_images, d_segs, h_segs, state)
+    if flags.numel() < len(h_images) or first_block.numel() < state.numel() // 3:
+        raise ValueError("jpeg_huffman_emit: one flag word per image and one first_block word per subsequence are expected")
+    U8 = torch.uint8
+    check(lib().fdet_jpeg_huffman_emit(ptr(scan, U8), scan.numel(), ptr(d_tables, U8), ptr(d_images, U8), h_images.ctypes.data,
+                                       len(h_images), ptr(d_segs, U8), h_segs.ctypes.data, len(h_segs), int(sub_bits),
+                                       ptr(state, torch.int64), state.numel() // 3, ptr(first_block, I32), ptr(coef, torch.int16),
+                                       coef.numel(), ptr(flags, I32), stream()),
+          "fdet_jpeg_huffman_emit")
+
+
+# ------------------------------------------------------------------------------------------
 # Baseline JPEG encode (csrc/fdet_jpeg_enc.hip; datasets/jpeg.py DeviceJpegEncoder drives these)
 # ------------------------------------------------------------------------------------------
 JPEG_SUBSAMPLINGS = {"4:4:4": 0, "4:2:2": 1, "4:2:0": 2}     # FDET_JPEG_SUB_*: PIL's numbering

@@ -104,6 +104,8 @@ def main(argv=None):
     ap.add_argument("--wider-gt", default=None, help="directory of the WIDER protocol's four .mat files: report Easy/Medium/Hard AP")
     ap.add_argument("--device-jpeg", action="store_true",
                     help="--wider-root: decode baseline JPEGs with the device decoder (datasets/jpeg.py) instead of PIL; same bytes")
+    ap.add_argument("--device-jpeg-huffman", action="store_true",
+                    help="--device-jpeg: Huffman-decode on the device too, so that only the file bytes cross to it")
     ap.add_argument("--flip", action="store_true", help="--tiled: every window a second time, mirrored left to right")
     ap.add_argument("--vote", action="store_true", help="--tiled: box voting instead of plain NMS across windows")
     ap.add_argument("--min-votes", type=int, default=1, help="--tiled --vote: leave out boxes with fewer members than this")
@@ -111,6 +113,8 @@ def main(argv=None):
     add_int8_arguments(ap)
     args = ap.parse_args(argv)
     check_int8_arguments(ap, args)
+    if args.device_jpeg_huffman and not args.device_jpeg:
+        ap.error("--device-jpeg-huffman needs --device-jpeg")
     if args.min_votes < 1:
         ap.error("--min-votes must be >= 1")
     if (args.flip or args.vote or args.min_votes > 1) and not args.tiled:
@@ -160,7 +164,8 @@ def run(args):
         paths, boxes = read_wider_annotations(args.wider_root, args.split, max_faces=args.max_faces, keep_placeholder=False)
         if args.max_images:
             paths, boxes = paths[:args.max_images], boxes[:args.max_images]
-        bank = bank_from_files(paths, "cuda", decoder="device" if args.device_jpeg else "pil")
+        bank = bank_from_files(paths, "cuda", decoder="device" if args.device_jpeg else "pil",
+                               huffman="device" if getattr(args, "device_jpeg_huffman", False) else "host")
     else:
         bank, boxes = synthetic_bank(args.synthetic_images, "cuda", seed=2)
     if len(bank) < args.batch_size:
@@ -213,7 +218,8 @@ def int8_report(model, val, bank, args, float_result):
     """The evaluator's numbers of the int8 model on the same batches, printed beside the float ones."""
     from .detect_images import quantize_loaded_model
     from .evaluation import DetectionEvaluator
-    m8 = quantize_loaded_model(model.eval(), args, bank, "device" if args.device_jpeg else "pil")
+    m8 = quantize_loaded_model(model.eval(), args, bank, "device" if args.device_jpeg else "pil",
+                               "device" if getattr(args, "device_jpeg_huffman", False) else "host")
     ev = DetectionEvaluator(iou_thresholds=tuple(args.iou), score_floor=args.score_floor)
     with torch.no_grad():
         for x, _, gt in val:

@@ -60,14 +60,14 @@ def build_parser() -> argparse.ArgumentParser:
     return ap
 
 
-def wider_batches(root, split, batch_size, transform, patches, decoder, **kw):
+def wider_batches(root, split, batch_size, transform, patches, decoder, huffman="host", **kw):
     """DeviceBatches over one split of a WIDER Face tree, filtered as the reference filters it (at most two faces)."""
     from .datasets.augment import DeviceBatches
     from .datasets.WIDERFace.annotations import bank_from_files, read_wider_annotations
     paths, boxes = read_wider_annotations(root, split, max_faces=2)
     if len(paths) < batch_size:
         raise SystemExit(f"{root}: the {split} split holds {len(paths)} images with at most two faces, a batch needs {batch_size}")
-    bank = bank_from_files(paths, "cuda", decoder=decoder)
+    bank = bank_from_files(paths, "cuda", decoder=decoder, huffman=huffman)
     return DeviceBatches(bank, boxes, batch_size, transform, patches, **kw)
 
 
@@ -76,7 +76,11 @@ def main(argv=None):
     # not a training option: build_parser() stays the set of options that shape the run
     ap.add_argument("--draw-dir", default=None,
                     help="write {train|validation}_epoch_{E}.png (image 0 of the first batch, predicted boxes) there")
+    ap.add_argument("--device-jpeg-huffman", action="store_true",
+                    help="--device-jpeg: Huffman-decode on the device too, so that only the file bytes cross to it")
     args = ap.parse_args(argv)
+    if args.device_jpeg_huffman and not args.device_jpeg:
+        ap.error("--device-jpeg-huffman needs --device-jpeg")
     torch.random.manual_seed(0)                                  # train_model.py:13
     from .models import ModelMeta
     from .models.PoolResnet import PoolResnet
@@ -105,10 +109,11 @@ def main(argv=None):
         from .datasets.augment import default_transform, training_transform
         shape = (args.size, args.size)
         decoder = "device" if args.device_jpeg else "pil"
+        huffman = "device" if args.device_jpeg_huffman else "host"
         train = wider_batches(args.wider_root, "train", args.batch_size, training_transform(shape, seed=1), args.patches, decoder,
-                              seed=1)
+                              huffman, seed=1)
         val = wider_batches(args.wider_root, "val", args.batch_size, default_transform(shape), args.patches, decoder,
-                            shuffle=False)
+                            huffman, shuffle=False)
     elif args.augment:
         from .datasets.augment import DeviceBatches, default_transform, synthetic_bank, training_transform
         shape = (args.size, args.size)
