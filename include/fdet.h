@@ -1474,8 +1474,8 @@ int fdet_q8_sepchain(const int8_t* x, const int8_t* const* h_w1, const float* co
                      void* stream);
 
 /* ---------------------------------------------------------------------------------------
- * Int8 inference: mixed widths -- the SSD detector (csrc/fdet_q8_ssd.hip; restated by tests/q8_ssd_cpu_ref.py, and the GPU
- * results equal that restatement bit for bit).  SSD(filters = 16) has 16, 32, 64, 128 and 256 channels, blocks whose width
+ * Int8 inference: mixed widths -- the SSD detector (csrc/fdet_q8.hip, the stem in csrc/fdet_stem_q8.hip; restated by
+ * tests/q8_ssd_cpu_ref.py, and the GPU results equal that restatement bit for bit).  SSD(filters = 16) has 16, 32, 64, 128 and 256 channels, blocks whose width
  * changes (each with a 1x1 skip conv), a floor pool 15 -> 7, four Linear(C,5) heads and a 16-filter stem: none of it fits
  * the entries above, which keep their shapes and refusals.  Quantisation, the Q8 layout, the preparation of (w_q, b_q, mul)
  * and the single-rounding float steps are those of "Int8 inference" above; accumulation is exact int32 (Cin <= 256:

@@ -20,23 +20,22 @@
 // roles from block to block (the output written into A is the next block's x, its ring the zeros GEMM 1 produced from the
 // halo), and the parameters of up to Q8S_WIN blocks are staged at once.
 #include "fdet_common.h"
+#include "fdet_q8_common.h"
 
 namespace {
 using namespace fdet;
 
-typedef int q8s_v4i __attribute__((ext_vector_type(4)));
-typedef float q8s_v4f __attribute__((ext_vector_type(4)));
+using q8::v4i;
+using q8::v4f;
 
-constexpr int Q8S_MAX_HW = 4096;
 constexpr int Q8S_THREADS = 256;
-constexpr size_t Q8S_LDS_MAX = 160 * 1024;
 constexpr size_t Q8S_LDS_PLAN = 80 * 1024;         // the planner's budget: two workgroups per CU
 constexpr int Q8SC_MAXB = 16;                      // blocks per chain launch
 constexpr int Q8SC_MAXHW = 16;
 constexpr int Q8S_WIN = 10;                        // blocks whose parameters the chain keeps in LDS at once
 
 __host__ __device__ inline bool q8s_shape_ok(int C, int H, int W) {
-  return (C == 64 || C == 128) && H >= 1 && W >= 1 && H <= Q8S_MAX_HW && W <= Q8S_MAX_HW;
+  return (C == 64 || C == 128) && q8::act_shape_ok(C, H, W, 64);
 }
 
 __host__ __device__ inline int q8s_param_bytes(int C) { return 2 * C * C + 21 * C; }
@@ -45,30 +44,7 @@ __host__ __device__ inline size_t q8s_tile_lds(int C, int R, int CW) {
   return (size_t)q8s_param_bytes(C) + (size_t)C * (2ull * (R + 2) * (CW + 2) + (size_t)R * CW);
 }
 
-inline size_t q8s_bytes(int N, int C, int H, int W) {
-  if (N < 1 || !q8s_shape_ok(C, H, W)) return 0;
-  const unsigned long long b = (unsigned long long)N * (H + 2) * (W + 2) * C;
-  return b < (1ull << 31) ? (size_t)b : 0;
-}
-
-__device__ __forceinline__ int q8s_round(float t) {
-  return (int)fminf(fmaxf(rintf(t), -127.0f), 127.0f);
-}
-
-__device__ __forceinline__ int q8s_pack4(int a, int b, int c, int d) {
-  return (a & 255) | ((b & 255) << 8) | ((c & 255) << 16) | (int)((unsigned)(d & 255) << 24);
-}
-
-__device__ __forceinline__ int q8s_byte(int w, int r) {
-  return (int)(signed char)((unsigned)w >> (8 * r));
-}
-
-__device__ __forceinline__ float q8s_lrelu(float v, float slope) { return v >= 0.0f ? v : v * slope; }
-
-__device__ __forceinline__ int q8s_max4(int a, int b) {
-  return q8s_pack4(max(q8s_byte(a, 0), q8s_byte(b, 0)), max(q8s_byte(a, 1), q8s_byte(b, 1)), max(q8s_byte(a, 2), q8s_byte(b, 2)),
-                   max(q8s_byte(a, 3), q8s_byte(b, 3)));
-}
+inline size_t q8s_bytes(int N, int C, int H, int W) { return q8s_shape_ok(C, H, W) ? q8::act_bytes(N, C, H, W, 64) : 0; }
 
 // one block's parameters, global -> LDS in the order of the header comment (every piece a multiple of 16 bytes)
 struct Q8SepParams {
@@ -84,16 +60,16 @@ template <int KC>
 __device__ __forceinline__ void q8s_stage_params(unsigned char* dst, const Q8SepParams& p) {
   constexpr int C = 64 * KC;
   constexpr int UW = C * C / 16, UD = 9 * C / 16, UM = C / 4;
-  q8s_v4i* d = reinterpret_cast<q8s_v4i*>(dst);
+  v4i* d = reinterpret_cast<v4i*>(dst);
   for (int i = threadIdx.x; i < 2 * UW + UD + 3 * UM; i += Q8S_THREADS) {
-    const q8s_v4i* s;
+    const v4i* s;
     int j = i;
-    if (j < UW) s = reinterpret_cast<const q8s_v4i*>(p.w1);
-    else if ((j -= UW) < UW) s = reinterpret_cast<const q8s_v4i*>(p.w2);
-    else if ((j -= UW) < UD) s = reinterpret_cast<const q8s_v4i*>(p.wd);
-    else if ((j -= UD) < UM) s = reinterpret_cast<const q8s_v4i*>(p.mul1);
-    else if ((j -= UM) < UM) s = reinterpret_cast<const q8s_v4i*>(p.mul2);
-    else { j -= UM; s = reinterpret_cast<const q8s_v4i*>(p.mul3); }
+    if (j < UW) s = reinterpret_cast<const v4i*>(p.w1);
+    else if ((j -= UW) < UW) s = reinterpret_cast<const v4i*>(p.w2);
+    else if ((j -= UW) < UD) s = reinterpret_cast<const v4i*>(p.wd);
+    else if ((j -= UD) < UM) s = reinterpret_cast<const v4i*>(p.mul1);
+    else if ((j -= UM) < UM) s = reinterpret_cast<const v4i*>(p.mul2);
+    else { j -= UM; s = reinterpret_cast<const v4i*>(p.mul3); }
     d[i] = s[j];
   }
 }
@@ -105,21 +81,21 @@ __device__ __forceinline__ void q8s_pointwise(const unsigned char* src, const un
   constexpr int C = 64 * KC, T = C / 16;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int lp = lane & 15, lk = lane >> 4;
-  q8s_v4i wf[T][KC];
+  v4i wf[T][KC];
 #pragma unroll
   for (int t = 0; t < T; ++t)
 #pragma unroll
-    for (int kc = 0; kc < KC; ++kc) wf[t][kc] = *reinterpret_cast<const q8s_v4i*>(w + (16 * t + lp) * C + kc * 64 + lk * 16);
+    for (int kc = 0; kc < KC; ++kc) wf[t][kc] = *reinterpret_cast<const v4i*>(w + (16 * t + lp) * C + kc * 64 + lk * 16);
   const int groups = (npos + 15) >> 4;
   for (int g = wave; g < groups; g += Q8S_THREADS / 64) {
     const int pos = g * 16 + lp;
     const unsigned char* xr = src + min(pos, npos - 1) * C + lk * 16;
-    q8s_v4i b[KC];
+    v4i b[KC];
 #pragma unroll
-    for (int kc = 0; kc < KC; ++kc) b[kc] = *reinterpret_cast<const q8s_v4i*>(xr + kc * 64);
+    for (int kc = 0; kc < KC; ++kc) b[kc] = *reinterpret_cast<const v4i*>(xr + kc * 64);
 #pragma unroll
     for (int t = 0; t < T; ++t) {
-      q8s_v4i acc = {0, 0, 0, 0};
+      v4i acc = {0, 0, 0, 0};
 #pragma unroll
       for (int kc = 0; kc < KC; ++kc) acc = __builtin_amdgcn_mfma_i32_16x16x64_i8(wf[t][kc], b[kc], acc, 0, 0, 0);
       if (pos < npos) epi(pos, 16 * t + 4 * lk, acc);
@@ -141,12 +117,11 @@ __device__ __forceinline__ void q8s_block(const unsigned char* X, unsigned char*
   const float* mul2 = mul1 + C;
   const float* mul3 = mul2 + C;
   // GEMM 1 on every haloed position
-  q8s_pointwise<KC>(X, w1, (R + 2) * CWP, [&](int pos, int co, q8s_v4i acc) {
-    const q8s_v4f m = *reinterpret_cast<const q8s_v4f*>(mul1 + co);
+  q8s_pointwise<KC>(X, w1, (R + 2) * CWP, [&](int pos, int co, v4i acc) {
+    const v4f m = *reinterpret_cast<const v4f*>(mul1 + co);
     int q[4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) q[r] = q8s_round(q8s_lrelu((float)acc[r] * m[r], slope));
-    *reinterpret_cast<int*>(A + pos * C + co) = q8s_pack4(q[0], q[1], q[2], q[3]);
+    q8::requant4(q, acc, m, slope, false, 0, 0.0f);
+    *reinterpret_cast<int*>(A + pos * C + co) = q8::pack4(q[0], q[1], q[2], q[3]);
   });
   __syncthreads();
   // depthwise 3x3: a thread owns channels 4 g .. 4 g + 3
@@ -156,7 +131,7 @@ __device__ __forceinline__ void q8s_block(const unsigned char* X, unsigned char*
     int wt[9];
 #pragma unroll
     for (int k = 0; k < 9; ++k) wt[k] = *reinterpret_cast<const int*>(wd + k * C + 4 * g);
-    const q8s_v4f m = *reinterpret_cast<const q8s_v4f*>(mul2 + 4 * g);
+    const v4f m = *reinterpret_cast<const v4f*>(mul2 + 4 * g);
     for (int p = threadIdx.x / G; p < R * CW; p += Q8S_THREADS / G) {
       const int r = p / CW, c = p - r * CW;
       const unsigned char* ap = A + (r * CWP + c) * C + 4 * g;
@@ -167,25 +142,24 @@ __device__ __forceinline__ void q8s_block(const unsigned char* X, unsigned char*
         for (int kx = 0; kx < 3; ++kx) {
           const int v = *reinterpret_cast<const int*>(ap + (ky * CWP + kx) * C);
 #pragma unroll
-          for (int j = 0; j < 4; ++j) acc[j] += q8s_byte(v, j) * q8s_byte(wt[ky * 3 + kx], j);
+          for (int j = 0; j < 4; ++j) acc[j] += q8::byte_of(v, j) * q8::byte_of(wt[ky * 3 + kx], j);
         }
       int q[4];
 #pragma unroll
-      for (int j = 0; j < 4; ++j) q[j] = q8s_round(q8s_lrelu((float)acc[j] * m[j], slope));
-      *reinterpret_cast<int*>(B + p * C + 4 * g) = q8s_pack4(q[0], q[1], q[2], q[3]);
+      for (int j = 0; j < 4; ++j) q[j] = q8::round_q(q8::lrelu((float)acc[j] * m[j], slope));
+      *reinterpret_cast<int*>(B + p * C + 4 * g) = q8::pack4(q[0], q[1], q[2], q[3]);
     }
   }
   __syncthreads();
   // GEMM 2 on the tile's own positions, + skip, into A (whose own positions the depthwise pass has finished reading)
-  q8s_pointwise<KC>(B, w2, R * CW, [&](int pos, int co, q8s_v4i acc) {
+  q8s_pointwise<KC>(B, w2, R * CW, [&](int pos, int co, v4i acc) {
     const int r = pos / CW, c = pos - r * CW;
     const int off = ((r + 1) * CWP + c + 1) * C + co;
-    const q8s_v4f m = *reinterpret_cast<const q8s_v4f*>(mul3 + co);
+    const v4f m = *reinterpret_cast<const v4f*>(mul3 + co);
     const int sk = *reinterpret_cast<const int*>(X + off);
     int q[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) q[j] = q8s_round((float)acc[j] * m[j] + (float)q8s_byte(sk, j) * skip_mul);
-    *reinterpret_cast<int*>(A + off) = q8s_pack4(q[0], q[1], q[2], q[3]);
+    q8::requant4(q, acc, m, 1.0f, true, sk, skip_mul);     // no activation: slope 1 (t * 1.0f is t)
+    *reinterpret_cast<int*>(A + off) = q8::pack4(q[0], q[1], q[2], q[3]);
   });
   __syncthreads();
 }
@@ -218,9 +192,9 @@ __global__ __launch_bounds__(Q8S_THREADS) void k_q8_sepblock(const signed char* 
     const signed char* src = x + ((size_t)n * HP + y0) * WP * C + (size_t)x0 * C;
     for (int i = threadIdx.x; i < (R + 2) * urow; i += Q8S_THREADS) {
       const int r = i / urow, u = i - r * urow;
-      q8s_v4i v = {0, 0, 0, 0};
-      if (y0 + r < HP && x0 + u / U < WP) v = *reinterpret_cast<const q8s_v4i*>(src + (size_t)r * WP * C + (size_t)u * 16);
-      reinterpret_cast<q8s_v4i*>(X)[i] = v;
+      v4i v = {0, 0, 0, 0};
+      if (y0 + r < HP && x0 + u / U < WP) v = *reinterpret_cast<const v4i*>(src + (size_t)r * WP * C + (size_t)u * 16);
+      reinterpret_cast<v4i*>(X)[i] = v;
     }
   }
   __syncthreads();
@@ -235,17 +209,17 @@ __global__ __launch_bounds__(Q8S_THREADS) void k_q8_sepblock(const signed char* 
       const int p = i / G;
       const int r = p / pc, c = p - r * pc;
       const unsigned char* s = A + ((2 * r + 1) * CWP + 2 * c + 1) * C + 4 * d;
-      const int top = q8s_max4(*reinterpret_cast<const int*>(s), *reinterpret_cast<const int*>(s + C));
-      const int bot = q8s_max4(*reinterpret_cast<const int*>(s + CWP * C), *reinterpret_cast<const int*>(s + CWP * C + C));
-      *reinterpret_cast<int*>(dst + ((size_t)r * (Wo + 2) + c) * C + 4 * d) = q8s_max4(top, bot);
+      const int top = q8::max4(*reinterpret_cast<const int*>(s), *reinterpret_cast<const int*>(s + C));
+      const int bot = q8::max4(*reinterpret_cast<const int*>(s + CWP * C), *reinterpret_cast<const int*>(s + CWP * C + C));
+      *reinterpret_cast<int*>(dst + ((size_t)r * (Wo + 2) + c) * C + 4 * d) = q8::max4(top, bot);
     }
   } else {
     signed char* dst = y + (((size_t)n * HP + y0 + 1) * WP + x0 + 1) * C;
     const int urow = cols * U;
     for (int i = threadIdx.x; i < rows * urow; i += Q8S_THREADS) {
       const int r = i / urow, u = i - r * urow;
-      *reinterpret_cast<q8s_v4i*>(dst + (size_t)r * WP * C + (size_t)u * 16) =
-          *reinterpret_cast<const q8s_v4i*>(A + ((r + 1) * CWP + 1) * C + u * 16);
+      *reinterpret_cast<v4i*>(dst + (size_t)r * WP * C + (size_t)u * 16) =
+          *reinterpret_cast<const v4i*>(A + ((r + 1) * CWP + 1) * C + u * 16);
     }
   }
 }
@@ -283,8 +257,8 @@ __global__ __launch_bounds__(Q8S_THREADS) void k_q8_sepchain(const Q8SepChainArg
   if (resident)
     for (int k = 0; k < a.nblocks; ++k) q8s_stage_params<1>(P + k * PB, a.prm[k]);
   for (int n = blockIdx.x; n < a.N; n += gridDim.x) {
-    const q8s_v4i* src = reinterpret_cast<const q8s_v4i*>(a.x + (size_t)n * plane);
-    for (int i = threadIdx.x; i < plane / 16; i += Q8S_THREADS) reinterpret_cast<q8s_v4i*>(X)[i] = src[i];
+    const v4i* src = reinterpret_cast<const v4i*>(a.x + (size_t)n * plane);
+    for (int i = threadIdx.x; i < plane / 16; i += Q8S_THREADS) reinterpret_cast<v4i*>(X)[i] = src[i];
     for (int k0 = 0; k0 < a.nblocks; k0 += Q8S_WIN) {
       const int cnt = min(Q8S_WIN, a.nblocks - k0);
       if (!resident)                                // (the previous window's last reads ended at the barrier that closes q8s_block)
@@ -300,7 +274,7 @@ __global__ __launch_bounds__(Q8S_THREADS) void k_q8_sepchain(const Q8SepChainArg
           for (int i = threadIdx.x; i < H * urow; i += Q8S_THREADS) {
             const int r = i / urow, u = i - r * urow;
             const int off = ((r + 1) * WP + 1) * C + u * 16;
-            *reinterpret_cast<q8s_v4i*>(dst + off) = *reinterpret_cast<const q8s_v4i*>(A + off);
+            *reinterpret_cast<v4i*>(dst + off) = *reinterpret_cast<const v4i*>(A + off);
           }
         }
         if (k + 1 == a.nblocks && a.out_f32 != nullptr) {
@@ -311,7 +285,7 @@ __global__ __launch_bounds__(Q8S_THREADS) void k_q8_sepchain(const Q8SepChainArg
             const int yy = p / W, xx = p - yy * W;
             const int v = *reinterpret_cast<const int*>(A + ((yy + 1) * WP + xx + 1) * C + 4 * c4);
 #pragma unroll
-            for (int j = 0; j < 4; ++j) dst[(size_t)(4 * c4 + j) * hw + p] = (float)q8s_byte(v, j) * a.out_scale;
+            for (int j = 0; j < 4; ++j) dst[(size_t)(4 * c4 + j) * hw + p] = (float)q8::byte_of(v, j) * a.out_scale;
           }
         }
         unsigned char* t = X;
@@ -322,8 +296,6 @@ __global__ __launch_bounds__(Q8S_THREADS) void k_q8_sepchain(const Q8SepChainArg
     __syncthreads();                                // the copies out of the last output end before the next image lands
   }
 }
-
-inline bool q8s_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 // The planner: among the tilings (bands x segments of equal size, rounded up; even when pooled) whose LDS fits the budget,
 // the fewest GEMM-1 MFMA column tiles (16 haloed positions each) over the map; ties go to the fewer tiles.
@@ -392,11 +364,11 @@ extern "C" int fdet_q8_sepblock(const int8_t* x, const int8_t* w1, const float* 
                                 const int8_t* w2, const float* mul3, float skip_mul, int8_t* y, int N, int C, int H, int W, int pool,
                                 int tile_rows, int tile_cols, float slope, void* stream) {
   FDET_REQUIRE(x && w1 && mul1 && wd && mul2 && w2 && mul3 && y && q8s_bytes(N, C, H, W) > 0,
-               "q8_sepblock: unsupported shape N=%d C=%d H=%d W=%d (C 64 or 128, 1 <= H, W <= %d, under 2 GiB)", N, C, H, W, Q8S_MAX_HW);
+               "q8_sepblock: unsupported shape N=%d C=%d H=%d W=%d (C 64 or 128, 1 <= H, W <= %d, under 2 GiB)", N, C, H, W, q8::MAX_HW);
   FDET_REQUIRE(pool == 0 || pool == 1, "q8_sepblock: pool must be 0 or 1");
   FDET_REQUIRE(!pool || (!(H & 1) && !(W & 1)), "q8_sepblock: the pooled form needs even H and W, got %dx%d", H, W);
-  FDET_REQUIRE(q8s_aligned16(x) && q8s_aligned16(w1) && q8s_aligned16(mul1) && q8s_aligned16(wd) && q8s_aligned16(mul2) &&
-               q8s_aligned16(w2) && q8s_aligned16(mul3) && q8s_aligned16(y), "q8_sepblock: every tensor must be 16-byte aligned");
+  FDET_REQUIRE(q8::aligned16(x) && q8::aligned16(w1) && q8::aligned16(mul1) && q8::aligned16(wd) && q8::aligned16(mul2) &&
+               q8::aligned16(w2) && q8::aligned16(mul3) && q8::aligned16(y), "q8_sepblock: every tensor must be 16-byte aligned");
   FDET_REQUIRE(x != y, "q8_sepblock: the output may not alias the input");
   FDET_REQUIRE((tile_rows == 0) == (tile_cols == 0) && tile_rows >= 0 && tile_cols >= 0,
                "q8_sepblock: tile_rows and tile_cols are both 0 (the planner) or both positive, got %d, %d", tile_rows, tile_cols);
@@ -405,11 +377,11 @@ extern "C" int fdet_q8_sepblock(const int8_t* x, const int8_t* w1, const float* 
   if (R == 0) {
     FDET_REQUIRE(q8s_plan(C, H, W, pool, &R, &CW, &lds), "q8_sepblock: no tiling for C=%d %dx%d", C, H, W);
   } else {
-    FDET_REQUIRE(R <= Q8S_MAX_HW && CW <= Q8S_MAX_HW && (!pool || (!(R & 1) && !(CW & 1))),
-                 "q8_sepblock: a forced tile is at most %d a side and even when pooled, got %dx%d", Q8S_MAX_HW, R, CW);
+    FDET_REQUIRE(R <= q8::MAX_HW && CW <= q8::MAX_HW && (!pool || (!(R & 1) && !(CW & 1))),
+                 "q8_sepblock: a forced tile is at most %d a side and even when pooled, got %dx%d", q8::MAX_HW, R, CW);
     lds = q8s_tile_lds(C, R, CW);
-    FDET_REQUIRE(lds <= Q8S_LDS_MAX, "q8_sepblock: a %dx%d tile of %d channels needs %zu bytes of LDS (at most %zu)", R, CW, C, lds,
-                 Q8S_LDS_MAX);
+    FDET_REQUIRE(lds <= q8::LDS_MAX, "q8_sepblock: a %dx%d tile of %d channels needs %zu bytes of LDS (at most %zu)", R, CW, C, lds,
+                 q8::LDS_MAX);
   }
   Q8SepGeo g{N, H, W, R, CW, (H + R - 1) / R, (W + CW - 1) / CW};
   FDET_REQUIRE((long long)N * g.bands * g.segs < (1ll << 31), "q8_sepblock: too many tiles");
@@ -435,7 +407,7 @@ extern "C" int fdet_q8_sepchain(const int8_t* x, const int8_t* const* h_w1, cons
   FDET_REQUIRE(out_f32 == nullptr || (out_scale > 0.0f && out_scale <= 3.0e38f), "q8_sepchain: out_scale must be positive and finite");
   Q8SepChainArgs a{};
   a.x = reinterpret_cast<const signed char*>(x);
-  bool ok = q8s_aligned16(x) && q8s_aligned16(out_f32);
+  bool ok = q8::aligned16(x) && q8::aligned16(out_f32);
   for (int k = 0; k < nblocks; ++k) {
     FDET_REQUIRE(h_w1[k] && h_mul1[k] && h_wd[k] && h_mul2[k] && h_w2[k] && h_mul3[k], "q8_sepchain: null tensor in block %d", k);
     a.prm[k] = Q8SepParams{reinterpret_cast<const signed char*>(h_w1[k]), reinterpret_cast<const signed char*>(h_wd[k]),
@@ -443,8 +415,8 @@ extern "C" int fdet_q8_sepchain(const int8_t* x, const int8_t* const* h_w1, cons
     a.skip_mul[k] = h_skip_mul[k];
     a.out[k] = h_out ? reinterpret_cast<signed char*>(h_out[k]) : nullptr;
     FDET_REQUIRE(a.out[k] == nullptr || a.out[k] != a.x, "q8_sepchain: an output may not alias x");
-    ok = ok && q8s_aligned16(h_w1[k]) && q8s_aligned16(h_mul1[k]) && q8s_aligned16(h_wd[k]) && q8s_aligned16(h_mul2[k]) &&
-         q8s_aligned16(h_w2[k]) && q8s_aligned16(h_mul3[k]) && q8s_aligned16(a.out[k]);
+    ok = ok && q8::aligned16(h_w1[k]) && q8::aligned16(h_mul1[k]) && q8::aligned16(h_wd[k]) && q8::aligned16(h_mul2[k]) &&
+         q8::aligned16(h_w2[k]) && q8::aligned16(h_mul3[k]) && q8::aligned16(a.out[k]);
   }
   FDET_REQUIRE(ok, "q8_sepchain: every tensor must be 16-byte aligned");
   a.out_f32 = out_f32;
@@ -453,12 +425,12 @@ extern "C" int fdet_q8_sepchain(const int8_t* x, const int8_t* const* h_w1, cons
   a.nblocks = nblocks;
   a.N = N; a.H = H; a.W = W;
   const size_t lds = q8s_chain_lds(nblocks, H, W);
-  FDET_REQUIRE(lds <= Q8S_LDS_MAX, "q8_sepchain: %zu bytes of LDS", lds);
+  FDET_REQUIRE(lds <= q8::LDS_MAX, "q8_sepchain: %zu bytes of LDS", lds);
   if (lds > 64 * 1024) {
     const int rc = set_lds_attr((const void*)k_q8_sepchain, lds, "fdet_q8_sepchain");
     if (rc != FDET_OK) return rc;
   }
-  const int per_cu = (int)(Q8S_LDS_MAX / lds) < 2 ? 1 : 2;
+  const int per_cu = (int)(q8::LDS_MAX / lds) < 2 ? 1 : 2;
   const int grid = N < num_cus() * per_cu ? N : num_cus() * per_cu;
   hipLaunchKernelGGL(k_q8_sepchain, dim3((unsigned)grid), dim3(Q8S_THREADS), lds, (hipStream_t)stream, a);
   return check_launch("fdet_q8_sepchain");

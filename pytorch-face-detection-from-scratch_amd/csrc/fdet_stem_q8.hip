@@ -1,8 +1,9 @@
 // Int8 inference: the Resnet stem (3x3, stride 2, pad 1, 3 -> F channels) from the uint8 frames straight into the int8
 // trunk's layout, in integer arithmetic on the integer matrix cores (v_mfma_i32_16x16x32_i8).  The arithmetic is the contract
-// of include/fdet.h ("Int8 inference", fdet_stem3_fwd_q8_u8); tests/q8_resnet_cpu_ref.py restates it in numpy and the GPU
-// tests demand equality.  The second half of the file is the PoolResnet stem (10x10, stride 8, pad 2) in the same arithmetic,
-// fdet_stem10_fwd_q8_u8.
+// of include/fdet.h ("Int8 inference", fdet_stem3_fwd_q8_u8, and fdet_stem3_fwd_q8x_u8 for F a multiple of 16);
+// tests/q8_resnet_cpu_ref.py restates it in numpy and the GPU tests demand equality.  The second half of the file is the
+// PoolResnet stem (10x10, stride 8, pad 2) in the same arithmetic, fdet_stem10_fwd_q8_u8.  The offset and the requantising
+// line of all three kernels are q8::stem_offset and q8::stem_requant (fdet_q8_common.h).
 //
 // K = 27 taps (k = (ci*3+ky)*3+kx, padded to 32 with zero weights), so the kernel is a gather in front of one MFMA step:
 //   A (weights): lane l holds the 8 taps k = 8 (l >> 4) .. + 7 of one output channel (row l & 15 of its 16-channel tile)
@@ -19,44 +20,139 @@
 // contract's.  Both operands take tap k from the same byte of the same lane group, so the sum does not depend on how the
 // instruction orders k inside a fragment; the one-hot tests (tests/test_gpu_q8_resnet.py) check taps, lanes and channels.
 #include "fdet_common.h"
-#include "fdet_stem3_q8.h"
+#include "fdet_q8_common.h"
 
 namespace {
 using namespace fdet;
 
-typedef int s3_v4i __attribute__((ext_vector_type(4)));
-typedef float s3_v4f __attribute__((ext_vector_type(4)));
+using q8::v4i;
+using q8::v4f;
 
-// (geometry, row staging, tap offsets and the B gather: fdet_stem3_q8.h, shared with k_stem3_q8x of fdet_q8_ssd.hip)
-constexpr int S3_MAX_HW = 4096;
-constexpr int S3_MAX_F = 256;
-typedef s3::Args Stem3Args;
+// What the two 3x3 stem kernels share (k_stem3_q8: 64 output channels per workgroup; k_stem3_q8x: 16): the launch geometry,
+// the staging of the input rows in LDS as x - 128, the tap offsets of a lane's B operand and its gather.
+namespace s3 {
 
-__host__ __device__ inline bool s3_shape_ok(int Cin, int F, int H, int W) {
-  return Cin == 3 && F >= 64 && F <= S3_MAX_F && (F & 63) == 0 && H >= 2 && W >= 2 && H <= S3_MAX_HW && W <= S3_MAX_HW &&
-         !(H & 1) && !(W & 1);
+constexpr int ROWS = 4;                             // output rows per workgroup: one per wave
+constexpr int SEG = 256;                            // output columns per workgroup: 16 MFMA column tiles
+constexpr int IN_ROWS = 2 * ROWS + 1;               // input rows under ROWS output rows
+constexpr int RS = 2 * SEG + 16;                    // bytes of one staged input row: image columns 2 ox0 - 4 .. 2 ox0 + 2 SEG + 11
+constexpr int LDS = 3 * IN_ROWS * RS;               // 14,256 bytes
+constexpr long long MAX_ITEMS = 1ll << 20;          // workgroups per launch (larger batches: consecutive launches)
+
+struct Args {
+  const unsigned char* frames;
+  const signed char* w;                              // [F][32]
+  const int* bias;
+  const float* mul;
+  signed char* q;
+  int N, F, H, W, Ho, Wo;
+  int segs, row_groups;
+  int dwords;                                        // 1: W % 4 == 0 and a 4-byte aligned frame pointer, rows are read as dwords
+};
+
+struct Item {
+  int n, ox0, oy0, ntiles;
+};
+
+// workgroup blockIdx.x -> (image, group of ROWS output rows, segment of SEG output columns)
+__device__ __forceinline__ Item item_of(const Args& a, int item) {
+  const int per_img = a.segs * a.row_groups;
+  const int n = item / per_img;
+  const int rem = item - n * per_img;
+  const int rg = rem / a.segs;
+  const int ox0 = (rem - rg * a.segs) * SEG;
+  return Item{n, ox0, rg * ROWS, (min(SEG, a.Wo - ox0) + 15) >> 4};
+}
+
+// The 9 input rows x 3 channels under the workgroup's output rows.  LDS row (ci, iy) holds input row 2 oy0 - 1 + iy of channel
+// ci; its byte i is image column 2 ox0 - 4 + i, stored as x - 128 (the byte x ^ 0x80), everything outside the image as -128
+// (the code 0 that the contract's zero padding stands for).  No barrier here: the caller has one before the first gather.
+__device__ __forceinline__ void stage_rows(const Args& a, const Item& it, unsigned char* rows) {
+  const int nd = ((32 * it.ntiles + 3) >> 2) + 1;          // dwords of a staged row that the tiles read (bytes 3 .. 32 ntiles + 3)
+  const int c0 = 2 * it.ox0 - 4;                            // image column of byte 0 (a multiple of 4)
+  const int y0 = 2 * it.oy0 - 1;
+  for (int u = threadIdx.x; u < 3 * IN_ROWS * nd; u += 256) {
+    const int lr = u / nd, d = u - lr * nd;
+    const int ci = lr / IN_ROWS, iy = lr - ci * IN_ROWS;
+    const int y = y0 + iy, c = c0 + 4 * d;
+    unsigned v = 0;                                         // outside the image: code 0
+    if (y >= 0 && y < a.H && c + 3 >= 0 && c < a.W) {
+      const unsigned char* src = a.frames + ((size_t)(it.n * 3 + ci) * a.H + y) * a.W;
+      if (a.dwords) {                                       // c and W are multiples of 4: the dword is inside the row as a whole
+        v = *reinterpret_cast<const unsigned*>(src + c);
+      } else {
+#pragma unroll
+        for (int b = 0; b < 4; ++b)
+          if (c + b >= 0 && c + b < a.W) v |= (unsigned)src[c + b] << (8 * b);
+      }
+    }
+    *reinterpret_cast<unsigned*>(rows + lr * RS + 4 * d) = v ^ 0x80808080u;          // x - 128 as a signed byte
+  }
+}
+
+// B operand of lane (lp = lane & 15, lk = lane >> 4) of wave j: tap k = 8 lk + e -> LDS row (ci, 2 j + ky), byte
+// 2 (ox - ox0) + kx + 3; taps 27..31 read tap 26 again (weight zero)
+__device__ __forceinline__ void tap_offsets(int (&off)[8], int lk, int lp, int j) {
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    const int k = min(8 * lk + e, 26);
+    const int ci = k / 9, ky = (k - 9 * ci) / 3, kx = k - 9 * ci - 3 * ky;
+    off[e] = (ci * IN_ROWS + 2 * j + ky) * RS + kx + 3 + 2 * lp;
+  }
+}
+
+__device__ __forceinline__ long gather(const unsigned char* rows, const int (&off)[8], int tile) {
+  unsigned lo = 0, hi = 0;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    lo |= (unsigned)rows[off[e] + 32 * tile] << (8 * e);
+    hi |= (unsigned)rows[off[e + 4] + 32 * tile] << (8 * e);
+  }
+  return (long)(((unsigned long)hi << 32) | lo);
+}
+
+// Launches `kern` over image chunks: grid (chunk images x segments x row groups, channel blocks).  The entry has validated the
+// arguments.
+template <typename Kern>
+inline int launch(Kern kern, int channel_blocks, const unsigned char* frames, const int8_t* w_q, const int32_t* b_q, const float* mul,
+                  int8_t* q, int N, int F, int H, int W, hipStream_t stream, const char* what) {
+  const int Ho = H / 2, Wo = W / 2;
+  const int segs = (Wo + SEG - 1) / SEG, row_groups = (Ho + ROWS - 1) / ROWS;
+  const long long per_img = (long long)segs * row_groups;
+  const int chunk = (int)std::max(1ll, MAX_ITEMS / per_img);
+  for (int n0 = 0; n0 < N; n0 += chunk) {
+    Args a{};
+    a.frames = frames + (size_t)n0 * 3 * H * W;
+    a.w = reinterpret_cast<const signed char*>(w_q);
+    a.bias = b_q;
+    a.mul = mul;
+    a.q = reinterpret_cast<signed char*>(q) + (size_t)n0 * (Ho + 2) * (Wo + 2) * F;
+    a.N = std::min(chunk, N - n0); a.F = F; a.H = H; a.W = W; a.Ho = Ho; a.Wo = Wo;
+    a.segs = segs; a.row_groups = row_groups;
+    a.dwords = (W & 3) == 0 && (reinterpret_cast<uintptr_t>(a.frames) & 3) == 0;
+    const dim3 grid((unsigned)(a.N * per_img), (unsigned)channel_blocks);
+    hipLaunchKernelGGL(kern, grid, dim3(256), 0, stream, a);
+    if (int rc = check_launch(what)) return rc;
+  }
+  return FDET_OK;
+}
+
+}  // namespace s3
+
+// F a multiple of f_mult: 64 for k_stem3_q8, 16 for k_stem3_q8x
+__host__ __device__ inline bool s3_shape_ok(int Cin, int F, int H, int W, int f_mult) {
+  return Cin == 3 && q8::act_shape_ok(F, H, W, f_mult) && H >= 2 && W >= 2 && !(H & 1) && !(W & 1);
 }
 
 // bytes of the output tensor, 0 when N images of this shape are not accepted (as fdet_q8_act_bytes: under 2^31 bytes)
-inline size_t s3_out_bytes(int N, int Cin, int F, int H, int W) {
-  if (N < 1 || !s3_shape_ok(Cin, F, H, W)) return 0;
-  const unsigned long long b = (unsigned long long)N * (H / 2 + 2) * (W / 2 + 2) * F;
-  return b < (1ull << 31) ? (size_t)b : 0;
-}
-
-// clamp(rintf(t), -127, 127): round half to even, -128 never produced (fdet_q8.hip's q8_round)
-__device__ __forceinline__ int s3_round(float t) {
-  return (int)fminf(fmaxf(rintf(t), -127.0f), 127.0f);
-}
-
-__device__ __forceinline__ int s3_pack4(int a, int b, int c, int d) {
-  return (a & 255) | ((b & 255) << 8) | ((c & 255) << 16) | (int)((unsigned)(d & 255) << 24);
+inline size_t s3_out_bytes(int N, int Cin, int F, int H, int W, int f_mult) {
+  return s3_shape_ok(Cin, F, H, W, f_mult) ? q8::act_bytes(N, F, H / 2, W / 2, f_mult) : 0;
 }
 
 // Workgroup = 4 waves on (image, group of 4 output rows, segment of 256 output columns) and the 64 output channels
 // blockIdx.y * 64 .. + 63.  It stages the 9 input rows x 3 channels under its rows once; wave j then walks the column tiles of
 // output row j.  LDS row (ci, iy) holds input row 2 oy0 - 1 + iy of channel ci; its byte i is image column 2 ox0 - 4 + i.
-__global__ __launch_bounds__(256) void k_stem3_q8(const Stem3Args a) {
+__global__ __launch_bounds__(256) void k_stem3_q8(const s3::Args a) {
   __shared__ __attribute__((aligned(16))) unsigned char rows[s3::LDS];
   const s3::Item it = s3::item_of(a, blockIdx.x);
   const int n = it.n, ox0 = it.ox0, oy0 = it.oy0, ntiles = it.ntiles;
@@ -69,23 +165,15 @@ __global__ __launch_bounds__(256) void k_stem3_q8(const Stem3Args a) {
 #pragma unroll
   for (int t = 0; t < 4; ++t)
     wa[t] = *reinterpret_cast<const long*>(a.w + (size_t)(co0 + 16 * (lp >> 2) + 4 * t + (lp & 3)) * 32 + 8 * lk);
-  // the lane's 16 output channels co0 + 16 lk .. + 15 (dword t, byte r = channel 4 t + r): multiplier and the constant
-  // bias + 128 * sum of the channel's weights -- the MFMA against a B of ones is that sum, in the accumulators' own layout
-  // (wrapping adds: the exact sum fits where the contract's acc does)
+  // the lane's 16 output channels co0 + 16 lk .. + 15 (dword t, byte r = channel 4 t + r): q8::stem_offset, the weight sums
+  // from the MFMA against a B of ones
   float m[4][4];
   unsigned cst[4][4];
 #pragma unroll
   for (int t = 0; t < 4; ++t) {
     const int co = co0 + 16 * lk + 4 * t;
-    const s3_v4f mv = *reinterpret_cast<const s3_v4f*>(a.mul + co);
-    const s3_v4i bv = *reinterpret_cast<const s3_v4i*>(a.bias + co);
-    const s3_v4i z = {0, 0, 0, 0};
-    const s3_v4i ws = __builtin_amdgcn_mfma_i32_16x16x32_i8(wa[t], 0x0101010101010101l, z, 0, 0, 0);
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      m[t][r] = mv[r];
-      cst[t][r] = (unsigned)bv[r] + 128u * (unsigned)ws[r];
-    }
+    const v4i z = {0, 0, 0, 0};
+    q8::stem_offset(cst[t], m[t], a.bias + co, a.mul + co, __builtin_amdgcn_mfma_i32_16x16x32_i8(wa[t], 0x0101010101010101l, z, 0, 0, 0));
   }
   int off[8];
   s3::tap_offsets(off, lk, lp, j);
@@ -98,36 +186,77 @@ __global__ __launch_bounds__(256) void k_stem3_q8(const Stem3Args a) {
     int o[4];
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
-      const s3_v4i z = {0, 0, 0, 0};
-      const s3_v4i acc = __builtin_amdgcn_mfma_i32_16x16x32_i8(wa[t], b, z, 0, 0, 0);
-      int qv[4];
-#pragma unroll
-      for (int r = 0; r < 4; ++r) qv[r] = s3_round((float)(int)((unsigned)acc[r] + cst[t][r]) * m[t][r]);
-      o[t] = s3_pack4(qv[0], qv[1], qv[2], qv[3]);
+      const v4i z = {0, 0, 0, 0};
+      o[t] = q8::stem_requant(__builtin_amdgcn_mfma_i32_16x16x32_i8(wa[t], b, z, 0, 0, 0), cst[t], m[t]);
     }
     const int px = 16 * tile + lp;
     if (ox0 + px < a.Wo) {
-      const s3_v4i ov = {o[0], o[1], o[2], o[3]};
-      *reinterpret_cast<s3_v4i*>(qrow + (size_t)px * a.F) = ov;
+      const v4i ov = {o[0], o[1], o[2], o[3]};
+      *reinterpret_cast<v4i*>(qrow + (size_t)px * a.F) = ov;
     }
   }
 }
 
-inline bool s3_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+// The same stem for F a multiple of 16 (the SSD detector's 16 filters): k_stem3_q8's arithmetic with ONE 16-channel tile per
+// workgroup: row m of the tile is channel co0 + m, so a lane ends up with the four channels co0 + 4 (l >> 4) + r of its
+// pixel, one dword store.  F % 64 == 0 goes to k_stem3_q8.
+__global__ __launch_bounds__(256) void k_stem3_q8x(const s3::Args a) {
+  __shared__ __attribute__((aligned(16))) unsigned char rows[s3::LDS];
+  const s3::Item it = s3::item_of(a, blockIdx.x);
+  const int n = it.n, ox0 = it.ox0, oy0 = it.oy0, ntiles = it.ntiles;
+  s3::stage_rows(a, it, rows);
+  const int lane = threadIdx.x & 63, j = threadIdx.x >> 6;
+  const int lp = lane & 15, lk = lane >> 4;
+  const int co0 = blockIdx.y * 16;
+  // A: row lp -> channel co0 + lp, its taps 8 lk .. + 7 (bytes 27..31 of a row are zero)
+  const long wa = *reinterpret_cast<const long*>(a.w + (size_t)(co0 + lp) * 32 + 8 * lk);
+  // the lane's four output channels co0 + 4 lk + r: q8::stem_offset, the weight sums from the MFMA against a B of ones
+  float m[4];
+  unsigned cst[4];
+  const v4i z = {0, 0, 0, 0};
+  q8::stem_offset(cst, m, a.bias + co0 + 4 * lk, a.mul + co0 + 4 * lk,
+                  __builtin_amdgcn_mfma_i32_16x16x32_i8(wa, 0x0101010101010101l, z, 0, 0, 0));
+  int off[8];
+  s3::tap_offsets(off, lk, lp, j);
+  __syncthreads();
+  const int oy = oy0 + j;
+  if (oy >= a.Ho) return;                                   // (after the only barrier)
+  signed char* qrow = a.q + ((size_t)(n * (a.Ho + 2) + oy + 1) * (a.Wo + 2) + ox0 + 1) * a.F + co0 + 4 * lk;
+  for (int tile = 0; tile < ntiles; ++tile) {
+    const long b = s3::gather(rows, off, tile);
+    const int o = q8::stem_requant(__builtin_amdgcn_mfma_i32_16x16x32_i8(wa, b, z, 0, 0, 0), cst, m);
+    const int px = 16 * tile + lp;
+    if (ox0 + px < a.Wo) *reinterpret_cast<int*>(qrow + (size_t)px * a.F) = o;
+  }
+}
 
 }  // namespace
 
-extern "C" int fdet_stem3_fwd_q8_ok(int N, int Cin, int F, int H, int W) { return s3_out_bytes(N, Cin, F, H, W) > 0 ? 1 : 0; }
+extern "C" int fdet_stem3_fwd_q8_ok(int N, int Cin, int F, int H, int W) { return s3_out_bytes(N, Cin, F, H, W, 64) > 0 ? 1 : 0; }
 
 extern "C" int fdet_stem3_fwd_q8_u8(const unsigned char* frames, const int8_t* w_q, const int32_t* b_q, const float* mul, int8_t* q,
                                     int N, int Cin, int F, int H, int W, void* stream) {
   FDET_REQUIRE(frames && w_q && b_q && mul && q, "stem3_fwd_q8: null argument");
-  FDET_REQUIRE(s3_out_bytes(N, Cin, F, H, W) > 0,
+  FDET_REQUIRE(s3_out_bytes(N, Cin, F, H, W, 64) > 0,
                "stem3_fwd_q8: unsupported shape N=%d Cin=%d F=%d %dx%d (3 channels, F %% 64 == 0, F <= %d, even H and W in 2..%d, "
-               "output under 2^31 bytes)", N, Cin, F, H, W, S3_MAX_F, S3_MAX_HW);
-  FDET_REQUIRE(s3_aligned16(w_q) && s3_aligned16(b_q) && s3_aligned16(mul) && s3_aligned16(q),
+               "output under 2^31 bytes)", N, Cin, F, H, W, q8::MAX_C, q8::MAX_HW);
+  FDET_REQUIRE(q8::aligned16(w_q) && q8::aligned16(b_q) && q8::aligned16(mul) && q8::aligned16(q),
                "stem3_fwd_q8: w_q, b_q, mul and q must be 16-byte aligned");
   return s3::launch(k_stem3_q8, F / 64, frames, w_q, b_q, mul, q, N, F, H, W, (hipStream_t)stream, "fdet_stem3_fwd_q8_u8");
+}
+
+extern "C" int fdet_stem3_fwd_q8x_ok(int N, int Cin, int F, int H, int W) { return s3_out_bytes(N, Cin, F, H, W, 16) > 0 ? 1 : 0; }
+
+extern "C" int fdet_stem3_fwd_q8x_u8(const unsigned char* frames, const int8_t* w_q, const int32_t* b_q, const float* mul, int8_t* q,
+                                     int N, int Cin, int F, int H, int W, void* stream) {
+  FDET_REQUIRE(frames && w_q && b_q && mul && q, "stem3_fwd_q8x: null argument");
+  FDET_REQUIRE(s3_out_bytes(N, Cin, F, H, W, 16) > 0,
+               "stem3_fwd_q8x: unsupported shape N=%d Cin=%d F=%d %dx%d (3 channels, F %% 16 == 0, F <= %d, even H and W in 2..%d, "
+               "output under 2^31 bytes)", N, Cin, F, H, W, q8::MAX_C, q8::MAX_HW);
+  FDET_REQUIRE(q8::aligned16(w_q) && q8::aligned16(b_q) && q8::aligned16(mul) && q8::aligned16(q),
+               "stem3_fwd_q8x: w_q, b_q, mul and q must be 16-byte aligned");
+  if ((F & 63) == 0) return fdet_stem3_fwd_q8_u8(frames, w_q, b_q, mul, q, N, Cin, F, H, W, stream);   // the same contract
+  return s3::launch(k_stem3_q8x, F / 16, frames, w_q, b_q, mul, q, N, F, H, W, (hipStream_t)stream, "fdet_stem3_fwd_q8x_u8");
 }
 
 namespace {
@@ -152,8 +281,6 @@ constexpr int S10_SEG = 64;                           // output columns per work
 constexpr int S10_IN_ROWS = 8 * S10_ROWS + 2;         // input rows under S10_ROWS output rows
 constexpr int S10_RS = 576;                           // LDS row pitch: >= 8 * S10_SEG + 8 and = 64 (mod 128)
 constexpr int S10_LDS = 3 * S10_IN_ROWS * S10_RS;     // 58,752 bytes
-constexpr int S10_MAX_HW = 4096;
-constexpr int S10_MAX_F = 256;
 constexpr long long S10_MAX_ITEMS = 1ll << 20;
 static_assert(S10_RS >= 8 * S10_SEG + 8 && S10_RS % 128 == 64 && ((S10_IN_ROWS - 8) / 2) % 2 == 1, "stem10 LDS pitch");
 
@@ -171,13 +298,11 @@ struct Stem10Args {
 };
 
 __host__ __device__ inline bool s10_shape_ok(int Cin, int F, int H, int W) {
-  return Cin == 3 && F >= 64 && F <= S10_MAX_F && (F & 63) == 0 && H >= 6 && W >= 6 && H <= S10_MAX_HW && W <= S10_MAX_HW;
+  return Cin == 3 && q8::act_shape_ok(F, H, W, 64) && H >= 6 && W >= 6;
 }
 
 inline size_t s10_out_bytes(int N, int Cin, int F, int H, int W) {
-  if (N < 1 || !s10_shape_ok(Cin, F, H, W)) return 0;
-  const unsigned long long b = (unsigned long long)N * ((H - 6) / 8 + 3) * ((W - 6) / 8 + 3) * F;
-  return b < (1ull << 31) ? (size_t)b : 0;
+  return s10_shape_ok(Cin, F, H, W) ? q8::act_bytes(N, F, (H - 6) / 8 + 1, (W - 6) / 8 + 1, 64) : 0;
 }
 
 // Workgroup = 4 waves on (image, group of 4 output rows, segment of 64 output columns) and the 64 output channels
@@ -202,12 +327,12 @@ __global__ __launch_bounds__(256) void k_stem10_q8(const Stem10Args a) {
   const int kperm = ((lk & 1) << 1) | (lk >> 1);            // {0, 2, 1, 3}[lk]
   // A: step s, tile t, row lp -> channel co0 + 16 (lp >> 2) + 4 t + (lp & 3), its K row 4 s + kperm (issued first: these 32
   // loads are in flight while the rows are staged)
-  s3_v4i wa[8][4];
+  v4i wa[8][4];
 #pragma unroll
   for (int s = 0; s < 8; ++s)
 #pragma unroll
     for (int t = 0; t < 4; ++t)
-      wa[s][t] = *reinterpret_cast<const s3_v4i*>(a.w + (size_t)(co0 + 16 * (lp >> 2) + 4 * t + (lp & 3)) * 512 + (4 * s + kperm) * 16);
+      wa[s][t] = *reinterpret_cast<const v4i*>(a.w + (size_t)(co0 + 16 * (lp >> 2) + 4 * t + (lp & 3)) * 512 + (4 * s + kperm) * 16);
   const int c0 = 8 * ox0 - 4;                               // dword path: staged dword d is image columns c0 + 4 d + 2 .. + 5
   const int y0 = 8 * oy0 - 2;
   if (a.align == 16) {
@@ -217,7 +342,7 @@ __global__ __launch_bounds__(256) void k_stem10_q8(const Stem10Args a) {
     const int nc = 8 * ntiles + 1;                          // 16-byte chunks of a staged row (bytes 0 .. 128 ntiles + 15 <= S10_RS)
     const int total = 3 * nr * nc;
     for (int u0 = threadIdx.x; u0 < total; u0 += 1024) {
-      s3_v4i dv[4];
+      v4i dv[4];
       unsigned pv[4];
       int dst[4];
       bool okd[4], okp[4];
@@ -231,7 +356,7 @@ __global__ __launch_bounds__(256) void k_stem10_q8(const Stem10Args a) {
         const unsigned char* src = a.frames + ((size_t)(n * 3 + ci) * a.H + min(max(y, 0), a.H - 1)) * a.W;
         okd[i] = row && c < a.W;
         okp[i] = row && c >= 4 && c - 4 < a.W;
-        dv[i] = *reinterpret_cast<const s3_v4i*>(src + min(c, a.W - 16));
+        dv[i] = *reinterpret_cast<const v4i*>(src + min(c, a.W - 16));
         pv[i] = *reinterpret_cast<const unsigned*>(src + min(max(c - 4, 0), a.W - 4));
         dst[i] = (ci * S10_IN_ROWS + iy) * S10_RS + 16 * k;
       }
@@ -241,9 +366,9 @@ __global__ __launch_bounds__(256) void k_stem10_q8(const Stem10Args a) {
         const unsigned p = okp[i] ? pv[i] : 0u;
         const unsigned d0 = okd[i] ? (unsigned)dv[i][0] : 0u, d1 = okd[i] ? (unsigned)dv[i][1] : 0u;
         const unsigned d2 = okd[i] ? (unsigned)dv[i][2] : 0u, d3 = okd[i] ? (unsigned)dv[i][3] : 0u;
-        const s3_v4i o = {(int)(((p >> 16) | (d0 << 16)) ^ 0x80808080u), (int)(((d0 >> 16) | (d1 << 16)) ^ 0x80808080u),
+        const v4i o = {(int)(((p >> 16) | (d0 << 16)) ^ 0x80808080u), (int)(((d0 >> 16) | (d1 << 16)) ^ 0x80808080u),
                           (int)(((d1 >> 16) | (d2 << 16)) ^ 0x80808080u), (int)(((d2 >> 16) | (d3 << 16)) ^ 0x80808080u)};
-        *reinterpret_cast<s3_v4i*>(rows + dst[i]) = o;
+        *reinterpret_cast<v4i*>(rows + dst[i]) = o;
       }
     }
   } else {
@@ -268,24 +393,17 @@ __global__ __launch_bounds__(256) void k_stem10_q8(const Stem10Args a) {
       *reinterpret_cast<unsigned*>(rows + (ci * S10_IN_ROWS + iy) * S10_RS + 4 * d) = v ^ 0x80808080u;   // x - 128 as a signed byte
     }
   }
-  // the lane's 16 output channels co0 + 16 lk .. + 15: multiplier and the constant bias + 128 * sum of the channel's weights
-  // (the MFMAs against a B of ones are that sum, in the accumulators' own layout; wrapping adds as in k_stem3_q8)
+  // the lane's 16 output channels co0 + 16 lk .. + 15: q8::stem_offset, the weight sums from the MFMAs against a B of ones
   float m[4][4];
   unsigned cst[4][4];
 #pragma unroll
   for (int t = 0; t < 4; ++t) {
     const int co = co0 + 16 * lk + 4 * t;
-    const s3_v4f mv = *reinterpret_cast<const s3_v4f*>(a.mul + co);
-    const s3_v4i bv = *reinterpret_cast<const s3_v4i*>(a.bias + co);
-    const s3_v4i ones = {0x01010101, 0x01010101, 0x01010101, 0x01010101};
-    s3_v4i ws = {0, 0, 0, 0};
+    const v4i ones = {0x01010101, 0x01010101, 0x01010101, 0x01010101};
+    v4i ws = {0, 0, 0, 0};
 #pragma unroll
     for (int s = 0; s < 8; ++s) ws = __builtin_amdgcn_mfma_i32_16x16x64_i8(wa[s][t], ones, ws, 0, 0, 0);
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      m[t][r] = mv[r];
-      cst[t][r] = (unsigned)bv[r] + 128u * (unsigned)ws[r];
-    }
+    q8::stem_offset(cst[t], m[t], a.bias + co, a.mul + co, ws);
   }
   // B: step s -> LDS row (ci, 8 j + ky) of K row min(4 s + kperm, 29) (rows 30 and 31 have zero weights), bytes 8 lp .. + 15
   int off[8];
@@ -300,29 +418,24 @@ __global__ __launch_bounds__(256) void k_stem10_q8(const Stem10Args a) {
   if (oy >= a.Ho) return;                                   // (after the only barrier)
   signed char* qrow = a.q + ((size_t)(n * (a.Ho + 2) + oy + 1) * (a.Wo + 2) + ox0 + 1) * a.F + co0 + 16 * lk;
   for (int tile = 0; tile < ntiles; ++tile) {
-    s3_v4i acc[4];
+    v4i acc[4];
 #pragma unroll
-    for (int t = 0; t < 4; ++t) acc[t] = s3_v4i{0, 0, 0, 0};
+    for (int t = 0; t < 4; ++t) acc[t] = v4i{0, 0, 0, 0};
 #pragma unroll
     for (int s = 0; s < 8; ++s) {
       const long b0 = *reinterpret_cast<const long*>(rows + off[s] + 128 * tile);
       const long b1 = *reinterpret_cast<const long*>(rows + off[s] + 128 * tile + 8);
-      const s3_v4i b = {(int)b0, (int)(b0 >> 32), (int)b1, (int)(b1 >> 32)};
+      const v4i b = {(int)b0, (int)(b0 >> 32), (int)b1, (int)(b1 >> 32)};
 #pragma unroll
       for (int t = 0; t < 4; ++t) acc[t] = __builtin_amdgcn_mfma_i32_16x16x64_i8(wa[s][t], b, acc[t], 0, 0, 0);
     }
     int o[4];
 #pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      int qv[4];
-#pragma unroll
-      for (int r = 0; r < 4; ++r) qv[r] = s3_round((float)(int)((unsigned)acc[t][r] + cst[t][r]) * m[t][r]);
-      o[t] = s3_pack4(qv[0], qv[1], qv[2], qv[3]);
-    }
+    for (int t = 0; t < 4; ++t) o[t] = q8::stem_requant(acc[t], cst[t], m[t]);
     const int px = 16 * tile + lp;
     if (ox0 + px < a.Wo) {
-      const s3_v4i ov = {o[0], o[1], o[2], o[3]};
-      *reinterpret_cast<s3_v4i*>(qrow + (size_t)px * a.F) = ov;
+      const v4i ov = {o[0], o[1], o[2], o[3]};
+      *reinterpret_cast<v4i*>(qrow + (size_t)px * a.F) = ov;
     }
   }
 }
@@ -336,8 +449,8 @@ extern "C" int fdet_stem10_fwd_q8_u8(const unsigned char* frames, const int8_t* 
   FDET_REQUIRE(frames && w_q && b_q && mul && q, "stem10_fwd_q8: null argument");
   FDET_REQUIRE(s10_out_bytes(N, Cin, F, H, W) > 0,
                "stem10_fwd_q8: unsupported shape N=%d Cin=%d F=%d %dx%d (3 channels, F %% 64 == 0, F <= %d, H and W in 6..%d, "
-               "output under 2^31 bytes)", N, Cin, F, H, W, S10_MAX_F, S10_MAX_HW);
-  FDET_REQUIRE(s3_aligned16(w_q) && s3_aligned16(b_q) && s3_aligned16(mul) && s3_aligned16(q),
+               "output under 2^31 bytes)", N, Cin, F, H, W, q8::MAX_C, q8::MAX_HW);
+  FDET_REQUIRE(q8::aligned16(w_q) && q8::aligned16(b_q) && q8::aligned16(mul) && q8::aligned16(q),
                "stem10_fwd_q8: w_q, b_q, mul and q must be 16-byte aligned");
   const int Ho = (H - 6) / 8 + 1, Wo = (W - 6) / 8 + 1;
   const int segs = (Wo + S10_SEG - 1) / S10_SEG, row_groups = (Ho + S10_ROWS - 1) / S10_ROWS;

@@ -10,6 +10,7 @@
 // Weights live in registers for the whole kernel (30 rows x (hi,lo) x 4 VGPRs = 240 per lane).
 #include "fdet_common.h"
 #include "fdet_ps.h"
+#include "fdet_q8_common.h"
 #include <algorithm>
 #include <cstdlib>
 #include <utility>
@@ -195,11 +196,6 @@ __device__ __forceinline__ unsigned sx_hi_pair(float f0, float f1) {
   return __builtin_bit_cast(unsigned, h);
 }
 
-// fdet_q8_quantize's rounding of one product: clamp(rintf(t), -127, 127), a NaN product -> 0
-__device__ __forceinline__ int sx_q8_round(float t) {
-  return t == t ? (int)fminf(fmaxf(rintf(t), -127.0f), 127.0f) : 0;
-}
-
 // P16 (precision16, PS output only): one MFMA pass on bf16(x) x bf16(w); the lo halves are neither computed nor staged and
 // only the hi plane of the output is written.
 // U8 (inference, PS output only): the input is the uint8 frame itself -- `x / 255` (models/PoolResnet.py:95) happens in the
@@ -362,8 +358,8 @@ k_stem_fwd_x3_pipe(const StemX3Args a) {
         _Pragma("unroll") for (int i = 0; i < 4; ++i) {                                         \
           const float ta = (acc[8 * gp + i] + sbias[m * 32 + 16 * gp + 4 * half + i]) * a.q_inv; \
           const float tb = (acc[8 * gp + 4 + i] + sbias[m * 32 + 16 * gp + 8 + 4 * half + i]) * a.q_inv; \
-          da |= (unsigned)(sx_q8_round(ta) & 255) << (8 * i);                                   \
-          db |= (unsigned)(sx_q8_round(tb) & 255) << (8 * i);                                   \
+          da |= (unsigned)(q8::round_q_nan0(ta) & 255) << (8 * i);                              \
+          db |= (unsigned)(q8::round_q_nan0(tb) & 255) << (8 * i);                              \
         }                                                                                       \
         auto r1 = __builtin_amdgcn_permlane32_swap(da, db, false, false);                       \
         const int G = 4 * m + 2 * gp + half;                                                    \

@@ -1946,7 +1946,8 @@ def q8_sepchain(x: Q8Tensor, weights: Q8SepChainWeights, outs: Optional[Sequence
 
 
 # ------------------------------------------------------------------------------------------
-# int8 inference, mixed widths: the SSD detector (csrc/fdet_q8_ssd.hip; include/fdet.h "Int8 inference: mixed widths")
+# int8 inference, mixed widths: the SSD detector (csrc/fdet_q8.hip, csrc/fdet_stem_q8.hip; include/fdet.h "Int8 inference:
+# mixed widths")
 # ------------------------------------------------------------------------------------------
 def q8x_supported(C: int, H: int, W: int) -> bool:
     """Q8 tensors of this shape exist for the q8x entries: C a multiple of 16 up to 256, 1 <= H, W <= 4096."""

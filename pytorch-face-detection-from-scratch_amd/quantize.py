@@ -24,8 +24,9 @@ SeparableCNN enters through that integer stem and runs every separab
 
     m8 = Int8SSD(model, calibrate_ssd(model, frames_iter))                  # (an SSD(filters=16); SSD.quantize does both)
 
-SSD has its own scales (SSDQuantParams), calibration (calibrate_ssd) and kernels (csrc/fdet_q8_ssd.hip: the
-Cin -> Cout conv with a floor pool, the 1x1 skip conv, the Linear(C,5) head, the 16-filter stem); tests/q8_ssd_cpu_ref.py
+SSD has its own scales (SSDQuantParams), calibration (calibrate_ssd) and entries (csrc/fdet_q8.hip: the
+Cin -> Cout conv with a floor pool, the 1x1 skip conv, the Linear(C,5) head; csrc/fdet_stem_q8.hip: the 16-filter stem);
+tests/q8_ssd_cpu_ref.py
 restates them.  `calibrate`, `QuantParams` and `quantize_model` are what they were and refuse an SSD.
 """
 from __future__ import annotations

@@ -1,4 +1,4 @@
-"""GPU checks of the int8 SSD (csrc/fdet_q8_ssd.hip, quantize.Int8SSD) against the numpy restatement
+"""GPU checks of the int8 SSD (csrc/fdet_q8.hip and csrc/fdet_stem_q8.hip, quantize.Int8SSD) against the numpy restatement
 tests/q8_ssd_cpu_ref.py.  The arithmetic is integer with one-rounding float steps, so every comparison of int8 tensors and of
 the heads' fp32 z is equality."""
 import os
@@ -192,6 +192,37 @@ def test_conv_equals_the_existing_kernel_where_both_run(C):
         torch.cuda.synchronize()
         assert torch.equal(ya.storage, yb.storage)
         assert np.array_equal(yb.nchw().cpu().numpy(), SC.conv3x3(x, w, b, mul, sk, sm, pool))
+
+
+@pytest.mark.parametrize("H,W,skip,pool", [(5, 18, False, False), (5, 18, True, False), (6, 18, True, True)],
+                         ids=["5x18-plain", "5x18-skip", "6x18-pooled-skip"])
+def test_three_chunk_conv_through_both_entries(H, W, skip, pool):
+    """C = 192 is three 64-channel chunks, the only width at which the chunk walk runs an odd count above one.  18 columns
+    cross the 16-column tile, 5 and 6 rows the 4-row group.  Both entries, from the same packed weights, write the same bytes,
+    and these are the restatement's."""
+    hp = _hp()
+    C, N = 192, 2
+    x, w, b, mul, sk, sm = _case(192, N, C, C, H, W, skip, pool)
+    want = SC.conv3x3(x, w, b, mul, sk, sm, pool)
+    sat = float(np.mean(np.abs(want.astype(np.int32)) == 127))
+    assert 0.002 <= sat <= 0.6, sat
+    wpk = hp.q8_pack_weights(_dev(w))
+    assert torch.equal(wpk, hp.q8x_pack_weights(_dev(w)))
+    shape = (N, C, H // 2, W // 2) if pool else (N, C, H, W)
+    ya, yb = hp.Q8Tensor(*shape, "cuda"), hp.Q8XTensor(*shape, "cuda")
+    xq = hp.Q8Tensor(N, C, H, W, "cuda")
+    _view(xq)[:, 1:-1, 1:-1, :] = _dev(x.transpose(0, 2, 3, 1))
+    sq = None
+    if skip:
+        sq = hp.Q8Tensor(N, C, H, W, "cuda")
+        _view(sq)[:, 1:-1, 1:-1, :] = _dev(sk.transpose(0, 2, 3, 1))
+    hp.q8_conv3x3(xq, wpk, _dev(b), _dev(mul), ya, skip=sq, skip_mul=float(sm) if skip else 0.0, pool=pool)
+    hp.q8x_conv3x3(xq, wpk, _dev(b), _dev(mul), yb, skip=sq, skip_mul=float(sm) if skip else 0.0, pool=pool)
+    torch.cuda.synchronize()
+    assert torch.equal(ya.storage, yb.storage)
+    for y in (ya, yb):
+        got = y.nchw().cpu().numpy()
+        assert got.shape == want.shape and np.array_equal(got, want), f"{int((got != want).sum())} of {want.size} differ"
 
 
 # ------------------------------------------------------------------------------------------------------- skip conv, head

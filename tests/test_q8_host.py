@@ -208,6 +208,7 @@ def test_size_helpers_and_argument_rejection_need_no_gpu():
     assert L.fdet_q8_supported(64, 61, 17) == 1
     assert L.fdet_q8_act_bytes(256, 64, 60, 60) == 256 * 62 * 62 * 64
     assert L.fdet_q8_act_bytes(1, 128, 1, 3) == 3 * 5 * 128
+    assert L.fdet_q8_act_bytes(1, 192, 5, 18) == L.fdet_q8x_act_bytes(1, 192, 5, 18) == 7 * 20 * 192    # one layout function
     assert L.fdet_q8_act_bytes(2, 60, 15, 15) == 0 and L.fdet_q8_act_bytes(0, 64, 15, 15) == 0
     assert L.fdet_q8_act_bytes(4096, 256, 60, 60) == 0                       # 2^31 bytes and more
     buf = ctypes.create_string_buffer(64)                                    # a host address: only ever compared with NULL
