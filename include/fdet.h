@@ -132,7 +132,8 @@ int fdet_ssd_encode_targets(const float* boxes, const int32_t* box_offsets, int 
  * (losses/SSDLoss.py:25-86, models/ModelMetaSSD.py:127-129): per-image hard negative mining
  * (rank of -log(conf) among the negatives, ties by index), BCE over positives + mined negatives
  * with rounded labels, smooth-L1 over positives, divided by the batch's positive count.
- *   pred/target [B,P,5]; loss [1]; grad [B,P,5] or NULL; mask [B,P] (1 = contributes) or NULL. */
+ *   pred/target [B,P,5]; loss [1]; grad [B,P,5] or NULL; mask [B,P] (1 = contributes) or NULL.
+ * A batch without a positive prior: loss = 0/0 = NaN as the reference, grad all zero as its autograd (nothing is selected). */
 size_t fdet_ssd_loss_ws_bytes(int B);
 int fdet_ssd_loss_fwd_bwd(const float* pred, const float* target, int B, int P, int neg_pos_ratio, float* loss,
                           float* grad, uint8_t* mask, void* ws, size_t ws_bytes, void* stream);

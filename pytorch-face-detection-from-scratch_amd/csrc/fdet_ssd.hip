@@ -161,7 +161,9 @@ k_ssd_loss_total(const double* __restrict__ part, int B, float* __restrict__ los
     double bce = 0.0, sl1 = 0.0, np = 0.0;
     for (int n = 0; n < B; ++n) { bce += part[n * 3]; sl1 += part[n * 3 + 1]; np += part[n * 3 + 2]; }
     loss[0] = (float)((sl1 + bce) / np);                             // :86 (0/0 = NaN as in the reference)
-    inv_npos[0] = (float)(1.0 / np);
+    // no positive in the batch: nothing was selected, every unscaled gradient is 0 and autograd leaves it 0
+    // (the 1/0 of :86 never reaches an unselected element), so the scale must not turn 0 into 0 * inf = NaN
+    inv_npos[0] = np > 0.0 ? (float)(1.0 / np) : 0.f;
   }
 }
 
@@ -178,7 +180,7 @@ __global__ void __launch_bounds__(64)
 k_ssd_loss_finish(const double* __restrict__ sums, float* __restrict__ loss, float* __restrict__ inv_npos) {
   if (threadIdx.x == 0) {
     loss[0] = (float)((sums[1] + sums[0]) / sums[2]);                  // :86 with the batch-wide sums
-    inv_npos[0] = (float)(1.0 / sums[2]);
+    inv_npos[0] = sums[2] > 0.0 ? (float)(1.0 / sums[2]) : 0.f;         // as k_ssd_loss_total: zero gradients stay zero
   }
 }
 
