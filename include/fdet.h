@@ -859,6 +859,47 @@ int fdet_render_boxes(const uint8_t* src, const fdet_aug_image* src_table, const
                       const fdet_aug_image* dst_table, const fdet_aug_image* h_dst_table, int outline, int pixelate,
                       int blocks, int red, int green, int blue, int32_t* ws, void* stream);
 
+/* fdet_render_boxes plus Gaussian blur as PIL computes it: steps 1, 2 and 4 above unchanged, and
+ *   3b. blur = 1.  PIL's ImageFilter.GaussianBlur is three box-blur passes along the rows and three along the columns
+ *      (BoxBlur.c), each in 32-bit integer fixed point with a uint8 rounding of its own; the only float arithmetic is
+ *      the derivation of three integers (r, ww, fw) per radius, done once on the host (render.blur_table).
+ *      1. the pixel rectangle [x0,x1] x [y0,y1] and the skip rule are step 2's.  S = max(x1-x0+1, y1-y0+1) on the
+ *         unclipped rectangle; the region R is the rectangle clipped to the image; an empty R does nothing
+ *      2. the box's parameters are entry min(S, n_tab-1) of blur_tab [n_tab][3] int32 (r, ww, fw) on the device;
+ *         h_blur_tab, the same values in host memory, is validated in 64 bits: r >= 0, ww >= 0, fw >= 0 and
+ *         (2r+1)*ww + 2*fw <= 2^24.  With that bound 255 * weights + 2^23 < 2^32: the device arithmetic is plain
+ *         unsigned 32-bit and nothing wraps.  The device does no float arithmetic for the blur.
+ *      3. one pass along a line v[0..n-1] of one channel:
+ *           out[i] = (ww * sum_{d=-r..r} v[c(i+d)] + fw * (v[c(i-r-1)] + v[c(i+r+1)]) + 2^23) >> 24,
+ *         c(j) = clamp(j, 0, n-1): the edges of R are replicated and nothing outside R is read
+ *      4. B = R's pixels of the SOURCE image taken through three passes along the rows of R, then three along its
+ *         columns, each pass starting from the previous pass's uint8 output
+ *      5. a pixel of R takes B's value unless a box of lower row index covers it (step 3's rule: the lowest index
+ *         wins).  Every box reads the source, so no order of execution changes a byte
+ *      6. the outline (step 4) comes after the blur
+ *   For one box this is im.paste(im.crop((cx0, cy0, cx1+1, cy1+1)).filter(GaussianBlur(radius)), (cx0, cy0)) on the
+ *   clipped box when the table holds PIL's parameters for that radius; for several, pasted in descending row index,
+ *   each crop taken from the original image.
+ * With blur = 0 dst holds fdet_render_boxes's bytes; blur_tab, h_blur_tab and rejected may then be NULL and ws needs
+ * (n_images+1) int32.  With blur = 1: ws [ws_bytes] is device scratch of fdet_render_blur_ws_bytes(...) bytes for the
+ * same h_src_table, h_counts and a host copy h_rows of rows ((n_images+1) int32, one int64 per box of h_counts, then
+ * 3 bytes per pixel of every box's R; 0 for bad arguments).  Every offset into ws is computed on the device and
+ * checked against ws_bytes: a box whose share does not fit (or whose R has a side above FDET_BLUR_MAX_LINE) is left
+ * as the copy and counted in rejected[0] (uint64, device, += the number of such boxes), which the caller must read as
+ * an error; nothing is written out of bounds.  The library allocates nothing.
+ * Validated on the host, FDET_EINVAL and nothing written: everything fdet_render_boxes validates; blur not 0 | 1;
+ * blur = 1 with pixelate = 1; with blur = 1 a NULL table or rejected, n_tab < 1, a table entry outside the bound of
+ * 3b.2, an image with h or w above FDET_BLUR_MAX_LINE, ws_bytes below the (n_images+1) int32 + one int64 per box. */
+#define FDET_BLUR_MAX_LINE 8192
+size_t fdet_render_blur_ws_bytes(const fdet_aug_image* h_src_table, const float* h_rows, const int32_t* h_counts,
+                                 int n_images, int K);
+int fdet_render_boxes_blur(const uint8_t* src, const fdet_aug_image* src_table, const fdet_aug_image* h_src_table,
+                           const float* rows, const int32_t* counts, const int32_t* h_counts, int n_images, int K,
+                           uint8_t* dst, const fdet_aug_image* dst_table, const fdet_aug_image* h_dst_table, int outline,
+                           int pixelate, int blur, int blocks, const int32_t* blur_tab, const int32_t* h_blur_tab,
+                           int n_tab, int red, int green, int blue, void* ws, size_t ws_bytes, uint64_t* rejected,
+                           void* stream);
+
 /* ---- tracking faces across frame sequences (csrc/fdet_track.hip) --------------------------
  * Associates the detections of consecutive frames with a table of FDET_TRACK_SLOTS tracks per sequence: identity
  * (an id per track, never reused) and gap bridging (a track the detector misses is still emitted for emit_misses

@@ -174,6 +174,8 @@ SIGNATURES = {
     "fdet_tile_gather_flags": (_I, [_P, _P, _P, _I, _P, _P, _P, _P, _I, _I, _I, _P, _P]),
     "fdet_tile_merge_vote": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _F, _D, _I, _I, _I, _P, _P, _P, _P, _P]),
     "fdet_render_boxes": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P]),
+    "fdet_render_blur_ws_bytes": (_SZ, [_P, _P, _P, _I, _I]),
+    "fdet_render_boxes_blur": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _I, _I, _I, _I, _P, _P, _I, _I, _I, _I, _P, _SZ, _P, _P]),
     "fdet_track_state_bytes": (_SZ, [_I]),
     "fdet_track_update": (_I, [_P, _P, _P, _P, _I, _I, _I, _D, _I, _I, _I, _I, _F, _P, _P, _P, _P, _P, _P, _P, _P]),
     "fdet_chip_extract": (_I, [_P, _P, _P, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P]),

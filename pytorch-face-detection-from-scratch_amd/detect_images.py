@@ -2,7 +2,7 @@
 
     python -m fdet_amd.detect_images --checkpoint CKPT --images DIR --out FILE [--model poolresnet --filters 128]
         [--tile 480 --overlap 0.25 --no-whole --edge-margin 0 --probability-threshold P --iou-threshold T --precision 16]
-        [--flip --vote --min-votes N] [--draw DIR [--anonymize pixelate] [--blocks N] [--draw-format png|jpg] [--no-outline]]
+        [--flip --vote --min-votes N] [--draw DIR [--anonymize pixelate|blur] [--blocks N] [--blur-radius R] [--draw-format png|jpg] [--no-outline]]
         [--chips DIR [--chip-size N] [--chip-margin F] [--chip-format png|jpg]] [--device-jpeg-encode] [--jpeg-quality Q]
         [--int8 [--calib DIR] [--calib-images N] [--int8-stem {float,integer}]]
 
@@ -118,8 +118,10 @@ def add_tile_arguments(ap) -> None:
 def add_draw_arguments(ap) -> None:
     """--draw and the options that need it (shared with track_frames); `check_draw_arguments` checks them."""
     ap.add_argument("--draw", default=None, metavar="DIR", help="also write every image, rendered, under DIR")
-    ap.add_argument("--anonymize", choices=("pixelate",), default=None, help="with --draw: pixelate every box")
-    ap.add_argument("--blocks", type=int, default=None, help="with --draw --anonymize: cells along the longer side of a box (8)")
+    ap.add_argument("--anonymize", choices=("pixelate", "blur"), default=None, help="with --draw: pixelate or Gaussian-blur every box")
+    ap.add_argument("--blocks", type=int, default=None,
+                    help="with --draw --anonymize: cells along the longer side of a box; blur: radius = longer side / N (8)")
+    ap.add_argument("--blur-radius", type=float, default=None, help="with --anonymize blur: one fixed radius for every box")
     ap.add_argument("--draw-format", choices=("png", "jpg"), default=None, help="with --draw: the files' format (png)")
     ap.add_argument("--no-outline", action="store_true", help="with --draw: no outlines")
 
@@ -132,6 +134,11 @@ def check_draw_arguments(ap, args) -> None:
                 ap.error(f"{flag} needs --draw")
     if args.blocks is not None and args.blocks < 1:
         ap.error("--blocks must be >= 1")
+    if args.blur_radius is not None:
+        if args.anonymize != "blur":
+            ap.error("--blur-radius needs --anonymize blur")
+        if not 0 <= args.blur_radius <= 4096:
+            ap.error("--blur-radius must be in 0..4096")
 
 
 def add_chip_arguments(ap, flag, what) -> None:
@@ -246,11 +253,11 @@ def run(args):
     """What `main` does with its parsed options."""
     from .datasets.WIDERFace.annotations import bank_from_files
     from .tiling import TiledDetector
-    model = load_model(args)
     root = Path(args.images)
     paths = image_paths(root)
-    if not paths:
+    if not paths:                                   # before the model is built: nothing to detect in needs no GPU to say so
         raise SystemExit(f"no image under {root}")
+    model = load_model(args)
     huffman = "device" if getattr(args, "device_jpeg_huffman", False) else "host"
     if getattr(args, "int8", False):
         decoder = "device" if args.device_jpeg else "pil"
@@ -266,7 +273,7 @@ def run(args):
         if args.draw is not None:
             from .render import render_detections, save_images
             drawn = render_detections(bank, rows, counts, outline=not args.no_outline, anonymize=args.anonymize,
-                                      blocks=8 if args.blocks is None else args.blocks)
+                                      blocks=8 if args.blocks is None else args.blocks, blur_radius=args.blur_radius)
             save_images(drawn, [(Path(args.draw) / os.path.relpath(p, root)).with_suffix("." + (args.draw_format or "png"))
                                 for p in chunk], **jpeg_encode_options(args))
         if getattr(args, "chips_dir", None) is not None:

@@ -333,6 +333,44 @@ def tile_merge(rows: torch.Tensor, counts: torch.Tensor, d_tiles: torch.Tensor, 
     return out, out_counts, rejected
 
 
+def render_blur_ws_bytes(h_table, h_rows, h_counts) -> int:
+    """fdet_render_blur_ws_bytes: the workspace `render_boxes_blur` needs for these host copies of the image table, the
+    rows (n,K,5) fp32 and the counts (n,) int32."""
+    n, K = int(h_rows.shape[0]), int(h_rows.shape[1])
+    size = int(lib().fdet_render_blur_ws_bytes(h_table.ctypes.data, h_rows.ctypes.data if K else None, h_counts.ctypes.data, n, K))
+    if size == 0:
+        raise ValueError("render_blur_ws_bytes: bad arguments (a count outside 0..K)")
+    return size
+
+
+def render_boxes_blur(src, rows: torch.Tensor, counts: torch.Tensor, h_counts, out, d_tab: torch.Tensor, h_tab, outline: bool = False,
+                      blocks: int = 8, color=(0, 0, 255), blur: bool = True, pixelate: bool = False, ws: Optional[torch.Tensor] = None,
+                      rejected: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """fdet_render_boxes_blur: the images of the bank `src` into the bank `out` (same sizes, its own buffer) with the first
+    counts[i] boxes of rows[i] blurred by the table d_tab / h_tab ((n_tab,3) int32 (r, ww, fw), device and host) and
+    outlined.  ws: uint8 device scratch (None: sized here from a host copy of `rows`).  -> rejected (1,) int64 counter,
+    += 1 per box the workspace does not hold; the caller must read it as an error."""
+    import numpy as np
+    n, K = int(rows.shape[0]), int(rows.shape[1])
+    dev = rows.device
+    U8 = torch.uint8
+    if not isinstance(h_tab, np.ndarray) or h_tab.dtype != np.int32 or h_tab.ndim != 2 or h_tab.shape[1] != 3 or not h_tab.flags.c_contiguous:
+        raise ValueError("render_boxes_blur: h_tab must be a contiguous (n_tab,3) numpy int32 array")
+    if tuple(d_tab.shape) != h_tab.shape or d_tab.dtype != I32:
+        raise ValueError("render_boxes_blur: d_tab must be the device copy of h_tab")
+    if ws is None:
+        h_rows = np.ascontiguousarray(rows.cpu().numpy())
+        ws = torch.empty(render_blur_ws_bytes(src.table, h_rows, h_counts), dtype=U8, device=dev)
+    if rejected is None:
+        rejected = torch.zeros(1, dtype=torch.int64, device=dev)
+    check(lib().fdet_render_boxes_blur(ptr(src.data, U8), ptr(src.d_table, U8), src.table.ctypes.data, ptr(rows) if K else None,
+                                       ptr(counts, I32), h_counts.ctypes.data, n, K, ptr(out.data, U8), ptr(out.d_table, U8),
+                                       out.table.ctypes.data, int(bool(outline)), int(bool(pixelate)), int(bool(blur)), int(blocks),
+                                       ptr(d_tab, I32), h_tab.ctypes.data, int(h_tab.shape[0]), int(color[0]), int(color[1]), int(color[2]),
+                                       ptr(ws, U8), int(ws.numel()), ptr(rejected, torch.int64), stream()), "fdet_render_boxes_blur")
+    return rejected
+
+
 def _tile_flags(h_flags, T):
     import numpy as np
     if not isinstance(h_flags, np.ndarray) or h_flags.dtype != np.uint8 or h_flags.shape != (T,) or not h_flags.flags.c_contiguous:

@@ -2,7 +2,7 @@
 
     python -m fdet_amd.track_frames --checkpoint CKPT --frames DIR --out FILE [--model poolresnet --filters 128]
         [--tiled --tile 480 --overlap 0.25] [--iou 0.3 --alpha 0.5 --max-misses 5 --min-hits 2 --emit-misses N]
-        [--draw DIR [--anonymize pixelate] [--blocks N] [--draw-format png|jpg] [--no-outline]]
+        [--draw DIR [--anonymize pixelate|blur] [--blocks N] [--blur-radius R] [--draw-format png|jpg] [--no-outline]]
         [--best-shots DIR [--chip-size N] [--chip-margin F] [--chip-format png|jpg]]
         [--device-jpeg-encode] [--jpeg-quality Q]
 
@@ -120,7 +120,7 @@ def run(args):
             if args.draw is not None:
                 from .render import render_detections, save_images
                 drawn = render_detections(bank, res.rows, res.counts, outline=not args.no_outline, anonymize=args.anonymize,
-                                          blocks=8 if args.blocks is None else args.blocks)
+                                          blocks=8 if args.blocks is None else args.blocks, blur_radius=args.blur_radius)
                 save_images(drawn, [(Path(args.draw) / p.name).with_suffix("." + (args.draw_format or "png")) for p in chunk],
                             **jpeg_encode_options(args))
             if best is not None:

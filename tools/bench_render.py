@@ -12,10 +12,12 @@ process; median / min / max over --repeats:
   pixelate          copy + pixelation
   outline_pixelate  copy + pixelation + outlines
   empty             the entry with every count zero: the copy as the entry issues it
+  blur              copy + Gaussian blur (fdet_render_boxes_blur; radius = longer side / --blocks), into a
+                    preallocated workspace
 
 and beside them the host path on the same boxes: PIL's ImageDraw for the outlines plus a numpy block-mean pixelation, on 16
 threads over host copies of the images (the transfers to and from the device, which the host path would also need, are not
-counted).  `render_detections_ms` is the Python surface end to end (allocation of the new bank, the read of `counts`,
+counted), and for the blur PIL's crop, GaussianBlur and paste per box.  `render_detections_ms` is the Python surface end to end (allocation of the new bank, the read of `counts`,
 the entry), by the host clock around a synchronise.  Prints one JSON line and, with --out, writes it.
 """
 import argparse
@@ -51,6 +53,22 @@ def host_render(img, boxes, blocks, pixelate):
     return np.asarray(im)
 
 
+def host_blur(img, boxes, blocks):
+    """The host baseline of the blur for one image: PIL crop, GaussianBlur, paste per box (later boxes over earlier ones)."""
+    import numpy as np
+    from PIL import Image, ImageFilter
+    im = Image.fromarray(img)
+    out = im.copy()
+    W, H = im.size
+    for _, x, y, w, h in boxes.tolist():
+        x0, y0, x1, y1 = int(x), int(y), int(x + w), int(y + h)
+        box = (max(x0, 0), max(y0, 0), min(x1, W - 1) + 1, min(y1, H - 1) + 1)
+        if box[0] >= box[2] or box[1] >= box[3]:
+            continue
+        out.paste(im.crop(box).filter(ImageFilter.GaussianBlur(max(x1 - x0 + 1, y1 - y0 + 1) / blocks)), box[:2])
+    return np.asarray(out)
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--images", type=int, default=256)
@@ -66,7 +84,8 @@ def main(argv=None):
     from concurrent.futures import ThreadPoolExecutor
     from fdet_amd._native import check, lib, ptr, stream
     from fdet_amd.datasets import augment as A
-    from fdet_amd.render import render_detections
+    from fdet_amd import hotpath
+    from fdet_amd.render import blur_table, render_detections
     if not torch.cuda.is_available():
         raise SystemExit("bench_render needs a GPU")
     bank, boxes = A.synthetic_bank(args.images, "cuda", seed=0, min_side=700, max_side=1024, max_faces=16)
@@ -93,12 +112,20 @@ def main(argv=None):
                                       h_cnt.ctypes.data, n, K, ptr(dst.data, U8), ptr(dst.d_table, U8), dst.table.ctypes.data, outline,
                                       pixelate, args.blocks, 0, 0, 255, ptr(ws, I32), stream()), "fdet_render_boxes")
 
+    d_tab, h_tab = blur_table(args.blocks, None, 2 * int(max(bank.table["h"].max(), bank.table["w"].max())) + 2, "cuda")
+    blur_ws = torch.empty(hotpath.render_blur_ws_bytes(bank.table, rows, counts), dtype=U8, device="cuda")
+    rejected = torch.zeros(1, dtype=torch.int64, device="cuda")
+
+    def blur():
+        hotpath.render_boxes_blur(bank, d_rows, d_counts, counts, dst, d_tab, h_tab, blocks=args.blocks, ws=blur_ws, rejected=rejected)
+
     variants = {
         "copy": lambda: dst.data.copy_(bank.data[first:first + dst.data.numel()]),
         "outline": lambda: entry(1, 0),
         "pixelate": lambda: entry(0, 1),
         "outline_pixelate": lambda: entry(1, 1),
         "empty": lambda: entry(1, 1, d_zeros, zeros),
+        "blur": blur,
     }
     for _ in range(args.warmup):
         for f in variants.values():
@@ -125,7 +152,11 @@ def main(argv=None):
            "device": {k: stats(v) for k, v in ms.items()}}
     med = {k: res["device"][k]["median_ms"] for k in variants}
     res["copy_GBps_read_plus_write"] = round(2 * float(sizes.sum()) / (med["copy"] * 1e-3) / 1e9, 1)
-    res["ratio_to_copy"] = {k: round(med[k] / med["copy"], 3) for k in ("outline", "pixelate", "outline_pixelate", "empty")}
+    res["ratio_to_copy"] = {k: round(med[k] / med["copy"], 3) for k in ("outline", "pixelate", "outline_pixelate", "empty", "blur")}
+    if int(rejected.item()):
+        raise SystemExit("bench_render: the blur rejected boxes")
+    res["blur_ws_MiB"] = round(blur_ws.numel() / 2 ** 20, 1)
+    res["blur_minus_copy_over_pixelate_minus_copy"] = round((med["blur"] - med["copy"]) / max(med["pixelate"] - med["copy"], 1e-6), 1)
     # the Python surface, host clock
     wall = []
     for _ in range(args.repeats):
@@ -136,6 +167,15 @@ def main(argv=None):
         wall.append((time.perf_counter() - t0) * 1e3)
         del out
     res["render_detections_ms"] = stats(wall)
+    wall = []
+    for _ in range(args.repeats):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out = render_detections(bank, d_rows, d_counts, outline=False, anonymize="blur", blocks=args.blocks)
+        torch.cuda.synchronize()
+        wall.append((time.perf_counter() - t0) * 1e3)
+        del out
+    res["render_detections_blur_ms"] = stats(wall)
     # the host path on the same boxes, 16 threads
     imgs = bank.to_arrays()
     host = {}
@@ -148,6 +188,14 @@ def main(argv=None):
             t.append((time.perf_counter() - t0) * 1e3)
         host[name] = stats(t)
         del outs
+    t = []
+    for _ in range(args.repeats):
+        t0 = time.perf_counter()
+        with ThreadPoolExecutor(max_workers=16) as ex:
+            outs = list(ex.map(lambda j: host_blur(imgs[j], boxes[j], args.blocks), range(n)))
+        t.append((time.perf_counter() - t0) * 1e3)
+    host["blur"] = stats(t)
+    del outs
     res["host_16_threads"] = host
     res["host_over_device"] = {k: round(host[k]["median_ms"] / med[k], 1) for k in host}
     line = json.dumps(res)
