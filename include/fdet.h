@@ -244,7 +244,7 @@ int fdet_conv3x3_wgrad_bf16x3(const float* x, const float* dz, float* dW, float*
  * bound one at a time; batched, every workgroup owns bands of a single layer and writes one slab. */
 size_t fdet_conv3x3_wgrad_bf16x3_batched_ws_bytes(int L, int N, int Cin, int Cout, int H, int W);
 /* Plan query of the bf16x3 / precision16 weight gradient of L layers (launches nothing): fills out[0..min(n,8)-1] with
- * ok, pipelined kernel, 32-lane rows (lpr32), float4 quads (pk4), packed narrow rows (pack), vector width, output-channel
+ * ok, pipelined kernel, 32-lane rows (lpr32), float4 quads (pk4), a reserved slot (pack: always 0), vector width, output-channel
  * tiles (MTC) and column segments (NSEG).  ok == 0 exactly when the entry points refuse the shape. */
 int fdet_conv3x3_wgrad_bf16x3_plan(int N, int Cin, int Cout, int H, int W, int L, int* out, int n);
 int fdet_conv3x3_wgrad_bf16x3_batched(const float* const* h_x, const float* const* h_dz, float* const* h_dW,

@@ -50,7 +50,7 @@ struct ChainArgs {
   const float* pre_ld;           // bwd: c of the first block to run
   const float* pre_sc;           // bwd: its dropout scale
   float* pre_st;                 // bwd: its dz2
-  int nlayers, N, H, W, WP, PT, bwd, stagger;
+  int nlayers, N, H, W, WP, PT, bwd;
   // PS I/O (fdet_ps.h): bit 0 = the tensors kept per layer (st / st2 / ld / pre_*) are PS image-0 pointers, except the
   // LAST st2 (chain output / input gradient), which stays fp32 NCHW; bit 1 = the forward input `in` is PS
   int psio, ps_hpwp, ps_wp, ps_plane, ps_img;                   // 16-byte units
@@ -154,9 +154,6 @@ k_block_chain_x3(const ChainArgs a) {
                 wsrc + (unsigned)(C16) * (A_UNITS * 16) + k_ * 1024);                              \
   }
   CH_DMA_W(0, 0, 0)
-  // Workgroups would otherwise run in lockstep and send their tile stores to HBM in the same microsecond, layer after
-  // layer: start them `stagger` x 64 cycles x (0..7) apart so that one workgroup's store burst meets the others' MFMAs.
-  for (int i = ((blockIdx.x >> 3) & 7) * a.stagger; i > 0; --i) __builtin_amdgcn_s_sleep(1);
 
   {  // zero X (halo rows / pad columns stay zero for the whole chain)
     f32x4* z = reinterpret_cast<f32x4*>(smem);
@@ -864,7 +861,6 @@ int launch_chain(ChainArgs& a, hipStream_t st) {
   if (!chain_geometry(FCH, a.H, a.W, a.WP, a.PT, lds))
     return fail(FDET_EINVAL, "block_chain_bf16x3: unsupported map %dx%d (needs 64 channels and H*roundup4(W+1) <= 256)", a.H, a.W);
   if (!chain_batch_ok(a.N, a.H, a.W)) return fail(FDET_EINVAL, "block_chain_bf16x3: tensor too large");
-  { const char* e_ = FDET_ENV_ONCE("FDET_CHAIN_STAGGER"); a.stagger = e_ ? atoi(e_) : 0; }
   if ((a.psio & 1) && (a.psio & 4) && a.bwd) {             // psio bit 2: precision16
     { if (int rc_ = set_lds_attr((const void*)k_block_chain_ps<true, true>, (size_t)(lds), __func__)) return rc_; }
     hipLaunchKernelGGL((k_block_chain_ps<true, true>), dim3(a.N), dim3(NTHR), lds, st, a);

@@ -23,7 +23,6 @@
 #include "fdet_conv3x3_x3.h"
 #include <algorithm>
 #include <cstdint>
-#include <cstdlib>
 
 using namespace fdet;
 
@@ -321,12 +320,12 @@ struct PwmArgs {
   unsigned cpr_magic;  // ceil(2^32 / (CiP / 8)): t / (CiP/8) = umulhi(t, magic) for the panel's piece indices
 };
 
-template <int MT, bool WL, bool ST, int KU, int PT>
+template <int MT, bool WL, bool ST, int KU, int PT = 1>
 __global__ void __launch_bounds__(256)
 k_mb_pw(const PwmArgs a) {
   // WL: [MT*32][CiP + 8] weight panel (row stride = odd number of 16-byte units); ST: then 4 x [32][MT*32 + 4] output staging.
-  // A wave owns PT x 32 positions (PT = 2 for narrow outputs: twice the operand bytes in flight per wave -- these layers
-  // are bound by memory latency x occupancy, PMC: waves parked 60-77 % of their cycles)
+  // A wave owns PT x 32 positions.  Only PT = 1 is built: two sub-tiles per wave measured slower (212 VGPRs: half the waves,
+  // DESIGN.md).  The parameter stays because hipcc orders the staged epilogue differently once the sub-tile loop is written out.
   extern __shared__ __attribute__((aligned(16))) u16 wpan[];
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
   const int l31 = lane & 31, half = lane >> 5;
@@ -648,44 +647,31 @@ extern "C" int fdet_mb_se_gate(const float* pool, int slots, int HW, const float
   return check_launch("fdet_mb_se_gate");
 }
 
-template <int MT, bool WL, bool ST, int KU, int PT>
+template <int MT, bool WL, bool ST, int KU>
 static int launch_pw4(PwmArgs a, size_t lds, hipStream_t st) {
   static bool attr_done = false;
   if (!attr_done && lds) {
-    FDET_REQUIRE(hipFuncSetAttribute((const void*)k_mb_pw<MT, WL, ST, KU, PT>, hipFuncAttributeMaxDynamicSharedMemorySize, 72 * 1024) == hipSuccess, "mb_pointwise: LDS");
+    FDET_REQUIRE(hipFuncSetAttribute((const void*)k_mb_pw<MT, WL, ST, KU>, hipFuncAttributeMaxDynamicSharedMemorySize, 72 * 1024) == hipSuccess, "mb_pointwise: LDS");
     attr_done = true;
   }
-  a.tiles_per_img = (a.P + 128 * PT - 1) / (128 * PT);
+  a.tiles_per_img = (a.P + 127) / 128;
   FDET_REQUIRE((size_t)a.N * a.tiles_per_img < 0x7fffffffu, "mb_pointwise: too many position tiles");
   dim3 grid((unsigned)((size_t)a.N * a.tiles_per_img), ((a.Cout + 31) / 32) / MT);
-  hipLaunchKernelGGL((k_mb_pw<MT, WL, ST, KU, PT>), grid, dim3(256), lds, st, a);
+  hipLaunchKernelGGL((k_mb_pw<MT, WL, ST, KU>), grid, dim3(256), lds, st, a);
   return check_launch("fdet_mb_pointwise");
 }
 
-template <int MT, bool WL, bool ST>
-static int launch_pw2(const PwmArgs& a, size_t lds, hipStream_t st) {
-  // two 32-position sub-tiles per wave while the accumulators stay within ~100 registers (MT <= 3)
-  static const int pt_env = std::getenv("FDET_MB_PW_PT") ? std::atoi(std::getenv("FDET_MB_PW_PT")) : 0;
-  constexpr bool can2 = MT <= 3;
-  const bool pt2 = can2 && pt_env == 2;                           // measured slower (212 VGPRs: half the waves): opt-in only
-  if constexpr (can2) {
-    if (pt2) return a.CiP >= 128 ? launch_pw4<MT, WL, ST, 4, 2>(a, lds, st) : launch_pw4<MT, WL, ST, 1, 2>(a, lds, st);
-  }
-  return a.CiP >= 128 ? launch_pw4<MT, WL, ST, 4, 1>(a, lds, st) : launch_pw4<MT, WL, ST, 1, 1>(a, lds, st);
-}
-
-template <int MT>
+template <int MT, int KU>
 static int launch_pw(const PwmArgs& a, hipStream_t st) {
   // LDS budget 72 KB (2 workgroups per CU): the weight panel first (above 64 KB it stays in L2), then the output staging
-  static const int no_stage = std::getenv("FDET_MB_PW_STAGE") ? !std::atoi(std::getenv("FDET_MB_PW_STAGE")) : 0;
   const size_t panel = (size_t)MT * 32 * (a.CiP + 8) * sizeof(u16);
   const size_t stage = (size_t)4 * 32 * (MT * 32 + 4) * sizeof(u16);
   const bool wl = panel <= 64 * 1024;
-  const bool stg = !no_stage && (wl ? panel : 0) + stage <= 72 * 1024;
-  if (wl && stg) return launch_pw2<MT, true, true>(a, panel + stage, st);
-  if (wl) return launch_pw2<MT, true, false>(a, panel, st);
-  if (stg) return launch_pw2<MT, false, true>(a, stage, st);
-  return launch_pw2<MT, false, false>(a, 0, st);
+  const bool stg = (wl ? panel : 0) + stage <= 72 * 1024;
+  if (wl && stg) return launch_pw4<MT, true, true, KU>(a, panel + stage, st);
+  if (wl) return launch_pw4<MT, true, false, KU>(a, panel, st);
+  if (stg) return launch_pw4<MT, false, true, KU>(a, stage, st);
+  return launch_pw4<MT, false, false, KU>(a, 0, st);
 }
 
 extern "C" int fdet_mb_pointwise(const void* x, const void* w, const float* bias, const float* gate, const void* res, void* y,
@@ -702,14 +688,13 @@ extern "C" int fdet_mb_pointwise(const void* x, const void* w, const float* bias
   // the wide outputs (240, 576 channels: more waves in flight per CU matter more than reading the input once), 3 tiles
   // when the count is a multiple of 3 but odd (72, 88, 96, 288 channels), and single tiles for the rest -- never for
   // output-dominated layers with an even count: 64-byte pieces of a position written by different workgroups cost 2.3x
-  static const int mt_force = std::getenv("FDET_MB_PW_MT") ? std::atoi(std::getenv("FDET_MB_PW_MT")) : 0;
-  int MT = CoT % 2 == 0 ? 2 : (CoT % 3 == 0 ? 3 : 1);
-  if (mt_force >= 1 && mt_force <= 3 && CoT % mt_force == 0) MT = mt_force;
+  const int MT = CoT % 2 == 0 ? 2 : (CoT % 3 == 0 ? 3 : 1);
+  const bool ku4 = a.CiP >= 128;                                  // four k-steps of operand loads in flight (k_mb_pw's KU)
   hipStream_t st = (hipStream_t)stream;
   switch (MT) {
-    case 3: return launch_pw<3>(a, st);
-    case 2: return launch_pw<2>(a, st);
-    default: return launch_pw<1>(a, st);
+    case 3: return ku4 ? launch_pw<3, 4>(a, st) : launch_pw<3, 1>(a, st);
+    case 2: return ku4 ? launch_pw<2, 4>(a, st) : launch_pw<2, 1>(a, st);
+    default: return ku4 ? launch_pw<1, 4>(a, st) : launch_pw<1, 1>(a, st);
   }
 }
 

@@ -16,8 +16,8 @@
 // over ALL of K (no K split, nothing to combine in LDS); per-workgroup slabs are reduced in fixed order.
 //
 // Lines (64 slots) stream through LDS rings: x needs lines L-1, L, L+1 for band L (5-line ring), dz line L (3-line
-// ring); the pieces issued at the head of band L (x line L+3, dz line L+2) have two whole bands to land; one barrier
-// per band.  Zero rows of the layout are processed like any other (they add zeros).
+// ring); the pieces issued at the head of band L (x line L+3, dz line L+2) are waited for at the head of band L+1 and
+// first read at the end of band L+1 (the fragments of band L+2's first step); one barrier per band.  Zero rows of the layout are processed like any other (they add zeros).
 #include "fdet_conv3x3_x3.h"
 #include "fdet_ps.h"
 #include "fdet_ldsdma.h"
@@ -70,7 +70,7 @@ __host__ __device__ constexpr int x_off(int S, int ky, int WP) {
 }
 
 // P16 (precision16, see fdet_conv3x3_ps.hip): one MFMA pass on the hi planes; only their pieces are moved.
-template <int WP, bool FL1, bool P16 = false>
+template <int WP, bool P16 = false>
 __global__ void __launch_bounds__(256, 1)
 k_wgrad3x3_ps(const PsWgArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -156,9 +156,9 @@ k_wgrad3x3_ps(const PsWgArgs a) {
         }                                                                                          \
   }
   int band = l0;
-  if (FL1) {
-    // one-band flight: everything issued so far is visible after this barrier; the fragments of a band's first step are
-    // read during the last step of the band before (no fragment-latency bubble behind the band barrier)
+  {
+    // everything issued so far is visible after this barrier; the fragments of a band's first step are read during the
+    // last step of the band before (no fragment-latency bubble behind the band barrier)
     __builtin_amdgcn_s_barrier();
     const char* zb_ = smem + lane_z + sz * (ZLS * 16);
     const char* xb0 = smem + lane_x + XS(0) * 1024;
@@ -175,10 +175,8 @@ k_wgrad3x3_ps(const PsWgArgs a) {
   const int n_full = row < a.real_lpi ? min(l1 - band, a.real_lpi - row) : 0;
   row += n_full;
   for (const int bend = band + n_full; band < bend; ++band) {
-    // FL1: every piece issued up to the head of the previous band has landed (x <= band+2, dz <= band+1)
-    // else: lines issued two bands ago (x band+1, dz band) have landed; the 8 pieces of the previous band may still fly
-    if (FL1) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
+    // every piece issued up to the head of the previous band has landed (x <= band+2, dz <= band+1)
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
     // ring slots freed by band-1: x line band-2 -> x line band+3 ; dz line band-1 -> dz line band+2
     if (!(WG_DBG & 1)) WG_ISSUE(band + 3, XS(4), band + 2, (sz + 2) % ZL)
@@ -191,15 +189,11 @@ k_wgrad3x3_ps(const PsWgArgs a) {
       const char* xb2 = smem + lane_x + XS(2) * 1024;
       const char* zbn = smem + lane_z + ((sz + 1) % ZL) * (ZLS * 16);   // the next band's lines
       const char* xb3 = smem + lane_x + XS(3) * 1024;
-      if (!FL1) {
-        WG_FRAGS(0, 0, zb_, xb0, xb1, xb2)
-        __builtin_amdgcn_sched_barrier(0);
-      }
 #pragma unroll
       for (int s = 0; s < 4; ++s) {
         const int F = s & 1;
         if (s < 3) WG_FRAGS(F ^ 1, s + 1, zb_, xb0, xb1, xb2)
-        else if (FL1) WG_FRAGS(0, 0, zbn, xb1, xb2, xb3)
+        else WG_FRAGS(0, 0, zbn, xb1, xb2, xb3)
 #pragma unroll
         for (int ky = 0; ky < 3; ++ky)
 #pragma unroll
@@ -229,14 +223,14 @@ k_wgrad3x3_ps(const PsWgArgs a) {
           }
         }
         // the next step's 24 transposed reads ride one per MFMA
-        if ((s < 3 || FL1) && !P16) {
+        if (!P16) {
 #pragma unroll
           for (int i = 0; i < 24; ++i) {
             __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
             __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
           }
           __builtin_amdgcn_sched_group_barrier(0x008, 3, 0);
-        } else if (s < 3 || FL1) {                           // P16: 9 MFMAs, 12 transposed reads
+        } else {                                            // P16: 9 MFMAs, 12 transposed reads
 #pragma unroll
           for (int i = 0; i < 9; ++i) {
             __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
@@ -259,7 +253,7 @@ k_wgrad3x3_ps(const PsWgArgs a) {
     }
     row += n_zero;
     if (row >= a.lpi) row = 0;
-    if (FL1 && band < l1) {                               // the rings hold x <= band+1, dz <= band (the last wait above)
+    if (band < l1) {                                      // the rings hold x <= band+1, dz <= band (the last wait above)
       const char* zb_ = smem + lane_z + sz * (ZLS * 16);
       const char* xb0 = smem + lane_x + XS(0) * 1024;
       const char* xb1 = smem + lane_x + XS(1) * 1024;
@@ -376,7 +370,6 @@ int wgrad_ps_run(const void* const* h_x, const void* const* h_dz, float* const* 
   a.magic_lpi = magic_of(a.lpi);
   const size_t lds = (size_t)WG_LDS_UNITS * 16;
   hipStream_t st = (hipStream_t)stream;
-  static const bool fl1 = [] { const char* e = getenv("FDET_WGPS_FLIGHT"); return !(e && e[0] == '2'); }();   // development: 2 = two-band flight
   auto go = [&](auto kern, bool& done) -> int {
     if (!done) {
       if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
@@ -388,16 +381,16 @@ int wgrad_ps_run(const void* const* h_x, const void* const* h_dz, float* const* 
     hipLaunchKernelGGL(kern, dim3(nslab, L), dim3(256), lds, st, a);
     return FDET_OK;
   };
-  static bool d64a = false, d64b = false, d32a = false, d32b = false, d16a = false, d16b = false, d64p = false, d32p = false, d16p = false;
+  static bool d64 = false, d32 = false, d16 = false, d64p = false, d32p = false, d16p = false;
   int rc0;
   if (p16) {
-    if (g.WP == 64) rc0 = go(k_wgrad3x3_ps<64, true, true>, d64p);
-    else if (g.WP == 16) rc0 = go(k_wgrad3x3_ps<16, true, true>, d16p);
-    else rc0 = go(k_wgrad3x3_ps<32, true, true>, d32p);
+    if (g.WP == 64) rc0 = go(k_wgrad3x3_ps<64, true>, d64p);
+    else if (g.WP == 16) rc0 = go(k_wgrad3x3_ps<16, true>, d16p);
+    else rc0 = go(k_wgrad3x3_ps<32, true>, d32p);
   }
-  else if (g.WP == 64) rc0 = fl1 ? go(k_wgrad3x3_ps<64, true>, d64a) : go(k_wgrad3x3_ps<64, false>, d64b);
-  else if (g.WP == 16) rc0 = fl1 ? go(k_wgrad3x3_ps<16, true>, d16a) : go(k_wgrad3x3_ps<16, false>, d16b);
-  else rc0 = fl1 ? go(k_wgrad3x3_ps<32, true>, d32a) : go(k_wgrad3x3_ps<32, false>, d32b);
+  else if (g.WP == 64) rc0 = go(k_wgrad3x3_ps<64>, d64);
+  else if (g.WP == 16) rc0 = go(k_wgrad3x3_ps<16>, d16);
+  else rc0 = go(k_wgrad3x3_ps<32>, d32);
   if (rc0 != FDET_OK) return rc0;
   int rc = check_launch("fdet_conv3x3_wgrad_ps_batched");
   if (rc != FDET_OK) return rc;

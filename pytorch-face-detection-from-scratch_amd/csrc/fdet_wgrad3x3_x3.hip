@@ -105,18 +105,15 @@ __device__ __forceinline__ void put_sp(__bf16* hi, __bf16* lo, int e, const type
 template <bool P16>
 __device__ __forceinline__ float bsum(float v) { return P16 ? (float)(__bf16)v : v; }
 
-// vector load; PACK rows are only 4-byte aligned (row width not a multiple of 4)
-template <int VW, bool UNALIGNED>
+// aligned vector load
+template <int VW>
 __device__ __forceinline__ typename Vec<VW>::T ldvec(const float* p) {
-  typename Vec<VW>::T v;
-  if (UNALIGNED) __builtin_memcpy(&v, p, 4 * VW);
-  else v = *reinterpret_cast<const typename Vec<VW>::T*>(p);
-  return v;
+  return *reinterpret_cast<const typename Vec<VW>::T*>(p);
 }
-// PACK: the quad was loaded s elements to the left of its place: out[i] = i + s < 4 ? in[i + s] : 0
-template <int VW, bool PACK>
+// PK4 (pipelined kernel): the quad was loaded s elements to the left of its place: out[i] = i + s < 4 ? in[i + s] : 0
+template <int VW, bool PK4>
 __device__ __forceinline__ typename Vec<VW>::T pk_shift(const typename Vec<VW>::T& v, int s) {
-  if constexpr (PACK && VW == 4) {
+  if constexpr (PK4 && VW == 4) {
     f32x4 a = v;
     if (s & 1) a = f32x4{a[1], a[2], a[3], 0.f};
     if (s & 2) a = f32x4{a[2], a[3], 0.f, 0.f};
@@ -151,12 +148,8 @@ __device__ __forceinline__ bf16x8 shift_chunks(const bf16x8& c_lo, const bf16x8&
 // over (dz position, x position) pairs is partitioned by dz ROW (band) and x COLUMN (segment), so a
 // segment stages its own x columns and dz columns [x0-1, x0+CW] -- lanes 14 / 15 of each 16-lane row
 // group fetch the two dz halo columns.
-// PACK (VW == 4, 4 <= W <= 16): narrow rows are staged FOUR rows per 16-lane group -- lane = (row
-// sub-index, column quad) -- with 16-byte loads; the last quad of a row whose width is not a multiple
-// of 4 loads the row's last four elements and shifts them into place (branch-free, never reads past
-// the row).  One dword-per-lane staging pass per row made the 15x15 layers instruction-issue bound.
 // P16 (precision16): operands rounded to bf16 (hi only), ONE MFMA per tap instead of three, fp32 accumulation.
-template <int MTC, int VW, bool SEG, bool PACK = false, bool P16 = false>
+template <int MTC, int VW, bool SEG, bool P16 = false>
 __global__ void __launch_bounds__(NTHR, 1)
 k_wgrad3x3_x3(const WgX3Args a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -204,10 +197,6 @@ k_wgrad3x3_x3(const WgX3Args a) {
   const int chl = tid >> 4;
   int x0 = 0, wcur = W;                               // current segment
   bool lane_ok = xv < W / VW;
-  // PACK geometry: column quad / row sub-index of this lane, load offset and right shift of the quad
-  const int xq = tid & 3, rsub = (tid >> 2) & 3;
-  const int pk_c0 = min(4 * xq, W - 4), pk_s = 4 * xq - pk_c0;
-  if (PACK) lane_ok = 4 * xq < W;
   const int co0 = cob * MB, ci0 = cib * 32;
   const int HW = a.H * W;
   float bpart[ZCH];
@@ -229,28 +218,24 @@ k_wgrad3x3_x3(const WgX3Args a) {
     const int hcol_ = xv == 14 ? x0 - 1 : x0 + wcur;                                              \
     const bool hok_ = SEG && xv >= 14 && hcol_ >= 0 && hcol_ < W;                                 \
     _Pragma("unroll") for (int r_ = 0; r_ < RZ; ++r_) {                                           \
-      const int rr_ = PACK ? 4 * r_ + rsub : r_;                                                  \
-      const int v = (V0) + rr_;                                                                   \
+      const int v = (V0) + r_;                                                                    \
       const int n = fdiv(v, a.magic_h1), yy = v - n * H1 - 1;                                     \
-      const bool rok = rr_ < R && v < a.VR && yy >= 0;                                            \
+      const bool rok = r_ < R && v < a.VR && yy >= 0;                                             \
       const float* rowp = gdz + ((size_t)n * a.Cout * a.H + yy) * W;                             \
       _Pragma("unroll") for (int c_ = 0; c_ < ZCH; ++c_) {                                        \
         const int ch = co0 + c_ * 16 + chl;                                                       \
-        pz[c_][r_] = (rok && lane_ok && ch < a.Cout)                                              \
-                         ? pk_shift<VW, PACK>(ldvec<VW, PACK>(rowp + (size_t)ch * HW + x0 + (PACK ? pk_c0 : xv * VW)), pk_s) : vzero<VW>(); \
+        pz[c_][r_] = (rok && lane_ok && ch < a.Cout) ? ldvec<VW>(rowp + (size_t)ch * HW + x0 + xv * VW) : vzero<VW>(); \
         if (SEG) pzh[c_][r_] = (rok && hok_ && ch < a.Cout) ? rowp[(size_t)ch * HW + hcol_] : 0.f; \
       }                                                                                           \
     }                                                                                             \
     _Pragma("unroll") for (int r_ = 0; r_ < RX; ++r_) {                                           \
-      const int rr_ = PACK ? 4 * r_ + rsub : r_;                                                  \
-      const int v = (V0) - 1 + rr_;                                                               \
+      const int v = (V0) - 1 + r_;                                                                \
       const int n = fdiv(max(v, 0), a.magic_h1), yy = v - n * H1 - 1;                             \
-      const bool rok = rr_ < R + 2 && v >= 0 && v < a.VR && yy >= 0;                              \
+      const bool rok = r_ < R + 2 && v >= 0 && v < a.VR && yy >= 0;                               \
       const float* rowp = gx + ((size_t)n * a.Cin * a.H + yy) * W;                               \
       _Pragma("unroll") for (int c_ = 0; c_ < XCH; ++c_) {                                        \
         const int ch = ci0 + c_ * 16 + chl;                                                       \
-        px[c_][r_] = (rok && lane_ok && ch < a.Cin)                                               \
-                         ? pk_shift<VW, PACK>(ldvec<VW, PACK>(rowp + (size_t)ch * HW + x0 + (PACK ? pk_c0 : xv * VW)), pk_s) : vzero<VW>(); \
+        px[c_][r_] = (rok && lane_ok && ch < a.Cin) ? ldvec<VW>(rowp + (size_t)ch * HW + x0 + xv * VW) : vzero<VW>(); \
       }                                                                                           \
     }                                                                                             \
   }
@@ -258,21 +243,19 @@ k_wgrad3x3_x3(const WgX3Args a) {
   {                                                                                               \
     if (SEG ? xv < 14 : lane_ok) {                                                                \
       _Pragma("unroll") for (int r_ = 0; r_ < RZ; ++r_) {                                         \
-        const int rr_ = PACK ? 4 * r_ + rsub : r_;                                                \
-        if (rr_ < R) {                                                                            \
+        if (r_ < R) {                                                                             \
           _Pragma("unroll") for (int c_ = 0; c_ < ZCH; ++c_) {                                    \
             const int row_ = (c_ * 16 + chl) * a.QZ;                                              \
-            put_sp<P16, VW>(Zh + row_, Zl + row_, ZP + rr_ * P + (PACK ? 4 * xq : xv * VW), pz[c_][r_]); \
+            put_sp<P16, VW>(Zh + row_, Zl + row_, ZP + r_ * P + xv * VW, pz[c_][r_]);             \
             _Pragma("unroll") for (int k_ = 0; k_ < VW; ++k_) bpart[c_] += bsum<P16>(vget<VW>(pz[c_][r_], k_)); \
           }                                                                                       \
         }                                                                                         \
       }                                                                                           \
       _Pragma("unroll") for (int r_ = 0; r_ < RX; ++r_) {                                         \
-        const int rr_ = PACK ? 4 * r_ + rsub : r_;                                                \
-        if (rr_ < R + 2) {                                                                        \
+        if (r_ < R + 2) {                                                                         \
           _Pragma("unroll") for (int c_ = 0; c_ < XCH; ++c_) {                                    \
             const int row_ = (c_ * 16 + chl) * a.PX;                                              \
-            put_sp<P16, VW>(Xh + row_, Xl + row_, XP + rr_ * P + (PACK ? 4 * xq : xv * VW), px[c_][r_]); \
+            put_sp<P16, VW>(Xh + row_, Xl + row_, XP + r_ * P + xv * VW, px[c_][r_]);             \
           }                                                                                       \
         }                                                                                         \
       }                                                                                           \
@@ -802,15 +785,11 @@ k_wgx3_reduce(const float* __restrict__ ws_all, const float* __restrict__ wsb_al
 
 unsigned magic_of(int d) { return (unsigned)((0x100000000ull + (unsigned)d - 1) / (unsigned)d); }
 
-struct WgX3Plan { int P, VR, R, QZ, PX, Kext, nbands, nblk, MTC, CoP, CiP, vw, NSEG, CW, pack, pipe, lpr32, pk4; size_t lds, ws_floats; bool ok; };
+struct WgX3Plan { int P, VR, R, QZ, PX, Kext, nbands, nblk, MTC, CoP, CiP, vw, NSEG, CW, pipe, lpr32, pk4; size_t lds, ws_floats; bool ok; };
 
 WgX3Plan plan_x3(int N, int Cin, int Cout, int H, int W, int L = 1) {
   WgX3Plan p{};
   p.vw = (W % 4 == 0) ? 4 : (W % 2 == 0 ? 2 : 1);
-  // four narrow rows per 16-lane group: opt-in (FDET_WGRAD_PACK=1) -- measured SLOWER than the
-  // dword-per-lane staging on the 15x15 layers (0.64 vs 0.50 ms per 16 layers), kept for tuning
-  p.pack = (W >= 4 && W <= 16 && FDET_ENV_ONCE("FDET_WGRAD_PACK") != nullptr) ? 1 : 0;
-  if (p.pack) p.vw = 4;
   p.NSEG = 1; p.CW = W;
   if (W / p.vw > 16 && p.vw == 4) { p.CW = 56; p.NSEG = (W + 55) / 56; }     // column segments (14 vector lanes)
   p.P = p.NSEG > 1 ? 64 : (W + 1 + 7) / 8 * 8;
@@ -818,12 +797,10 @@ WgX3Plan plan_x3(int N, int Cin, int Cout, int H, int W, int L = 1) {
   p.CoP = (Cout + 31) / 32 * 32;
   p.CiP = (Cin + 31) / 32 * 32;
   p.MTC = (p.CoP % 64 == 0) ? 2 : 1;
-  const int wv = p.pack ? 4 : p.CW / p.vw;
-  p.ok = wv <= 16 && p.VR < (1 << 20) && (size_t)N * std::max(Cin, Cout) * H * W < ((size_t)1 << 31);
+  p.ok = p.CW / p.vw <= 16 && p.VR < (1 << 20) && (size_t)N * std::max(Cin, Cout) * H * W < ((size_t)1 << 31);
   const int rows_total = p.VR - 1;
   const int zch = p.MTC * 2;
-  const int rmul = p.pack ? 4 : 1;
-  const int rz = rmul * (zreg(p.vw) / (zch * p.vw)), rx = rmul * (xreg(p.vw) / (2 * p.vw));
+  const int rz = zreg(p.vw) / (zch * p.vw), rx = xreg(p.vw) / (2 * p.vw);
   int bestR = 0; double bestC = 1e30;
   for (int r = 1; r <= rz && r + 2 <= rx && r <= rows_total; ++r) {
     const int Q = r * p.P;
@@ -845,8 +822,8 @@ WgX3Plan plan_x3(int N, int Cin, int Cout, int H, int W, int L = 1) {
   {
     const char* e = FDET_ENV_ONCE("FDET_WGRAD_PIPE");
     const int rp = 32 / (4 * p.vw);
-    const bool lpr32 = p.P == 32 && p.NSEG == 1 && !p.pack && W <= 32;      // one-float lanes, 32 per row (30x30)
-    p.pipe = p.ok && p.MTC == 2 && p.NSEG == 1 && !p.pack && ((p.vw != 2 && rp * p.P == 128) || lpr32) && rows_total >= 8 &&
+    const bool lpr32 = p.P == 32 && p.NSEG == 1 && W <= 32;      // one-float lanes, 32 per row (30x30)
+    p.pipe = p.ok && p.MTC == 2 && p.NSEG == 1 && ((p.vw != 2 && rp * p.P == 128) || lpr32) && rows_total >= 8 &&
              (size_t)N * std::max(Cin, Cout) * H * W < ((size_t)1 << 29) && !(e && e[0] == '0');   // 32-bit byte offsets
     p.lpr32 = p.pipe && lpr32;
     {
@@ -892,11 +869,10 @@ int launch_x3(const WgX3Args& a, const WgX3Plan& p, dim3 grid, hipStream_t st) {
     else if (p.lpr32) go(k_wgrad3x3_x3_pipe<1, 0, 32, 0, P16>);
     else if (p.pk4) go(k_wgrad3x3_x3_pipe<4, 0, 16, 1, P16>);
     else go(k_wgrad3x3_x3_pipe<4, 0, 16, 0, P16>);      // p.vw == 4 (plan_x3 routes the one-float 16-lane form to the staged kernel)
-  } else if (p.NSEG > 1) go(k_wgrad3x3_x3<MTC, 4, true, false, P16>);
-  else if (p.pack) go(k_wgrad3x3_x3<MTC, 4, false, true, P16>);
-  else if (p.vw == 4) go(k_wgrad3x3_x3<MTC, 4, false, false, P16>);
-  else if (p.vw == 2) go(k_wgrad3x3_x3<MTC, 2, false, false, P16>);
-  else go(k_wgrad3x3_x3<MTC, 1, false, false, P16>);
+  } else if (p.NSEG > 1) go(k_wgrad3x3_x3<MTC, 4, true, P16>);
+  else if (p.vw == 4) go(k_wgrad3x3_x3<MTC, 4, false, P16>);
+  else if (p.vw == 2) go(k_wgrad3x3_x3<MTC, 2, false, P16>);
+  else go(k_wgrad3x3_x3<MTC, 1, false, P16>);
   return rc;
 }
 
@@ -940,7 +916,7 @@ extern "C" int fdet_conv3x3_wgrad_bf16x3_plan(int N, int Cin, int Cout, int H, i
   FDET_REQUIRE(out && n >= 0 && N > 0 && Cin > 0 && Cout > 0 && H > 0 && W > 0 && L >= 1 && L <= MAXL,
                "conv3x3_wgrad_bf16x3_plan: bad arguments");
   const WgX3Plan p = plan_x3(N, Cin, Cout, H, W, L);
-  const int v[8] = {p.ok ? 1 : 0, p.pipe, p.lpr32, p.pk4, p.pack, p.vw, p.MTC, p.NSEG};
+  const int v[8] = {p.ok ? 1 : 0, p.pipe, p.lpr32, p.pk4, 0 /* reserved */, p.vw, p.MTC, p.NSEG};
   for (int i = 0; i < n && i < 8; ++i) out[i] = v[i];
   return FDET_OK;
 }

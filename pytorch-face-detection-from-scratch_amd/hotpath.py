@@ -1147,7 +1147,7 @@ WGRAD_PLAN_FIELDS = ("ok", "pipe", "lpr32", "pk4", "pack", "vw", "mtc", "nseg")
 
 def conv3x3_wgrad_x3_plan(Nn, cin, cout, H, W, L: int = 1) -> dict:
     """The bf16x3 / precision16 weight-gradient plan of L same-shape layers (fdet_conv3x3_wgrad_bf16x3_plan; launches
-    nothing): ok, pipe, lpr32, pk4, pack, vw, mtc, nseg."""
+    nothing): ok, pipe, lpr32, pk4, pack (reserved, always 0), vw, mtc, nseg."""
     import ctypes
     out = (ctypes.c_int * len(WGRAD_PLAN_FIELDS))()
     check(lib().fdet_conv3x3_wgrad_bf16x3_plan(int(Nn), int(cin), int(cout), int(H), int(W), int(L), out, len(out)),

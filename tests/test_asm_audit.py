@@ -59,11 +59,10 @@ def test_no_instruction_touches_in_flight_asm_loads(src, tmp_path):
 # reach the wait (a merged, dropped or duplicated store changes a run length).
 PS_CONV_TUS = list(range(16))          # PS_TU = 8 * P16 + 2 * mode + (WP == 64): FWD_FULL, DGRAD_ACT, FWD_POOL, DGRAD_ADDPOOL x {32, 64} x precision
 VM_KERNELS = {
-    # k_wgrad3x3_ps<WP, FL1 = true> (the default one-band flight) waits with vmcnt(0) only: listed so that a future counted
-    # wait is audited.  FL1 = false counts asm DMA pieces themselves (volatile asm: the compiler cannot merge or drop them).
-    "fdet_wgrad3x3_ps.hip": ["_ZN12_GLOBAL__N_113k_wgrad3x3_psILi64ELb1ELb0E", "_ZN12_GLOBAL__N_113k_wgrad3x3_psILi32ELb1ELb0E",
-                             "_ZN12_GLOBAL__N_113k_wgrad3x3_psILi16ELb1ELb0E", "_ZN12_GLOBAL__N_113k_wgrad3x3_psILi64ELb1ELb1E",
-                             "_ZN12_GLOBAL__N_113k_wgrad3x3_psILi32ELb1ELb1E", "_ZN12_GLOBAL__N_113k_wgrad3x3_psILi16ELb1ELb1E"],
+    # k_wgrad3x3_ps<WP, P16> waits with vmcnt(0) only: listed so that a future counted wait is audited.
+    "fdet_wgrad3x3_ps.hip": ["_ZN12_GLOBAL__N_113k_wgrad3x3_psILi64ELb0E", "_ZN12_GLOBAL__N_113k_wgrad3x3_psILi32ELb0E",
+                             "_ZN12_GLOBAL__N_113k_wgrad3x3_psILi16ELb0E", "_ZN12_GLOBAL__N_113k_wgrad3x3_psILi64ELb1E",
+                             "_ZN12_GLOBAL__N_113k_wgrad3x3_psILi32ELb1E", "_ZN12_GLOBAL__N_113k_wgrad3x3_psILi16ELb1E"],
     "fdet_chain_x3.hip": ["_ZN12_GLOBAL__N_116k_block_chain_psILb0ELb0E", "_ZN12_GLOBAL__N_116k_block_chain_psILb1ELb0E",
                           "_ZN12_GLOBAL__N_116k_block_chain_psILb0ELb1E", "_ZN12_GLOBAL__N_116k_block_chain_psILb1ELb1E",
                           "_ZN12_GLOBAL__N_116k_block_chain_x3ILb0E"],

@@ -6,6 +6,11 @@ deployed geometry and a sweep of batch sizes around each switch, every stage the
 uint8 frame path) to must be accepted by the side-effect-free query of that entry point -- the same check function the entry
 point runs before it launches anything.  Nothing here launches a kernel: the queries only read sizes, and the engines are
 built without a device (wg_num_cus() falls back to the MI355X's 256 CUs)."""
+import json
+import os
+import subprocess
+import sys
+
 import pytest
 
 import fdet_amd  # noqa: F401
@@ -152,3 +157,20 @@ def test_queries_refuse_what_the_kernels_cannot_run():
     assert not hp.block_chain_ok(4, 64, 20, 20)                             # 20 x 24 positions > 256
     assert hp.block_chain_ok(4, 64, 15, 15, True) and hp.block_chain_ok(4, 64, 15, 15, False)
     assert not hp.block_chain_ok(150000, 64, 15, 15, False)
+
+
+def test_weight_gradient_plan_ignores_the_retired_pack_switch():
+    """FDET_WGRAD_PACK selected a packed narrow-row staging that is gone: in a child process with it set (the library reads
+    its switches once per process), the plans of narrow maps (4..16 columns, where it applied) report pack == 0 and equal
+    the plans of this process, whose environment is the child's without the switch."""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    shapes = [(2, 64, 64, 15, W) for W in (15, 4, 16)]
+    code = ("import sys, json; sys.path.insert(0, sys.argv[1]); import fdet_amd; from fdet_amd import hotpath as hp; "
+            "print(json.dumps([hp.conv3x3_wgrad_x3_plan(*s) for s in json.loads(sys.argv[2])]))")
+    assert "FDET_WGRAD_PACK" not in os.environ, "this test needs a process started without the retired switch"
+    r = subprocess.run([sys.executable, "-c", code, root, json.dumps(shapes)], env=dict(os.environ, FDET_WGRAD_PACK="1"),
+                       capture_output=True, text=True, timeout=120, cwd=root)
+    assert r.returncode == 0, r.stderr[-2000:]
+    with_switch = json.loads(r.stdout.strip().splitlines()[-1])
+    assert [p["pack"] for p in with_switch] == [0, 0, 0] and all(p["ok"] for p in with_switch), with_switch
+    assert with_switch == [hp.conv3x3_wgrad_x3_plan(*s) for s in shapes]

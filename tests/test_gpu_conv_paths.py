@@ -14,7 +14,7 @@ within close_bf16's bound (one bf16 rounding of the stored value), weight gradie
 Outputs start as NaN inside a sentinel band that must survive; every launch runs twice and must repeat bit for bit.
 
 The environment switches the runners read once per process (FDET_CONV_KERNEL, FDET_SB_AL, FDET_WGRAD_PIPE,
-FDET_WGRAD_PK4, FDET_WGRAD_PACK) are covered by re-running subsets of this file in
+FDET_WGRAD_PK4) are covered by re-running subsets of this file in
 child processes (test_switch_groups); FDET_CONV_TILE is read at every call and covered in-process."""
 import os
 import subprocess
@@ -206,31 +206,27 @@ def expected_route(kind, N, ci, co, H, W, p, p16):
 
 
 def expected_wgrad_plan(N, ci, co, H, W, L=1):
-    """plan_x3's route fields: ok, pipe, lpr32, pk4, pack, vw, mtc, nseg."""
+    """plan_x3's route fields: ok, pipe, lpr32, pk4, pack (reserved, always 0), vw, mtc, nseg."""
     env = os.environ
     vw = 4 if W % 4 == 0 else (2 if W % 2 == 0 else 1)
-    pack = int(4 <= W <= 16 and "FDET_WGRAD_PACK" in env)
-    if pack:
-        vw = 4
     nseg, cw = 1, W
     if W // vw > 16 and vw == 4:
         cw, nseg = 56, (W + 55) // 56
     P = 64 if nseg > 1 else (W + 1 + 7) // 8 * 8
     cop = (co + 31) // 32 * 32
     mtc = 2 if cop % 64 == 0 else 1
-    wv = 4 if pack else cw // vw
-    ok = wv <= 16
+    ok = cw // vw <= 16
     rows_total = N * (H + 1)
-    lpr32 = P == 32 and nseg == 1 and not pack and W <= 32
+    lpr32 = P == 32 and nseg == 1 and W <= 32
     rp = 32 // (4 * vw)
-    pipe = (ok and mtc == 2 and nseg == 1 and not pack and ((vw != 2 and rp * P == 128) or lpr32) and rows_total >= 8
+    pipe = (ok and mtc == 2 and nseg == 1 and ((vw != 2 and rp * P == 128) or lpr32) and rows_total >= 8
             and env.get("FDET_WGRAD_PIPE", "")[:1] != "0")
     lpr32 = pipe and lpr32
     pk4 = pipe and env.get("FDET_WGRAD_PK4", "")[:1] != "0" and (
         (not lpr32 and vw == 1 and 13 <= W <= 16 and P == 16) or (lpr32 and W >= 29 and P == 32))
     if pipe and vw == 1 and not lpr32 and not pk4:
         pipe = lpr32 = False
-    return dict(ok=int(ok), pipe=int(pipe), lpr32=int(lpr32), pk4=int(pk4), pack=pack, vw=vw, mtc=mtc, nseg=nseg)
+    return dict(ok=int(ok), pipe=int(pipe), lpr32=int(lpr32), pk4=int(pk4), pack=0, vw=vw, mtc=mtc, nseg=nseg)
 
 
 # ----------------------------------------------------------------------------------------------------------------------
@@ -547,7 +543,7 @@ def _wgrad(hp, case, x, dz, p16):
 
 # weight-gradient plans: the pipelined kernel's float4 rows (P = 64), 16-lane one-float rows with float4 quads (13, 15),
 # the 32-lane rows (24..32 columns, VW 4 / 2: odd rows that wide exceed 16 lanes and are refused; float4 quads from 29), the staged kernel at VW 4 / 2 / 1 with MTC 1 / 2, column
-# segments (rows wider than 64 floats), packed narrow rows (FDET_WGRAD_PACK=1, 4..16 columns)
+# segments (rows wider than 64 floats)
 WGRAD_CASES = [(3, 64, 64, 3, 60, 0, 0), (2, 64, 128, 5, 56, 1, 2), (3, 64, 64, 3, 13, 0, 1), (5, 128, 64, 2, 15, 2, 0),
                (3, 64, 64, 3, 28, 0, 0), (3, 32, 64, 2, 24, 1, 1), (3, 64, 64, 3, 30, 2, 2), (3, 96, 64, 2, 26, 0, 0),
                (1, 64, 64, 5, 9, 0, 0), (3, 64, 32, 3, 60, 0, 1), (1, 48, 96, 3, 14, 2, 0), (2, 64, 64, 1, 11, 0, 0),
@@ -731,7 +727,7 @@ def test_conv_tile_configs(hp, monkeypatch, tile, chans):
 SWITCH_GROUPS = [
     ({"FDET_CONV_KERNEL": "general", "FDET_WGRAD_PIPE": "0"}, "test_conv_path and (W6 or W3 or W1-)"),
     ({"FDET_SB_AL": "0", "FDET_WGRAD_PK4": "0"}, "test_conv_path and (W3 or W4 or W1)"),
-    ({"FDET_SB_AL": "1", "FDET_WGRAD_PACK": "1"}, "test_conv_path and (W1 or W2 or W3)"),
+    ({"FDET_SB_AL": "1"}, "test_conv_path and (W1 or W2 or W3)"),
 ]
 
 
