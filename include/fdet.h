@@ -916,6 +916,10 @@ int fdet_render_boxes_blur(const uint8_t* src, const fdet_aug_image* src_table, 
 typedef struct fdet_track {
   int32_t id, x1q, y1q, x2q, y2q, hits, misses, born;
   float score;
+  /* reserved[0] = vx256, reserved[1] = vy256 under fdet_track_update_motion: the velocity of the box in 1/256 pixel per
+   * frame, applied to all four corners alike; reserved[2] is unused.  fdet_track_update never reads the three words: it
+   * carries those of a live track through unchanged and zeroes them when the slot is freed (step 6) and when a track is
+   * born into it (step 7).  A state is driven by one of the two entries from fresh on. */
   int32_t reserved[3];
 } fdet_track;                        /* 48 bytes */
 typedef struct fdet_track_seq {
@@ -963,6 +967,33 @@ int fdet_track_update(const float* rows, const int32_t* counts, const int32_t* s
                       int n_seq, int T, int K, double iou_threshold, int alpha256, int max_misses, int min_hits,
                       int emit_misses, float birth_score, void* state, float* out_rows, int32_t* out_ids,
                       int32_t* out_misses, int32_t* out_counts, int32_t* det_ids, uint64_t* rejected, void* stream);
+
+/* fdet_track_update with a constant-velocity motion model: an integer alpha-beta filter on each track's centre velocity
+ * (vx256, vy256 = reserved[0], reserved[1] of fdet_track) and an optional growth of the emitted box while a track coasts.
+ * The same kernel source, launch shape, limits, rejection and host validation; the nine steps above with these changes
+ * (int64, arithmetic shifts, M = FDET_TRACK_MAX_COORD):
+ *   0.  predict, every live track, before step 2: per axis s = (v256 + 8) >> 4 (1/16 pixel); both corners of the axis move
+ *       by s when the moved pixel corners (q + s + 8) >> 4 both stay within +-M, else the corners stay and the axis'
+ *       velocity becomes 0.  Widths are kept, so the >= 16 invariants of step 5 hold.
+ *   5'. matched track, before the blend of step 5, q the predicted corners and D the detection's pixel corners:
+ *       rx = 16 * (D.x1 + D.x2) - (x1q + x2q) (twice the centre residual in 1/16 pixel),
+ *       vx256 <- clamp(vx256 + ((beta256 * 8 * rx + 128) >> 8), -256 * max_speed, 256 * max_speed); y likewise.  Then step
+ *       5 as it is, on the predicted q.
+ *   6'. unmatched track that survives step 6: v256 <- (v256 * damp256 + 128) >> 8 per axis.
+ *   9'. a track emitted with misses = m > 0: gx = min((grow256 * m * (P.x2 - P.x1) + 256) >> 9, M), gy from the height, and
+ *       the row is [score, P.x1 - gx, P.y1 - gy, P.x2 - P.x1 + 2 gx, P.y2 - P.y1 + 2 gy]; every value stays below 2^17 in
+ *       magnitude, exact in fp32.  Matching (steps 3, 4) uses the un-grown box and the state is never grown.
+ * A freed slot is all zero and a track is born with velocity 0, as above.  A rejected sequence leaves its state untouched,
+ * the velocities included.  With beta256 = 0 and grow256 = 0 outputs and state equal fdet_track_update's byte for byte
+ * from a fresh state; with alpha256 = beta256 = 256 a box moving by whole pixels per frame, |v| <= max_speed, is predicted
+ * exactly from its third frame on.
+ * Validated on the host as fdet_track_update, and: beta256, damp256, grow256 outside 0..256, max_speed outside 0..1024
+ * (pixels per frame) give FDET_EINVAL with nothing launched. */
+int fdet_track_update_motion(const float* rows, const int32_t* counts, const int32_t* seq_offset, const int32_t* h_seq_offset,
+                             int n_seq, int T, int K, double iou_threshold, int alpha256, int max_misses, int min_hits,
+                             int emit_misses, float birth_score, int beta256, int damp256, int max_speed, int grow256,
+                             void* state, float* out_rows, int32_t* out_ids, int32_t* out_misses, int32_t* out_counts,
+                             int32_t* det_ids, uint64_t* rejected, void* stream);
 
 /* ---- face chips and the sharpest chip of each track (csrc/fdet_chips.hip) ------------------
  * fdet_chip_extract cuts one fixed-size square crop ("chip") per detection row out of the image bank;

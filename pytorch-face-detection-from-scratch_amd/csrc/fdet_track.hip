@@ -18,6 +18,11 @@
 //     masks, so the loop over a detection's candidate tracks is a scalar bit scan with no dependent LDS read;
 //   * updates, frees, births (ranks by ballot: the k-th birth in row order takes the k-th free slot in slot order, which
 //     is what taking the lowest free slot one birth at a time gives) and the emission are one thread per slot.
+// fdet_track_update_motion is the same kernel with MOTION = true: the two velocity words of a track (F_VX, F_VY) are fields of
+// the LDS state like the others, the prediction (step 0) and the damping (step 6') are done by the slot's own thread where
+// it computes P and where it counts the miss, the velocity update (step 5') where it blends, and the growth (step 9') where
+// it emits.  Each touches only words of its own slot, so the motion steps add no barrier; with MOTION = false they are
+// compiled out and the kernel is fdet_track_update's as before.
 // The only floating-point operations are the fp32 sums x + w, y + h of the validity test and the one double multiply of the
 // eligibility test.  Built with -ffp-contract=off like every file here.
 #include "fdet_common.h"
@@ -34,6 +39,7 @@ static_assert(NTHR == ND && 2 * NS == NTHR && NS == 2 * WAVE, "one thread per de
 
 // words of fdet_track
 enum { F_ID, F_X1, F_Y1, F_X2, F_Y2, F_HITS, F_MISS, F_BORN, F_SCORE, F_R0, F_R1, F_R2, NF };
+enum { F_VX = F_R0, F_VY = F_R1 };           // fdet_track_update_motion: the velocity in 1/256 pixel per frame
 
 // the best partner found so far for a track or a detection; inter == 0 means none (an eligible pair has inter > 0).
 // Corners within +-FDET_TRACK_MAX_COORD (the tracks' too: a weighted mean of detections' corners) keep a side <= 2^15, an area
@@ -67,12 +73,18 @@ __device__ __forceinline__ unsigned long long uniform64(unsigned long long v) {
   return ((unsigned long long)hi << 32) | lo;
 }
 
+// the parameters of the motion steps; fdet_track_update passes zeros and reads none
+struct Motion {
+  int beta256, damp256, vmax256, grow256;
+};
+
+template <bool MOTION>
 __global__ void __launch_bounds__(NTHR)
 k_track_update(const float* __restrict__ rows, const int32_t* __restrict__ counts, const int32_t* __restrict__ seq_offset, int T,
                int K, double thr, int alpha256, int max_misses, int min_hits, int emit_misses, float birth_score,
                int32_t* __restrict__ state, float* __restrict__ out_rows, int32_t* __restrict__ out_ids,
                int32_t* __restrict__ out_misses, int32_t* __restrict__ out_counts, int32_t* __restrict__ det_ids,
-               unsigned long long* __restrict__ rejected) {
+               unsigned long long* __restrict__ rejected, Motion mo) {
   __shared__ int tf[NF][NS];                 // the tracks, field-major
   __shared__ int hdr[4];                     // next_id, frame, dropped, reserved
   __shared__ int tP[4][NS];                  // step 2: the tracks' boxes in pixels
@@ -185,7 +197,23 @@ k_track_update(const float* __restrict__ rows, const int32_t* __restrict__ count
     if (isSlot) {
       live = tf[F_ID][sl] != 0;
       if (live) {
-        q0 = (tf[F_X1][sl] + 8) >> 4; q1 = (tf[F_Y1][sl] + 8) >> 4; q2 = (tf[F_X2][sl] + 8) >> 4; q3 = (tf[F_Y2][sl] + 8) >> 4;
+        int c[4] = {tf[F_X1][sl], tf[F_Y1][sl], tf[F_X2][sl], tf[F_Y2][sl]};
+        if (MOTION) {                        // step 0: both corners of an axis move, or the axis stops
+          constexpr int M = FDET_TRACK_MAX_COORD;
+#pragma unroll
+          for (int a = 0; a < 2; ++a) {
+            const int s = (tf[F_VX + a][sl] + 8) >> 4;        // |v256| <= 2^18, |q| < 2^19: 32 bits hold every value
+            const int qa = c[a] + s, qb = c[2 + a] + s;
+            const int pa = (qa + 8) >> 4, pb = (qb + 8) >> 4;
+            if (pa >= -M && pa <= M && pb >= -M && pb <= M) {
+              c[a] = qa; c[2 + a] = qb;
+              tf[F_X1 + a][sl] = qa; tf[F_X2 + a][sl] = qb;
+            } else {
+              tf[F_VX + a][sl] = 0;
+            }
+          }
+        }
+        q0 = (c[0] + 8) >> 4; q1 = (c[1] + 8) >> 4; q2 = (c[2] + 8) >> 4; q3 = (c[3] + 8) >> 4;
         tP[0][sl] = q0; tP[1][sl] = q1; tP[2][sl] = q2; tP[3][sl] = q3;
       }
       tDet[sl] = -1;
@@ -256,6 +284,14 @@ k_track_update(const float* __restrict__ rows, const int32_t* __restrict__ count
     if (live) {
       const int d = tDet[sl];
       if (d >= 0) {
+        if (MOTION) {                        // step 5': from the predicted corners, before they are blended
+#pragma unroll
+          for (int a = 0; a < 2; ++a) {
+            const long long r = 16ll * (dB[a][d] + dB[2 + a][d]) - ((long long)tf[F_X1 + a][sl] + tf[F_X2 + a][sl]);
+            const long long v = (long long)tf[F_VX + a][sl] + (((long long)mo.beta256 * 8 * r + 128) >> 8);
+            tf[F_VX + a][sl] = (int)min(max(v, -(long long)mo.vmax256), (long long)mo.vmax256);
+          }
+        }
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
           const long long q = (long long)tf[F_X1 + e][sl], D = (long long)dB[e][d];
@@ -270,6 +306,9 @@ k_track_update(const float* __restrict__ rows, const int32_t* __restrict__ count
         if (m > max_misses) {
 #pragma unroll
           for (int e = 0; e < NF; ++e) tf[e][sl] = 0;
+        } else if (MOTION) {                 // step 6'
+          tf[F_VX][sl] = (tf[F_VX][sl] * mo.damp256 + 128) >> 8;
+          tf[F_VY][sl] = (tf[F_VY][sl] * mo.damp256 + 128) >> 8;
         }
       }
     }
@@ -325,8 +364,15 @@ k_track_update(const float* __restrict__ rows, const int32_t* __restrict__ count
         const int p = (swid ? ctl[16] : 0) + __popcll(bal & below);
         const int p0 = (tf[F_X1][sl] + 8) >> 4, p1 = (tf[F_Y1][sl] + 8) >> 4;
         const int p2 = (tf[F_X2][sl] + 8) >> 4, p3 = (tf[F_Y2][sl] + 8) >> 4;
+        int gx = 0, gy = 0;
+        if (MOTION) {                        // step 9': misses = 0 gives 0; misses has no bound, so 64 bits
+          const long long gm = (long long)mo.grow256 * tf[F_MISS][sl];
+          gx = (int)min((gm * (p2 - p0) + 256) >> 9, (long long)FDET_TRACK_MAX_COORD);
+          gy = (int)min((gm * (p3 - p1) + 256) >> 9, (long long)FDET_TRACK_MAX_COORD);
+        }
         o[p * 5 + 0] = __int_as_float(tf[F_SCORE][sl]);
-        o[p * 5 + 1] = (float)p0; o[p * 5 + 2] = (float)p1; o[p * 5 + 3] = (float)(p2 - p0); o[p * 5 + 4] = (float)(p3 - p1);
+        o[p * 5 + 1] = (float)(p0 - gx); o[p * 5 + 2] = (float)(p1 - gy);
+        o[p * 5 + 3] = (float)(p2 - p0 + 2 * gx); o[p * 5 + 4] = (float)(p3 - p1 + 2 * gy);
         oi[p] = tf[F_ID][sl];
         om[p] = tf[F_MISS][sl];
       }
@@ -366,11 +412,12 @@ extern "C" size_t fdet_track_state_bytes(int n_seq) {
   return n_seq < 1 ? 0 : (size_t)n_seq * (sizeof(fdet_track_seq) + (size_t)NS * sizeof(fdet_track));
 }
 
-extern "C" int fdet_track_update(const float* rows, const int32_t* counts, const int32_t* seq_offset, const int32_t* h_seq_offset,
-                                 int n_seq, int T, int K, double iou_threshold, int alpha256, int max_misses, int min_hits,
-                                 int emit_misses, float birth_score, void* state, float* out_rows, int32_t* out_ids,
-                                 int32_t* out_misses, int32_t* out_counts, int32_t* det_ids, uint64_t* rejected, void* stream) {
-  const char* what = "fdet_track_update";
+namespace {
+
+int track_update(const char* what, bool motion, Motion mo, const float* rows, const int32_t* counts, const int32_t* seq_offset,
+                 const int32_t* h_seq_offset, int n_seq, int T, int K, double iou_threshold, int alpha256, int max_misses,
+                 int min_hits, int emit_misses, float birth_score, void* state, float* out_rows, int32_t* out_ids,
+                 int32_t* out_misses, int32_t* out_counts, int32_t* det_ids, uint64_t* rejected, void* stream) {
   FDET_REQUIRE(n_seq >= 1 && T >= 0 && K >= 0, "%s: bad sizes n_seq=%d T=%d K=%d", what, n_seq, T, K);
   FDET_REQUIRE(alpha256 >= 1 && alpha256 <= 256, "%s: alpha256=%d must be in 1..256", what, alpha256);
   FDET_REQUIRE(max_misses >= 0 && min_hits >= 1 && emit_misses >= 0 && emit_misses <= max_misses,
@@ -386,8 +433,35 @@ extern "C" int fdet_track_update(const float* rows, const int32_t* counts, const
     FDET_REQUIRE(h_seq_offset[s + 1] >= h_seq_offset[s], "%s: seq_offset[%d]=%d < seq_offset[%d]=%d", what, s + 1,
                  h_seq_offset[s + 1], s, h_seq_offset[s]);
   if (T == 0) return FDET_OK;                // no frame: every state stays as it is
-  hipLaunchKernelGGL(k_track_update, dim3(n_seq), dim3(NTHR), 0, (hipStream_t)stream, rows, counts, seq_offset, T, K,
-                     iou_threshold, alpha256, max_misses, min_hits, emit_misses, birth_score, reinterpret_cast<int32_t*>(state),
-                     out_rows, out_ids, out_misses, out_counts, det_ids, reinterpret_cast<unsigned long long*>(rejected));
+  hipLaunchKernelGGL(motion ? k_track_update<true> : k_track_update<false>, dim3(n_seq), dim3(NTHR), 0, (hipStream_t)stream, rows,
+                     counts, seq_offset, T, K, iou_threshold, alpha256, max_misses, min_hits, emit_misses, birth_score,
+                     reinterpret_cast<int32_t*>(state), out_rows, out_ids, out_misses, out_counts, det_ids,
+                     reinterpret_cast<unsigned long long*>(rejected), mo);
   return check_launch(what);
+}
+
+}  // namespace
+
+extern "C" int fdet_track_update(const float* rows, const int32_t* counts, const int32_t* seq_offset, const int32_t* h_seq_offset,
+                                 int n_seq, int T, int K, double iou_threshold, int alpha256, int max_misses, int min_hits,
+                                 int emit_misses, float birth_score, void* state, float* out_rows, int32_t* out_ids,
+                                 int32_t* out_misses, int32_t* out_counts, int32_t* det_ids, uint64_t* rejected, void* stream) {
+  return track_update("fdet_track_update", false, Motion{0, 0, 0, 0}, rows, counts, seq_offset, h_seq_offset, n_seq, T, K,
+                      iou_threshold, alpha256, max_misses, min_hits, emit_misses, birth_score, state, out_rows, out_ids, out_misses,
+                      out_counts, det_ids, rejected, stream);
+}
+
+extern "C" int fdet_track_update_motion(const float* rows, const int32_t* counts, const int32_t* seq_offset,
+                                        const int32_t* h_seq_offset, int n_seq, int T, int K, double iou_threshold, int alpha256,
+                                        int max_misses, int min_hits, int emit_misses, float birth_score, int beta256, int damp256,
+                                        int max_speed, int grow256, void* state, float* out_rows, int32_t* out_ids,
+                                        int32_t* out_misses, int32_t* out_counts, int32_t* det_ids, uint64_t* rejected,
+                                        void* stream) {
+  const char* what = "fdet_track_update_motion";
+  FDET_REQUIRE(beta256 >= 0 && beta256 <= 256 && damp256 >= 0 && damp256 <= 256 && grow256 >= 0 && grow256 <= 256,
+               "%s: beta256=%d, damp256=%d and grow256=%d must be in 0..256", what, beta256, damp256, grow256);
+  FDET_REQUIRE(max_speed >= 0 && max_speed <= 1024, "%s: max_speed=%d must be in 0..1024", what, max_speed);
+  return track_update(what, true, Motion{beta256, damp256, 256 * max_speed, grow256}, rows, counts, seq_offset, h_seq_offset, n_seq,
+                      T, K, iou_threshold, alpha256, max_misses, min_hits, emit_misses, birth_score, state, out_rows, out_ids,
+                      out_misses, out_counts, det_ids, rejected, stream);
 }

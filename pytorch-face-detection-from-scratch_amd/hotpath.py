@@ -454,6 +454,13 @@ def track_update(rows: torch.Tensor, counts: torch.Tensor, seq_offset: torch.Ten
     in time order; state: (n_seq * 6160,) uint8 on the device, updated in place (zeros = fresh) ->
     (out_rows (T,128,5), out_ids (T,128) int32, out_misses (T,128) int32, out_counts (T,) int32, det_ids (T,K) int32,
     rejected (1,) int64 counter, += 1 per rejected sequence).  One launch, no host synchronisation."""
+    return _track_update("fdet_track_update", (), rows, counts, seq_offset, h_seq_offset, state, iou_threshold, alpha256, max_misses,
+                         min_hits, emit_misses, birth_score, rejected)
+
+
+def _track_update(entry, motion, rows, counts, seq_offset, h_seq_offset, state, iou_threshold, alpha256, max_misses, min_hits,
+                  emit_misses, birth_score, rejected):
+    """The two tracker entries: `motion` holds the integers fdet_track_update_motion takes after birth_score, or nothing."""
     import numpy as np
     if rows.dim() != 3 or rows.shape[2] != 5 or rows.dtype != F32:
         raise ValueError(f"track_update: rows must be (T,K,5) float32, got {tuple(rows.shape)} {rows.dtype}")
@@ -478,12 +485,24 @@ def track_update(rows: torch.Tensor, counts: torch.Tensor, seq_offset: torch.Ten
     def p(t, dtype=F32):                                     # an empty tensor has no storage to point at
         return ptr(t, dtype) if t.numel() else None
 
-    check(lib().fdet_track_update(p(rows.contiguous()), p(counts.contiguous(), I32), ptr(seq_offset.contiguous(), I32),
-                                  h_seq_offset.ctypes.data, n, T, K, float(iou_threshold), int(alpha256), int(max_misses),
-                                  int(min_hits), int(emit_misses), float(birth_score), ptr(state, torch.uint8), p(out_rows),
-                                  p(out_ids, I32), p(out_misses, I32), p(out_counts, I32), p(det_ids, I32),
-                                  ptr(rejected, torch.int64), stream()), "fdet_track_update")
+    check(getattr(lib(), entry)(p(rows.contiguous()), p(counts.contiguous(), I32), ptr(seq_offset.contiguous(), I32),
+                                h_seq_offset.ctypes.data, n, T, K, float(iou_threshold), int(alpha256), int(max_misses),
+                                int(min_hits), int(emit_misses), float(birth_score), *motion,
+                                ptr(state, torch.uint8), p(out_rows), p(out_ids, I32), p(out_misses, I32), p(out_counts, I32),
+                                p(det_ids, I32), ptr(rejected, torch.int64), stream()), entry)
     return out_rows, out_ids, out_misses, out_counts, det_ids, rejected
+
+
+def track_update_motion(rows: torch.Tensor, counts: torch.Tensor, seq_offset: torch.Tensor, h_seq_offset, state: torch.Tensor,
+                        iou_threshold: float, alpha256: int, max_misses: int, min_hits: int, emit_misses: int, birth_score: float,
+                        beta256: int, damp256: int, max_speed: int, grow256: int, rejected: Optional[torch.Tensor] = None):
+    """fdet_track_update_motion: `track_update` with the constant-velocity motion model.  beta256 (0..256): gain of the
+    velocity update; damp256 (0..256): what a missed track keeps of its velocity per frame; max_speed (0..1024): pixels per
+    frame; grow256 (0..256): growth of the emitted box per missed frame.  The same arguments, state and results otherwise;
+    the velocities live in reserved[0..1] of each track, and a state is driven by one of the two entries from fresh on."""
+    return _track_update("fdet_track_update_motion", (int(beta256), int(damp256), int(max_speed), int(grow256)), rows, counts,
+                         seq_offset, h_seq_offset, state, iou_threshold, alpha256, max_misses, min_hits, emit_misses, birth_score,
+                         rejected)
 
 
 # ------------------------------------------------------------------------------------------

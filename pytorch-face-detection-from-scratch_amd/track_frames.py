@@ -2,6 +2,7 @@
 
     python -m fdet_amd.track_frames --checkpoint CKPT --frames DIR --out FILE [--model poolresnet --filters 128]
         [--tiled --tile 480 --overlap 0.25] [--iou 0.3 --alpha 0.5 --max-misses 5 --min-hits 2 --emit-misses N]
+        [--motion constant_velocity [--motion-beta 0.5] [--motion-damping 1.0] [--max-speed 64] [--coast-grow 0.0]]
         [--draw DIR [--anonymize pixelate|blur] [--blocks N] [--blur-radius R] [--draw-format png|jpg] [--no-outline]]
         [--best-shots DIR [--chip-size N] [--chip-margin F] [--chip-format png|jpg]]
         [--device-jpeg-encode] [--jpeg-quality Q]
@@ -11,7 +12,9 @@ same size.  They are detected in chunks of --max-frames: without --tiled each fr
 with --tiled `TiledDetector` also runs the --tile windows.  `tracking.FaceTracker` carries its state from chunk to chunk.
 FILE receives one line per emitted track and frame, `frame,id,x,y,w,h,score,-1,-1,-1` with frames counted from 1 and the box
 in source pixels.  `--draw DIR` writes every frame with the TRACKER's boxes rendered into it (`render.render_detections`), so
-with `--anonymize pixelate` a face the detector misses for up to --emit-misses frames stays covered.  The model options are
+with `--anonymize pixelate` a face the detector misses for up to --emit-misses frames stays covered; with `--motion
+constant_velocity` the missed track moves on at its estimated velocity, so that also holds for a face that moves, and
+`--coast-grow` widens the covered box frame by frame while it is missed (`tracking.FaceTracker`).  The model options are
 those of `detect_images`.  `--best-shots DIR` writes one picture per track, `DIR/seq0_track<id>.png`: the sharpest
 `--chip-size` x `--chip-size` crop (112) among the frames in which the detector saw the track, cut with `--chip-margin` (0.25)
 and kept on the device from chunk to chunk (`chips.BestShots`).  Files only: there is no camera or video-container input.
@@ -70,6 +73,11 @@ def main(argv=None):
     ap.add_argument("--min-hits", type=int, default=2)
     ap.add_argument("--emit-misses", type=int, default=None, help="frames a missed track is still emitted (--max-misses)")
     ap.add_argument("--birth-score", type=float, default=0.0)
+    ap.add_argument("--motion", choices=["constant_velocity"], default=None, help="motion model of the tracks (none)")
+    ap.add_argument("--motion-beta", type=float, default=0.5, help="gain of the velocity update, 0..1")
+    ap.add_argument("--motion-damping", type=float, default=1.0, help="velocity a missed track keeps per frame, 0..1")
+    ap.add_argument("--max-speed", type=int, default=64, help="bound on a track's velocity, pixels per frame")
+    ap.add_argument("--coast-grow", type=float, default=0.0, help="growth of a missed track's emitted box per frame, 0..1")
     add_draw_arguments(ap)
     add_chip_arguments(ap, "--best-shots", "also write the sharpest crop of every track under DIR")
     add_jpeg_encode_arguments(ap)
@@ -98,7 +106,8 @@ def run(args):
     from .tiling import TiledDetector
     from .tracking import FaceTracker
     tracker = FaceTracker(1, iou_threshold=args.iou, alpha=args.alpha, max_misses=args.max_misses, min_hits=args.min_hits,
-                          emit_misses=args.emit_misses, birth_score=args.birth_score)         # checks its options first
+                          emit_misses=args.emit_misses, birth_score=args.birth_score, motion=args.motion, beta=args.motion_beta,
+                          damping=args.motion_damping, max_speed=args.max_speed, coast_grow=args.coast_grow)      # checks its options first
     model = load_model(args)
     det = TiledDetector(model, tile_sizes=tuple(args.tile) if args.tiled else (), overlap=args.overlap,
                         include_whole=not (args.tiled and args.no_whole), edge_margin=args.edge_margin,

@@ -13,6 +13,12 @@ for `emit_misses` frames at its last box, so rendering the tracker's rows instea
 `fdet_track_update` (csrc/fdet_track.hip) does the association in one launch per call, one workgroup per sequence, with
 exact integer arithmetic; include/fdet.h states the rule step by step, tests/track_cpu_ref.py restates it in numpy and
 DESIGN.md 5h gives the limits and the measurements.  The reference project has no counterpart.
+
+A missed track stays where it was, which bridges a gap only for a face that stands still.  `motion="constant_velocity"`
+(`fdet_track_update_motion`) gives every track a velocity, estimated from its matches by an integer alpha-beta filter, moves
+the box by it in every frame, matched or not, and can grow the emitted box while the track coasts:
+
+    tr = FaceTracker(max_misses=3, min_hits=1, motion="constant_velocity", coast_grow=0.1)
 """
 from __future__ import annotations
 
@@ -29,6 +35,12 @@ TRACK_DTYPE = np.dtype([("id", "<i4"), ("x1q", "<i4"), ("y1q", "<i4"), ("x2q", "
                         ("misses", "<i4"), ("born", "<i4"), ("score", "<f4"), ("reserved", "<i4", (3,))])     # fdet_track
 SEQ_DTYPE = np.dtype([("next_id", "<i4"), ("frame", "<i4"), ("dropped", "<i4"), ("reserved", "<i4")])         # fdet_track_seq
 STATE_DTYPE = np.dtype([("seq", SEQ_DTYPE), ("tracks", TRACK_DTYPE, (hp.TRACK_SLOTS,))])
+# the same 48 bytes as a tracker with a motion model keeps them: reserved[0], reserved[1] are the velocity in 1/256 pixel per frame
+MOTION_TRACK_DTYPE = np.dtype([(n, "<i4") for n in ("id", "x1q", "y1q", "x2q", "y2q", "hits", "misses", "born")] +
+                              [("score", "<f4"), ("vx256", "<i4"), ("vy256", "<i4"), ("reserved", "<i4")])
+MOTION_STATE_DTYPE = np.dtype([("seq", SEQ_DTYPE), ("tracks", MOTION_TRACK_DTYPE, (hp.TRACK_SLOTS,))])
+assert MOTION_TRACK_DTYPE.itemsize == 48 and MOTION_STATE_DTYPE.itemsize == hp.TRACK_STATE_BYTES
+MOTION_MODELS = (None, "constant_velocity")
 assert TRACK_DTYPE.itemsize == 48 and SEQ_DTYPE.itemsize == 16 and STATE_DTYPE.itemsize == hp.TRACK_STATE_BYTES
 
 TrackResult = namedtuple("TrackResult", "rows counts ids misses det_ids")
@@ -45,15 +57,34 @@ def alpha_to_256(alpha: float) -> int:
     return a
 
 
+def unit_to_256(name: str, value: float) -> int:
+    """rint(value * 256), which must lie in 0..256."""
+    v = int(np.rint(float(value) * 256))
+    if not 0 <= v <= 256:
+        raise ValueError(f"FaceTracker: {name}={value} gives {v}/256, 0..256 are supported ({name} in [0, 1])")
+    return v
+
+
 class FaceTracker:
     """n_seq independent sequences (cameras, files), each with 128 track slots.  iou_threshold: least overlap of a track and a
     detection that may be matched, in [0, 1).  alpha: weight of the new detection in a matched track's box (1 = take the
     detection, smaller = smoother).  max_misses: a track that goes unmatched for more frames than this dies.  min_hits: a
     track is emitted from its min_hits-th detection on (2 keeps one-frame false positives out).  emit_misses: an unmatched
-    track is emitted for this many frames (None = max_misses, 0 = never).  birth_score: least score that starts a track."""
+    track is emitted for this many frames (None = max_misses, 0 = never).  birth_score: least score that starts a track.
+
+    motion: None (a missed track stays where it was; `fdet_track_update`) or "constant_velocity" (`fdet_track_update_motion`,
+    fixed at construction: a state is driven by one entry from fresh on).  With it every track carries a velocity and its box
+    moves by it each frame before matching, so a moving face is still covered, and still matched, after a gap.  beta in
+    [0, 1]: gain of the velocity update from a match's centre residual (1 with alpha = 1 predicts exact constant motion from
+    the third frame on, 0 never moves anything).  damping in [0, 1]: what a missed track keeps of its velocity per frame.
+    max_speed: bound on the velocity in whole pixels per frame, 0..1024.  coast_grow in [0, 1]: the emitted box of a track
+    missed for m frames grows by coast_grow * m / 2 of its width and height on every side; the state and the matching never
+    grow.  beta = 0.5, damping = 1.0 and max_speed = 64 are guesses: nobody has measured them on real video.  They are
+    ignored without a motion model."""
 
     def __init__(self, n_seq: int = 1, iou_threshold: float = 0.3, alpha: float = 0.5, max_misses: int = 5, min_hits: int = 2,
-                 emit_misses: Optional[int] = None, birth_score: float = 0.0, device="cuda"):
+                 emit_misses: Optional[int] = None, birth_score: float = 0.0, device="cuda", motion: Optional[str] = None,
+                 beta: float = 0.5, damping: float = 1.0, max_speed: int = 64, coast_grow: float = 0.0):
         self.n_seq = int(n_seq)
         if self.n_seq < 1:
             raise ValueError(f"FaceTracker: n_seq={n_seq} must be >= 1")
@@ -67,6 +98,14 @@ class FaceTracker:
             raise ValueError(f"FaceTracker: max_misses={max_misses} must be >= 0, min_hits={min_hits} >= 1 and "
                              f"emit_misses={emit_misses} in 0..max_misses")
         self.birth_score = float(birth_score)
+        if motion not in MOTION_MODELS:
+            raise ValueError(f"FaceTracker: motion={motion!r} must be one of {MOTION_MODELS}")
+        self.motion = motion
+        self.beta256, self.damp256 = unit_to_256("beta", beta), unit_to_256("damping", damping)
+        self.grow256 = unit_to_256("coast_grow", coast_grow)
+        self.max_speed = int(max_speed)
+        if self.max_speed != max_speed or not 0 <= self.max_speed <= 1024:
+            raise ValueError(f"FaceTracker: max_speed={max_speed} must be a whole number of pixels per frame in 0..1024")
         self.device = torch.device(device)
         self.state = torch.zeros(self.n_seq * hp.TRACK_STATE_BYTES, dtype=torch.uint8, device=self.device)
 
@@ -75,8 +114,9 @@ class FaceTracker:
         self.state.zero_()
 
     def snapshot(self) -> np.ndarray:
-        """Host copy of the state: (n_seq,) records {seq: fdet_track_seq, tracks: (128,) fdet_track}."""
-        return self.state.cpu().numpy().view(STATE_DTYPE).copy()
+        """Host copy of the state: (n_seq,) records {seq: fdet_track_seq, tracks: (128,) fdet_track}.  With a motion model
+        the same bytes are viewed as MOTION_STATE_DTYPE, whose tracks name the velocities vx256, vy256."""
+        return self.state.cpu().numpy().view(STATE_DTYPE if self.motion is None else MOTION_STATE_DTYPE).copy()
 
     @property
     def dropped(self) -> int:
@@ -100,11 +140,15 @@ class FaceTracker:
         if h_off.size != self.n_seq + 1:
             raise ValueError(f"FaceTracker.update: seq_offset must hold n_seq + 1 = {self.n_seq + 1} values, got {h_off.size}")
         d_off = torch.from_numpy(h_off).to(self.device)
-        out_rows, out_ids, out_misses, out_counts, det_ids, rejected = hp.track_update(
-            rows, counts, d_off, h_off, self.state, self.iou_threshold, self.alpha256, self.max_misses, self.min_hits,
-            self.emit_misses, self.birth_score)
+        args = (rows, counts, d_off, h_off, self.state, self.iou_threshold, self.alpha256, self.max_misses, self.min_hits,
+                self.emit_misses, self.birth_score)
+        if self.motion is None:
+            out_rows, out_ids, out_misses, out_counts, det_ids, rejected = hp.track_update(*args)
+        else:
+            out_rows, out_ids, out_misses, out_counts, det_ids, rejected = hp.track_update_motion(
+                *args, self.beta256, self.damp256, self.max_speed, self.grow256)
         n_rej = int(rejected.item())
         if n_rej:
-            raise FdetError(f"FaceTracker.update: {n_rej} sequence(s) rejected by fdet_track_update (a count outside 0..K={int(rows.shape[1])}, "
+            raise FdetError(f"FaceTracker.update: {n_rej} sequence(s) rejected by fdet_track_update{'' if self.motion is None else '_motion'} (a count outside 0..K={int(rows.shape[1])}, "
                             f"or more than {hp.TRACK_MAX_DETS} valid detections in one frame); their state is unchanged")
         return TrackResult(out_rows, out_counts, out_ids, out_misses, det_ids)

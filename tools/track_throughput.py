@@ -1,7 +1,7 @@
 """Timings of the tracker (csrc/fdet_track.hip, fdet_amd/tracking.py): device events for the device paths, a host clock for the
 host path, every shape warmed up, median / min / max over --launches launches, the paths alternated launch by launch.
 
-    python tools/track_throughput.py [--launches 40] [--out profiles/r11_track.json]
+    python tools/track_throughput.py [--launches 40] [--motion] [--out profiles/r11_track.json]
 
 Two configurations, 1 sequence x 256 frames and 16 sequences x 256 frames, about 8 faces per frame (seeded synthetic
 sequences: moving boxes, 20 % dropouts, false positives; K = 100 rows per frame as a 10 x 10 head gives).  Three times each:
@@ -15,6 +15,13 @@ and, for the single sequence, two reduced launches that say where the time of th
   no_tracks              the same rows with birth_score = inf, so no track ever exists: the walk plus step 1 (rows read,
                          validated and compacted, det_ids written); what the full launch adds to it is matching, updates,
                          births and the emitted rows
+With --motion, fdet_track_update_motion (FaceTracker's default motion parameters) is timed too, in both configurations,
+alternated launch by launch with fdet_track_update on the same rows, and checked against tests/track_motion_cpu_ref.py;
+motion_over_old is the ratio of the two medians, the cost of the motion steps.  The tracks move, so the matching of that
+launch is not the old entry's; motion_neutral is the new entry with beta256 = 0, which computes the old entry's bytes (checked)
+and so times the added instructions alone, and neutral_over_old is its ratio.  In that alternation every path always follows
+the same other path (the new entry follows the detector), so ab_rotated times the three tracker launches once more by
+themselves, the order rotated launch by launch so that each follows each equally often; its ratios are the ones to quote.
 
 Prints one JSON line and, with --out, writes it.
 """
@@ -34,6 +41,7 @@ def main(argv=None):
     ap.add_argument("--launches", type=int, default=40)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--host-launches", type=int, default=3, help="repetitions of the host restatement (seconds each)")
+    ap.add_argument("--motion", action="store_true", help="also time fdet_track_update_motion, alternated with the old entry")
     ap.add_argument("--out", default=None)
     args = ap.parse_args(argv)
     import numpy as np
@@ -46,20 +54,26 @@ def main(argv=None):
     n_l = max(30, args.launches)
     T, K = 256, 100
     PAR = dict(iou_threshold=0.3, alpha256=128, max_misses=5, min_hits=2, emit_misses=5, birth_score=0.0)
+    MOTION = dict(beta256=128, damp256=256, max_speed=64, grow256=0)
+    if args.motion:
+        import track_motion_cpu_ref as RM
 
     def stats(ms):
         a = np.sort(np.asarray(ms))
         return {"median_ms": round(float(np.median(a)), 4), "min_ms": round(float(a[0]), 4), "max_ms": round(float(a[-1]), 4),
                 "p10_ms": round(float(a[len(a) // 10]), 4), "p90_ms": round(float(a[(len(a) * 9) // 10]), 4), "launches": len(a)}
 
-    def timed(fns, n):
+    def timed(fns, n, rotate=False):
         for _ in range(args.warmup):
             for f in fns.values():
                 f()
         torch.cuda.synchronize()
         out = {k: [] for k in fns}
-        for _ in range(n):
-            for k, f in fns.items():
+        for i in range(n):
+            order = list(fns.items())
+            if rotate:
+                order = order[i % len(order):] + order[:i % len(order)]
+            for k, f in order:
                 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 e0.record()
                 f()
@@ -79,6 +93,8 @@ def main(argv=None):
 
     res = {"tool": "track_throughput", "device": torch.cuda.get_device_name(0), "frames_per_sequence": T, "K": K,
            "params": PAR, "configs": {}}
+    if args.motion:
+        res["motion_params"] = MOTION
     for n_seq in (1, 16):
         parts = [R.synthetic_sequence(T, K, 100 + s, faces=8, size=(1280, 720), false_positives=0.8) for s in range(n_seq)]
         rows = np.concatenate([p[0] for p in parts])
@@ -93,12 +109,38 @@ def main(argv=None):
             state.zero_()                                    # every launch starts from the fresh state (a 6 KiB memset)
             keep["out"] = hp.track_update(r, c, d_off, h_off, state, rejected=rej, **par)
 
+        def device_motion():
+            state.zero_()
+            keep["motion"] = hp.track_update_motion(d_rows, d_counts, d_off, h_off, state, rejected=rej, **PAR, **MOTION)
+
+        def device_neutral():
+            state.zero_()
+            keep["neutral"] = hp.track_update_motion(d_rows, d_counts, d_off, h_off, state, rejected=rej, **PAR,
+                                                     **{**MOTION, "beta256": 0})
+
         fns = {"fdet_track_update": device, "detector_256_frames": detector}
+        if args.motion:
+            fns["fdet_track_update_motion"] = device_motion
+            fns["motion_neutral"] = device_neutral
         if n_seq == 1:
             zero_counts = torch.zeros_like(d_counts)
             fns["no_detections"] = lambda: device(d_rows, zero_counts)
             fns["no_tracks"] = lambda: device(d_rows, d_counts, {**PAR, "birth_score": float("inf")})
         t = timed(fns, n_l)
+        motion_equal = None
+        if args.motion:
+            ab = timed({"fdet_track_update": device, "fdet_track_update_motion": device_motion, "motion_neutral": device_neutral},
+                       3 * ((n_l + 2) // 3), rotate=True)
+            device_motion()
+            torch.cuda.synchronize()
+            got_m = [o.cpu().numpy() for o in keep["motion"][:5]]
+            s_m = R.fresh_state(n_seq)
+            want_m = RM.track_update_motion(rows, counts, h_off, s_m, **PAR, **MOTION)
+            motion_equal = all(np.array_equal(a, b) for a, b in zip(got_m, want_m[:5])) and \
+                state.cpu().numpy().tobytes() == s_m.tobytes()
+            device_neutral()
+            torch.cuda.synchronize()
+            got_n, state_n = [o.cpu().numpy() for o in keep["neutral"][:5]], state.cpu().numpy().tobytes()
         device()
         torch.cuda.synchronize()
         got = [o.cpu().numpy() for o in keep["out"][:5]]
@@ -118,6 +160,17 @@ def main(argv=None):
                  "rejected": int(rej.item()), "equal_to_restatement": bool(equal),
                  **{k: stats(v) for k, v in t.items()}, "host_restatement": stats(host_s)}
         d_ms = entry["fdet_track_update"]["median_ms"]
+        if args.motion:
+            entry["motion_equal_to_restatement"] = bool(motion_equal)
+            entry["motion_ids"] = int(s_m["seq"]["next_id"].sum())
+            entry["motion_over_old"] = round(entry["fdet_track_update_motion"]["median_ms"] / d_ms, 4)
+            entry["neutral_equal_to_old_entry"] = bool(all(np.array_equal(a, b) for a, b in zip(got_n, got)) and
+                                                       state_n == got_state.tobytes())
+            entry["neutral_over_old"] = round(entry["motion_neutral"]["median_ms"] / d_ms, 4)
+            entry["ab_rotated"] = {k: stats(v) for k, v in ab.items()}
+            ab_ms = entry["ab_rotated"]["fdet_track_update"]["median_ms"]
+            entry["ab_rotated"]["motion_over_old"] = round(entry["ab_rotated"]["fdet_track_update_motion"]["median_ms"] / ab_ms, 4)
+            entry["ab_rotated"]["neutral_over_old"] = round(entry["ab_rotated"]["motion_neutral"]["median_ms"] / ab_ms, 4)
         matched = int((got[4] != 0).sum()) - int(got_state["seq"]["next_id"].sum())
         entry["matches_per_frame"] = round(matched / (n_seq * T), 2)
         if "no_detections" in entry:
