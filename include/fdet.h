@@ -995,6 +995,62 @@ int fdet_track_update_motion(const float* rows, const int32_t* counts, const int
                              void* state, float* out_rows, int32_t* out_ids, int32_t* out_misses, int32_t* out_counts,
                              int32_t* det_ids, uint64_t* rejected, void* stream);
 
+/* Offline refinement of the tracker's output (csrc/fdet_track_refine.hip): a second pass over WHOLE
+ * sequences that back-fills a track before its first detection, interpolates the gaps between its detections, stitches
+ * the fragments of one face into one id and drops short chains.  One workgroup per sequence, no host synchronisation;
+ * no counterpart in the reference.  Integer arithmetic (int64, arithmetic shifts, floor division) apart from step 1 of
+ * fdet_track_update on an anchor's row and the one double multiply of the stitching threshold.
+ *
+ * det_rows [T,K,5] are the rows that were given to fdet_track_update(_motion) (only rows with det_ids > 0 are read),
+ * det_ids [T,K] what it returned for them (values <= 0: no id), trk_rows [T,128,5] / trk_ids / trk_misses [T,128] /
+ * trk_counts [T] its out_rows / out_ids / out_misses / out_counts.  seq_offset / h_seq_offset as there; every sequence's
+ * frames are ALL its frames in time order (cutting a video into calls is the caller's business).
+ * Outputs: out_rows [T,256,5] fp32 [score,x,y,w,h], out_ids / out_misses / out_kind [T,256], out_counts [T]; rows past
+ * out_counts[t] are zeroed.  out_kind: 0 = detected, 1 = coasted by the online tracker, 2 = interpolated, 3 = back-filled.
+ * Per sequence:
+ *   1. anchors.  Track id i has an anchor at frame t when (a) it was emitted at t with trk_misses == 0: the box is the
+ *      emitted row's, or (b) it was not emitted at t at all and a row j has det_ids[t][j] == i (the detections before
+ *      the min_hits-th): the box is that row's.  Either box is the row's corners by step 1 of fdet_track_update (the
+ *      identity on an emitted row, whose values are integers), the score is the row's score.  An emitted row with
+ *      trk_misses != 0 is a coasted row.  An id that has coasted rows but no anchor in the sequence passes through
+ *      untouched: its rows keep kind 1 under its own id, and none of the steps 2..5 concern it.
+ *   2. stitch (skipped when stitch_gap < 0).  Chains are built from the tracks with anchors in ascending id.  A chain is
+ *      named by its lowest id and remembers the frame L and the box A of its last anchor.  Track j with first anchor
+ *      (f, F) may join a chain with L < f, f - L - 1 <= stitch_gap and (double)inter > stitch_iou * (double)uni, inter
+ *      and uni by step 3 of fdet_track_update on A and F.  Among those it joins the one with the largest IoU (compared
+ *      exactly by cross-multiplication as in step 4), the lowest chain id on a tie.  Every row and anchor of j takes the
+ *      chain's id, and (L, A) become j's last anchor.  A track that joins nothing starts a chain.
+ *   3. length filter.  A chain with fewer than min_length anchors disappears from every frame, coasted rows included.
+ *   4. interpolate.  For consecutive anchors (a, A), (b, B) of a chain with b - a >= 2, every frame a < t < b gets, per
+ *      corner c, A.c + floor((2 * (B.c - A.c) * (t - a) + (b - a)) / (2 * (b - a))) (round half up), score = A's
+ *      score, misses = t - a, kind 2.
+ *   5. back-fill.  For a chain's first anchor (f, F), every frame t of the sequence with f - lookback <= t < f gets F
+ *      grown by step 9' of fdet_track_update_motion with m = f - t and grow256; score = F's score, misses = m, kind 3.
+ *   6. per frame and chain at most one row.  An anchor (kind 0: the row it came from, copied as it is, misses 0) wins
+ *      over an interpolated row, that over a coasted row of the input (copied as it is, with its misses; of several
+ *      member tracks coasting in one frame, the one with the highest id), and a back-filled row comes last.
+ *   7. order and room.  Rows of kinds 0..2 in ascending chain id, then rows of kind 3 in ascending chain id; the first
+ *      FDET_TRACK_REFINE_ROWS are written and rejected[1] += the number that did not fit, which is not an error.
+ * Rejection: a sequence with a trk_counts[t] outside 0..128, an emitted id <= 0, ids spanning more than
+ * FDET_TRACK_REFINE_MAX_IDS (highest - lowest + 1, emitted ids and det_ids > 0 alike), an anchor whose row is not valid
+ * by step 1, or more than FDET_TRACK_SLOTS anchors in one frame (neither is something fdet_track_update produces) is
+ * rejected as a whole: its frames get zeroed outputs and rejected[0] += 1; other sequences are unaffected.  An id
+ * occurring twice in one frame is malformed as well: which occurrence counts is unspecified, but nothing is read or
+ * written out of bounds.
+ * ws: fdet_track_refine_ws_bytes(n_seq, T) bytes of device memory (T * 4100; 0 when nothing is launched), 4-byte aligned.
+ * Validated on the host, FDET_EINVAL and nothing launched: h_seq_offset not monotone from 0 to T; n_seq < 1, K < 0, T < 0
+ * or T > 2^24; lookback outside 0..1024; grow256 outside 0..256; stitch_gap > 65535; stitch_iou not in [0, 1);
+ * min_length < 1; ws_bytes too small; a required pointer NULL (det_rows and det_ids when T * K > 0, seq_offset,
+ * h_seq_offset and rejected always, the rest when T > 0). */
+#define FDET_TRACK_REFINE_ROWS     256    /* rows per refined frame */
+#define FDET_TRACK_REFINE_MAX_IDS  4096   /* span of ids (highest - lowest + 1) in one sequence of one call */
+size_t fdet_track_refine_ws_bytes(int n_seq, int T);
+int fdet_track_refine(const float* det_rows, const int32_t* det_ids, int K, const float* trk_rows, const int32_t* trk_ids,
+                      const int32_t* trk_misses, const int32_t* trk_counts, const int32_t* seq_offset,
+                      const int32_t* h_seq_offset, int n_seq, int T, int lookback, int grow256, int stitch_gap,
+                      double stitch_iou, int min_length, float* out_rows, int32_t* out_ids, int32_t* out_misses,
+                      int32_t* out_kind, int32_t* out_counts, void* ws, size_t ws_bytes, uint64_t* rejected, void* stream);
+
 /* ---- face chips and the sharpest chip of each track (csrc/fdet_chips.hip) ------------------
  * fdet_chip_extract cuts one fixed-size square crop ("chip") per detection row out of the image bank;
  * fdet_chip_best_update keeps, per track id, the sharpest chip seen so far.  No counterpart in the reference.  Integer

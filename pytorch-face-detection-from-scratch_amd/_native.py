@@ -180,6 +180,8 @@ SIGNATURES = {
     "fdet_track_update": (_I, [_P, _P, _P, _P, _I, _I, _I, _D, _I, _I, _I, _I, _F, _P, _P, _P, _P, _P, _P, _P, _P]),
     "fdet_track_update_motion": (_I, [_P, _P, _P, _P, _I, _I, _I, _D, _I, _I, _I, _I, _F, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P,
                                       _P]),
+    "fdet_track_refine_ws_bytes": (_SZ, [_I, _I]),
+    "fdet_track_refine": (_I, [_P, _P, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _D, _I, _P, _P, _P, _P, _P, _P, _SZ, _P, _P]),
     "fdet_chip_extract": (_I, [_P, _P, _P, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P]),
     "fdet_chip_gallery_bytes": (_SZ, [_I, _I]),
     "fdet_chip_best_update": (_I, [_P, _P, _I, _I, _P, _I, _P, _P, _I, _P, _I, _I, _I, _P, _P, _P, _P, _P]),

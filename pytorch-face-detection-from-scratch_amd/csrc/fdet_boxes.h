@@ -2,8 +2,9 @@
 // fp32 overlap, the greedy sweep and the LDS carve of the candidate arrays.  Each is a rule that a restatement test checks
 // bit for bit, and each is stated here once: fdet_detect.hip (YOLO decode / NMS / reduce, step metrics), fdet_ssd.hip (SSD
 // reduce, the tie count of the SSD loss), fdet_tiles.hip (tile merge, with and without box voting), fdet_eval.hip and
-// fdet_eval_wider.hip (rank and key) all call these.  The tracker, the chip and the render kernels follow integer rules
-// of their own, and the WIDER evaluator's fp64 "+1" overlap is a different rule: they are not here.
+// fdet_eval_wider.hip (rank and key) all call these, and fdet_track_refine.hip the ordered compaction.  The tracker, the
+// chip and the render kernels follow integer rules of their own, and the WIDER evaluator's fp64 "+1" overlap is a different
+// rule: they are not here.
 //
 // Every file that includes this is built with -ffp-contract=off: the results are compared BIT-EXACTLY with the
 // reference's CPU arithmetic (separate mul and add, IEEE division), so no FMA contraction is allowed in these functions.

@@ -436,7 +436,7 @@ def tile_merge_vote(rows: torch.Tensor, counts: torch.Tensor, d_tiles: torch.Ten
 
 
 # ------------------------------------------------------------------------------------------
-# Tracking across frame sequences (csrc/fdet_track.hip; tracking.py drives this)
+# Tracking across frame sequences (csrc/fdet_track.hip, csrc/fdet_track_refine.hip; tracking.py drives this)
 # ------------------------------------------------------------------------------------------
 TRACK_SLOTS, TRACK_MAX_DETS, TRACK_MAX_COORD = 128, 256, 16384      # FDET_TRACK_* of include/fdet.h
 TRACK_STATE_BYTES = 16 + TRACK_SLOTS * 48                           # per sequence
@@ -503,6 +503,59 @@ def track_update_motion(rows: torch.Tensor, counts: torch.Tensor, seq_offset: to
     return _track_update("fdet_track_update_motion", (int(beta256), int(damp256), int(max_speed), int(grow256)), rows, counts,
                          seq_offset, h_seq_offset, state, iou_threshold, alpha256, max_misses, min_hits, emit_misses, birth_score,
                          rejected)
+
+
+TRACK_REFINE_ROWS, TRACK_REFINE_MAX_IDS = 256, 4096                 # FDET_TRACK_REFINE_* of include/fdet.h
+
+
+def track_refine(det_rows: torch.Tensor, det_ids: torch.Tensor, trk_rows: torch.Tensor, trk_ids: torch.Tensor,
+                 trk_misses: torch.Tensor, trk_counts: torch.Tensor, seq_offset: torch.Tensor, h_seq_offset, lookback: int,
+                 grow256: int, stitch_gap: int, stitch_iou: float, min_length: int, rejected: Optional[torch.Tensor] = None):
+    """fdet_track_refine over whole sequences: det_rows (T,K,5) the rows given to `track_update`, det_ids (T,K) int32 what it
+    returned for them, trk_rows (T,128,5) / trk_ids / trk_misses (T,128) int32 / trk_counts (T,) int32 its outputs; seq_offset
+    and h_seq_offset as there ->
+    (out_rows (T,256,5), out_ids, out_misses, out_kind (T,256) int32, out_counts (T,) int32, rejected (2,) int64: [0] += 1 per
+    rejected sequence, [1] += rows that found no room).  One launch, no host synchronisation."""
+    import numpy as np
+    if det_rows.dim() != 3 or det_rows.shape[2] != 5 or det_rows.dtype != F32:
+        raise ValueError(f"track_refine: det_rows must be (T,K,5) float32, got {tuple(det_rows.shape)} {det_rows.dtype}")
+    T, K = int(det_rows.shape[0]), int(det_rows.shape[1])
+    if not isinstance(h_seq_offset, np.ndarray) or h_seq_offset.dtype != np.int32 or h_seq_offset.ndim != 1 or \
+            not h_seq_offset.flags.c_contiguous or h_seq_offset.size < 2:
+        raise ValueError("track_refine: h_seq_offset must be a contiguous (n_seq+1,) numpy int32 array")
+    n = int(h_seq_offset.size) - 1
+    if tuple(det_ids.shape) != (T, K) or det_ids.dtype != I32:
+        raise ValueError(f"track_refine: det_ids must be ({T},{K}) int32, got {tuple(det_ids.shape)} {det_ids.dtype}")
+    if tuple(trk_rows.shape) != (T, TRACK_SLOTS, 5) or trk_rows.dtype != F32:
+        raise ValueError(f"track_refine: trk_rows must be ({T},{TRACK_SLOTS},5) float32, got {tuple(trk_rows.shape)} {trk_rows.dtype}")
+    for name, t in (("trk_ids", trk_ids), ("trk_misses", trk_misses)):
+        if tuple(t.shape) != (T, TRACK_SLOTS) or t.dtype != I32:
+            raise ValueError(f"track_refine: {name} must be ({T},{TRACK_SLOTS}) int32, got {tuple(t.shape)} {t.dtype}")
+    if tuple(trk_counts.shape) != (T,) or trk_counts.dtype != I32 or tuple(seq_offset.shape) != (n + 1,) or seq_offset.dtype != I32:
+        raise ValueError("track_refine: trk_counts must be (T,) int32 and seq_offset (n_seq+1,) int32")
+    dev = det_rows.device
+    out_rows = torch.empty(T, TRACK_REFINE_ROWS, 5, dtype=F32, device=dev)
+    out_ids = torch.empty(T, TRACK_REFINE_ROWS, dtype=I32, device=dev)
+    out_misses = torch.empty(T, TRACK_REFINE_ROWS, dtype=I32, device=dev)
+    out_kind = torch.empty(T, TRACK_REFINE_ROWS, dtype=I32, device=dev)
+    out_counts = torch.empty(T, dtype=I32, device=dev)
+    if rejected is None:
+        rejected = torch.zeros(2, dtype=torch.int64, device=dev)
+    if rejected.dtype != torch.int64 or rejected.numel() != 2:
+        raise ValueError("track_refine: rejected must hold 2 int64")
+    ws_bytes = int(lib().fdet_track_refine_ws_bytes(n, T))
+    ws = torch.empty(max(ws_bytes, 4) // 4, dtype=I32, device=dev)
+
+    def p(t, dtype=F32):                                     # an empty tensor has no storage to point at
+        return ptr(t, dtype) if t.numel() else None
+
+    check(lib().fdet_track_refine(p(det_rows.contiguous()), p(det_ids.contiguous(), I32), K, p(trk_rows.contiguous()),
+                                  p(trk_ids.contiguous(), I32), p(trk_misses.contiguous(), I32), p(trk_counts.contiguous(), I32),
+                                  ptr(seq_offset.contiguous(), I32), h_seq_offset.ctypes.data, n, T, int(lookback), int(grow256),
+                                  int(stitch_gap), float(stitch_iou), int(min_length), p(out_rows), p(out_ids, I32),
+                                  p(out_misses, I32), p(out_kind, I32), p(out_counts, I32), ptr(ws, I32), ws_bytes,
+                                  ptr(rejected, torch.int64), stream()), "fdet_track_refine")
+    return out_rows, out_ids, out_misses, out_kind, out_counts, rejected
 
 
 # ------------------------------------------------------------------------------------------

@@ -3,6 +3,7 @@
     python -m fdet_amd.track_frames --checkpoint CKPT --frames DIR --out FILE [--model poolresnet --filters 128]
         [--tiled --tile 480 --overlap 0.25] [--iou 0.3 --alpha 0.5 --max-misses 5 --min-hits 2 --emit-misses N]
         [--motion constant_velocity [--motion-beta 0.5] [--motion-damping 1.0] [--max-speed 64] [--coast-grow 0.0]]
+        [--refine [--lookback 5] [--stitch-gap 10] [--stitch-iou 0.1] [--min-length 1]]
         [--draw DIR [--anonymize pixelate|blur] [--blocks N] [--blur-radius R] [--draw-format png|jpg] [--no-outline]]
         [--best-shots DIR [--chip-size N] [--chip-margin F] [--chip-format png|jpg]]
         [--device-jpeg-encode] [--jpeg-quality Q]
@@ -17,7 +18,12 @@ constant_velocity` the missed track moves on at its estimated velocity, so that 
 `--coast-grow` widens the covered box frame by frame while it is missed (`tracking.FaceTracker`).  The model options are
 those of `detect_images`.  `--best-shots DIR` writes one picture per track, `DIR/seq0_track<id>.png`: the sharpest
 `--chip-size` x `--chip-size` crop (112) among the frames in which the detector saw the track, cut with `--chip-margin` (0.25)
-and kept on the device from chunk to chunk (`chips.BestShots`).  Files only: there is no camera or video-container input.
+and kept on the device from chunk to chunk (`chips.BestShots`).  `--refine` is for a finished recording: a
+first pass detects and tracks every chunk and logs it (`tracking.TrackLog`), `tracking.refine_tracks` then looks at the whole
+sequence once (back-fill for --lookback frames before a track's first detection, growing by --coast-grow; interpolated gaps;
+fragments within --stitch-gap frames overlapping by more than --stitch-iou stitched into one id; chains of fewer than
+--min-length detections dropped), and a second pass over the chunks writes FILE and --draw from the refined rows, so a face
+is also covered before the detector first found it.  --best-shots still goes by the online ids.  Files only: there is no camera or video-container input.
 """
 import argparse
 import os
@@ -78,6 +84,11 @@ def main(argv=None):
     ap.add_argument("--motion-damping", type=float, default=1.0, help="velocity a missed track keeps per frame, 0..1")
     ap.add_argument("--max-speed", type=int, default=64, help="bound on a track's velocity, pixels per frame")
     ap.add_argument("--coast-grow", type=float, default=0.0, help="growth of a missed track's emitted box per frame, 0..1")
+    ap.add_argument("--refine", action="store_true", help="second pass over the whole sequence: back-fill, interpolate, stitch ids")
+    ap.add_argument("--lookback", type=int, default=5, help="--refine: frames a track is back-filled before its first detection")
+    ap.add_argument("--stitch-gap", type=int, default=10, help="--refine: longest gap between two fragments of one id (-1: none)")
+    ap.add_argument("--stitch-iou", type=float, default=0.1, help="--refine: least overlap of two fragments of one id")
+    ap.add_argument("--min-length", type=int, default=1, help="--refine: detections a chain needs to be kept")
     add_draw_arguments(ap)
     add_chip_arguments(ap, "--best-shots", "also write the sharpest crop of every track under DIR")
     add_jpeg_encode_arguments(ap)
@@ -87,6 +98,9 @@ def main(argv=None):
     check_chip_arguments(ap, args, "--best-shots")
     if args.max_frames < 1:
         ap.error("--max-frames must be >= 1")
+    if args.refine and not (0 <= args.lookback <= 1024 and args.stitch_gap <= 65535 and 0.0 <= args.stitch_iou < 1.0 and
+                            args.min_length >= 1):
+        ap.error("--refine: --lookback must be in 0..1024, --stitch-gap at most 65535, --stitch-iou in [0, 1) and --min-length >= 1")
     if not os.path.isdir(args.frames):
         ap.error(f"--frames: {args.frames} is not a directory")
     args.paths = frame_paths(args.frames)
@@ -120,21 +134,44 @@ def run(args):
     out = Path(args.out)
     if out.parent != Path(""):
         out.parent.mkdir(parents=True, exist_ok=True)
+    refine = getattr(args, "refine", False)
+    log = None
+    if refine:
+        from .tracking import TrackLog
+        log = TrackLog(1)
+
+    def draw(bank, chunk, rows, counts):
+        from .render import render_detections, save_images
+        drawn = render_detections(bank, rows, counts, outline=not args.no_outline, anonymize=args.anonymize,
+                                  blocks=8 if args.blocks is None else args.blocks, blur_radius=args.blur_radius)
+        save_images(drawn, [(Path(args.draw) / p.name).with_suffix("." + (args.draw_format or "png")) for p in chunk],
+                    **jpeg_encode_options(args))
+
     with open(out, "w") as f:
         for a in range(0, len(paths), args.max_frames):
             chunk = paths[a:a + args.max_frames]
             bank = bank_from_files(chunk, "cuda")
             rows, counts = det.detect(bank, range(len(bank)))
             res = tracker.update(rows, counts)
-            if args.draw is not None:
-                from .render import render_detections, save_images
-                drawn = render_detections(bank, res.rows, res.counts, outline=not args.no_outline, anonymize=args.anonymize,
-                                          blocks=8 if args.blocks is None else args.blocks, blur_radius=args.blur_radius)
-                save_images(drawn, [(Path(args.draw) / p.name).with_suffix("." + (args.draw_format or "png")) for p in chunk],
-                            **jpeg_encode_options(args))
+            if refine:                                       # the first pass only logs; the text and the pictures come below
+                log.append(rows, res)
+            elif args.draw is not None:
+                draw(bank, chunk, res.rows, res.counts)
             if best is not None:
                 best.update(bank, res)
-            lines += write_mot(f, a + 1, res.rows.cpu().numpy(), res.counts.cpu().numpy(), res.ids.cpu().numpy())
+            if not refine:
+                lines += write_mot(f, a + 1, res.rows.cpu().numpy(), res.counts.cpu().numpy(), res.ids.cpu().numpy())
+        if refine:
+            ref = log.refine(lookback=args.lookback, coast_grow=args.coast_grow, stitch_gap=args.stitch_gap,
+                             stitch_iou=args.stitch_iou, min_length=args.min_length).tracks      # one sequence: already in file order
+            for a in range(0, len(paths), args.max_frames):
+                chunk = paths[a:a + args.max_frames]
+                rows, counts, ids = (t[a:a + len(chunk)] for t in (ref.rows, ref.counts, ref.ids))
+                if args.draw is not None:
+                    draw(bank_from_files(chunk, "cuda"), chunk, rows, counts)
+                lines += write_mot(f, a + 1, rows.cpu().numpy(), counts.cpu().numpy(), ids.cpu().numpy())
+            if ref.overflow:
+                print(f"--refine: {ref.overflow} rows found no room in their frame's 256")
     if best is not None:
         shots = best.save(args.chips_dir, getattr(args, "chip_format", None) or "png", **jpeg_encode_options(args))
         print(f"{len(shots)} best shots -> {args.chips_dir}" + (f" ({best.overflow} detections of tracks beyond id {best.capacity} left out)"

@@ -19,6 +19,15 @@ A missed track stays where it was, which bridges a gap only for a face that stan
 the box by it in every frame, matched or not, and can grow the emitted box while the track coasts:
 
     tr = FaceTracker(max_misses=3, min_hits=1, motion="constant_velocity", coast_grow=0.1)
+
+The tracker cannot know what comes later.  On a finished recording `refine_tracks` (`fdet_track_refine`,
+csrc/fdet_track_refine.hip) looks at whole sequences after the fact: it back-fills a track before its first detection,
+interpolates the gaps between its detections, stitches the fragments of a face that was lost into one id and drops short
+chains; `TrackLog` collects what a video tracked in several `update` calls needs for it:
+
+    log = TrackLog()
+    log.append(rows, tr.update(rows, counts))       # per call
+    refined = log.refine(lookback=5, min_length=3).tracks
 """
 from __future__ import annotations
 
@@ -152,3 +161,113 @@ class FaceTracker:
             raise FdetError(f"FaceTracker.update: {n_rej} sequence(s) rejected by fdet_track_update{'' if self.motion is None else '_motion'} (a count outside 0..K={int(rows.shape[1])}, "
                             f"or more than {hp.TRACK_MAX_DETS} valid detections in one frame); their state is unchanged")
         return TrackResult(out_rows, out_counts, out_ids, out_misses, det_ids)
+
+
+class RefinedTracks(namedtuple("RefinedTracks", "rows counts ids misses kind")):
+    """rows (T,256,5) fp32 [score,x,y,w,h] and counts (T,) int32 in the shape `render_detections` takes; ids / misses / kind
+    (T,256) int32: each row's chain id, the frames since (kind 3: until) the detection it stands on, and what it is:
+    0 = detected, 1 = coasted by the online tracker, 2 = interpolated between two detections, 3 = back-filled before the
+    first.  `overflow`: rows that found no room in a frame's 256 (not an error)."""
+    overflow = 0
+
+
+KIND_DETECTED, KIND_COASTED, KIND_INTERPOLATED, KIND_BACKFILLED = 0, 1, 2, 3
+
+
+def _host_offsets(what: str, seq_offset, n_seq: Optional[int], T: int) -> np.ndarray:
+    if seq_offset is None:
+        if n_seq not in (None, 1):
+            raise ValueError(f"{what}: seq_offset is needed with n_seq={n_seq}")
+        seq_offset = (0, T)
+    h_off = np.ascontiguousarray(np.asarray(seq_offset.cpu() if isinstance(seq_offset, torch.Tensor) else seq_offset,
+                                            dtype=np.int64).reshape(-1).astype(np.int32))
+    if h_off.size < 2 or (n_seq is not None and h_off.size != n_seq + 1):
+        raise ValueError(f"{what}: seq_offset must hold n_seq + 1 values, got {h_off.size}")
+    return h_off
+
+
+def refine_tracks(det_rows: torch.Tensor, result: TrackResult, seq_offset=None, lookback: int = 5, coast_grow: float = 0.0,
+                  stitch_gap: int = 10, stitch_iou: float = 0.1, min_length: int = 1) -> RefinedTracks:
+    """The second, offline pass over WHOLE sequences (`fdet_track_refine`, include/fdet.h states the rule): det_rows are the
+    rows that were given to `FaceTracker.update` and `result` is what it returned, every sequence of seq_offset with ALL its
+    frames in time order (see `TrackLog` for a video tracked in several calls).  A track is back-filled for `lookback` frames
+    before its first detection (standing still, growing by coast_grow per frame as a coasting track does), the gaps between
+    its detections are interpolated whatever their length, a track born within `stitch_gap` frames after another's last
+    detection and overlapping it by more than `stitch_iou` takes that one's id (stitch_gap < 0: never), and a chain with fewer
+    than `min_length` detections is dropped, coasted rows and all.  The detections before a track's min_hits-th come back too.
+    Raises FdetError on a rejected sequence (a count outside 0..128, an id <= 0, ids spanning more than 4096 in one sequence);
+    that counter is the only host read.  lookback = 5, stitch_gap = 10, stitch_iou = 0.1 and min_length = 1 are guesses:
+    nobody has measured them on real video."""
+    T = int(det_rows.shape[0])
+    h_off = _host_offsets("refine_tracks", seq_offset, None, T)
+    d_off = torch.from_numpy(h_off).to(det_rows.device)
+    out_rows, out_ids, out_misses, out_kind, out_counts, rejected = hp.track_refine(
+        det_rows, result.det_ids, result.rows, result.ids, result.misses, result.counts, d_off, h_off, int(lookback),
+        unit_to_256("coast_grow", coast_grow), int(stitch_gap), float(stitch_iou), int(min_length))
+    n_rej, overflow = (int(v) for v in rejected.cpu().tolist())
+    if n_rej:
+        raise FdetError(f"refine_tracks: {n_rej} sequence(s) rejected by fdet_track_refine (a count outside 0..{hp.TRACK_SLOTS}, an "
+                        f"emitted id <= 0, ids spanning more than {hp.TRACK_REFINE_MAX_IDS}, or rows that fdet_track_update does "
+                        "not produce)")
+    res = RefinedTracks(out_rows, out_counts, out_ids, out_misses, out_kind)
+    res.overflow = overflow
+    return res
+
+
+RefinedLog = namedtuple("RefinedLog", "tracks seq_offset position")
+RefinedLog.__doc__ = """tracks: the RefinedTracks of every logged frame, sequence-major (all frames of sequence 0 in time order,
+then sequence 1, ...); seq_offset (n_seq+1,) int32 numpy: sequence s owns frames seq_offset[s]..seq_offset[s+1]-1 of it;
+position (T,) int64 numpy: position[i] is the place of output frame i in the order of appending (the frames of the first
+`append` from 0, those of the second after them, ...)."""
+
+
+class TrackLog:
+    """Keeps what `FaceTracker.update` saw and returned, call by call, for `refine_tracks` over the whole video:
+
+        log = TrackLog()
+        for rows, counts in chunks:
+            log.append(rows, tracker.update(rows, counts))
+        refined = log.refine(lookback=5, min_length=3)
+
+    The tensors stay on the device.  The result does not depend on how the video was cut into calls."""
+
+    def __init__(self, n_seq: int = 1):
+        self.n_seq = int(n_seq)
+        if self.n_seq < 1:
+            raise ValueError(f"TrackLog: n_seq={n_seq} must be >= 1")
+        self._chunks = []
+
+    def __len__(self) -> int:
+        return sum(int(c[0].shape[0]) for c in self._chunks)
+
+    def append(self, det_rows: torch.Tensor, result: TrackResult, seq_offset=None) -> None:
+        """det_rows, seq_offset: what was given to `update`; result: what it returned."""
+        T = int(det_rows.shape[0])
+        if int(result.rows.shape[0]) != T or tuple(result.det_ids.shape) != tuple(det_rows.shape[:2]):
+            raise ValueError("TrackLog.append: result does not belong to det_rows")
+        h_off = _host_offsets("TrackLog.append", seq_offset, self.n_seq, T).astype(np.int64)
+        if h_off[0] != 0 or h_off[-1] != T or (np.diff(h_off) < 0).any():
+            raise ValueError(f"TrackLog.append: seq_offset must run from 0 to T={T} without going back")
+        self._chunks.append((det_rows, result, h_off))
+
+    def refine(self, **kw) -> RefinedLog:
+        """Gathers every sequence's frames into time order and runs `refine_tracks` (its keyword arguments) once."""
+        if not self._chunks:
+            raise ValueError("TrackLog.refine: nothing was appended")
+        base = np.concatenate([[0], np.cumsum([int(c[0].shape[0]) for c in self._chunks])]).astype(np.int64)
+        position = [np.arange(base[i] + c[2][s], base[i] + c[2][s + 1]) for s in range(self.n_seq)
+                    for i, c in enumerate(self._chunks)]
+        position = np.concatenate(position).astype(np.int64)
+        lengths = [sum(int(c[2][s + 1] - c[2][s]) for c in self._chunks) for s in range(self.n_seq)]
+        seq_offset = np.concatenate([[0], np.cumsum(lengths)]).astype(np.int32)
+        dev = self._chunks[0][0].device
+        K = max(int(c[0].shape[1]) for c in self._chunks)
+
+        def padded(t):                                       # calls may differ in K: rows past a call's K carry no id
+            return t if int(t.shape[1]) == K else torch.nn.functional.pad(t, (0, 0) * (t.dim() - 2) + (0, K - int(t.shape[1])))
+
+        order = torch.from_numpy(position).to(dev)
+        det_rows = torch.cat([padded(c[0]) for c in self._chunks]).index_select(0, order)
+        result = TrackResult(*(torch.cat([padded(getattr(c[1], f)) if f == "det_ids" else getattr(c[1], f) for c in self._chunks])
+                               .index_select(0, order) for f in TrackResult._fields))
+        return RefinedLog(refine_tracks(det_rows, result, seq_offset, **kw), seq_offset, position)

@@ -1,7 +1,7 @@
 """Timings of the tracker (csrc/fdet_track.hip, fdet_amd/tracking.py): device events for the device paths, a host clock for the
 host path, every shape warmed up, median / min / max over --launches launches, the paths alternated launch by launch.
 
-    python tools/track_throughput.py [--launches 40] [--motion] [--out profiles/r11_track.json]
+    python tools/track_throughput.py [--launches 40] [--motion] [--refine] [--out profiles/r11_track.json]
 
 Two configurations, 1 sequence x 256 frames and 16 sequences x 256 frames, about 8 faces per frame (seeded synthetic
 sequences: moving boxes, 20 % dropouts, false positives; K = 100 rows per frame as a 10 x 10 head gives).  Three times each:
@@ -22,6 +22,12 @@ launch is not the old entry's; motion_neutral is the new entry with beta256 = 0,
 and so times the added instructions alone, and neutral_over_old is its ratio.  In that alternation every path always follows
 the same other path (the new entry follows the detector), so ab_rotated times the three tracker launches once more by
 themselves, the order rotated launch by launch so that each follows each equally often; its ratios are the ones to quote.
+With --refine, fdet_track_refine (the offline second pass, default parameters of tracking.refine_tracks) runs on what
+fdet_track_update returned for the same frames, in both configurations, the order rotated launch by launch with
+fdet_track_update; it is checked against tests/track_refine_cpu_ref.py, which is timed once on the host (copies included).
+refine_over_update is the ratio of the two medians.  Two reduced launches say where its time goes: refine_no_stitch
+(stitch_gap = -1: pass 3 is skipped) and refine_no_rows (no emitted row and no det_id: the two walks over the frames alone,
+barriers and dependent loads, with nothing to link, stitch or write but zeros).
 
 Prints one JSON line and, with --out, writes it.
 """
@@ -42,6 +48,7 @@ def main(argv=None):
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--host-launches", type=int, default=3, help="repetitions of the host restatement (seconds each)")
     ap.add_argument("--motion", action="store_true", help="also time fdet_track_update_motion, alternated with the old entry")
+    ap.add_argument("--refine", action="store_true", help="also time fdet_track_refine on the tracker's output")
     ap.add_argument("--out", default=None)
     args = ap.parse_args(argv)
     import numpy as np
@@ -57,6 +64,9 @@ def main(argv=None):
     MOTION = dict(beta256=128, damp256=256, max_speed=64, grow256=0)
     if args.motion:
         import track_motion_cpu_ref as RM
+    REFINE = dict(lookback=5, grow256=0, stitch_gap=10, stitch_iou=0.1, min_length=1)
+    if args.refine:
+        import track_refine_cpu_ref as RR
 
     def stats(ms):
         a = np.sort(np.asarray(ms))
@@ -95,6 +105,8 @@ def main(argv=None):
            "params": PAR, "configs": {}}
     if args.motion:
         res["motion_params"] = MOTION
+    if args.refine:
+        res["refine_params"] = REFINE
     for n_seq in (1, 16):
         parts = [R.synthetic_sequence(T, K, 100 + s, faces=8, size=(1280, 720), false_positives=0.8) for s in range(n_seq)]
         rows = np.concatenate([p[0] for p in parts])
@@ -171,6 +183,42 @@ def main(argv=None):
             ab_ms = entry["ab_rotated"]["fdet_track_update"]["median_ms"]
             entry["ab_rotated"]["motion_over_old"] = round(entry["ab_rotated"]["fdet_track_update_motion"]["median_ms"] / ab_ms, 4)
             entry["ab_rotated"]["neutral_over_old"] = round(entry["ab_rotated"]["motion_neutral"]["median_ms"] / ab_ms, 4)
+        if args.refine:
+            o = keep["out"]                                  # what the online pass returned: rows, ids, misses, counts, det_ids
+            rej2 = torch.zeros(2, dtype=torch.int64, device="cuda")
+            no_counts, no_ids = torch.zeros_like(o[3]), torch.zeros_like(o[4])
+
+            def refine(par=REFINE, c=o[3], di=o[4]):
+                keep["refine"] = hp.track_refine(d_rows, di, o[0], o[1], o[2], c, d_off, h_off, rejected=rej2, **par)
+
+            fr = {"fdet_track_update": device, "fdet_track_refine": refine,
+                  "refine_no_stitch": lambda: refine({**REFINE, "stitch_gap": -1}),
+                  "refine_no_rows": lambda: refine(REFINE, no_counts, no_ids)}
+            tr = timed(fr, 4 * ((n_l + 3) // 4), rotate=True)
+            rej2.zero_()
+            refine()
+            torch.cuda.synchronize()
+            got_r = [x.cpu().numpy() for x in keep["refine"][:5]] + [keep["refine"][5].cpu().tolist()]
+            t0 = time.perf_counter()
+            h_in = [x.cpu().numpy() for x in (d_rows, o[4], o[0], o[1], o[2], o[3])]
+            want_r = RR.track_refine(*h_in, h_off, **REFINE)
+            host_refine_ms = (time.perf_counter() - t0) * 1e3
+            entry["refine"] = {k: stats(v) for k, v in tr.items()}
+            r = entry["refine"]
+            r["equal_to_restatement"] = bool(all(a.tobytes() == b.tobytes() for a, b in zip(got_r[:5], want_r[:5])) and
+                                             got_r[5] == want_r[5])
+            r["host_restatement_ms"] = round(host_refine_ms, 1)
+            r["rejected"] = got_r[5]
+            r["rows_by_kind"] = [int((got_r[3][got_r[1] > 0] == k).sum()) for k in range(4)]
+            r["stitches"], r["chains"] = want_r[6]["stitches"], int(sum(len(np.unique(got_r[1][a:b][got_r[1][a:b] > 0]))
+                                                                  for a, b in zip(h_off[:-1], h_off[1:])))
+            u_ms, f_ms = r["fdet_track_update"]["median_ms"], r["fdet_track_refine"]["median_ms"]
+            r["refine_over_update"] = round(f_ms / u_ms, 3)
+            r["host_over_device"] = round(host_refine_ms / f_ms, 1)
+            r["us_per_frame_of_a_sequence"] = round(f_ms / T * 1e3, 3)
+            r["split_ms"] = {"walks_alone": r["refine_no_rows"]["median_ms"],
+                             "stitch": round(f_ms - r["refine_no_stitch"]["median_ms"], 4),
+                             "anchors_links_rows": round(r["refine_no_stitch"]["median_ms"] - r["refine_no_rows"]["median_ms"], 4)}
         matched = int((got[4] != 0).sum()) - int(got_state["seq"]["next_id"].sum())
         entry["matches_per_frame"] = round(matched / (n_seq * T), 2)
         if "no_detections" in entry:
